@@ -2,8 +2,10 @@
 """V-JEPA pretraining-step benchmark on MI355X (BASELINE.json metric: clips/sec, fwd+bwd+EMA, ViT-L/16 16x224x224).
 
     python bench.py --gpus 1 --steps 10 --warmup 3
-    python bench.py --gpus N --steps K --warmup W          # N > 1 without a launcher: re-executes itself under
-                                                           # torch.distributed.run (one rank per GPU, 127.0.0.1 rendezvous)
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full  # + roofline pass and CPU baseline (see below)
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR   # + what the last timed step computed, as DIR/*.npy
+    python bench.py --gpus N --steps K --warmup W          # N > 1 without a launcher: starts itself again in a child process
+                                                           # under torch.distributed.run (one rank per GPU, 127.0.0.1 rendezvous)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W             # the same ranks started by an external launcher
 
@@ -11,6 +13,12 @@ A "step" is one pass of the hot path (reference app/vjepa/train.py:414-487: sche
 context+predictor forward/backward, latent loss, gradient all-reduce, AdamW, EMA) over one batch of synthetic
 clips already resident in HBM, with mask indices drawn by the reference-compatible multiblock collator.
 Weak scaling: every rank processes its own B=24 clips.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write the outputs of the last
+timed step when --dump-outputs is given, print the line (`roofline` and `cpu_baseline` are null).  `--full` adds the
+measurements below, each after the timed region (`--no-roofline-pass` / `--no-cpu-baseline` drop one of them again).
+--dump-outputs DIR writes the loss and step statistics of rank 0's last timed step and fixed, seeded samples of the
+updated parameters, EMA target, gradients and Adam moments (float32 / float64, about 40 MB), before anything else runs.
 
 `roofline.achieved / frac` is the WHOLE STEP (the north-star quantity): matmul FLOPs of the step (engine/flops.py) over the
 timed region, against the dense bf16 MFMA peak.  Its sub-objects `gemm_family`, `dominant_kernel`, `attn_fwd`, `attn_bwd`
@@ -90,16 +98,20 @@ def build(wl, device, world_size):
     return trainer, sched, wd_sched
 
 
+MAX_DISTINCT_BATCHES = 64   # ViT-L: 64 x 231 MB of clips; longer runs cycle, so set-up time and HBM stay bounded
+
+
 def make_inputs(wl, n_steps, rank, device, host=False):
     """Synthetic batches resident in HBM (host=True: in pinned host memory, for the --h2d input-edge run).  Large
-    workloads keep only `distinct_batches` different batches and cycle through them."""
+    workloads keep only `distinct_batches` different batches and cycle through them; every workload keeps at most
+    MAX_DISTINCT_BATCHES.  Batch i depends only on (i, rank): the same arguments give the same inputs in every run."""
     from jepa_amd.src.masks.multiblock3d import MaskCollator
     coll = MaskCollator(cfgs_mask=wl["masks"], crop_size=wl["crop"], num_frames=wl["frames"],
                         patch_size=wl["patch"], tubelet_size=wl["tubelet"])
     B = wl["batch"]
     batches = []
     gen = torch.Generator(device=device)
-    for step in range(min(n_steps, wl.get("distinct_batches", n_steps))):
+    for step in range(min(n_steps, wl.get("distinct_batches", n_steps), MAX_DISTINCT_BATCHES)):
         gen.manual_seed(1234 + step + 1000 * rank)
         clips = torch.randn(B, 3, wl["frames"], wl["crop"], wl["crop"], device=device, generator=gen)  # never zeros
         torch.manual_seed(4321 + step + 1000 * rank)
@@ -190,9 +202,10 @@ def _free_port():
 
 def self_launch(args):
     """`python bench.py --gpus N` with N > 1 and no launcher environment: start the N ranks ourselves, one process per GPU,
-    by re-executing this file under torch.distributed.run (the reference's launcher spawns one process per device the same
-    way, app/main.py:28-71).  Rank 0 of the children prints the ONE JSON line on the inherited stdout.  Returns when there
-    is nothing to do (N = 1, or the ranks were already started by torchrun / the driver: WORLD_SIZE is set)."""
+    by running this file again under torch.distributed.run in a child process (the reference's launcher spawns one process
+    per device the same way, app/main.py:28-71) and exiting with its status.  Rank 0 of the children prints the ONE JSON
+    line on the inherited stdout.  Returns when there is nothing to do (N = 1, or the ranks were already started by
+    torchrun / the driver: WORLD_SIZE is set)."""
     if args.gpus <= 1 or "WORLD_SIZE" in os.environ:
         return
     if args.stub_step_ms is None:
@@ -203,7 +216,8 @@ def self_launch(args):
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     log("self-launch: " + " ".join(cmd))
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    import subprocess
+    raise SystemExit(subprocess.call(cmd))
 
 
 def timed_loop(run, sync, warmup, steps):
@@ -223,6 +237,35 @@ def timed_loop(run, sync, warmup, steps):
     host_enqueue = time.perf_counter() - t0
     sync()
     return time.perf_counter() - t0, host_enqueue, t_first, last
+
+
+DUMP_SAMPLE = 1 << 21   # elements per sampled arena (8 MB in float32); five arenas -> 40 MB
+
+
+def dump_outputs(trainer, out, out_dir):
+    """What the last timed step handed its caller: the StepOutput (losses, gradient norms, skip flag) and the updated
+    state -- encoder + predictor weights, EMA target, gradients, Adam moments -- as fixed, seeded samples of the fp32
+    arenas (the same indices in every run with the same workload).  Files: out_dir/<name>.npy, float32 / float64."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    trainer.sync_update()
+    torch.cuda.synchronize()
+    h = out._fetch()
+    enc_norm, pred_norm = out.raw_grad_norms
+    arrays = {"loss": np.array([out.loss], dtype=np.float64),
+              "step_output": np.array([out.loss_jepa, out.loss_reg, enc_norm, pred_norm, float(out.skipped)], dtype=np.float64),
+              "step_stats": np.array(h, dtype=np.float64)}
+    a, t = trainer.arena, trainer.tarena
+    for name, buf in (("params", a.P), ("grads", a.G), ("adam_exp_avg", a.M1), ("adam_exp_avg_sq", a.M2),
+                      ("target_params", t.P)):
+        n = buf.numel()
+        if n > DUMP_SAMPLE:
+            idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            buf = buf[idx.to(buf.device)]
+        arrays[name] = buf.float().cpu().numpy()
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    log(f"outputs of the last timed step -> {out_dir}: " + ", ".join(f"{k} {v.shape}" for k, v in arrays.items()))
 
 
 def max_over_ranks(x, world, device):
@@ -304,15 +347,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="vitl16", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch override (default: the recipe's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline-pass", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the instrumented roofline pass and the CPU baseline leg")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-roofline-pass", action="store_true", help="with --full: skip the roofline pass")
     ap.add_argument("--h2d", action="store_true",
                     help="input-edge run: batches start in pinned HOST memory and go through the double-buffered "
                          "prefetcher (engine/input.py); reported on stderr, never as `value`")
-    ap.add_argument("--gemm-csv", default=None, help="write one line per GEMM / attention launch of the roofline pass")
+    ap.add_argument("--gemm-csv", default=None,
+                    help="with --full: write one line per GEMM / attention launch of the roofline pass")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--stub-step-ms", type=float, default=None, help=argparse.SUPPRESS)   # launcher test: see stub_main()
     args = ap.parse_args()
+    if args.gemm_csv and (not args.full or args.no_roofline_pass):
+        ap.error("--gemm-csv is written by the roofline pass: it needs --full (and no --no-roofline-pass)")
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline(args.workload)), flush=True)
         return
@@ -371,6 +421,8 @@ def main():
         torch.cuda.synchronize()
 
     elapsed, host_enqueue, t_first, last = timed_loop(run, sync, args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:   # before anything else runs a step
+        dump_outputs(trainer, last, args.dump_outputs)
     ranks_ms = [1e3 * e / args.steps for e in per_rank(elapsed, world, device)]   # every rank's own clock around the same K steps
     log(f"host enqueue time {1e3 * host_enqueue / args.steps:.1f} ms/step incl. queue back-pressure, "
         f"{1e3 * t_first:.1f} ms for the first step (GPU step {1e3 * elapsed / args.steps:.1f} ms)")
@@ -457,7 +509,7 @@ def main():
         log(f"input-edge run (PCIe-inclusive): {json.dumps(input_edge)}")
 
     roof = None
-    if not args.no_roofline_pass:
+    if args.full and not args.no_roofline_pass:
         from jepa_amd.engine import chain
         from jepa_amd.engine.layers import side_stream
         side = side_stream(device)
@@ -543,7 +595,7 @@ def main():
                              "ms_per_step": round(fam["attn_bwd"]["ms"] / n_inst, 2)}}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("cpu baseline leg (bounded subprocess)")
         cpu = cpu_baseline_subprocess(args.workload)
 

@@ -5,22 +5,19 @@ A checkpoint dictionary written the way jepa_amd.app.vjepa.train.save_checkpoint
   * app/vjepa/utils.py:28-83   load_checkpoint  -> reference modules + a torch.optim.AdamW built by the reference's init_opt
   * evals/video_classification_frozen/eval.py:414-441  load_pretrained (the `module.` / `backbone.` key stripper)
 and a CPU forward of the loaded reference encoder is compared with the pinned oracle on the same weights.
-The reference-dependent tests carry the `reference` marker (skipped where /root/reference is absent, e.g. the GPU box);
-the id / group-size contract of the optimizer state is also checked without the reference against a torch AdamW built
-from the documented grouping."""
-import ast
+What the reference's own code did with such checkpoints -- the tensors it loaded, the optimizer state it placed, its groups
+and its forward -- is recorded in tests/golden/reference_api.npz (oracle/make_golden_reference.py); the tests load the same
+checkpoints the way those loaders do and must reproduce that record.  The id / group-size contract of the
+optimizer state is also checked against a torch AdamW built from the documented grouping."""
 import copy
-import logging
 import os
 import sys
 
-import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tests.golden_util import fingerprint_matches, load_reference_api, tensor_fingerprint  # noqa: E402
 from tests.step_util import TINY, build_models, oracle_cfg  # noqa: E402
-
-REF = "/root/reference"
 
 
 def _fake_trained_state(enc, pred, step=3, seed=0):
@@ -77,13 +74,6 @@ def test_optimizer_state_ids_match_a_torch_adamw_built_like_init_opt():
     assert step == 3 and torch.equal(Z1[used], M1[used]) and torch.equal(Z2[used], M2[used])
 
 
-def _ref_imports():
-    if REF not in sys.path:
-        sys.path.insert(0, REF)
-    import app.vjepa.utils as RU            # noqa: E402  (reference module, read-only)
-    return RU
-
-
 class _DDPLike(torch.nn.Module):
     """The reference checkpoints DistributedDataParallel-wrapped modules: their state-dict keys start with `module.`."""
 
@@ -92,9 +82,20 @@ class _DDPLike(torch.nn.Module):
         self.module = m
 
 
-@pytest.mark.reference
+def _check_state(z, prefix, sd):
+    """A state dict against the one the reference's loader ended up with: names, shapes, the same tensors."""
+    assert list(sd.keys()) == list(z[prefix + "_keys"]), prefix
+    for k, shape, fp in zip(z[prefix + "_keys"], z[prefix + "_shapes"], z[prefix + "_fp"]):
+        assert ",".join(map(str, sd[k].shape)) == shape, (prefix, k)
+        assert fingerprint_matches(tensor_fingerprint(sd[k]), fp), (prefix, k)
+
+
 def test_reference_load_checkpoint_reads_a_jepa_amd_checkpoint(tmp_path):
-    RU = _ref_imports()
+    """The reference's load_checkpoint (app/vjepa/utils.py:28-83) restated: strict load_state_dict of the three
+    `module.`-wrapped modules, then the AdamW state into an optimizer grouped as the reference's init_opt groups it.  The
+    outcome -- epoch, module tensors, optimizer state by parameter name -- equals what the reference's own code produced
+    from the same checkpoint (recorded by oracle/make_golden_reference.py)."""
+    z = load_reference_api()
     enc, pred = build_models(TINY, 2, perturb_small=True)
     tgt = copy.deepcopy(enc)
     with torch.no_grad():
@@ -103,20 +104,36 @@ def test_reference_load_checkpoint_reads_a_jepa_amd_checkpoint(tmp_path):
     opt_sd, groups, slot_of, M1, M2 = _fake_trained_state(enc, pred, step=5)
     path = os.path.join(tmp_path, "jepa-latest.pth.tar")
     torch.save(_checkpoint(enc, pred, tgt, opt_sd, epoch=7), path)
-    # fresh reference modules (different seed -> different weights) + the reference's own optimizer
-    torch.manual_seed(123)
-    r_enc, r_pred = RU.init_video_model(device="cpu", patch_size=16, num_frames=TINY["frames"], tubelet_size=2,
-                                        model_name="vit_tiny", crop_size=TINY["crop"], pred_depth=TINY["pred_depth"],
-                                        pred_embed_dim=TINY["pred_dim"], uniform_power=True, use_mask_tokens=True,
-                                        num_mask_tokens=2, zero_init_mask_tokens=True, use_sdpa=True)
+    # fresh modules (different seed -> different weights; init_video_model is seed-for-seed the reference's:
+    # tests/test_host_parity.py) + an AdamW with the reference's four groups, parameter by parameter
+    r_enc, r_pred = build_models(TINY, 2, seed=123)
     r_tgt = copy.deepcopy(r_enc)
-    r_opt, r_scaler, _, _ = RU.init_opt(encoder=r_enc, predictor=r_pred, wd=0.04, final_wd=0.4, start_lr=2e-4, ref_lr=6e-4,
-                                        final_lr=1e-6, iterations_per_epoch=10, warmup=1, num_epochs=4, ipe_scale=1.25,
-                                        mixed_precision=False, betas=(0.9, 0.999), eps=1e-8)
+    by_name = {pre + n: p for pre, m in (("e.", r_enc), ("p.", r_pred)) for n, p in m.named_parameters()}
+    names = list(z["ckpt/group_names"])
+    r_groups, o = [], 0
+    for size, wd_ex in zip(z["ckpt/group_sizes"].tolist(), z["ckpt/group_wd_exclude"].tolist()):
+        g = {"params": [by_name[n] for n in names[o:o + size]]}
+        if wd_ex:
+            g.update(WD_exclude=True, weight_decay=0)
+        r_groups.append(g)
+        o += size
+    assert o == len(names) == len(by_name)
+    r_opt = torch.optim.AdamW(r_groups, betas=(0.9, 0.999), eps=1e-8)
     w_enc, w_pred, w_tgt = _DDPLike(r_enc), _DDPLike(r_pred), _DDPLike(r_tgt)
-    *_, epoch = RU.load_checkpoint(r_path=path, encoder=w_enc, predictor=w_pred, target_encoder=w_tgt, opt=r_opt,
-                                   scaler=r_scaler)
-    assert epoch == 7, "the reference's load_checkpoint swallowed an exception and restarted at epoch 0"
+    ck = torch.load(path, map_location="cpu")
+    w_enc.load_state_dict(ck["encoder"])
+    w_pred.load_state_dict(ck["predictor"])
+    w_tgt.load_state_dict(ck["target_encoder"])
+    r_opt.load_state_dict(ck["opt"])
+    assert ck["epoch"] == int(z["ckpt/epoch"][0]) == 7
+    for tag, w in (("enc", w_enc), ("pred", w_pred), ("tgt", w_tgt)):
+        _check_state(z, "ckpt/" + tag, w.state_dict())
+    st = [(n, r_opt.state[p]) for n in names for p in [by_name[n]] if p in r_opt.state]
+    assert [n for n, _ in st] == list(z["ckpt/opt_state_names"])
+    for (n, s), fp in zip(st, z["ckpt/opt_state_fp"]):
+        assert fingerprint_matches(tensor_fingerprint(s["exp_avg"]), fp[0]), n
+        assert fingerprint_matches(tensor_fingerprint(s["exp_avg_sq"]), fp[1]), n
+        assert float(s["step"]) == 5.0
     for ours, theirs in ((enc, r_enc), (pred, r_pred), (tgt, r_tgt)):
         a, b = ours.state_dict(), theirs.state_dict()
         assert list(a.keys()) == list(b.keys())
@@ -136,23 +153,14 @@ def test_reference_load_checkpoint_reads_a_jepa_amd_checkpoint(tmp_path):
     assert len(ours_by_name) == len(list(r_enc.named_parameters())) + len(list(r_pred.named_parameters()))
 
 
-def _reference_function(rel_path, name, extra_globals):
-    """Execute ONE function definition out of a reference file that cannot be imported here (its module pulls in
-    torchvision / decord): the reference's own source, read in place, never copied."""
-    src = open(os.path.join(REF, rel_path)).read()
-    node = next(n for n in ast.parse(src).body if isinstance(n, ast.FunctionDef) and n.name == name)
-    ns = dict(extra_globals)
-    exec(compile(ast.Module(body=[node], type_ignores=[]), rel_path, "exec"), ns)
-    return ns[name]
-
-
-@pytest.mark.reference
-def test_reference_eval_loader_and_cpu_forward(tmp_path, capsys):
-    """evals/video_classification_frozen/eval.py:414-441 strips `module.` / `backbone.` and loads the TARGET encoder into
-    a bare reference VisionTransformer; its CPU forward equals the pinned oracle's on the same weights (1e-5)."""
-    _ref_imports()
-    import src.models.vision_transformer as RV            # noqa: E402  (reference)
+def test_reference_eval_loader_and_cpu_forward(tmp_path):
+    """evals/video_classification_frozen/eval.py:414-441 (load_pretrained) restated: the TARGET encoder's keys with `module.`
+    / `backbone.` stripped are exactly the bare reference VisionTransformer's, and carry the tensors the reference's own
+    loader ended up with; the reference's CPU forward of that encoder (recorded by oracle/make_golden_reference.py) equals
+    the pinned oracle's on the same weights (1e-5)."""
+    from jepa_amd.src.models.vision_transformer import vit_tiny
     from oracle import vjepa_oracle as O
+    z = load_reference_api()
     enc, pred = build_models(TINY, 2, perturb_small=True)
     tgt = copy.deepcopy(enc)
     with torch.no_grad():
@@ -161,18 +169,18 @@ def test_reference_eval_loader_and_cpu_forward(tmp_path, capsys):
     opt_sd, *_ = _fake_trained_state(enc, pred)
     path = os.path.join(tmp_path, "jepa-latest.pth.tar")
     torch.save(_checkpoint(enc, pred, tgt, opt_sd, epoch=3), path)
-    load_pretrained = _reference_function("evals/video_classification_frozen/eval.py", "load_pretrained",
-                                          {"torch": torch, "logger": logging.getLogger("ref-eval")})
+    ck = torch.load(path, map_location="cpu")
+    sd = {k.replace("module.", "").replace("backbone.", ""): v for k, v in ck["target_encoder"].items()}
+    _check_state(z, "eval/bare", sd)     # no key missing, none unexpected, every tensor as the reference loaded it
     torch.manual_seed(99)
-    bare = RV.vit_tiny(img_size=TINY["crop"], patch_size=16, num_frames=TINY["frames"], tubelet_size=2,
-                       uniform_power=True, use_sdpa=True)
-    bare = load_pretrained(encoder=bare, pretrained=path, checkpoint_key="target_encoder")
-    capsys.readouterr()   # the reference prints the whole model
+    bare = vit_tiny(img_size=TINY["crop"], patch_size=16, num_frames=TINY["frames"], tubelet_size=2, uniform_power=True,
+                    use_sdpa=True)
+    bare.load_state_dict(sd)             # the same-named module of this package takes it strictly
     for k, v in tgt.backbone.state_dict().items():
         assert torch.equal(bare.state_dict()[k], v), k
     clips = torch.randn(2, 3, TINY["frames"], TINY["crop"], TINY["crop"], generator=torch.Generator().manual_seed(1))
-    with torch.no_grad():
-        y_ref = bare(clips)
+    y_ref = torch.from_numpy(z["eval/y"])
     w = {k: v.detach().clone() for k, v in tgt.backbone.state_dict().items()}
     y_or = O.encoder_forward(w, clips, oracle_cfg(TINY, 2))
+    assert y_ref.shape == y_or.shape
     assert (y_ref - y_or).abs().max() <= 1e-5 * y_or.abs().max() + 1e-6

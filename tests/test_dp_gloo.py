@@ -55,6 +55,9 @@ def _worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     from jepa_amd.engine import dp
     from jepa_amd.src.utils.distributed import AllReduce, init_distributed
+    # host-side ranks: init_distributed picks nccl whenever a GPU is visible, so on a GPU host this worker hides it to stay
+    # on the gloo path the test is about (every tensor here lives on the CPU)
+    torch.cuda.is_available = lambda: False
     ws, rk = init_distributed()
     assert (ws, rk) == (world, rank) and dist.get_backend() == "gloo"
     arena, vit, pred = _fake_arena()

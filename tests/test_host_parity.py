@@ -1,15 +1,14 @@
 """Host-side (CPU) parity of the drop-in Python layer with the reference: position tables, mask collator,
-schedules (against the committed golden fixtures) and -- when /root/reference is mounted -- seed-for-seed model
-initialisation, state-dict names and tensor helpers against the live reference modules."""
+schedules, seed-for-seed model initialisation, state-dict names and collator draws over random configurations, all against
+golden fixtures recorded from the reference (oracle/make_golden.py, oracle/make_golden_reference.py)."""
 import os
 import sys
 
 import numpy as np
-import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from tests.golden_util import load_tables  # noqa: E402
+from tests.golden_util import collator_digests, fingerprint_matches, load_reference_api, load_tables, tensor_fingerprint  # noqa: E402
 
 VITL_MASKS = [
     dict(aspect_ratio=(0.75, 1.5), num_blocks=8, spatial_scale=(0.15, 0.15), temporal_scale=(1.0, 1.0),
@@ -99,85 +98,39 @@ def test_repeat_interleave_batch():
     assert torch.equal(repeat_interleave_batch(x, 2, repeat=1), x)
 
 
-@pytest.mark.reference
 def test_init_video_model_is_seed_for_seed_identical_to_reference():
-    import importlib
-    saved = {k: v for k, v in sys.modules.items() if k == "src" or k.startswith("src.") or k == "app" or k.startswith("app.")}
-    for k in saved:
-        del sys.modules[k]
-    sys.path.insert(0, "/root/reference")
-    try:
-        ref_init = importlib.import_module("app.vjepa.utils").init_video_model
-    finally:
-        sys.path.remove("/root/reference")
+    """init_video_model under seed 0 against the reference's own (recorded by oracle/make_golden_reference.py): the same
+    state-dict names, shapes and tensors (the same draws: equal up to the last bit of the host's CPU kernels), the same
+    trainable parameters and backbone attributes."""
     from jepa_amd.app.vjepa.utils import init_video_model
+    z = load_reference_api()
     kw = dict(device="cpu", patch_size=16, num_frames=8, tubelet_size=2, model_name="vit_tiny", crop_size=64,
               pred_depth=2, pred_embed_dim=96, uniform_power=True, use_mask_tokens=True, num_mask_tokens=2,
               zero_init_mask_tokens=True, use_sdpa=True)
     torch.manual_seed(0)
-    re, rp = ref_init(**kw)
-    torch.manual_seed(0)
     oe, op = init_video_model(**kw)
-    for ref, ours in ((re, oe), (rp, op)):
-        rs, os_ = ref.state_dict(), ours.state_dict()
-        assert list(rs.keys()) == list(os_.keys())
-        for k in rs:
-            assert rs[k].shape == os_[k].shape, k
-            assert torch.equal(rs[k], os_[k]), k
-        assert [n for n, p in ref.named_parameters() if p.requires_grad] == \
-            [n for n, p in ours.named_parameters() if p.requires_grad]
-    for attr in ("embed_dim", "num_heads", "num_patches", "patch_size", "tubelet_size", "num_frames", "input_size"):
-        assert getattr(re.backbone, attr) == getattr(oe.backbone, attr)
+    for tag, ours in (("enc", oe), ("pred", op)):
+        sd = ours.state_dict()
+        assert list(sd.keys()) == list(z[f"init/{tag}_keys"])
+        for k, shape, fp in zip(z[f"init/{tag}_keys"], z[f"init/{tag}_shapes"], z[f"init/{tag}_fp"]):
+            assert ",".join(map(str, sd[k].shape)) == shape, k
+            assert fingerprint_matches(tensor_fingerprint(sd[k]), fp), k
+        assert [n for n, p in ours.named_parameters() if p.requires_grad] == list(z[f"init/{tag}_trainable"])
+    attrs = ("embed_dim", "num_heads", "num_patches", "patch_size", "tubelet_size", "num_frames", "input_size")
+    assert [int(getattr(oe.backbone, a)) for a in attrs] == z["init/attrs"].tolist()
 
 
-@pytest.mark.reference
 def test_collators_match_the_live_reference_over_random_configs():
-    """40 random (config, seed, batch) draws of both collators against the reference's own classes imported from
-    /root/reference: index tensors bit-identical, including the shared step counter and max_keep / max_temporal_keep."""
-    import random
-    sys.path.insert(0, "/root/reference")
-    from src.masks.multiblock3d import MaskCollator as RefMB       # noqa: E402  (reference, read-only)
-    from src.masks.random_tube import MaskCollator as RefTube      # noqa: E402
+    """40 random (config, seed, batch) multiblock draws and 10 random-tube draws (tests.golden_util.collator_trials) against
+    what the reference's own classes drew (recorded by oracle/make_golden_reference.py): index tensors bit-identical,
+    including the shared step counter and max_keep / max_temporal_keep."""
     from jepa_amd.src.masks.multiblock3d import MaskCollator as OurMB
     from jepa_amd.src.masks.random_tube import MaskCollator as OurTube
-    rnd = random.Random(7)
-    for trial in range(40):
-        crop = rnd.choice([64, 128, 224, 384])
-        frames = rnd.choice([8, 16])
-        n_masks = rnd.choice([1, 2, 3])
-        cfgs = []
-        for _ in range(n_masks):
-            lo = rnd.choice([0.15, 0.2, 0.5, 0.7])
-            cfgs.append(dict(aspect_ratio=rnd.choice([(0.75, 1.5), (0.3, 3.0)]), num_blocks=rnd.choice([1, 2, 4, 8]),
-                             spatial_scale=(lo, rnd.choice([lo, min(0.9, lo + 0.2)])),
-                             temporal_scale=rnd.choice([(1.0, 1.0), (0.5, 1.0), (0.25, 0.75)]),
-                             max_temporal_keep=rnd.choice([1.0, 0.5]), max_keep=rnd.choice([None, None, 64])))
-        kw = dict(cfgs_mask=cfgs, crop_size=crop, num_frames=frames, patch_size=16, tubelet_size=2)
-        ours, ref = OurMB(**kw), RefMB(**kw)
-        B = rnd.choice([1, 2, 5, 24])
-        for it in range(3):
-            seed = rnd.randrange(1 << 30)
-            batch = [(torch.zeros(1), 0) for _ in range(B)]
-            torch.manual_seed(seed)
-            _, me_o, mp_o = ours(batch)
-            torch.manual_seed(seed)
-            _, me_r, mp_r = ref(batch)
-            for a, b in zip(me_o + mp_o, me_r + mp_r):
-                assert a.dtype == b.dtype and torch.equal(a, b), (trial, it)
-            if rnd.random() < 0.3:   # the resume path replays the counter (train.py:322-326)
-                ours.step()
-                ref.step()
-    for trial in range(10):
-        ratio = rnd.choice([0.5, 0.75, 0.9])
-        kw = dict(cfgs_mask=[dict(ratio=ratio)], crop_size=224, num_frames=16, patch_size=16, tubelet_size=2)
-        ours, ref = OurTube(**kw), RefTube(**kw)
-        seed = rnd.randrange(1 << 30)
-        batch = [(torch.zeros(1), 0) for _ in range(4)]
-        torch.manual_seed(seed)
-        np.random.seed(seed % (1 << 31))
-        _, me_o, mp_o = ours(batch)
-        torch.manual_seed(seed)
-        np.random.seed(seed % (1 << 31))
-        _, me_r, mp_r = ref(batch)
-        for a, b in zip(me_o + mp_o, me_r + mp_r):
-            assert torch.equal(a, b), ("tube", trial)
+    z = load_reference_api()
+    mb, tube = collator_digests(OurMB, OurTube)
+    ref_mb, ref_tube = list(z["coll/multiblock_sha"]), list(z["coll/tube_sha"])
+    assert len(mb) == len(ref_mb) == 120 and len(tube) == len(ref_tube) == 10
+    for i, (a, b) in enumerate(zip(mb, ref_mb)):
+        assert a == b, ("multiblock", i // 3, i % 3)
+    for i, (a, b) in enumerate(zip(tube, ref_tube)):
+        assert a == b, ("tube", i)

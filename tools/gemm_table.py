@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Per-shape table of the step's GEMM / attention launches from `bench.py --gemm-csv FILE` (one line per launch,
+"""Per-shape table of the step's GEMM / attention launches from `bench.py --full --gemm-csv FILE` (one line per launch,
 HIP-event durations on the launch stream, serial pass): shape, launches per step, mean us, TF/s, share of family time.
 
     python tools/gemm_table.py gpurun_out/gemm.csv 3 > profiles/r02_gemm_shapes.md      (3 = instrumented steps)
