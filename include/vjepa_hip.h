@@ -205,6 +205,17 @@ int vj_xattn_fwd(const void* q, int64_t q_bstride, const void* kv, const void* r
  * <- (dy [B,1,H*hd] bf16, saved q, kv, lse2).  NQ must be 1. */
 int vj_xattn_bwd(const void* q, int64_t q_bstride, const void* kv, const void* dy, const float* lse2, void* dq, void* dkv,
                  int64_t B, int64_t NQ, int64_t N, int64_t H, int64_t hd, float scale, vj_stream_t stream);
+/* The two calls above keep every score of a (sample, head) in LDS and refuse more keys than that holds (forward N <= 38 264,
+ * backward N <= 19 132).  The _ws forms take the same arguments plus a workspace and have no key limit: within those limits they
+ * run the same kernels (same bits, ws_bytes 0); above them, split-key kernels (fixed 2048-key chunks, fp32 partials in ws merged in
+ * ascending chunk order, no atomics: deterministic).  vj_xattn_ws_bytes(backward = 0 / 1) is the workspace size (0 when none is
+ * needed, < 0 for bad dimensions).  Split backward: 10*N*hd + 16*N bytes per (sample, head). */
+int64_t vj_xattn_ws_bytes(int64_t B, int64_t NQ, int64_t N, int64_t H, int64_t hd, int backward);
+int vj_xattn_fwd_ws(const void* q, int64_t q_bstride, const void* kv, const void* resid, void* out, float* lse2, int64_t B,
+                    int64_t NQ, int64_t N, int64_t H, int64_t hd, float scale, void* ws, int64_t ws_bytes, vj_stream_t stream);
+int vj_xattn_bwd_ws(const void* q, int64_t q_bstride, const void* kv, const void* dy, const float* lse2, void* dq, void* dkv,
+                    int64_t B, int64_t NQ, int64_t N, int64_t H, int64_t hd, float scale, void* ws, int64_t ws_bytes,
+                    vj_stream_t stream);
 
 /* ---- predictor token assembly (predictor.py:194-221) --------------------------------------------------------
  * out[b, j<Ke] = embed[b,j] + pos[idx_e[b,j]];  out[b, Ke+j] = mask_token + pos[idx_p[b,j]] */

@@ -10,6 +10,11 @@
 // (16-byte row chunks, eight consecutive lanes cover one 128-byte row of hd = 64), keeps the N scores / probabilities in LDS
 // (fp32) and reduces in a fixed order (deterministic).  Algorithmic bytes: forward 4 N hd per (b, h, query); backward
 // reads K and V twice and writes dK and dV once: 12 N hd.
+// Those single-workgroup kernels hold N fp32 scores (forward) or two such arrays (backward) in LDS, so they serve N <= 38 264
+// (forward) and N <= 19 132 (backward).  Above that the _ws entry points run split-key kernels instead: fixed chunks of XA_CHUNK
+// keys, one workgroup per (b, h[, query], chunk), fp32 partials in a caller-provided workspace merged in ascending chunk order.
+// Algorithmic bytes of the split forms: forward 4 N hd per (b, h, query) (+ hd + 2 fp32 per chunk); backward 10 N hd + 16 N per
+// (b, h) -- pass 1 reads K and V and writes p_j and dP_j (fp32), pass 2 reads p_j, dP_j and K and writes dK and dV.
 //   forward : s_j = (q . k_j) scale log2e ; p_j = 2^(s_j - max) ; y = sum_j p_j v_j / sum_j p_j ; out = residual + y ;
 //             lse2 = max + log2(sum)
 //   backward: p_j = 2^(s_j - lse2) ; dP_j = dy . v_j ; delta = sum_j p_j dP_j ; dS_j = p_j (dP_j - delta) ;
@@ -189,6 +194,225 @@ __global__ __launch_bounds__(XA_THREADS) void xattn_bwd_kernel(const bf16_t* __r
   }
 }
 
+// ---- split-key forms (vj_xattn_fwd_ws / vj_xattn_bwd_ws above the single-workgroup limits) ------------------------------
+// A chunk of XA_CHUNK consecutive keys per workgroup.  The chunk is a compile-time constant, so the chunk count -- and with it
+// every summation order -- depends on N alone, never on the device.  Partials go to the caller's workspace (fp32) and are
+// merged in ascending chunk order; no atomics.
+#define XA_CHUNK 2048
+
+// forward partials, grid (B*H*NQ, chunks): over its keys, m_c = max s_j, l_c = sum_j 2^(s_j - m_c), y_c = sum_j 2^(s_j - m_c) v_j
+__global__ __launch_bounds__(XA_THREADS) void xattn_fwd_split_kernel(const bf16_t* __restrict__ q, int64_t q_bstride,
+                                                                     const bf16_t* __restrict__ kv, float* __restrict__ ws_y,
+                                                                     float* __restrict__ ws_ml, int NQ, int N, int H, int hd,
+                                                                     float scale, int nch) {
+  __shared__ __attribute__((aligned(16))) float xs[XA_LDS_FIXED + XA_CHUNK];
+  float* qv = xs;
+  float* red = xs + 128;
+  float* part = xs + 136;
+  float* sc = xs + XA_LDS_FIXED;
+  const int bhq = blockIdx.x, ch = blockIdx.y;
+  const int iq = bhq % NQ, bh = bhq / NQ;
+  const int h = bh % H, b = bh / H;
+  const int j0 = ch * XA_CHUNK, n = min(XA_CHUNK, N - j0);
+  const int64_t D = (int64_t)H * hd, rs = 2 * D;
+  const bf16_t* kbase = kv + ((int64_t)b * N + j0) * rs + (int64_t)h * hd;
+  const bf16_t* vbase = kbase + D;
+  const bf16_t* qp = q + (int64_t)b * q_bstride + (int64_t)iq * D + (int64_t)h * hd;
+  if ((int)threadIdx.x < hd) qv[threadIdx.x] = bf2f(qp[threadIdx.x]) * (scale * XA_LOG2E);
+  __syncthreads();
+  xa_scores(kbase, rs, n, hd, qv, sc);
+  float mx = -INFINITY;
+  for (int j = threadIdx.x; j < n; j += XA_THREADS) mx = fmaxf(mx, sc[j]);
+  mx = xa_block_reduce(mx, red, true);
+  float sum = 0.f;
+  for (int j = threadIdx.x; j < n; j += XA_THREADS) {
+    const float p = __builtin_amdgcn_exp2f(sc[j] - mx);
+    sc[j] = p;
+    sum += p;
+  }
+  sum = xa_block_reduce(sum, red, false);
+  const float y = xa_weighted_rows(vbase, rs, n, hd, sc, part);
+  const int64_t slot = (int64_t)bhq * nch + ch;
+  if ((int)threadIdx.x < hd) ws_y[slot * hd + threadIdx.x] = y;
+  if (threadIdx.x == 0) {
+    ws_ml[2 * slot] = mx;
+    ws_ml[2 * slot + 1] = sum;
+  }
+}
+
+// forward combine, grid B*H*NQ: M = max m_c ; L = sum_c 2^(m_c - M) l_c ; out = resid + sum_c 2^(m_c - M) y_c / L ; lse2 = M + log2 L
+__global__ __launch_bounds__(128) void xattn_fwd_combine_kernel(const float* __restrict__ ws_y, const float* __restrict__ ws_ml,
+                                                                const bf16_t* __restrict__ resid, bf16_t* __restrict__ out,
+                                                                float* __restrict__ lse2, int NQ, int H, int hd, int nch) {
+  const int bhq = blockIdx.x, d = threadIdx.x;
+  const int iq = bhq % NQ, bh = bhq / NQ;
+  const int h = bh % H, b = bh / H;
+  const float* ml = ws_ml + (int64_t)bhq * nch * 2;
+  const float* yc = ws_y + (int64_t)bhq * nch * hd;
+  float M = -INFINITY;
+  for (int c = 0; c < nch; c++) M = fmaxf(M, ml[2 * c]);
+  float L = 0.f, y = 0.f;
+  for (int c = 0; c < nch; c++) {
+    const float w = __builtin_amdgcn_exp2f(ml[2 * c] - M);
+    L += w * ml[2 * c + 1];
+    if (d < hd) y += w * yc[(int64_t)c * hd + d];
+  }
+  if (d < hd) {
+    const int64_t D = (int64_t)H * hd;
+    float v = y / L;
+    if (resid) v += bf2f(resid[(int64_t)iq * D + (int64_t)h * hd + d]);
+    out[((int64_t)b * NQ + iq) * D + (int64_t)h * hd + d] = f2bf(v);
+  }
+  if (d == 0 && lse2) lse2[(int64_t)bh * NQ + iq] = M + log2f(L);
+}
+
+// backward pass 1, grid (B*H, chunks): p_j = 2^(s_j - lse2) and dP_j = dy . v_j to the workspace, and the chunk's part of
+// delta = sum_j p_j dP_j
+__global__ __launch_bounds__(XA_THREADS) void xattn_bwd_split_p_kernel(const bf16_t* __restrict__ q, int64_t q_bstride,
+                                                                       const bf16_t* __restrict__ kv,
+                                                                       const bf16_t* __restrict__ dy,
+                                                                       const float* __restrict__ lse2, float* __restrict__ ws_p,
+                                                                       float* __restrict__ ws_dp, float* __restrict__ ws_delta,
+                                                                       int N, int H, int hd, float scale, int nch) {
+  __shared__ __attribute__((aligned(16))) float qv[128], dyv[128], red[8];
+  const int bh = blockIdx.x, ch = blockIdx.y;
+  const int h = bh % H, b = bh / H;
+  const int j0 = ch * XA_CHUNK, n = min(XA_CHUNK, N - j0);
+  const int64_t D = (int64_t)H * hd, rs = 2 * D;
+  const bf16_t* kbase = kv + ((int64_t)b * N + j0) * rs + (int64_t)h * hd;
+  const bf16_t* qp = q + (int64_t)b * q_bstride + (int64_t)h * hd;
+  if ((int)threadIdx.x < hd) {
+    qv[threadIdx.x] = bf2f(qp[threadIdx.x]) * (scale * XA_LOG2E);
+    dyv[threadIdx.x] = bf2f(dy[(int64_t)b * D + (int64_t)h * hd + threadIdx.x]);
+  }
+  __syncthreads();
+  const float l2 = lse2[bh];
+  float* pp = ws_p + (int64_t)bh * N + j0;
+  float* dpp = ws_dp + (int64_t)bh * N + j0;
+  const int nc8 = hd >> 3;
+  float dl = 0.f;
+  for (int j = threadIdx.x; j < n; j += XA_THREADS) {
+    const bf16_t* kp = kbase + (int64_t)j * rs;
+    float s = 0.f, e = 0.f;
+    for (int c = 0; c < nc8; c++) {
+      const u32x4_t wk = *(const u32x4_t*)(kp + c * 8);
+      const u32x4_t wv = *(const u32x4_t*)(kp + D + c * 8);
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        s += bf_lo(wk[i]) * qv[c * 8 + 2 * i] + bf_hi(wk[i]) * qv[c * 8 + 2 * i + 1];
+        e += bf_lo(wv[i]) * dyv[c * 8 + 2 * i] + bf_hi(wv[i]) * dyv[c * 8 + 2 * i + 1];
+      }
+    }
+    const float p = __builtin_amdgcn_exp2f(s - l2);
+    pp[j] = p;
+    dpp[j] = e;
+    dl += p * e;
+  }
+  dl = xa_block_reduce(dl, red, false);
+  if (threadIdx.x == 0) ws_delta[(int64_t)bh * nch + ch] = dl;
+}
+
+// backward pass 2, grid (B*H, chunks): delta = the chunk partials summed in ascending order (the same sum in every workgroup),
+// dS_j = p_j (dP_j - delta), this chunk's dq partial sum_j dS_j k_j (unscaled) to the workspace, dk_j = scale dS_j q and
+// dv_j = p_j dy stored directly (every key has one owner)
+__global__ __launch_bounds__(XA_THREADS) void xattn_bwd_split_d_kernel(const bf16_t* __restrict__ q, int64_t q_bstride,
+                                                                       const bf16_t* __restrict__ dy,
+                                                                       const bf16_t* __restrict__ kv,
+                                                                       const float* __restrict__ ws_p,
+                                                                       const float* __restrict__ ws_dp,
+                                                                       const float* __restrict__ ws_delta,
+                                                                       float* __restrict__ ws_dq, bf16_t* __restrict__ dkv,
+                                                                       int N, int H, int hd, float scale, int nch) {
+  __shared__ __attribute__((aligned(16))) float part[2048], sc[XA_CHUNK], ds[XA_CHUNK], dyv[128], qraw[128];
+  const int bh = blockIdx.x, ch = blockIdx.y;
+  const int h = bh % H, b = bh / H;
+  const int j0 = ch * XA_CHUNK, n = min(XA_CHUNK, N - j0);
+  const int64_t D = (int64_t)H * hd, rs = 2 * D;
+  const bf16_t* kbase = kv + ((int64_t)b * N + j0) * rs + (int64_t)h * hd;
+  const bf16_t* qp = q + (int64_t)b * q_bstride + (int64_t)h * hd;
+  if ((int)threadIdx.x < hd) {
+    qraw[threadIdx.x] = bf2f(qp[threadIdx.x]);
+    dyv[threadIdx.x] = bf2f(dy[(int64_t)b * D + (int64_t)h * hd + threadIdx.x]);
+  }
+  float delta = 0.f;
+  for (int c = 0; c < nch; c++) delta += ws_delta[(int64_t)bh * nch + c];
+  const float* pp = ws_p + (int64_t)bh * N + j0;
+  const float* dpp = ws_dp + (int64_t)bh * N + j0;
+  for (int j = threadIdx.x; j < n; j += XA_THREADS) {
+    const float p = pp[j];
+    sc[j] = p;
+    ds[j] = p * (dpp[j] - delta);
+  }
+  __syncthreads();
+  const float dqv = xa_weighted_rows(kbase, rs, n, hd, ds, part);
+  if ((int)threadIdx.x < hd) ws_dq[((int64_t)bh * nch + ch) * hd + threadIdx.x] = dqv;
+  const int nc8 = hd >> 3, ngrp = XA_THREADS / nc8;
+  const int c = threadIdx.x % nc8, rg = threadIdx.x / nc8;
+  if (rg < ngrp) {
+    float q8[8], d8[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      q8[i] = qraw[c * 8 + i] * scale;
+      d8[i] = dyv[c * 8 + i];
+    }
+    bf16_t* dkb = dkv + ((int64_t)b * N + j0) * rs + (int64_t)h * hd + c * 8;
+    for (int j = rg; j < n; j += ngrp) {
+      const float s = ds[j], p = sc[j];
+      u32x4_t wk, wv;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        wk[i] = pack_bf2(s * q8[2 * i], s * q8[2 * i + 1]);
+        wv[i] = pack_bf2(p * d8[2 * i], p * d8[2 * i + 1]);
+      }
+      *(u32x4_t*)(dkb + (int64_t)j * rs) = wk;
+      *(u32x4_t*)(dkb + (int64_t)j * rs + D) = wv;
+    }
+  }
+}
+
+// dq = scale * sum_c dq_c (ascending chunk order), grid B*H
+__global__ __launch_bounds__(128) void xattn_bwd_dq_kernel(const float* __restrict__ ws_dq, bf16_t* __restrict__ dq, int hd,
+                                                           float scale, int nch) {
+  const int bh = blockIdx.x, d = threadIdx.x;
+  if (d >= hd) return;
+  const float* pd = ws_dq + (int64_t)bh * nch * hd + d;
+  float t = 0.f;
+  for (int c = 0; c < nch; c++) t += pd[(int64_t)c * hd];
+  dq[(int64_t)bh * hd + d] = f2bf(t * scale);   // dq [B, H*hd]: (b*H + h)*hd + d
+}
+
+// the single-workgroup kernels keep every score of a (b, h, query) in dynamic LDS: 1 (forward) or 2 (backward) fp32 arrays of N
+#define XA_LDS_MAX (160 * 1024 - 2048)
+inline int64_t xa_max_keys(int arrays) { return ((int64_t)XA_LDS_MAX / 4 - XA_LDS_FIXED) / arrays; }
+
+// workspace of the split forms: every sub-array 256-byte aligned
+struct XaSplit {
+  int64_t nch, off[4], bytes;
+};
+inline int64_t xa_align(int64_t x) { return (x + 255) & ~(int64_t)255; }
+XaSplit xa_split_layout(int64_t B, int64_t NQ, int64_t N, int64_t H, int64_t hd, int backward) {
+  XaSplit s{};
+  s.nch = (N + XA_CHUNK - 1) / XA_CHUNK;
+  int64_t sz[4];
+  if (!backward) {   // y partials [B*H*NQ][nch][hd], (m, l) [B*H*NQ][nch][2]
+    sz[0] = B * H * NQ * s.nch * hd * 4;
+    sz[1] = B * H * NQ * s.nch * 2 * 4;
+    sz[2] = sz[3] = 0;
+  } else {           // p [B*H][N], dP [B*H][N], delta partials [B*H][nch], dq partials [B*H][nch][hd]
+    sz[0] = B * H * N * 4;
+    sz[1] = B * H * N * 4;
+    sz[2] = B * H * s.nch * 4;
+    sz[3] = B * H * s.nch * hd * 4;
+  }
+  int64_t o = 0;
+  for (int i = 0; i < 4; i++) {
+    s.off[i] = o;
+    o += xa_align(sz[i]);
+  }
+  s.bytes = o;
+  return s;
+}
+
 int xa_check(const char* who, int64_t B, int64_t NQ, int64_t N, int64_t H, int64_t hd, int64_t* lds_bytes, int arrays) {
   VJ_CHECK_ARG(B >= 0 && NQ >= 1 && N >= 1 && H >= 1, "%s: bad dims", who);
   VJ_CHECK_ARG(hd % 8 == 0 && hd >= 8 && hd <= 128, "%s: head_dim=%ld unsupported (need %%8==0, <=128)", who, (long)hd);
@@ -227,5 +451,69 @@ extern "C" int vj_xattn_bwd(const void* q, int64_t q_bstride, const void* kv, co
   hipLaunchKernelGGL(xattn_bwd_kernel, dim3((unsigned)(B * H)), dim3(XA_THREADS), (size_t)lds, stream, (const bf16_t*)q, q_bstride,
                      (const bf16_t*)kv, (const bf16_t*)dy, lse2, (bf16_t*)dq, (bf16_t*)dkv, (int)B, (int)N, (int)H, (int)hd, scale);
   VJ_LAUNCH_CHECK("vj_xattn_bwd");
+  return 0;
+}
+
+extern "C" int64_t vj_xattn_ws_bytes(int64_t B, int64_t NQ, int64_t N, int64_t H, int64_t hd, int backward) {
+  if (B < 0 || NQ < 1 || N < 1 || H < 1 || hd < 8 || hd > 128 || hd % 8 != 0) return -1;
+  if (N <= xa_max_keys(backward ? 2 : 1)) return 0;   // the single-workgroup kernel runs: no workspace
+  return xa_split_layout(B, NQ, N, H, hd, backward).bytes;
+}
+
+namespace {
+int xa_check_split(const char* who, int64_t B, int64_t NQ, int64_t N, int64_t H, int64_t hd, const XaSplit& s, void* ws,
+                   int64_t ws_bytes) {
+  VJ_CHECK_ARG(B >= 0 && NQ >= 1 && N >= 1 && H >= 1, "%s: bad dims", who);
+  VJ_CHECK_ARG(hd % 8 == 0 && hd >= 8 && hd <= 128, "%s: head_dim=%ld unsupported (need %%8==0, <=128)", who, (long)hd);
+  VJ_CHECK_ARG(N < (1ll << 31) && B * H * NQ * XA_THREADS <= 0xffffffffll && s.nch <= 65535, "%s: grid too large", who);
+  if (B == 0) return 0;   // nothing to launch: vj_xattn_ws_bytes is 0, so no workspace is required
+  VJ_CHECK_ARG(ws != nullptr && ws_bytes >= s.bytes, "%s: workspace of %ld bytes, need %ld (vj_xattn_ws_bytes)", who,
+               (long)ws_bytes, (long)s.bytes);
+  return 0;
+}
+}  // namespace
+
+extern "C" int vj_xattn_fwd_ws(const void* q, int64_t q_bstride, const void* kv, const void* resid, void* out, float* lse2,
+                               int64_t B, int64_t NQ, int64_t N, int64_t H, int64_t hd, float scale, void* ws, int64_t ws_bytes,
+                               hipStream_t stream) {
+  if (N <= xa_max_keys(1)) return vj_xattn_fwd(q, q_bstride, kv, resid, out, lse2, B, NQ, N, H, hd, scale, stream);
+  const XaSplit s = xa_split_layout(B, NQ, N, H, hd, 0);
+  if (int rc = xa_check_split("vj_xattn_fwd_ws", B, NQ, N, H, hd, s, ws, ws_bytes)) return rc;
+  if (B == 0) return 0;
+  float* ws_y = (float*)((char*)ws + s.off[0]);
+  float* ws_ml = (float*)((char*)ws + s.off[1]);
+  hipLaunchKernelGGL(xattn_fwd_split_kernel, dim3((unsigned)(B * H * NQ), (unsigned)s.nch), dim3(XA_THREADS), 0, stream,
+                     (const bf16_t*)q, q_bstride, (const bf16_t*)kv, ws_y, ws_ml, (int)NQ, (int)N, (int)H, (int)hd, scale,
+                     (int)s.nch);
+  VJ_LAUNCH_CHECK("vj_xattn_fwd_ws");
+  hipLaunchKernelGGL(xattn_fwd_combine_kernel, dim3((unsigned)(B * H * NQ)), dim3(128), 0, stream, (const float*)ws_y,
+                     (const float*)ws_ml, (const bf16_t*)resid, (bf16_t*)out, lse2, (int)NQ, (int)H, (int)hd, (int)s.nch);
+  VJ_LAUNCH_CHECK("vj_xattn_fwd_ws");
+  return 0;
+}
+
+extern "C" int vj_xattn_bwd_ws(const void* q, int64_t q_bstride, const void* kv, const void* dy, const float* lse2, void* dq,
+                               void* dkv, int64_t B, int64_t NQ, int64_t N, int64_t H, int64_t hd, float scale, void* ws,
+                               int64_t ws_bytes, hipStream_t stream) {
+  VJ_CHECK_ARG(NQ == 1, "vj_xattn_bwd_ws: one query per sample (AttentiveClassifier, attentive_pooler.py:120); got %ld", (long)NQ);
+  if (N <= xa_max_keys(2)) return vj_xattn_bwd(q, q_bstride, kv, dy, lse2, dq, dkv, B, NQ, N, H, hd, scale, stream);
+  const XaSplit s = xa_split_layout(B, NQ, N, H, hd, 1);
+  if (int rc = xa_check_split("vj_xattn_bwd_ws", B, NQ, N, H, hd, s, ws, ws_bytes)) return rc;
+  if (B == 0) return 0;
+  float* ws_p = (float*)((char*)ws + s.off[0]);
+  float* ws_dp = (float*)((char*)ws + s.off[1]);
+  float* ws_delta = (float*)((char*)ws + s.off[2]);
+  float* ws_dq = (float*)((char*)ws + s.off[3]);
+  const dim3 grid((unsigned)(B * H), (unsigned)s.nch);
+  hipLaunchKernelGGL(xattn_bwd_split_p_kernel, grid, dim3(XA_THREADS), 0, stream, (const bf16_t*)q, q_bstride, (const bf16_t*)kv,
+                     (const bf16_t*)dy, lse2, ws_p, ws_dp, ws_delta, (int)N, (int)H, (int)hd, scale, (int)s.nch);
+  VJ_LAUNCH_CHECK("vj_xattn_bwd_ws");
+  hipLaunchKernelGGL(xattn_bwd_split_d_kernel, grid, dim3(XA_THREADS), 0, stream, (const bf16_t*)q, q_bstride, (const bf16_t*)dy,
+                     (const bf16_t*)kv, (const float*)ws_p, (const float*)ws_dp, (const float*)ws_delta, ws_dq, (bf16_t*)dkv,
+                     (int)N, (int)H, (int)hd, scale, (int)s.nch);
+  VJ_LAUNCH_CHECK("vj_xattn_bwd_ws");
+  hipLaunchKernelGGL(xattn_bwd_dq_kernel, dim3((unsigned)(B * H)), dim3(128), 0, stream, (const float*)ws_dq, (bf16_t*)dq, (int)hd,
+                     scale, (int)s.nch);
+  VJ_LAUNCH_CHECK("vj_xattn_bwd_ws");
   return 0;
 }

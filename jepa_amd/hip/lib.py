@@ -87,6 +87,9 @@ SIGNATURES = {
     "vj_attn_bwd_colsum": (I32, [P, P, P, P, P, I64, I64, I64, I64, F32, P, I64, P, P, P]),
     "vj_xattn_fwd": (I32, [P, I64, P, P, P, P, I64, I64, I64, I64, I64, F32, P]),
     "vj_xattn_bwd": (I32, [P, I64, P, P, P, P, P, I64, I64, I64, I64, I64, F32, P]),
+    "vj_xattn_ws_bytes": (I64, [I64, I64, I64, I64, I64, I32]),
+    "vj_xattn_fwd_ws": (I32, [P, I64, P, P, P, P, I64, I64, I64, I64, I64, F32, P, I64, P]),
+    "vj_xattn_bwd_ws": (I32, [P, I64, P, P, P, P, P, I64, I64, I64, I64, I64, F32, P, I64, P]),
     "vj_pred_assemble_fwd": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, P]),
     "vj_target_rows": (I32, [P, P, P, P, P, I64, I64, I64, I64, F32, F32, P]),
     "vj_latent_loss_ws_bytes": (I64, []),

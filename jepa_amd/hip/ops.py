@@ -475,26 +475,42 @@ def reduce_segments(segs, alpha=1.0, accumulate=False, stream=None):
 
 
 # ---------------------------------------------------------------- predictor / loss
+def _xattn_ws(B, NQ, N, H, hd, backward, device, stream):
+    """Workspace of vj_xattn_{fwd,bwd}_ws from the caching allocator: (None, 0) while N fits the single-workgroup kernels."""
+    nbytes = load_library().vj_xattn_ws_bytes(B, NQ, N, H, hd, int(backward))
+    if nbytes < 0:
+        raise ValueError(f"xattn: unsupported dims B={B} NQ={NQ} N={N} H={H} head_dim={hd}")
+    if nbytes == 0:
+        return None, 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    if stream is not None:   # allocated on the current stream, used on another: keep it alive until that stream gets past it
+        ws.record_stream(torch.cuda.ExternalStream(stream, device=device))
+    return ws, nbytes
+
+
 def xattn_fwd(q, kv, B, NQ, N, H, hd, scale, resid=None, shared_q=True, save_lse=True, stream=None):
-    """Few-query cross-attention (vj_xattn_fwd): q [NQ, D] (shared_q) or [B, NQ, D], kv [B*N, 2*D] packed -> out [B*NQ, D] bf16,
-    lse2 [B, H, NQ] fp32 (None when not saved)."""
+    """Few-query cross-attention (vj_xattn_fwd_ws, any N): q [NQ, D] (shared_q) or [B, NQ, D], kv [B*N, 2*D] packed -> out [B*NQ, D]
+    bf16, lse2 [B, H, NQ] fp32 (None when not saved)."""
     D = H * hd
     _req(q, torch.bfloat16, "q"); _req(kv, torch.bfloat16, "kv")
     out = torch.empty((B * NQ, D), dtype=torch.bfloat16, device=kv.device)
     lse = torch.empty((B, H, NQ), dtype=torch.float32, device=kv.device) if save_lse else None
-    check(load_library().vj_xattn_fwd(_ptr(q), 0 if shared_q else NQ * D, _ptr(kv), _ptr(resid), _ptr(out), _ptr(lse), B, NQ, N, H,
-                                      hd, float(scale), _stream(stream)), "vj_xattn_fwd")
+    ws, nws = _xattn_ws(B, NQ, N, H, hd, False, kv.device, stream)
+    check(load_library().vj_xattn_fwd_ws(_ptr(q), 0 if shared_q else NQ * D, _ptr(kv), _ptr(resid), _ptr(out), _ptr(lse), B, NQ, N,
+                                         H, hd, float(scale), _ptr(ws), nws, _stream(stream)), "vj_xattn_fwd_ws")
     return out, lse
 
 
 def xattn_bwd(q, kv, dy, lse, B, N, H, hd, scale, shared_q=True, stream=None):
-    """Backward of xattn_fwd for one query per sample: returns dq [B, D] bf16 (per sample) and dkv [B*N, 2*D] bf16."""
+    """Backward of xattn_fwd for one query per sample (vj_xattn_bwd_ws, any N): returns dq [B, D] bf16 (per sample) and
+    dkv [B*N, 2*D] bf16."""
     D = H * hd
     _req(q, torch.bfloat16, "q"); _req(kv, torch.bfloat16, "kv"); _req(dy, torch.bfloat16, "dy")
     dq = torch.empty((B, D), dtype=torch.bfloat16, device=kv.device)
     dkv = torch.empty_like(kv)
-    check(load_library().vj_xattn_bwd(_ptr(q), 0 if shared_q else D, _ptr(kv), _ptr(dy), _ptr(lse), _ptr(dq), _ptr(dkv), B, 1, N, H,
-                                      hd, float(scale), _stream(stream)), "vj_xattn_bwd")
+    ws, nws = _xattn_ws(B, 1, N, H, hd, True, kv.device, stream)
+    check(load_library().vj_xattn_bwd_ws(_ptr(q), 0 if shared_q else D, _ptr(kv), _ptr(dy), _ptr(lse), _ptr(dq), _ptr(dkv), B, 1, N,
+                                         H, hd, float(scale), _ptr(ws), nws, _stream(stream)), "vj_xattn_bwd_ws")
     return dq, dkv
 
 

@@ -25,6 +25,48 @@ class SyntheticClips(torch.utils.data.Dataset):
         return clips, 0, [torch.arange(self.num_frames) for _ in range(self.num_clips)]
 
 
+class SyntheticVideoClassification(torch.utils.data.Dataset):
+    """Seeded labelled clips for the frozen video-classification eval, in the item layout of the reference's VideoDataset
+    under the eval transform (video_dataset.py:156-184, evals/video_classification_frozen/utils.py:172-190):
+    ([S segments] of [V views] of fp32 [3,T,H,W], label, [S] of int64 frame indices).
+
+    Item i depends on (seed, i) alone: its label is uniform in [0, num_classes) and every view is N(0,1) noise plus the
+    pattern of its class.  A class's pattern (a plane wave per channel whose frequency, phase and amplitude are drawn from
+    (pattern_seed, label)) does not depend on `seed`, so splits built with different seeds (training / validation) share
+    their classes and a probe trained on one split can classify the other.  Item and pattern generators are seeded from
+    disjoint ranges."""
+
+    def __init__(self, length, num_classes, frames_per_clip, crop_size, num_segments=1, num_views_per_segment=1,
+                 frame_step=4, seed=0, signal=1.0, pattern_seed=0):
+        self.length, self.num_classes, self.frames, self.crop = length, num_classes, frames_per_clip, crop_size
+        self.S, self.V, self.frame_step, self.seed, self.signal = num_segments, num_views_per_segment, frame_step, seed, signal
+        self.pattern_seed = pattern_seed
+
+    def __len__(self):
+        return self.length
+
+    def _pattern(self, label):
+        g = torch.Generator().manual_seed((1 << 62) + self.pattern_seed * 1_000_003 + label)   # items use seeds < 2^62
+        f = 1.0 + 3.0 * torch.rand(3, 3, generator=g)                  # cycles per clip along (t, h, w), per channel
+        phase = 6.283185307179586 * torch.rand(3, generator=g)
+        amp = self.signal * (0.5 + torch.rand(3, generator=g))
+        t = torch.arange(self.frames, dtype=torch.float32) / self.frames
+        s = torch.arange(self.crop, dtype=torch.float32) / self.crop
+        arg = (f[:, 0, None, None, None] * t[None, :, None, None] + f[:, 1, None, None, None] * s[None, None, :, None]
+               + f[:, 2, None, None, None] * s[None, None, None, :])
+        return amp[:, None, None, None] * torch.cos(6.283185307179586 * arg + phase[:, None, None, None])
+
+    def __getitem__(self, i):
+        g = torch.Generator().manual_seed((self.seed * 1_000_003 + i) % (1 << 62))
+        label = int(torch.randint(0, self.num_classes, (1,), generator=g))
+        pat = self._pattern(label)
+        clips = [[torch.randn(3, self.frames, self.crop, self.crop, generator=g) + pat for _ in range(self.V)]
+                 for _ in range(self.S)]
+        span = self.frames * self.frame_step
+        indices = [torch.arange(s * span, (s + 1) * span, self.frame_step, dtype=torch.int64) for s in range(self.S)]
+        return clips, label, indices
+
+
 def init_data(batch_size, transform=None, shared_transform=None, data='ImageNet', collator=None, pin_mem=True,
               num_workers=8, world_size=1, rank=0, root_path=None, image_folder=None, training=True, copy_data=False,
               drop_last=True, tokenize_txt=True, subset_file=None, clip_len=8, frame_sample_rate=2, duration=None,

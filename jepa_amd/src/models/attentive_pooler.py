@@ -4,6 +4,8 @@ forward and backward run on the gfx950 kernels behind the C ABI (bf16 MFMA GEMMs
 fp32-statistics LayerNorm, transpose-free weight gradients, the few-query cross-attention of csrc/xattn.hip) inside two autograd
 nodes, so `loss.backward()` + any torch optimizer of the reference's eval loop (evals/video_classification_frozen/eval.py:298-352)
 work unchanged.  Parameters stay fp32 nn.Parameters (the reference's layout); every step casts the five matrices to bf16.
+Any number of feature tokens: attend_across_segments feeds all segments at once (36 864 tokens for ViT-H/16-384 K400 16x8x3), and the
+cross-attention runs split-key kernels where one workgroup cannot hold every score (ops.xattn_fwd / xattn_bwd pick the kernel).
 
 What is supported is what the reference's evals instantiate: AttentiveClassifier(embed_dim, num_heads, depth=1, num_classes)
 (eval.py:205-210) -- one query token, complete_block=True, no extra self-attention blocks; other settings raise.

@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """Attentive probe on frozen features (row f4 widened): time of one training step (forward + backward of AttentiveClassifier, no
 optimizer) and of the cross-attention kernels alone, at the reference's eval shape (ViT-L tokens of one 16x224x224 clip per sample).
-python tools/probe_bench.py [--batch 16] [--reps 20]"""
+--tokens N [N ...] times ViT-L (head_dim 64) and ViT-H (head_dim 80) widths at those key counts instead, e.g. the probes of the K400
+16x8x3 evals (8 segments attended across: 12 544 keys at 224, 36 864 at 384) or both sides of the single-workgroup limits
+(forward 38 264, backward 19 132 keys), where the _ws entry points switch to the split-key kernels.
+python tools/probe_bench.py [--batch 16] [--reps 20] [--tokens 12544 36864]"""
 import argparse
 import os
 import sys
@@ -10,6 +13,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from jepa_amd.hip import ops  # noqa: E402
+from jepa_amd.hip.lib import load_library  # noqa: E402
 from jepa_amd.src.models.attentive_pooler import AttentiveClassifier  # noqa: E402
 
 
@@ -29,9 +33,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--tokens", type=int, nargs="*", default=None, help="probe key counts N (default: one clip of ViT-L 224 / ViT-H 384)")
     a = ap.parse_args()
     dev = "cuda"
-    for tag, N, D, H in (("ViT-L 16x224", 1568, 1024, 16), ("ViT-H 16x384", 4608, 1280, 16)):
+    lib = load_library()
+    shapes = (("ViT-L 16x224", 1568, 1024, 16), ("ViT-H 16x384", 4608, 1280, 16)) if not a.tokens else \
+        [(f"{w} N={N}", N, D, 16) for N in a.tokens for w, D in (("ViT-L", 1024), ("ViT-H", 1280))]
+    for tag, N, D, H in shapes:
         B, hd = a.batch, D // H
         torch.manual_seed(0)
         m = AttentiveClassifier(embed_dim=D, num_heads=H, depth=1, num_classes=400).to(dev)
@@ -52,8 +60,13 @@ def main():
         uf = timeit(lambda: ops.xattn_fwd(q, kv, B, 1, N, H, hd, hd ** -0.5), a.reps)
         ub = timeit(lambda: ops.xattn_bwd(q, kv, dy, lse, B, N, H, hd, hd ** -0.5), a.reps)
         byt = B * N * 2 * D * 2.0
-        print(f"{tag}: xattn fwd {uf:7.1f} us = {byt / uf / 1e6:5.2f} TB/s of K+V read once | bwd {ub:7.1f} us = {3 * byt / ub / 1e6:5.2f} TB/s "
-              f"(K, V read twice, dK, dV written)")
+        fs = "split" if lib.vj_xattn_ws_bytes(B, 1, N, H, hd, 0) > 0 else "1-wg"
+        bs = "split" if lib.vj_xattn_ws_bytes(B, 1, N, H, hd, 1) > 0 else "1-wg"
+        # bwd: K+V read once, and the kernel's algorithmic bytes (single workgroup: K, V read twice + dK, dV written = 3x K+V, the
+        # figure this tool printed before the split kernels; split: 2.5x K+V + 16 bytes of p / dP per key and head)
+        alg = 3 * byt if bs == "1-wg" else 2.5 * byt + 16.0 * B * N * H
+        print(f"{tag}: xattn fwd [{fs}] {uf:8.1f} us = {byt / uf / 1e6:5.2f} TB/s of K+V | bwd [{bs}] {ub:8.1f} us = {byt / ub / 1e6:5.2f} "
+              f"TB/s of K+V, {alg / ub / 1e6:5.2f} TB/s algorithmic")
 
 
 if __name__ == "__main__":
