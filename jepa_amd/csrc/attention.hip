@@ -152,7 +152,7 @@ __global__ __launch_bounds__(8 * 64 / QT) void attn_fwd_sm_kernel(const bf16_t* 
     char* v_lds = k_lds + RT::BYTES;
     if (DIST >= 2 && (FAST || t + 1 < nt)) wait_vmcnt<2 * NDMA>();
     else wait_vmcnt<0>();
-    raw_barrier();
+    lgkm_barrier();
     if constexpr (FAST) issue(t + DIST, nxt_off, std::true_type{});
     else if (t + DIST < nt) issue(t + DIST, nxt_off, std::false_type{});
     cur_off = cur_off + BUFB == RINGB ? 0 : cur_off + BUFB;
@@ -408,7 +408,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(const bf16_t* __rest
     // this wave's part of tile t (and the statistics registers of tile t+1) has landed; the barrier publishes every
     // wave's part and the statistics row written an iteration ago, and frees the other buffers
     wait_vmcnt<0>();
-    raw_barrier();
+    lgkm_barrier();
     if (t + 1 < nt) {
       if (tid < 64) {
         stat[((t + 1) & 1) * 128 + tid] = lse_r;
@@ -514,7 +514,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(const bf16_t* __rest
         ck[dt][r] = row16_sum(a);   // over the 16 keys of the lane row (li)
         cv[dt][r] = row16_sum(c);
       }
-    raw_barrier();   // every wave is done with the {Q, dO} images: the first 4 x 2 x HDP floats of the ring become the combine buffer
+    lgkm_barrier();   // every wave is done with the {Q, dO} images: the first 4 x 2 x HDP floats of the ring become the combine buffer
     float* red = (float*)smem;
     if (li == 0) {
 #pragma unroll
@@ -525,7 +525,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(const bf16_t* __rest
           red[(w * 2 + 1) * HDP + dt * 16 + 4 * g + r] = cv[dt][r];
         }
     }
-    raw_barrier();
+    lgkm_barrier();
     if (tid < 2 * HDP) {
       const int which = tid / HDP, d = tid % HDP;
       if (d < hd) {
@@ -662,7 +662,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
     char* v_lds = k_lds + RowTile<HDP>::BYTES;
     if (DIST >= 2 && t + 1 < nt) wait_vmcnt<NDMA2>();
     else wait_vmcnt<0>();
-    raw_barrier();
+    lgkm_barrier();
     if (t + DIST < nt) {
       if ((t + DIST) * 64 + 64 <= S) dma.template issue<true>(kbase, rs, vbase, rs, (t + DIST) * 64, S, smem + nxt_off);
       else dma.template issue<false>(kbase, rs, vbase, rs, (t + DIST) * 64, S, smem + nxt_off);
@@ -759,7 +759,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
         if constexpr (QW == 4) a = a + dqacc[2][dt][r] + dqacc[3][dt][r];
         cq[dt][r] = row16_sum(a);
       }
-    raw_barrier();   // every wave is done with the {K, V} ring: its first 4 x HDP floats become the combine buffer
+    lgkm_barrier();   // every wave is done with the {K, V} ring: its first 4 x HDP floats become the combine buffer
     float* red = (float*)smem;
     if (li == 0) {
 #pragma unroll
@@ -767,7 +767,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
 #pragma unroll
         for (int r = 0; r < 4; r++) red[w * HDP + dt * 16 + 4 * g + r] = cq[dt][r];
     }
-    raw_barrier();
+    lgkm_barrier();
     if (tid < hd) colq[((int64_t)b * nqb + qb) * os + (int64_t)h * hd + tid] =
         (red[tid] + red[HDP + tid] + red[2 * HDP + tid] + red[3 * HDP + tid]) * scale;
   }

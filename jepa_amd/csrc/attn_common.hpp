@@ -1,7 +1,8 @@
 // Shared pieces of the attention kernels (attention.hip: forward + the two-kernel backward; attention_bwd_fused.hip: the one-pass
-// backward of round 6): LDS-DMA helpers, the swizzled row-major tile image, transposed fragment reads, segment tables.
+// backward of round 6): the swizzled row-major tile image, transposed fragment reads, segment tables.
 #pragma once
 #include "common.hpp"
+#include "lds_pipe.hpp"
 #include "options.hpp"
 #include "../../include/vjepa_hip.h"
 #include <type_traits>
@@ -14,33 +15,6 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
   typedef __bf16 bf2_t __attribute__((ext_vector_type(2)));
   bf2_t v = {(__bf16)lo, (__bf16)hi};
   return __builtin_bit_cast(uint32_t, v);
-}
-
-// 16 bytes per lane, global -> LDS, asynchronous (vmcnt).  Issued through inline assembly on purpose: the compiler
-// then does not know that LDS is written behind its back and inserts no conservative `s_waitcnt vmcnt(0)` in front of
-// later LDS reads (it does so for ds_read_b64_tr_b16 after the builtin form, which would collapse the prefetch
-// distance); completion is tracked by hand with wait_vmcnt<N>() + raw_barrier().  lds_base must be wave-uniform: the
-// hardware adds lane * 16.
-__device__ __forceinline__ unsigned lds_addr(const char* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const char*)p;
-}
-__device__ __forceinline__ void dma16(const void* gsrc, unsigned lds_base) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_base), "v"(gsrc) : "memory");
-}
-// the same with a wave-uniform 64-bit base in SGPRs and a 32-bit per-lane byte offset: no 64-bit vector address
-// arithmetic per instruction (the attention kernels are bound by VALU issue)
-__device__ __forceinline__ void dma16_sv(const void* sbase, unsigned voff, unsigned lds_base) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_base), "v"(voff), "s"(sbase) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void raw_barrier() {   // s_barrier without the vmcnt(0) drain of __syncthreads()
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0) only: this wave's LDS reads of the previous tile are complete
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
 }
 
 #define DEFER_LOG2 5.0f  // forward softmax: rescale O only when a row max grows by more than 2^5

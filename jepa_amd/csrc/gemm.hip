@@ -50,11 +50,6 @@ __device__ __forceinline__ void stage_issue(const bf16_t* __restrict__ G, int64_
   }
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N > 0 ? N : 0) : "memory");
-}
-
 // NS = LDS ring depth.  NS == 2 is the classic double buffer (stage t+1 while multiplying t, drain before the
 // barrier).  NS > 2 keeps NS-2 stages of LDS-DMA in flight ACROSS the per-K-tile barrier with a counted
 // s_waitcnt vmcnt (never 0 in steady state) and a raw s_barrier, which is what hides HBM/L2 latency when the
@@ -184,6 +179,21 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float4* __rest
   }
 }
 
+// the split-K tail of every launcher (declared in gemm_common.hpp)
+void vj_splitk_finish_plan(int nk, int& splitk, int& ktiles_per) {
+  ktiles_per = (nk + splitk - 1) / splitk;
+  splitk = (nk + ktiles_per - 1) / ktiles_per;   // no empty slices
+}
+int vj_splitk_reduce(const GemmArgs& b, hipStream_t stream) {
+  if (b.splitk <= 1) return 0;
+  int64_t g = cdiv64(b.M * b.N / 4, 256);
+  if (g > 256 * 8) g = 256 * 8;
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, stream, (const float4*)b.ws, (float*)b.C, b.M, b.N,
+                     b.ldc, b.splitk, b.alpha, b.beta);
+  VJ_LAUNCH_CHECK("vj_gemm_bf16(split-K reduce)");
+  return 0;
+}
+
 template <int BK, int NS, int EPI, int BM, int BN, int WM, int WN>
 static int launch_gemm(const GemmArgs& a, void* ws, int64_t ws_bytes, hipStream_t stream) {
   constexpr int smem = NS * (BM + BN) * BK * 2;
@@ -209,21 +219,12 @@ static int launch_gemm(const GemmArgs& a, void* ws, int64_t ws_bytes, hipStream_
     b.splitk = pick_splitk(tiles, nk, slots, us_kt, 8, a.M, a.N, ws_bytes);
     b.ws = (float*)ws;
   }
-  b.ktiles_per = (nk + b.splitk - 1) / b.splitk;
-  b.splitk = (nk + b.ktiles_per - 1) / b.ktiles_per;  // no empty slices
+  vj_splitk_finish_plan(nk, b.splitk, b.ktiles_per);
   const int nblk = b.tiles_m * b.tiles_n * b.splitk;
   hipLaunchKernelGGL((gemm_nt_kernel<BK, NS, EPI, BM, BN, WM, WN>), dim3(nblk), dim3(WM * WN * 64), smem, stream,
                      b);
   VJ_LAUNCH_CHECK("vj_gemm_bf16_nt");
-  if (b.splitk > 1) {
-    const int64_t n4 = a.M * a.N / 4;
-    int64_t g = cdiv64(n4, 256);
-    if (g > 256 * 8) g = 256 * 8;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, stream, (const float4*)b.ws,
-                       (float*)a.C, a.M, a.N, a.ldc, b.splitk, a.alpha, a.beta);
-    VJ_LAUNCH_CHECK("vj_gemm_bf16_nt(splitk reduce)");
-  }
-  return 0;
+  return vj_splitk_reduce(b, stream);
 }
 
 // flags: bits 4-5 = tile config (0 auto, 1 = 128x128, 2 = 256x256); bits 6-7 = pipeline (0 auto, 1 = BK64 double buffer, 2 = BK32 4-stage
@@ -232,13 +233,26 @@ static int launch_gemm(const GemmArgs& a, void* ws, int64_t ws_bytes, hipStream_
 //        the 4-wave kernel existed through round 5; all measured slower in the step: profiles/r03_abab_switches.md, r05_gemm_4wp.md.)
 int vj_gemm_launch_8phase(const GemmArgs& a, int epilogue, void* ws, int64_t ws_bytes, hipStream_t stream);  // gemm8.hip
 int vj_gemm_launch_4w(const GemmArgs& a, int epilogue, void* ws, int64_t ws_bytes, hipStream_t stream);      // gemm4w.hip
-int vj_gemm_launch_8phase_persist(const GemmArgs& a, int epilogue, hipStream_t stream);                        // gemm8p.hip (-100: n/a)
+int vj_gemm_launch_8phase_persist(const GemmArgs& a, int epilogue, hipStream_t stream);                        // gemm8p.hip (VJ_PERSIST_NA: n/a)
+
+extern "C" int64_t vj_gemm_colsum_rows(int64_t M) { return 2 * cdiv64(M, 256); }   // rows of colpart: (row tile, wave row) slots
+
+// vj_gemm_bf16_nt_dgelu_colsum's request: column sums of the output into colpart[rows][N] IF the persistent kernel takes the problem
+struct ColsumReq {
+  float* colpart;
+  int64_t rows;
+  int* fused;   // out: 1 when the sums were written
+};
+
+// the automatic selection hands a problem to the 256x256 8-phase kernels (gemm8p.hip / gemm8.hip) from this many 256x256 tiles on
+constexpr int64_t AUTO_256_MIN_TILES = 90, AUTO_256_MIN_TILES_WGRAD = 40;
 
 template <int EPI>
-static int dispatch_gemm(const GemmArgs& a, int flags, void* ws, int64_t ws_bytes, hipStream_t stream) {   // (flags: by value, edited below)
+static int dispatch_gemm(GemmArgs a, int flags, void* ws, int64_t ws_bytes, hipStream_t stream, const ColsumReq* cs) {   // (a, flags: by value, edited below)
   int cfg = (flags >> 4) & 3;
   int pipe = (flags >> 6) & 3;
   const bool is_wgrad = (EPI == EPI_F32 && ws != nullptr);
+  bool auto_256 = false;
   if (a.lnf_rs != nullptr) flags &= ~0x100;   // the 4-wave kernel carries no folded-LayerNorm epilogue
   // bit 8: the 4-wave 256x128 kernel with two workgroups per CU (gemm4w.hip)
   if ((flags & 0x100) && a.K % 64 == 0) return vj_gemm_launch_4w(a, EPI, ws, ws_bytes, stream);
@@ -256,8 +270,9 @@ static int dispatch_gemm(const GemmArgs& a, int flags, void* ws, int64_t ws_byte
     const int use_4w = a.lnf_rs != nullptr ? 0 : vj_opt(VJ_OPT_GEMM_4W);
     if (use_4w == 1 && !is_wgrad && a.K % 64 == 0 && t4w >= 64) return vj_gemm_launch_4w(a, EPI, ws, ws_bytes, stream);
     const int64_t t256 = cdiv64(a.M, 256) * cdiv64(a.N, 256);
-    if (!is_wgrad && a.K % 64 == 0 && t256 >= 90) pipe = 3;
-    if (is_wgrad && a.K % 64 == 0 && t256 >= 40) pipe = 3;   // qkv/fc1/fc2 wgrads: 8-phase + split-K (0.97-1.08 vs 0.78-0.96 PF)
+    // (qkv/fc1/fc2 wgrads: 8-phase + split-K, 0.97-1.08 vs 0.78-0.96 PF)
+    auto_256 = a.K % 64 == 0 && t256 >= (is_wgrad ? AUTO_256_MIN_TILES_WGRAD : AUTO_256_MIN_TILES);
+    if (auto_256) pipe = 3;
   }
   if (cfg == 0) cfg = 1;
   if (pipe == 0) pipe = 1;       // BK64 double buffer (beats the BK32 ring on every step shape)
@@ -266,8 +281,20 @@ static int dispatch_gemm(const GemmArgs& a, int flags, void* ws, int64_t ws_byte
     // persistent variant (gemm8p.hip): one workgroup per CU walks its tiles, next tile's operands prefetched under the
     // current tile, epilogue stores drained under the next K loop; bit-identical outputs.  Run-time option "gemm_persist".
     if (EPI != EPI_F32 && vj_opt(VJ_OPT_GEMM_PERSIST) != 0 && !(a.dbg & 2)) {
+      // fused column sums: only where the automatic selection itself picked this kernel (no flags, no 4-wave or diagnostic option)
+      if (EPI == EPI_DGELU && cs != nullptr && cs->colpart != nullptr && auto_256 && flags == 0 && vj_opt(VJ_OPT_GEMM_4W) == 0 && a.dbg == 0) {
+        VJ_CHECK_ARG(cs->rows >= vj_gemm_colsum_rows(a.M), "vj_gemm_bf16_nt_dgelu_colsum: colpart has %ld rows, needs %ld", (long)cs->rows,
+                     (long)vj_gemm_colsum_rows(a.M));
+        a.colpart = cs->colpart;
+        const int rc = vj_gemm_launch_8phase_persist(a, EPI, stream);
+        if (rc != VJ_PERSIST_NA) {
+          *cs->fused = (rc == 0);
+          return rc;
+        }
+        a.colpart = nullptr;   // declined (aliasing operands, N % 8, a misaligned colpart): the plain GEMM, the caller sums C itself
+      }
       const int rc = vj_gemm_launch_8phase_persist(a, EPI, stream);
-      if (rc != -100) return rc;
+      if (rc != VJ_PERSIST_NA) return rc;
     }
     if (a.lnf_rs == nullptr) return vj_gemm_launch_8phase(a, EPI, ws, ws_bytes, stream);
     pipe = 1;   // folded LayerNorm: only the persistent kernel and the generic kernels below carry that epilogue
@@ -284,7 +311,8 @@ static int dispatch_gemm(const GemmArgs& a, int flags, void* ws, int64_t ws_byte
 static int gemm_entry(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M,
                       int64_t N, int64_t K, const float* bias, const void* residual, int64_t ldr, const void* aux_in,
                       void* aux_out, int64_t ldaux, int epilogue, float alpha, float beta, int flags, void* ws,
-                      int64_t ws_bytes, hipStream_t stream, const float* lnf_rs = nullptr, const float* lnf_c = nullptr) {
+                      int64_t ws_bytes, hipStream_t stream, const float* lnf_rs = nullptr, const float* lnf_c = nullptr,
+                      const ColsumReq* cs = nullptr) {
   VJ_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "vj_gemm_bf16_nt: negative dim");
   if (M == 0 || N == 0) return 0;
   VJ_CHECK_ARG(K > 0 && K % 32 == 0, "vj_gemm_bf16_nt: K=%ld must be a positive multiple of 32 (pad the operands)", (long)K);
@@ -309,21 +337,14 @@ static int gemm_entry(const void* A, int64_t lda, const void* B, int64_t ldb, vo
   a.aux_in = (const bf16_t*)aux_in; a.aux_out = (bf16_t*)aux_out;
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldr = ldr; a.ldaux = ldaux;
   a.alpha = alpha; a.beta = beta;
-  a.tiles_m = a.tiles_n = 0; a.splitk = 1; a.ktiles_per = 0; a.ws = nullptr;
   a.dbg = vj_opt(VJ_OPT_GEMM_DBG);
-  a.zero_row = nullptr;
-  a.colpart = nullptr;
-  a.raster = 0;
   a.lnf_rs = lnf_rs;
   a.lnf_c = lnf_c;
   a.qscale = qscale;
   a.qcols = qscale != 0.f ? N / 3 : 0;
-  switch (epilogue) {
-    case EPI_BF16: return dispatch_gemm<EPI_BF16>(a, flags, nullptr, 0, stream);
-    case EPI_GELU: return dispatch_gemm<EPI_GELU>(a, flags, nullptr, 0, stream);
-    case EPI_DGELU: return dispatch_gemm<EPI_DGELU>(a, flags, nullptr, 0, stream);
-    default: return dispatch_gemm<EPI_F32>(a, flags, ws, ws_bytes, stream);
-  }
+  return with_epilogue(epilogue, ws, ws_bytes, [&](auto epi, void* w, int64_t wb) {
+    return dispatch_gemm<decltype(epi)::value>(a, flags, w, wb, stream, cs);
+  });
 }
 
 extern "C" int vj_gemm_bf16_nt(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
@@ -355,44 +376,15 @@ extern "C" int vj_gemm_bf16_nt_lnfold(const void* X, int64_t ldx, const void* Wf
 // takes the problem, colpart[2 * cdiv(M,256)][N] = per-(row tile, wave row) fp32 column sums of C before the bf16 rounding
 // (*fused = 1; reduce them with vj_reduce_segments).  Otherwise the plain GEMM runs and *fused = 0 (the caller sums C itself).
 // C is bit-identical to vj_gemm_bf16_nt's either way.  Replaces: autograd of Mlp.fc1's bias (modules.py:31-34).
-extern "C" int64_t vj_gemm_colsum_rows(int64_t M) { return 2 * cdiv64(M, 256); }
-
 extern "C" int vj_gemm_bf16_nt_dgelu_colsum(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
                                             int64_t M, int64_t N, int64_t K, const void* aux_in, int64_t ldaux,
                                             float* colpart, int64_t colpart_rows, int flags, int* fused,
                                             hipStream_t stream) {
   VJ_CHECK_ARG(fused != nullptr, "vj_gemm_bf16_nt_dgelu_colsum: null `fused`");
   *fused = 0;
-  const int64_t t256 = cdiv64(M, 256) * cdiv64(N, 256);
-  if (colpart != nullptr && flags == 0 && M > 0 && N > 0 && K > 0 && K % 64 == 0 && t256 >= 90 && vj_opt(VJ_OPT_GEMM_4W) == 0 &&
-      vj_opt(VJ_OPT_GEMM_PERSIST) != 0 && vj_opt(VJ_OPT_GEMM_DBG) == 0 && aux_in != nullptr && lda % 8 == 0 && ldb % 8 == 0 &&
-      lda >= K && ldb >= K && ((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && ldc % 4 == 0 && ldc >= N &&
-      ldaux % 4 == 0 && N % 4 == 0 && (uintptr_t)C % 8 == 0) {
-    // the same kernel the automatic selection of vj_gemm_bf16_nt picks for this shape (>= 90 tiles of 256 x 256, K % 64 == 0)
-    VJ_CHECK_ARG(colpart_rows >= vj_gemm_colsum_rows(M), "vj_gemm_bf16_nt_dgelu_colsum: colpart has %ld rows, needs %ld",
-                 (long)colpart_rows, (long)vj_gemm_colsum_rows(M));
-    GemmArgs a;
-    a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = C; a.bias = nullptr; a.res = nullptr;
-    a.aux_in = (const bf16_t*)aux_in; a.aux_out = nullptr;
-    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldr = 0; a.ldaux = ldaux;
-    a.alpha = 1.0f; a.beta = 0.0f;
-    a.tiles_m = a.tiles_n = 0; a.splitk = 1; a.ktiles_per = 0; a.ws = nullptr;
-    a.dbg = 0;
-    a.zero_row = nullptr;
-    a.qscale = 0.f;
-    a.qcols = 0;
-    a.colpart = colpart;
-    a.raster = 0;
-    a.lnf_rs = nullptr;
-    a.lnf_c = nullptr;
-    const int rc = vj_gemm_launch_8phase_persist(a, EPI_DGELU, stream);
-    if (rc != -100) {
-      *fused = (rc == 0);
-      return rc;
-    }
-  }
+  const ColsumReq cs = {colpart, colpart_rows, fused};
   return gemm_entry(A, lda, B, ldb, C, ldc, M, N, K, nullptr, nullptr, 0, aux_in, nullptr, ldaux, EPI_DGELU, 1.0f, 0.0f, flags,
-                    nullptr, 0, stream);
+                    nullptr, 0, stream, nullptr, nullptr, &cs);
 }
 
 // wgrad form: C (fp32) = alpha * A B^T + beta * C with the long K (= tokens) dimension split across workgroups

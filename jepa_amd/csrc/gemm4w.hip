@@ -26,22 +26,13 @@
 #define W4_BM 256
 #define W4_BN 128
 #define W4_BK 64
-#define W4_PART 16384
 #define W4_SLOTS 5
-
-__device__ __forceinline__ void bar4() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::: "memory");
-}
 
 // wait until at most `parts` younger parts (4 DMA instructions each) are still in flight
 __device__ __forceinline__ void wait_parts(int parts) {
-  if (parts >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else if (parts == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (parts >= 2) wait_vmcnt<8>();
+  else if (parts == 1) wait_vmcnt<4>();
+  else wait_vmcnt<0>();
 }
 
 // part index p: -1 = A0(0);  3T = B(T), 3T+1 = A1(T), 3T+2 = A0(T+1).  Slot (p+5) % 5: part p+5 overwrites part p, and
@@ -49,19 +40,12 @@ __device__ __forceinline__ void wait_parts(int parts) {
 // A part is 128 rows x 128 bytes = 1024 16-byte chunks; thread `tid` moves chunks tid, tid+256, tid+512, tid+768, i.e.
 // rows r0, r0+32, r0+64, r0+96 (r0 = tid >> 3) at the same (swizzled) chunk column.  Interior tiles address them as
 // WAVE-UNIFORM row-group base (SGPR pair, fixed for the whole K loop) + one 32-bit per-thread byte offset
-// (row r0, swizzled chunk, + 128 bytes per K-tile): the saddr form of global_load_lds_dwordx4.  No 64-bit VALU address
-// arithmetic and two address VGPRs in total; issued through inline assembly so that the compiler, which cannot see
-// that LDS is written behind its back, also adds no vmcnt(0) of its own in front of later LDS reads.
+// (row r0, swizzled chunk, + 128 bytes per K-tile): the saddr form of global_load_lds_dwordx4 (dma16_sv, lds_pipe.hpp).  No
+// 64-bit VALU address arithmetic and two address VGPRs in total.
 struct PartBase {
   const char* a[8];   // A0 chunks j = 0..3 (wave row j >> 1, rows +32 (j & 1)), then the same for A1 (+64 rows)
   const char* b[4];   // B chunks j = 0..3 (rows +32 j)
 };
-__device__ __forceinline__ unsigned lds_addr4(const char* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const char*)p;
-}
-__device__ __forceinline__ void dma16_s(const char* sbase, unsigned voff, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_dst), "v"(voff), "s"(sbase) : "memory");
-}
 
 // interior tiles: all 256 x 128 rows exist.  kind 0: A0, 1: B, 2: A1.  voff already includes the K-tile's 128 bytes.
 template <int KIND>
@@ -69,7 +53,7 @@ __device__ __forceinline__ void issue_fast(const PartBase& s, unsigned voff, uns
 #pragma unroll
   for (int j = 0; j < 4; j++) {
     const char* base = KIND == 1 ? s.b[j] : s.a[(KIND == 2 ? 4 : 0) + j];
-    dma16_s(base, voff, lds_slot + j * 4096 + wave_u * 1024);   // chunk (j * 256 + wave * 64 + lane) * 16 bytes
+    dma16_sv(base, voff, lds_slot + j * 4096 + wave_u * 1024);   // chunk (j * 256 + wave * 64 + lane) * 16 bytes
   }
 }
 
@@ -131,12 +115,12 @@ __device__ __forceinline__ void k_loop_4w(const GemmArgs& p, char* smem, f32x4_t
       src.b[j] = b0 + (j * 32) * p.ldb * 2;
     }
   }
-  const unsigned lds0 = lds_addr4(smem);
+  const unsigned lds0 = lds_addr(smem);
   // kind: 0 A0, 1 B, 2 A1 ; tile = its K-tile ; sl = its ring slot
   auto issue = [&](auto kind_tag, int tile, int sl) {
     constexpr int KIND = decltype(kind_tag)::value;
-    if constexpr (EDGE) issue_edge(p, KIND, tile, m0, n0, kt0, smem + sl * W4_PART, tid, wave_u);
-    else issue_fast<KIND>(src, (KIND == 1 ? voff_b : voff_a) + (unsigned)tile * 128u, lds0 + sl * W4_PART, wave_u);
+    if constexpr (EDGE) issue_edge(p, KIND, tile, m0, n0, kt0, smem + sl * LDS_PART_BYTES, tid, wave_u);
+    else issue_fast<KIND>(src, (KIND == 1 ? voff_b : voff_a) + (unsigned)tile * 128u, lds0 + sl * LDS_PART_BYTES, wave_u);
   };
   using K0 = std::integral_constant<int, 0>;
   using K1 = std::integral_constant<int, 1>;
@@ -157,9 +141,9 @@ __device__ __forceinline__ void k_loop_4w(const GemmArgs& p, char* smem, f32x4_t
   issue_if(0, K1{}, 0, 0);
   issue_if(1, K2{}, 0, 1);
   wait_for(0);
-  bar4();
+  section_barrier();
   {
-    const char* slot = smem + 4 * W4_PART;
+    const char* slot = smem + 4 * LDS_PART_BYTES;
 #pragma unroll
     for (int i = 0; i < 4; i++)
 #pragma unroll
@@ -195,31 +179,31 @@ __device__ __forceinline__ void k_loop_4w(const GemmArgs& p, char* smem, f32x4_t
     const int pb = 3 * t;
     // ---------------- phase 0: rb0 <- B(t); part +3 = B(t+1)
     {
-      const char* slot = smem + s0 * W4_PART;
+      const char* slot = smem + s0 * LDS_PART_BYTES;
 #pragma unroll
       for (int j = 0; j < 2; j++)
 #pragma unroll
         for (int ks = 0; ks < 2; ks++) rb0[j][ks] = *(const bf16x8_t*)(slot + b_base[ks] + j * 2048);
       if constexpr (TAIL) issue_if(pb + 3, K1{}, t + 1, slot_of(3));
       else issue(K1{}, t + 1, slot_of(3));
-      bar4();
+      section_barrier();
       mma(Q00{}, rb0, ra0);
     }
     // ---------------- phase 1: rb1 <- B(t); A1(t) must land
     {
-      const char* slot = smem + s0 * W4_PART;
+      const char* slot = smem + s0 * LDS_PART_BYTES;
 #pragma unroll
       for (int j = 0; j < 2; j++)
 #pragma unroll
         for (int ks = 0; ks < 2; ks++) rb1[j][ks] = *(const bf16x8_t*)(slot + b_base[ks] + (2 + j) * 2048);
       if constexpr (TAIL) wait_for(pb + 1);
       else wait_parts(2);
-      bar4();
+      section_barrier();
       mma(Q01{}, rb1, ra0);
     }
     // ---------------- phase 2: ra1 <- A1(t); part +3 = A1(t+1); A0(t+1) must land
     {
-      const char* slot = smem + slot_of(1) * W4_PART;
+      const char* slot = smem + slot_of(1) * LDS_PART_BYTES;
 #pragma unroll
       for (int i = 0; i < 4; i++)
 #pragma unroll
@@ -231,13 +215,13 @@ __device__ __forceinline__ void k_loop_4w(const GemmArgs& p, char* smem, f32x4_t
         issue(K2{}, t + 1, slot_of(4));
         wait_parts(2);
       }
-      bar4();
+      section_barrier();
       mma(Q11{}, rb1, ra1);
     }
     // ---------------- phase 3: ra0 <- A0(t+1); part +3 = A0(t+2); B(t+1) must land
     {
       if (!TAIL || t + 1 < nk) {
-        const char* slot = smem + slot_of(2) * W4_PART;
+        const char* slot = smem + slot_of(2) * LDS_PART_BYTES;
 #pragma unroll
         for (int i = 0; i < 4; i++)
 #pragma unroll
@@ -250,7 +234,7 @@ __device__ __forceinline__ void k_loop_4w(const GemmArgs& p, char* smem, f32x4_t
         issue(K0{}, t + 2, slot_of(5));
         wait_parts(2);
       }
-      bar4();
+      section_barrier();
       mma(Q10{}, rb0, ra1);
     }
     s0 = slot_of(3);
@@ -259,8 +243,8 @@ __device__ __forceinline__ void k_loop_4w(const GemmArgs& p, char* smem, f32x4_t
   for (; t < nk - 2; t++) k_tile(t, std::false_type{});
   if (nk >= 3) issued = 3 * nk - 4;   // what the steady state left in flight: parts up to 3(nk-3)+5
   for (; t < nk; t++) k_tile(t, std::true_type{});
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  bar4();   // every wave is past its last LDS read and every DMA has landed: the ring is free, 16 KB of it per wave
+  wait_vmcnt<0>();
+  section_barrier();   // every wave is past its last LDS read and every DMA has landed: the ring is free, 16 KB of it per wave
 }
 
 template <int EPI>
@@ -304,12 +288,9 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_4w_kernel(GemmArgs p) {
 // (A persistent form of this kernel -- two workgroups per CU walking tile lists -- was built in round 5: bit-identical, slower on every
 //  shape and policy, profiles/r05_gemm_4wp.md.)
 
-__global__ void splitk_reduce_kernel(const float4* ws, float* out, int64_t M, int64_t N, int64_t ldc, int S,
-                                     float alpha, float beta);   // gemm.hip
-
 template <int EPI>
 static int launch4w(const GemmArgs& a, void* ws, int64_t ws_bytes, hipStream_t stream) {
-  constexpr int smem = W4_SLOTS * W4_PART;
+  constexpr int smem = W4_SLOTS * LDS_PART_BYTES;
   static VjPerDeviceOnce attr_once;   // the dynamic-LDS limit is a per-device attribute of the function
   attr_once([] {
     (void)hipFuncSetAttribute((const void*)gemm_nt_4w_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
@@ -334,26 +315,12 @@ static int launch4w(const GemmArgs& a, void* ws, int64_t ws_bytes, hipStream_t s
     b.splitk = pick_splitk(tiles, nk, 512, 1.45, 8, a.M, a.N, ws_bytes);
     b.ws = (float*)ws;
   }
-  b.ktiles_per = (nk + b.splitk - 1) / b.splitk;
-  b.splitk = (nk + b.ktiles_per - 1) / b.ktiles_per;
+  vj_splitk_finish_plan(nk, b.splitk, b.ktiles_per);
   hipLaunchKernelGGL(gemm_nt_4w_kernel<EPI>, dim3(b.tiles_m * b.tiles_n * b.splitk), dim3(256), smem, stream, b);
   VJ_LAUNCH_CHECK("vj_gemm_bf16_nt(4-wave)");
-  if (b.splitk > 1) {
-    const int64_t n4 = a.M * a.N / 4;
-    int64_t g = cdiv64(n4, 256);
-    if (g > 256 * 8) g = 256 * 8;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, stream, (const float4*)b.ws,
-                       (float*)a.C, a.M, a.N, a.ldc, b.splitk, a.alpha, a.beta);
-    VJ_LAUNCH_CHECK("vj_gemm_bf16_nt(4-wave splitk reduce)");
-  }
-  return 0;
+  return vj_splitk_reduce(b, stream);
 }
 
 int vj_gemm_launch_4w(const GemmArgs& a, int epilogue, void* ws, int64_t ws_bytes, hipStream_t stream) {
-  switch (epilogue) {
-    case EPI_BF16: return launch4w<EPI_BF16>(a, nullptr, 0, stream);
-    case EPI_GELU: return launch4w<EPI_GELU>(a, nullptr, 0, stream);
-    case EPI_DGELU: return launch4w<EPI_DGELU>(a, nullptr, 0, stream);
-    default: return launch4w<EPI_F32>(a, ws, ws_bytes, stream);
-  }
+  return with_epilogue(epilogue, ws, ws_bytes, [&](auto epi, void* w, int64_t wb) { return launch4w<decltype(epi)::value>(a, w, wb, stream); });
 }

@@ -18,37 +18,6 @@
 #define P8_BM 256
 #define P8_BN 256
 #define P8_BK 64
-#define PART_BYTES 16384
-
-__device__ __forceinline__ void cfence() { asm volatile("" ::: "memory"); }
-
-__device__ __forceinline__ void bar() {
-  cfence();
-  __builtin_amdgcn_sched_barrier(0);   // nothing (MFMA, ds_read, DMA issue) may be scheduled across a section boundary
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-  cfence();
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-// LDS-DMA through inline assembly (both addressing forms): the compiler then neither tracks these loads in its own
-// vmcnt bookkeeping nor assumes LDS was written, so the only waits in the K loop are the counted ones placed by hand.
-__device__ __forceinline__ unsigned lds_addr8(const char* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const char*)p;
-}
-__device__ __forceinline__ void dma16_v(const void* gsrc, unsigned lds_dst) {   // 64-bit per-lane address
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_dst), "v"(gsrc) : "memory");
-}
-__device__ __forceinline__ void dma16_sv(const char* sbase, unsigned voff, unsigned lds_dst) {   // SGPR base + 32-bit lane offset
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_dst), "v"(voff), "s"(sbase) : "memory");
-}
 
 // Interior tiles (all 256 x 256 rows exist): a part's two chunks per thread are rows r0 and r0 + 64 of the part at the
 // same swizzled chunk column, so their addresses are a WAVE-UNIFORM base per (operand, sub-part, j) -- fixed for the
@@ -69,7 +38,7 @@ __device__ __forceinline__ void issue_part(const GemmArgs& p, const PartBase8& p
   const int qq = q + 1;
   const int kind = qq & 3;
   const int t = qq >> 2;
-  const unsigned slot = lds_addr8(smem) + ((q + 8) & 7) * PART_BYTES;
+  const unsigned slot = lds_addr(smem) + ((q + 8) & 7) * LDS_PART_BYTES;
   const bool isA = (kind == 0) || (kind == 3);
   const int sub = (kind == 0) ? 0 : (kind == 3 ? 1 : kind - 1);  // mq for A parts, nq for B parts
   if constexpr (!EDGE) {
@@ -164,29 +133,29 @@ __device__ __forceinline__ void gemm8_body(const GemmArgs& p, char* smem, int tm
 #pragma unroll
   for (int q = 0; q < 3; q++)
     if (q <= last_part) issue_part<EDGE>(p, pb, q, m0, n0, kt0, smem, tid, wave_u);
-  if (last_part >= 2) wait_vm<6>();
-  else wait_vm<0>();
-  bar();
-  if (late_group) bar();
+  if (last_part >= 2) wait_vmcnt<6>();
+  else wait_vmcnt<0>();
+  section_barrier();
+  if (late_group) section_barrier();
   // L(-1): A0 fragments of tile 0; issue part 3; part 0 must have landed before the next barrier
   {
-    const char* slot = smem + 7 * PART_BYTES;   // (-1 + 8) % 8
+    const char* slot = smem + 7 * LDS_PART_BYTES;   // (-1 + 8) % 8
 #pragma unroll
     for (int i = 0; i < 4; i++)
 #pragma unroll
       for (int ks = 0; ks < 2; ks++) ra0[i][ks] = *(const bf16x8_t*)(slot + a_off[i][ks]);
     if (3 <= last_part) issue_part<EDGE>(p, pb, 3, m0, n0, kt0, smem, tid, wave_u);
-    if (3 <= last_part) wait_vm<6>();
-    else wait_vm<0>();
+    if (3 <= last_part) wait_vmcnt<6>();
+    else wait_vmcnt<0>();
   }
-  bar();
-  bar();
+  section_barrier();
+  section_barrier();
 
   for (int t = 0; t < nk; t++) {
 #pragma unroll
     for (int ph = 0; ph < 4; ph++) {
       const int q = 4 * t + ph;
-      const char* slot = smem + (q & 7) * PART_BYTES;
+      const char* slot = smem + (q & 7) * LDS_PART_BYTES;
       // ---------------- L(q)
 #ifdef VJ_GEMM8_SKIP_READS   // timing experiment (A/B build `python -m jepa_amd.build skipreads -DVJ_GEMM8_SKIP_READS`): after the
       if (t > 0) {          // first K-tile the fragment reads are skipped -- WRONG results, same MFMA operands forever -- which
@@ -215,14 +184,14 @@ __device__ __forceinline__ void gemm8_body(const GemmArgs& p, char* smem, int tm
       }
       if (q + 4 <= last_part) {
         issue_part<EDGE>(p, pb, q + 4, m0, n0, kt0, smem, tid, wave_u);
-        wait_vm<6>();                              // part q+1 landed; q+2..q+4 in flight
+        wait_vmcnt<6>();                              // part q+1 landed; q+2..q+4 in flight
       } else {                                     // tail: fewer younger parts behind part q+1
         const int younger = last_part - (q + 1);
-        if (younger >= 2) wait_vm<4>();
-        else if (younger == 1) wait_vm<2>();
-        else wait_vm<0>();
+        if (younger >= 2) wait_vmcnt<4>();
+        else if (younger == 1) wait_vmcnt<2>();
+        else wait_vmcnt<0>();
       }
-      bar();
+      section_barrier();
       // ---------------- C(q): one quadrant x K = 64
       __builtin_amdgcn_s_setprio(1);
       if (ph == 0) {
@@ -260,10 +229,10 @@ __device__ __forceinline__ void gemm8_body(const GemmArgs& p, char* smem, int tm
               acc[4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rb0[j][ks], ra1[i][ks], acc[4 + i][j], 0, 0, 0);
       }
       __builtin_amdgcn_s_setprio(0);
-      bar();
+      section_barrier();
     }
   }
-  if (!late_group) bar();   // the early group matches the late group's extra barrier
+  if (!late_group) section_barrier();   // the early group matches the late group's extra barrier
   if (p.dbg & 1) {   // diagnostics: no output traffic (keeps the accumulators alive through one predicated store)
     if (acc[0][0][0] == 12345.678f && acc[7][3][3] == 0.5f) *(float*)p.C = acc[3][2][1];
     return;
@@ -295,12 +264,9 @@ __global__ __launch_bounds__(512) void gemm_nt_8phase_kernel(GemmArgs p) {
   else gemm8_body<EPI, true>(p, smem, tm, tn, slice);
 }
 
-__global__ void splitk_reduce_kernel(const float4* ws, float* out, int64_t M, int64_t N, int64_t ldc, int S,
-                                     float alpha, float beta);   // gemm.hip
-
 template <int EPI>
 static int launch8(const GemmArgs& a, void* ws, int64_t ws_bytes, hipStream_t stream) {
-  constexpr int smem = 8 * PART_BYTES;
+  constexpr int smem = 8 * LDS_PART_BYTES;
   // function-local static with an initialiser: set exactly once, thread-safe (the C ABI is re-entrant)
   static VjPerDeviceOnce attr_once;   // the dynamic-LDS limit is a per-device attribute of the function
   attr_once([] {
@@ -317,27 +283,13 @@ static int launch8(const GemmArgs& a, void* ws, int64_t ws_bytes, hipStream_t st
     b.splitk = pick_splitk(tiles, nk, 256, 1.45, 8, a.M, a.N, ws_bytes);
     b.ws = (float*)ws;
   }
-  b.ktiles_per = (nk + b.splitk - 1) / b.splitk;
-  b.splitk = (nk + b.ktiles_per - 1) / b.ktiles_per;
+  vj_splitk_finish_plan(nk, b.splitk, b.ktiles_per);
   hipLaunchKernelGGL(gemm_nt_8phase_kernel<EPI>, dim3(b.tiles_m * b.tiles_n * b.splitk), dim3(512), smem, stream, b);
   VJ_LAUNCH_CHECK("vj_gemm_bf16_nt(8-phase)");
-  if (b.splitk > 1) {
-    const int64_t n4 = a.M * a.N / 4;
-    int64_t g = cdiv64(n4, 256);
-    if (g > 256 * 8) g = 256 * 8;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, stream, (const float4*)b.ws,
-                       (float*)a.C, a.M, a.N, a.ldc, b.splitk, a.alpha, a.beta);
-    VJ_LAUNCH_CHECK("vj_gemm_bf16_nt(8-phase splitk reduce)");
-  }
-  return 0;
+  return vj_splitk_reduce(b, stream);
 }
 
 // entry used by gemm.hip's dispatcher (pipeline 3); requires K % 64 == 0
 int vj_gemm_launch_8phase(const GemmArgs& a, int epilogue, void* ws, int64_t ws_bytes, hipStream_t stream) {
-  switch (epilogue) {
-    case EPI_BF16: return launch8<EPI_BF16>(a, nullptr, 0, stream);
-    case EPI_GELU: return launch8<EPI_GELU>(a, nullptr, 0, stream);
-    case EPI_DGELU: return launch8<EPI_DGELU>(a, nullptr, 0, stream);
-    default: return launch8<EPI_F32>(a, ws, ws_bytes, stream);
-  }
+  return with_epilogue(epilogue, ws, ws_bytes, [&](auto epi, void* w, int64_t wb) { return launch8<decltype(epi)::value>(a, w, wb, stream); });
 }

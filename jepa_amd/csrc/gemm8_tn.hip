@@ -17,15 +17,13 @@
 //   * a fragment = two transpose reads (token rows 4g..4g+3 and 16+4g..16+4g+3 of a 32-token step).  The k-slot ->
 //     token map differs from a plain row read but is the same for both operands, which is all a dot product needs;
 //   * tokens beyond T (last K-tile) contribute zero: dY rows are redirected to a zero row (X rows re-read row T-1);
-//   * the LDS-DMA is issued through inline assembly so that the compiler does not put an `s_waitcnt vmcnt(0)` in front
-//     of the transpose reads (it does after the builtin form; see attention.hip).
+//   * the LDS-DMA is issued through inline assembly (lds_pipe.hpp): after the builtin form the compiler puts an
+//     `s_waitcnt vmcnt(0)` in front of the transpose reads.
 //
 // Split-K over the token tiles and the fp32 epilogue are shared with the NT kernels (gemm_common.hpp).
 #include <type_traits>
 #include "gemm_common.hpp"
 #include "options.hpp"
-
-#define TN_PART_BYTES 16384
 
 namespace {
 
@@ -34,25 +32,6 @@ namespace {
 // (the round-4 host-allocated buffer took a global mutex per launch and a device-wide synchronise on first use, which would
 // have invalidated a stream capture in progress).
 __device__ __attribute__((aligned(256))) bf16_t g_tn_zero_row[128];
-
-__device__ __forceinline__ void tn_cfence() { asm volatile("" ::: "memory"); }
-__device__ __forceinline__ void tn_bar() {
-  tn_cfence();
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-  tn_cfence();
-}
-template <int N>
-__device__ __forceinline__ void tn_wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ unsigned tn_lds_addr(const char* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const char*)p;
-}
-__device__ __forceinline__ void tn_dma16(const void* gsrc, unsigned lds_base) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_base), "v"(gsrc) : "memory");
-}
 
 typedef __attribute__((ext_vector_type(4))) short tn_s16x4_t;
 typedef __attribute__((ext_vector_type(8))) short tn_s16x8_t;
@@ -81,7 +60,7 @@ __device__ __forceinline__ void tn_issue_part(const GemmArgs& p, int q, int64_t 
   const int kind = qq & 3;
   const int t = qq >> 2;
   const int64_t tok0 = (int64_t)(kt0 + t) * 64;
-  char* slot = smem + ((q + 8) & 7) * TN_PART_BYTES;
+  char* slot = smem + ((q + 8) & 7) * LDS_PART_BYTES;
   const bool isA = (kind == 0) || (kind == 3);
   const int half = (kind == 0 || kind == 1) ? 0 : 1;
   const int64_t cbase = (isA ? m0 : n0) + half * 128;
@@ -101,7 +80,7 @@ __device__ __forceinline__ void tn_issue_part(const GemmArgs& p, int q, int64_t 
       const bf16_t* zsrc = g_tn_zero_row + tl.sc8;
       src = row <= last_row ? src : zsrc;
     }
-    tn_dma16(src, tn_lds_addr(slot + (j * 512 + wave_u * 64) * 16));
+    dma16_v(src, lds_addr(slot + (j * 512 + wave_u * 64) * 16));
   }
 }
 
@@ -120,19 +99,16 @@ struct TnFast {
   unsigned row32[2];      // bytes of 32 rows
   int tail_tile;          // slice-relative index of the partial token tile, or -1
 };
-__device__ __forceinline__ void tn_dma_sv(const char* sbase, unsigned voff, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_dst), "v"(voff), "s"(sbase) : "memory");
-}
 template <int KIND>
 __device__ __forceinline__ void tn_issue_fast(TnFast& f, int q, char* smem, int sc8, unsigned rowoff_a, unsigned rowoff_b,
                                               int wave_u) {
   constexpr bool isA = (KIND == 0) || (KIND == 3);
-  const unsigned slot = tn_lds_addr(smem + ((q + 8) & 7) * TN_PART_BYTES) + (unsigned)(wave_u * 64) * 16;
+  const unsigned slot = lds_addr(smem + ((q + 8) & 7) * LDS_PART_BYTES) + (unsigned)(wave_u * 64) * 16;
   const int rel = sc8 < f.lim[KIND] ? sc8 : f.lim[KIND];
   const unsigned v0 = (isA ? rowoff_a : rowoff_b) + ((unsigned)rel << 1);
   const unsigned v1 = v0 + f.row32[isA ? 0 : 1];
-  tn_dma_sv(f.base[KIND], v0, slot);
-  tn_dma_sv(f.base[KIND], v1, slot + 512 * 16);
+  dma16_sv(f.base[KIND], v0, slot);
+  dma16_sv(f.base[KIND], v1, slot + 512 * 16);
   f.base[KIND] += f.step[isA ? 0 : 1];
 }
 
@@ -228,10 +204,10 @@ __global__ __launch_bounds__(512) void gemm_tn_8phase_kernel(std::conditional_t<
   // Slot reuse: part p+8 is issued in L(p+3), at least two barriers after the last read of part p by either group.
   auto wait_landed = [&](int q) {   // tail-safe form of "part q+2 has landed": parts q+3 .. min(q+5, last_part) may be in flight
     const int younger = last_part - (q + 2);
-    if (younger >= 3) tn_wait_vm<6>();
-    else if (younger == 2) tn_wait_vm<4>();
-    else if (younger == 1) tn_wait_vm<2>();
-    else tn_wait_vm<0>();
+    if (younger >= 3) wait_vmcnt<6>();
+    else if (younger == 2) wait_vmcnt<4>();
+    else if (younger == 1) wait_vmcnt<2>();
+    else wait_vmcnt<0>();
   };
   // 16 MFMAs of one accumulator quadrant with NF fragment loads (two transpose reads each) spread underneath them
   auto mma_rd = [&](f32x4_t (&acc4)[4][2], const bf16x8_t (&rb)[2][2], const bf16x8_t (&ra)[4][2], auto nf_tag, auto&& load_frag)
@@ -308,17 +284,17 @@ __global__ __launch_bounds__(512) void gemm_tn_8phase_kernel(std::conditional_t<
   for (int q = 0; q < 5; q++)
     if (q <= last_part) tn_issue_part(p, q, m0, n0, kt0, smem, tl, wave_u);
   wait_landed(-1);
-  tn_bar();
-  if (late_group) tn_bar();
+  section_barrier();
+  if (late_group) section_barrier();
   {
-    const char* slot = smem + 7 * TN_PART_BYTES;   // part -1: A0 of K-tile 0
+    const char* slot = smem + 7 * LDS_PART_BYTES;   // part -1: A0 of K-tile 0
 #pragma unroll
     for (int i = 0; i < 4; i++)
 #pragma unroll
       for (int ks = 0; ks < 2; ks++) ra0[i][ks] = tn_frag(slot + a_off[i] + ks * 32 * 256);
   }
-  tn_bar();
-  tn_bar();
+  section_barrier();
+  section_barrier();
 
   for (int t = 0; t < nk; t++) {
 #pragma unroll
@@ -326,7 +302,7 @@ __global__ __launch_bounds__(512) void gemm_tn_8phase_kernel(std::conditional_t<
       const int q = 4 * t + ph;
       // ---------------- L(q)
       if (ph == 0) {
-        const char* slot = smem + (q & 7) * TN_PART_BYTES;
+        const char* slot = smem + (q & 7) * LDS_PART_BYTES;
 #pragma unroll
         for (int j = 0; j < 2; j++)
 #pragma unroll
@@ -338,13 +314,13 @@ __global__ __launch_bounds__(512) void gemm_tn_8phase_kernel(std::conditional_t<
         else if (ph == 1) issue_loop(std::integral_constant<int, 3>{}, q + 5, t + 1);
         else if (ph == 2) issue_loop(std::integral_constant<int, 0>{}, q + 5, t + 2);
         else issue_loop(std::integral_constant<int, 1>{}, q + 5, t + 2);
-        tn_wait_vm<6>();                              // part q+2 landed; q+3..q+5 in flight
+        wait_vmcnt<6>();                              // part q+2 landed; q+3..q+5 in flight
       } else {
         wait_landed(q);
       }
-      tn_bar();
+      section_barrier();
       // ---------------- C(q): one quadrant x 64 tokens, with the reads of part q+1 underneath
-      const char* nslot = smem + ((q + 1) & 7) * TN_PART_BYTES;
+      const char* nslot = smem + ((q + 1) & 7) * LDS_PART_BYTES;
       if (ph == 0) {
         mma_rd(acc[0][0], rb0, ra0, NF4{}, [&](int f) { rb1[f >> 1][f & 1] = tn_frag(nslot + b_off[f >> 1] + (f & 1) * 32 * 256); });
       } else if (ph == 1) {
@@ -356,10 +332,10 @@ __global__ __launch_bounds__(512) void gemm_tn_8phase_kernel(std::conditional_t<
       } else {
         mma_rd(acc[1][0], rb0, ra1, NF0{}, [&](int) {});
       }
-      tn_bar();
+      section_barrier();
     }
   }
-  if (!late_group) tn_bar();
+  if (!late_group) section_barrier();
 
   const int elane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
   const int efrow = elane & 15, efg = elane >> 4;
@@ -372,9 +348,6 @@ __global__ __launch_bounds__(512) void gemm_tn_8phase_kernel(std::conditional_t<
 }
 
 }  // namespace
-
-__global__ void splitk_reduce_kernel(const float4* ws, float* out, int64_t M, int64_t N, int64_t ldc, int S,
-                                     float alpha, float beta);   // gemm.hip
 
 static int tn_check(const char* who, const void* dY, int64_t ldy, const void* X, int64_t ldx, const float* dW, int64_t ldw,
                     int64_t T, int64_t N1, int64_t N2) {
@@ -391,32 +364,13 @@ static int tn_check(const char* who, const void* dY, int64_t ldy, const void* X,
 static GemmArgs tn_args(const void* dY, int64_t ldy, const void* X, int64_t ldx, float* dW, int64_t ldw, int64_t T,
                         int64_t N1, int64_t N2, float alpha, float beta) {
   GemmArgs b;
-  b.colpart = nullptr;
-  b.lnf_rs = nullptr;
-  b.lnf_c = nullptr;
-  b.raster = 0;
-  b.qscale = 0.f;
-  b.qcols = 0;
-  b.A = (const bf16_t*)dY; b.B = (const bf16_t*)X; b.C = dW; b.bias = nullptr; b.res = nullptr; b.aux_in = nullptr;
-  b.aux_out = nullptr;
-  b.M = N1; b.N = N2; b.K = T; b.lda = ldy; b.ldb = ldx; b.ldc = ldw; b.ldr = 0; b.ldaux = 0;
+  b.A = (const bf16_t*)dY; b.B = (const bf16_t*)X; b.C = dW;
+  b.M = N1; b.N = N2; b.K = T; b.lda = ldy; b.ldb = ldx; b.ldc = ldw;
   b.alpha = alpha; b.beta = beta;
   b.tiles_m = (int)cdiv64(N1, 256);
   b.tiles_n = (int)cdiv64(N2, 256);
-  b.dbg = 0;
-  b.zero_row = nullptr;   // (the TN kernel reads the zero-initialised device global g_tn_zero_row)
-  b.splitk = 1;
   b.ktiles_per = (int)cdiv64(T, 64);
-  b.ws = nullptr;
   return b;
-}
-
-static void tn_reduce(const GemmArgs& b, float alpha, float beta, hipStream_t stream) {
-  const int64_t n4 = b.M * b.N / 4;
-  int64_t g = cdiv64(n4, 256);
-  if (g > 256 * 8) g = 256 * 8;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, stream, (const float4*)b.ws, (float*)b.C, b.M, b.N,
-                     b.ldc, b.splitk, alpha, beta);
 }
 
 template <bool GROUPED>
@@ -424,7 +378,7 @@ static void tn_set_attr() {
   static VjPerDeviceOnce attr_once;   // the dynamic-LDS limit is a per-device attribute of the function
   attr_once([] {
     (void)hipFuncSetAttribute((const void*)gemm_tn_8phase_kernel<GROUPED>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              8 * TN_PART_BYTES);
+                              8 * LDS_PART_BYTES);
   });
 }
 
@@ -443,15 +397,10 @@ extern "C" int vj_gemm_bf16_tn_splitk(const void* dY, int64_t ldy, const void* X
   const int nk = (int)cdiv64(T, 64);
   b.splitk = pick_splitk((int64_t)b.tiles_m * b.tiles_n, nk, 256, 1.45, 8, N1, N2, ws_bytes);
   b.ws = (float*)ws;
-  b.ktiles_per = (nk + b.splitk - 1) / b.splitk;
-  b.splitk = (nk + b.ktiles_per - 1) / b.ktiles_per;
-  hipLaunchKernelGGL(gemm_tn_8phase_kernel<false>, dim3(b.tiles_m * b.tiles_n * b.splitk), dim3(512), 8 * TN_PART_BYTES, stream, a);
+  vj_splitk_finish_plan(nk, b.splitk, b.ktiles_per);
+  hipLaunchKernelGGL(gemm_tn_8phase_kernel<false>, dim3(b.tiles_m * b.tiles_n * b.splitk), dim3(512), 8 * LDS_PART_BYTES, stream, a);
   VJ_LAUNCH_CHECK("vj_gemm_bf16_tn_splitk");
-  if (b.splitk > 1) {
-    tn_reduce(b, alpha, beta, stream);
-    VJ_LAUNCH_CHECK("vj_gemm_bf16_tn_splitk(reduce)");
-  }
-  return 0;
+  return vj_splitk_reduce(b, stream);
 }
 
 // The weight gradients of n <= 4 Linear layers over the SAME T tokens in one launch (a transformer block's qkv, proj,
@@ -489,8 +438,8 @@ extern "C" int vj_gemm_bf16_tn_grouped(const void* probs_v, int64_t n, int64_t T
   const int nk = (int)cdiv64(T, 64);
   // one split factor for the group: pick_splitk's cost model on the summed tile count / output size
   int splitk = pick_splitk(tiles, nk, 256, 1.45, 8, out_elems, 1, ws_bytes);
-  const int ktiles_per = (nk + splitk - 1) / splitk;
-  splitk = (nk + ktiles_per - 1) / ktiles_per;
+  int ktiles_per;
+  vj_splitk_finish_plan(nk, splitk, ktiles_per);
   int64_t units = 0, ws_off = 0;
   for (int i = 0; i < a.n; i++) {
     a.g[i].splitk = splitk;
@@ -506,11 +455,9 @@ extern "C" int vj_gemm_bf16_tn_grouped(const void* probs_v, int64_t n, int64_t T
   }
   VJ_CHECK_ARG(units < (1ll << 31), "vj_gemm_bf16_tn_grouped: grid too large");
   tn_set_attr<true>();
-  hipLaunchKernelGGL(gemm_tn_8phase_kernel<true>, dim3((unsigned)units), dim3(512), 8 * TN_PART_BYTES, stream, a);
+  hipLaunchKernelGGL(gemm_tn_8phase_kernel<true>, dim3((unsigned)units), dim3(512), 8 * LDS_PART_BYTES, stream, a);
   VJ_LAUNCH_CHECK("vj_gemm_bf16_tn_grouped");
-  if (splitk > 1) {
-    for (int i = 0; i < a.n; i++) tn_reduce(a.g[i], alpha, beta, stream);
-    VJ_LAUNCH_CHECK("vj_gemm_bf16_tn_grouped(reduce)");
-  }
+  for (int i = 0; i < a.n; i++)
+    if (int rc = vj_splitk_reduce(a.g[i], stream)) return rc;
   return 0;
 }

@@ -46,31 +46,10 @@
 #include "gemm_common.hpp"
 #include "options.hpp"
 
-#define PP_PART 16384
-#define PP_RING (8 * PP_PART)
+#define PP_RING (8 * LDS_PART_BYTES)
 #define PP_STAGE_PER_WAVE 4096
 
 namespace {
-
-__device__ __forceinline__ void pp_bar() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);   // nothing (MFMA, ds_read, DMA issue) may be scheduled across a section boundary
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::: "memory");
-}
-template <int N>
-__device__ __forceinline__ void pp_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ unsigned pp_lds(const char* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const char*)p;
-}
-// LDS-DMA, SGPR base + 32-bit lane offset form, through inline assembly (the compiler neither counts it nor assumes an LDS write).
-// (a non-temporal hint on the streaming operand was measured in round 5: +1.4 / +2.8 ms per step, profiles/r05_gemm_nt.md)
-__device__ __forceinline__ void pp_dma(const char* sbase, unsigned voff, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_dst), "v"(voff), "s"(sbase) : "memory");
-}
 
 // the 8 wave-uniform row-group bases of one tile: A rows m0 + j*128 + mq*64, B rows n0 + j*128 + nq*32 (byte pointers at k = 0)
 struct PpBases {
@@ -149,36 +128,36 @@ __device__ __forceinline__ void pp_body(const GemmArgs& p) {
     voff_a = (unsigned)((r0 * p.lda + c * 8) * 2);
     voff_b = (unsigned)((rb * p.ldb + c * 8) * 2);
   }
-  const unsigned ring = pp_lds(smem);
+  const unsigned ring = lds_addr(smem);
   const unsigned dst_lane = (unsigned)(wave_u * 64) * 16;   // this wave's 1 KB piece inside each 8 KB half-part
 
   // issue one part (two DMA instructions per thread): kind 0 B0, 1 B1, 2 A1, 3 A0 of K-tile `kt` into ring half `half`
   auto issue = [&](auto kind_tag, const PpBases& bs, int kt, int half) __attribute__((always_inline)) {
     constexpr int KIND = decltype(kind_tag)::value;
-    const unsigned slot = ring + (unsigned)(half * 4 + KIND) * PP_PART + dst_lane;
+    const unsigned slot = ring + (unsigned)(half * 4 + KIND) * LDS_PART_BYTES + dst_lane;
     const unsigned koff = (unsigned)kt * 128u;
     if constexpr (KIND == 0 || KIND == 1) {
-      pp_dma(bs.b[KIND][0], voff_b + koff, slot);
-      pp_dma(bs.b[KIND][1], voff_b + koff, slot + 512 * 16);
+      dma16_sv(bs.b[KIND][0], voff_b + koff, slot);
+      dma16_sv(bs.b[KIND][1], voff_b + koff, slot + 512 * 16);
     } else {
       constexpr int MQ = KIND == 2 ? 1 : 0;
-      pp_dma(bs.a[MQ][0], voff_a + koff, slot);
-      pp_dma(bs.a[MQ][1], voff_a + koff, slot + 512 * 16);
+      dma16_sv(bs.a[MQ][0], voff_a + koff, slot);
+      dma16_sv(bs.a[MQ][1], voff_a + koff, slot + 512 * 16);
     }
   };
   // the same for the NEXT tile (tail of the K loop, once per tile): only its two origin pointers are kept in SGPRs, the
   // row-group bases are derived at the issue site (a handful of SALU instructions per part)
   auto issue_next = [&](auto kind_tag, const char* a0n, const char* b0n, int kt, int half) __attribute__((always_inline)) {
     constexpr int KIND = decltype(kind_tag)::value;
-    const unsigned slot = ring + (unsigned)(half * 4 + KIND) * PP_PART + dst_lane;
+    const unsigned slot = ring + (unsigned)(half * 4 + KIND) * LDS_PART_BYTES + dst_lane;
     const unsigned koff = (unsigned)kt * 128u;
     if constexpr (KIND == 0 || KIND == 1) {
-      pp_dma(b0n + (int64_t)(KIND * 32) * ldb2, voff_b + koff, slot);
-      pp_dma(b0n + (int64_t)(128 + KIND * 32) * ldb2, voff_b + koff, slot + 512 * 16);
+      dma16_sv(b0n + (int64_t)(KIND * 32) * ldb2, voff_b + koff, slot);
+      dma16_sv(b0n + (int64_t)(128 + KIND * 32) * ldb2, voff_b + koff, slot + 512 * 16);
     } else {
       constexpr int MQ = KIND == 2 ? 1 : 0;
-      pp_dma(a0n + (int64_t)(MQ * 64) * lda2, voff_a + koff, slot);
-      pp_dma(a0n + (int64_t)(128 + MQ * 64) * lda2, voff_a + koff, slot + 512 * 16);
+      dma16_sv(a0n + (int64_t)(MQ * 64) * lda2, voff_a + koff, slot);
+      dma16_sv(a0n + (int64_t)(128 + MQ * 64) * lda2, voff_a + koff, slot + 512 * 16);
     }
   };
   using K_B0 = std::integral_constant<int, 0>;
@@ -280,12 +259,12 @@ __device__ __forceinline__ void pp_body(const GemmArgs& p) {
     constexpr int MODE = decltype(mode_tag)::value;
     constexpr bool LIVE = decltype(live_tag)::value;
     constexpr bool HEAD0 = MODE == PP_HEAD0, TAIL0 = MODE == PP_TAIL0, TAIL1 = MODE == PP_TAIL1;
-    const char* half_c = smem + h * 4 * PP_PART;
+    const char* half_c = smem + h * 4 * LDS_PART_BYTES;
     const int ho = h ^ 1;
     // ---------------- LX
     if constexpr (LIVE) {
-      read_b(rb0, half_c + 0 * PP_PART);
-      read_b(rb1, half_c + 1 * PP_PART);
+      read_b(rb0, half_c + 0 * LDS_PART_BYTES);
+      read_b(rb1, half_c + 1 * LDS_PART_BYTES);
     }
     if constexpr (TAIL1) {
       issue_next(K_A1{}, a0n, b0n, 0, ho);
@@ -297,17 +276,17 @@ __device__ __forceinline__ void pp_body(const GemmArgs& p) {
       issue(K_A1{}, cur, t + 1, ho);
       issue(K_A0{}, cur, t + 2, ho);
     }
-    if constexpr (!HEAD0) pp_wait<8>();
-    pp_bar();
+    if constexpr (!HEAD0) wait_vmcnt<8>();
+    section_barrier();
     if constexpr (LIVE) {
       mma(Q00{}, rb0, ra0);
       mma(Q01{}, rb1, ra0);
     }
-    pp_bar();
+    section_barrier();
     // ---------------- LY
     if constexpr (LIVE) {
-      read_a(ra1, half_c + 2 * PP_PART);
-      if constexpr (!TAIL1) read_a(ra0, half_c + 3 * PP_PART);   // (the next tile's A0(0) is read at its start, after the epilogue)
+      read_a(ra1, half_c + 2 * LDS_PART_BYTES);
+      if constexpr (!TAIL1) read_a(ra0, half_c + 3 * LDS_PART_BYTES);   // (the next tile's A0(0) is read at its start, after the epilogue)
     }
     if constexpr (TAIL1) {
       issue_next(K_B0{}, a0n, b0n, 1, h);
@@ -319,13 +298,13 @@ __device__ __forceinline__ void pp_body(const GemmArgs& p) {
       issue(K_B0{}, cur, t + 2, h);
       issue(K_B1{}, cur, t + 2, h);
     }
-    if constexpr (!HEAD0 && !TAIL1) pp_wait<8>();
-    pp_bar();
+    if constexpr (!HEAD0 && !TAIL1) wait_vmcnt<8>();
+    section_barrier();
     if constexpr (LIVE) {
       mma(Q11{}, rb1, ra1);
       mma(Q10{}, rb0, ra1);
     }
-    pp_bar();
+    section_barrier();
   };
 
   // ---- first tile: parts -1 .. 5 in flight, all landed before anybody reads
@@ -341,7 +320,7 @@ __device__ __forceinline__ void pp_body(const GemmArgs& p) {
   issue(K_A0{}, cur, 1, 0);
   issue(K_B0{}, cur, 1, 1);
   issue(K_B1{}, cur, 1, 1);
-  pp_wait<0>();
+  wait_vmcnt<0>();
 
   // li_cur / li_nx: this workgroup's current and next tile, as positions in its XCD's band (static round-robin lists: li_nx = li_cur +
   // wgs_x; handing tiles out dynamically from per-XCD counters was built in round 5 and measured level: profiles/r05_gemm_dyn.md)
@@ -369,13 +348,13 @@ __device__ __forceinline__ void pp_body(const GemmArgs& p) {
         for (int j = 0; j < 4; j++) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
       // ---- tile start: part 6 = A1(1) -> half h^1 slot 2 (its previous content, A1 of the previous tile's last K-tile, was
       //      read >= 2 sections + one epilogue ago); every other part up to 5 landed before this wave's last vmcnt(0)
-      pp_bar();   // (part 6 is issued by LX(0))
+      section_barrier();   // (part 6 is issued by LX(0))
       lap(4, st_tiles != 0);       // [epilogue end -> past the next tile's first barrier: the skew between the eight waves]
       next_origin();
-      if (late_group) pp_bar();
-      read_a(ra0, smem + ((h ^ 1) * 4 + 3) * PP_PART);   // L(-1): A0(0)
-      pp_bar();
-      pp_bar();
+      if (late_group) section_barrier();
+      read_a(ra0, smem + ((h ^ 1) * 4 + 3) * LDS_PART_BYTES);   // L(-1): A0(0)
+      section_barrier();
+      section_barrier();
       lap(0, st_tiles != 0);   // [tile start: first barrier -> K loop] (the first tile starts its clock here)
       // ONE tail for every tile: the last tile "prefetches" its own first parts again (never read; retired by the epilogue's
       // vmcnt(0)).  A has_next diamond around two copies of the tail costs ~300 spilled VGPRs (hipcc 7.2).
@@ -383,13 +362,13 @@ __device__ __forceinline__ void pp_body(const GemmArgs& p) {
       for (int t = 1; t < nk - 2; t++) k_tile4(M_STEADY{}, role_tag, t, h ^ (t & 1));
       k_tile4(M_TAIL0{}, role_tag, nk - 2, h ^ (nk & 1));
       k_tile4(M_TAIL1{}, role_tag, nk - 1, h ^ ((nk - 1) & 1));
-      if (!late_group) pp_bar();   // the early group matches the late group's extra barrier
+      if (!late_group) section_barrier();   // the early group matches the late group's extra barrier
       lap(1, true);                // [K loop]
 
       // ---- epilogue: staged through this wave's private 4 KB (the ring holds the next tile's parts).  Its first action
       //      (bias loads + s_waitcnt vmcnt(0)) also retires every LDS-DMA this wave has issued.
       if (p.dbg & 1) {   // diagnostics: no output traffic (keeps the accumulators alive through one predicated store)
-        pp_wait<0>();
+        wait_vmcnt<0>();
         if (acc[0][0][0] == 12345.678f && acc[7][3][3] == 0.5f) *(float*)p.C = acc[3][2][1];
       } else {
         // lane id re-derived through a VOLATILE asm: everything the epilogue computes from it (LDS staging offsets, row /
@@ -398,7 +377,7 @@ __device__ __forceinline__ void pp_body(const GemmArgs& p) {
         int elane;
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(elane));
         const int efrow = elane & 15, efg = elane >> 4;
-        pp_wait<0>();
+        wait_vmcnt<0>();
         lap(2, true);              // [wait for the next tile's prefetched parts]
         // (column sums, EPI_DGELU with p.colpart: a shifted edge tile owns only its rows >= tm * 256; slot = 2 tm + wave row)
         (void)gemm_epilogue_try_staged<EPI, 2, true, PRE>(p, acc, m0 + wm_t * 128, n0 + wn_t * 64, efrow, efg, elane,
@@ -410,16 +389,16 @@ __device__ __forceinline__ void pp_body(const GemmArgs& p) {
       compute_tile(R_LIVE{});
     } else {
       // idle wave of a half tile (always of the late group): the late group's four tile-start barriers, its DMA share, the waits
-      pp_bar();
+      section_barrier();
       next_origin();
-      pp_bar();
-      pp_bar();
-      pp_bar();
+      section_barrier();
+      section_barrier();
+      section_barrier();
       k_tile4(M_HEAD0{}, R_IDLE{}, 0, h);
       for (int t = 1; t < nk - 2; t++) k_tile4(M_STEADY{}, R_IDLE{}, t, h ^ (t & 1));
       k_tile4(M_TAIL0{}, R_IDLE{}, nk - 2, h ^ (nk & 1));
       k_tile4(M_TAIL1{}, R_IDLE{}, nk - 1, h ^ ((nk - 1) & 1));
-      pp_wait<0>();
+      wait_vmcnt<0>();
     }
     h ^= (nk & 1);               // ring half of the next tile's K-tile 0
     if constexpr (STAMP) st_tiles++;
@@ -540,13 +519,12 @@ int vj_gemm_launch_8phase_persist(const GemmArgs& a, int epilogue, hipStream_t s
   if (g_num_cus == 0) {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      return -100;
+      return VJ_PERSIST_NA;
     g_num_cus = n;
   }
-  switch (epilogue) {
-    case EPI_BF16: return persist_ok<EPI_BF16>(a, g_num_cus) ? launch8p<EPI_BF16>(a, stream) : -100;
-    case EPI_GELU: return persist_ok<EPI_GELU>(a, g_num_cus) ? launch8p<EPI_GELU>(a, stream) : -100;
-    case EPI_DGELU: return persist_ok<EPI_DGELU>(a, g_num_cus) ? launch8p<EPI_DGELU>(a, stream) : -100;
-    default: return -100;
-  }
+  return with_epilogue(epilogue, nullptr, 0, [&](auto epi, void*, int64_t) {
+    constexpr int EPI = decltype(epi)::value;
+    if constexpr (EPI == EPI_F32) return VJ_PERSIST_NA;   // bf16-output epilogues only
+    else return persist_ok<EPI>(a, g_num_cus) ? launch8p<EPI>(a, stream) : VJ_PERSIST_NA;
+  });
 }

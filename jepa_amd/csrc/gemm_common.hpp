@@ -1,40 +1,59 @@
 // Shared pieces of the bf16 MFMA GEMM kernels: argument block, epilogue selector and the fused epilogue.
 #pragma once
 #include "common.hpp"
+#include "lds_pipe.hpp"
+#include <climits>
+#include <type_traits>
 
 enum { EPI_BF16 = 0, EPI_GELU = 1, EPI_DGELU = 2, EPI_F32 = 3 };
 #define EPI_QKV_API 4   // C-ABI only: EPI_BF16 whose first N/3 output columns (the q part of a qkv projection) are multiplied by alpha
 
-struct GemmArgs {
-  const bf16_t* A;
-  const bf16_t* B;
-  void* C;
-  const float* bias;      // [N] fp32, nullable
-  const bf16_t* res;      // [M,N] bf16 residual, nullable (EPI_BF16)
-  const bf16_t* aux_in;   // [M,N] bf16 saved GELU derivative gelu'(u) (EPI_DGELU): what EPI_GELU wrote to aux_out
-  bf16_t* aux_out;        // [M,N] bf16 gelu'(u) of the bf16-rounded pre-activation u = acc + bias, nullable (EPI_GELU)
-  int64_t M, N, K, lda, ldb, ldc, ldr, ldaux;
-  float alpha, beta;
-  int tiles_m, tiles_n;
-  int splitk;          // > 1: K is cut into `splitk` slices, raw fp32 partials go to ws[slice][M][N] (EPI_F32 only)
-  int ktiles_per;      // K-tiles per slice
-  float* ws;
-  const bf16_t* zero_row;   // 128 bf16 zeros: source of token rows beyond T in the TN weight-gradient kernel (gemm8_tn.hip)
-  int dbg;             // diagnostics (env VJ_GEMM_DBG, tools/gemm_ksweep.py): bit0 = drop the epilogue, bit1 = direct (unstaged) stores
-  float qscale;        // EPI_BF16 without residual: != 0 -> columns n < qcols are multiplied by qscale before the bf16 rounding (the q part
-  int64_t qcols;       //   of a qkv projection carries the soft-max scale scale*log2(e): ONE rounding of c*q, attention.hip); qcols % 4 == 0
-  float* colpart;      // EPI_DGELU on the persistent kernel, nullable: fp32 column-sum partials of the OUTPUT, [2 * tiles_m][N]
-                       // (row slot = 2 * row tile + wave row): the bias gradient of the Linear whose dY this GEMM produces
-  int raster;          // persistent kernel: tile order (tile_of_raster; 0 = the default 8-row groups)
+struct GemmArgs {   // every member has a default: a launcher sets what it means to set, a new member needs no edit anywhere else
+  const bf16_t* A = nullptr;
+  const bf16_t* B = nullptr;
+  void* C = nullptr;
+  const float* bias = nullptr;      // [N] fp32, nullable
+  const bf16_t* res = nullptr;      // [M,N] bf16 residual, nullable (EPI_BF16)
+  const bf16_t* aux_in = nullptr;   // [M,N] bf16 saved GELU derivative gelu'(u) (EPI_DGELU): what EPI_GELU wrote to aux_out
+  bf16_t* aux_out = nullptr;        // [M,N] bf16 gelu'(u) of the bf16-rounded pre-activation u = acc + bias, nullable (EPI_GELU)
+  int64_t M = 0, N = 0, K = 0, lda = 0, ldb = 0, ldc = 0, ldr = 0, ldaux = 0;
+  float alpha = 1.f, beta = 0.f;
+  int tiles_m = 0, tiles_n = 0;
+  int splitk = 1;          // > 1: K is cut into `splitk` slices, raw fp32 partials go to ws[slice][M][N] (EPI_F32 only)
+  int ktiles_per = 0;      // K-tiles per slice
+  float* ws = nullptr;
+  const bf16_t* zero_row = nullptr;   // unused (the TN weight-gradient kernel reads the zero-initialised device global g_tn_zero_row); kept for the layout
+  int dbg = 0;             // diagnostics (env VJ_GEMM_DBG, tools/gemm_ksweep.py): bit0 = drop the epilogue, bit1 = direct (unstaged) stores
+  float qscale = 0.f;      // EPI_BF16 without residual: != 0 -> columns n < qcols are multiplied by qscale before the bf16 rounding (the q part
+  int64_t qcols = 0;       //   of a qkv projection carries the soft-max scale scale*log2(e): ONE rounding of c*q, attention.hip); qcols % 4 == 0
+  float* colpart = nullptr;   // EPI_DGELU on the persistent kernel, nullable: fp32 column-sum partials of the OUTPUT, [2 * tiles_m][N]
+                              // (row slot = 2 * row tile + wave row): the bias gradient of the Linear whose dY this GEMM produces
+  int raster = 0;          // persistent kernel: tile order (tile_of_raster; 0 = the default 8-row groups)
   // LayerNorm folded into this GEMM (round 5; bf16 / GELU epilogues without residual or saved derivative): A holds the RAW rows x
   // (not LayerNorm(x)), B = bf16(W * diag(gamma)), bias = b + W beta, lnf_c[n] = sum_k B[n,k] and lnf_rs[m] = {rstd_m, -mean_m * rstd_m}:
   //   out[m,n] = rstd_m * (acc[m,n] - mean_m * c[n]) + bias[n]  =  LayerNorm(x)[m,:] . W[n,:] + b[n]      (vj_gemm_bf16_nt_lnfold)
-  const float* lnf_rs;   // [M][2] fp32, nullable (null: plain epilogue)
-  const float* lnf_c;    // [N] fp32
+  const float* lnf_rs = nullptr;   // [M][2] fp32, nullable (null: plain epilogue)
+  const float* lnf_c = nullptr;    // [N] fp32
   int half_tiles = 0;    // persistent kernel: N % 256 == 128 and the shifted last column tile computes its own 128 columns only (gemm8p.hip)
   int epi_pre = 0;       // persistent kernel: form of the epilogue (option gemm_epi_pre: 4 = pipelined passes, 0 = straight passes; PRE below)
 };
+static_assert(std::is_trivially_copyable_v<GemmArgs> && sizeof(GemmArgs) == 216, "GemmArgs is a kernel argument: its layout is part of every GEMM kernel");
 
+// vj_gemm_launch_8phase_persist (gemm8p.hip): the persistent kernel does not apply, the caller keeps the one-tile-per-workgroup kernel
+// (internal to the library; a value that neither a hipError_t nor an argument error, -1, takes)
+constexpr int VJ_PERSIST_NA = INT_MIN;
+
+// run-time `epilogue` -> the EPI_* template argument of a launcher: f(std::integral_constant<int, EPI>{}, ws, ws_bytes).  Only the fp32
+// (weight-gradient) epilogue is given the split-K workspace.
+template <class F>
+static inline int with_epilogue(int epilogue, void* ws, int64_t ws_bytes, F&& f) {
+  switch (epilogue) {
+    case EPI_BF16: return f(std::integral_constant<int, EPI_BF16>{}, (void*)nullptr, (int64_t)0);
+    case EPI_GELU: return f(std::integral_constant<int, EPI_GELU>{}, (void*)nullptr, (int64_t)0);
+    case EPI_DGELU: return f(std::integral_constant<int, EPI_DGELU>{}, (void*)nullptr, (int64_t)0);
+    default: return f(std::integral_constant<int, EPI_F32>{}, ws, ws_bytes);
+  }
+}
 
 // Fused epilogue.  acc[i][j] comes from MFMA 16x16x32 issued with swapped operands (D = Bfrag x Afrag): lane
 // (g = lane>>4, r = lane&15) owns row m = .. + i*16 + r and the 4 consecutive columns n = .. + j*16 + 4g + {0..3}.
@@ -751,6 +770,12 @@ static inline int pick_splitk(int64_t tiles, int nk, int slots, double us_per_kt
   }
   return best;
 }
+
+// The tail every split-K launcher shares (gemm.hip, next to splitk_reduce_kernel).  Plan: K-tiles per slice for the slice count picked
+// above, then the slice count that leaves no slice empty.  Reduce: after the GEMM launch, C = alpha * sum of the b.splitk partials in b.ws
+// + beta * C (nothing to do for b.splitk == 1); returns 0 or the launch error.
+void vj_splitk_finish_plan(int nk, int& splitk, int& ktiles_per);
+int vj_splitk_reduce(const GemmArgs& b, hipStream_t stream);
 
 // XCD-aware, grouped tile mapping (bijective for any grid size): workgroup `bid` of `nblk` -> logical tile index such
 // that each XCD (private L2; hardware dispatches workgroup b to XCD b % 8) works on a contiguous band of tiles.
