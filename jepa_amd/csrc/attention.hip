@@ -26,24 +26,26 @@
 // =============================================================================================================
 // RS = where the soft-max row sums come from: 0 vector adds (v_pk_add_f32 on the fp32 probabilities), 1 the V pad column (head_dim 24),
 // 2 an all-ones A operand: two extra P MFMAs per key tile and 16-row block put sum_k bf16(P) in every row of a 16 x 16 accumulator --
-// packed f32 adds next to MFMAs cost twice their stand-alone time (profiles/r03_valu_mfma_probe.md), the two MFMAs 32 cycles
-template <int HDP, int QT, int NBUF, int RS>
-__global__ __launch_bounds__(8 * 64 / QT) void attn_fwd_sm_kernel(const bf16_t* __restrict__ qkv_all,
+// packed f32 adds next to MFMAs cost twice their stand-alone time (profiles/r03_valu_mfma_probe.md), the two MFMAs 32 cycles.
+// RS = 0 is not instantiated since round 4 (profiles/r04_abab_rowsums.md).  Its arm stays in the source: without the (dead) partial sums
+// `ls2` / `lrun` hipcc schedules the RS = 1 and RS = 2 kernels differently (profiles/epilogue_variants_refactor.md).
+template <int HDP, int NBUF, int RS>
+__global__ __launch_bounds__(256) void attn_fwd_sm_kernel(const bf16_t* __restrict__ qkv_all,
                                                           bf16_t* __restrict__ o_all, float* __restrict__ lse2_all,
                                                           AttnSegs sg, int H, int hd, float sc) {
-  constexpr int NT = 8 * 64 / QT;
+  constexpr int QT = 2, NT = 256;   // 16-query tiles per wave; threads (four waves, 128 queries per workgroup)
   using RT = RowTile<HDP, NT>;
   constexpr int DIST = NBUF - 1;
-  static_assert(RT::CAN_FULL || NT == 512, "tile items must be a multiple of the workgroup size");
+  static_assert(RT::CAN_FULL, "tile items must be a multiple of the workgroup size");
   constexpr bool PSUM = RS == 1;
   static_assert(!PSUM || (HDP == 32 && RT::CAN_FULL && RT::NIT == 1), "row sums on the pad column: 32-wide class, one DMA item per thread");
-  constexpr int NDMA = RT::CAN_FULL ? RT::NIT : 1;
+  constexpr int NDMA = RT::NIT;
   __shared__ __attribute__((aligned(16))) char smem[NBUF * 2 * RT::BYTES];
   const TrFrag<HDP> trf(threadIdx.x & 63);
   constexpr int KS = HDP / 32, DT = HeadTiles<HDP>::DT;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int li = lane & 15, g = lane >> 4;
-  int logical = xcd_remap(blockIdx.x, gridDim.x);
+  int logical = xcd_logical(blockIdx.x, gridDim.x);
   const int si = attn_seg_of(sg, logical);
   const int S = sg.S[si], nqb = sg.nb[si];
   const int64_t rs = (int64_t)3 * H * hd;
@@ -86,11 +88,10 @@ __global__ __launch_bounds__(8 * 64 / QT) void attn_fwd_sm_kernel(const bf16_t* 
   const int nt = (S + 63) / 64;
   int dma_row[NDMA];
   unsigned dma_voff[NDMA], dma_col2[NDMA];
-  const bool dma_on = RT::CAN_FULL || tid < 64 * RT::CHP;
   bool vpad = false;           // PSUM: this thread's DMA item is the pad chunk (columns >= hd) of its V row
 #pragma unroll
   for (int it = 0; it < NDMA; it++) {
-    const int item = RT::CAN_FULL ? tid + it * NT : (tid < 64 * RT::CHP ? tid : 0);
+    const int item = tid + it * NT;
     const int row = item / RT::CHP, c = (item % RT::CHP) ^ rm_swz<HDP>(row);
     const int col = c * 8 < hd ? c * 8 : 0;
     if constexpr (PSUM) vpad = c * 8 >= hd;
@@ -126,13 +127,11 @@ __global__ __launch_bounds__(8 * 64 / QT) void attn_fwd_sm_kernel(const bf16_t* 
         vo = (unsigned)r * rs2 + dma_col2[it];
       }
       char* dst = kb + (it * NT + wu * 64) * 16;
-      if (dma_on) {
-        dma16_sv(kt, vo, lds_addr(dst));
-        if constexpr (PSUM) {
-          if (!vpad) dma16_sv(vt, vo, lds_addr(dst + RT::BYTES));   // never all lanes of a wave: one pad chunk per 4 lanes
-        } else {
-          dma16_sv(vt, vo, lds_addr(dst + RT::BYTES));
-        }
+      dma16_sv(kt, vo, lds_addr(dst));
+      if constexpr (PSUM) {
+        if (!vpad) dma16_sv(vt, vo, lds_addr(dst + RT::BYTES));   // never all lanes of a wave: one pad chunk per 4 lanes
+      } else {
+        dma16_sv(vt, vo, lds_addr(dst + RT::BYTES));
       }
     }
   };
@@ -265,7 +264,7 @@ __global__ __launch_bounds__(8 * 64 / QT) void attn_fwd_sm_kernel(const bf16_t* 
         for (int qt = 0; qt < QT; qt++) lacc[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf[qt][c], lacc[qt], 0, 0, 0);
     }
   };
-  const int nfull = RT::CAN_FULL ? S / 64 : 0;
+  const int nfull = S / 64;
   const int t_fast = nfull - DIST > 0 ? nfull - DIST : 0;
   int t = 1;
   if (t_fast > 0) iter(0, std::true_type{}, std::true_type{});
@@ -315,7 +314,7 @@ __global__ __launch_bounds__(8 * 64 / QT) void attn_fwd_sm_kernel(const bf16_t* 
 // 16 MFMAs + the soft-max arithmetic of 16 scores per lane: the kernel is bound by LDS INSTRUCTIONS.  The Q / dO fragments
 // and their transposed reads do not depend on the key, so KT = 2 reuses every one of them for two key tiles.
 // =============================================================================================================
-template <int HDP, int KT, bool SM>
+template <int HDP, int KT>
 __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(const bf16_t* __restrict__ qkv_all,
                                                             const bf16_t* __restrict__ dout_all,
                                                             const float* __restrict__ lse2_all,
@@ -331,7 +330,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(const bf16_t* __rest
   constexpr int KS = HDP / 32, DT = HeadTiles<HDP>::DT;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int li = lane & 15, g = lane >> 4;
-  int logical = xcd_remap(blockIdx.x, gridDim.x);
+  int logical = xcd_logical(blockIdx.x, gridDim.x);
   const int si = attn_seg_of(sg, logical);
   const int S = sg.S[si], nkb = sg.nb[si];
   const int64_t rs = (int64_t)3 * H * hd;
@@ -366,9 +365,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(const bf16_t* __rest
       const int d0 = ks * 32 + 8 * g;
       kf[kt][ks] = load_frag_global(kbase + (int64_t)key[kt] * rs + d0, key_ok[kt] && d0 < hd);
       vf[kt][ks] = load_frag_global(vbase + (int64_t)key[kt] * rs + d0, key_ok[kt] && d0 < hd);
-      // SM: K is the stationary operand of the score product here and is used for nothing else (dK contracts dS with Q):
+      // K is the stationary operand of the score product here and is used for nothing else (dK contracts dS with Q):
       // it carries the soft-max scale, bf16(k * scale * log2 e)
-      if constexpr (SM) kf[kt][ks] = scale_frag(kf[kt][ks], sc);
+      kf[kt][ks] = scale_frag(kf[kt][ks], sc);
     }
   f32x4_t dvacc[KT][DT], dkacc[KT][DT];
 #pragma unroll
@@ -380,7 +379,6 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(const bf16_t* __rest
     }
 
   float lse_r = 0.f, dl_r = 0.f;
-  const f32x2_t sc2 = {sc, sc};
   const int nt = (S + 63) / 64;
   const bool wave_live = kb * (64 * KT) + __builtin_amdgcn_readfirstlane(w) * (16 * KT) < S;   // wave-uniform
   const TileDma<HDP, 256> dma(tid, hd);
@@ -436,11 +434,11 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(const bf16_t* __rest
         const float4 lse4 = *(const float4*)(lse_s + qt * 16 + 4 * g);   // queries qt*16 + 4g + {0..3}
         const float4 ndl4 = *(const float4*)(dl_s + qt * 16 + 4 * g);    // -delta of the same queries
         // the dP accumulator STARTS at -delta[q] (this lane's four rows): dP - delta comes out of the matrix pipe
-        // SM: the score accumulator starts at -lse2[q] the same way, so P = exp2(accumulator) (padded queries: -inf -> P = 0)
+        // the score accumulator starts at -lse2[q] the same way, so P = exp2(accumulator) (padded queries: lse = +inf -> -inf -> P = 0)
         f32x4_t sacc[KT], dpacc[KT];
 #pragma unroll
         for (int kt = 0; kt < KT; kt++) {
-          sacc[kt] = SM ? (f32x4_t){-lse4.x, -lse4.y, -lse4.z, -lse4.w} : (f32x4_t){0.f, 0.f, 0.f, 0.f};
+          sacc[kt] = (f32x4_t){-lse4.x, -lse4.y, -lse4.z, -lse4.w};
           dpacc[kt] = (f32x4_t){ndl4.x, ndl4.y, ndl4.z, ndl4.w};
         }
 #pragma unroll
@@ -453,15 +451,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(const bf16_t* __rest
             dpacc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da, vf[kt][ks], dpacc[kt], 0, 0, 0);
           }
         }
-        const f32x2_t nl[2] = {{-lse4.x, -lse4.y}, {-lse4.z, -lse4.w}};
 #pragma unroll
         for (int kt = 0; kt < KT; kt++)
 #pragma unroll
-          for (int hf = 0; hf < 2; hf++) {   // 2-vectors: v_pk_fma_f32 / v_pk_mul_f32
-            const f32x2_t sv = {sacc[kt][2 * hf], sacc[kt][2 * hf + 1]}, dpv = {dpacc[kt][2 * hf], dpacc[kt][2 * hf + 1]};
-            f32x2_t a = sv;
-            if constexpr (!SM) a = __builtin_elementwise_fma(sv, sc2, nl[hf]);   // padded queries: lse = +inf -> P = 0
-            const f32x2_t e = {__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1])};
+          for (int hf = 0; hf < 2; hf++) {   // 2-vectors: v_pk_mul_f32
+            const f32x2_t dpv = {dpacc[kt][2 * hf], dpacc[kt][2 * hf + 1]};
+            const f32x2_t e = {__builtin_amdgcn_exp2f(sacc[kt][2 * hf]), __builtin_amdgcn_exp2f(sacc[kt][2 * hf + 1])};
             const f32x2_t ds = e * dpv;
             pv[kt][q2][2 * hf] = e[0];
             pv[kt][q2][2 * hf + 1] = e[1];
@@ -566,9 +561,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(const bf16_t* __rest
 //   delta[q] = sum_d dO[q,d] O[q,d] (the softmax-backward row term) is computed HERE, from the dO fragments the wave holds
 //   anyway plus one read of its O rows, and written to `delta` for the dK/dV kernel, which is launched after this one:
 //   the separate delta pass (one more kernel on the critical path of every attention backward) is gone.
-// QW = 16-query tiles per wave (2: 128 queries per workgroup, the form of rounds 2-4; 4: 256 -- every K / V fragment, every transposed
-// K read of a key tile then serves four query tiles: the kernel is bound by LDS instruction count at head_dim 24, see the dK/dV kernel)
-template <int HDP, bool SM, int QW = 2>
+template <int HDP>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv_all,
                                                           const bf16_t* __restrict__ o_all,
                                                           const bf16_t* __restrict__ dout_all,
@@ -581,9 +574,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
   __shared__ __attribute__((aligned(16))) char smem[RINGB];
   const TrFrag<HDP> trf(threadIdx.x & 63);
   constexpr int KS = HDP / 32, DT = HeadTiles<HDP>::DT;
+  constexpr int QW = 2;   // 16-query tiles per wave
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int li = lane & 15, g = lane >> 4;
-  int logical = xcd_remap(blockIdx.x, gridDim.x);
+  int logical = xcd_logical(blockIdx.x, gridDim.x);
   const int si = attn_seg_of(sg, logical);
   const int S = sg.S[si], nqb = sg.nb[si];
   const int64_t rs = (int64_t)3 * H * hd;
@@ -626,11 +620,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
     lse_q[qt] = q < S ? lse2[((int64_t)b * H + h) * S + q] : INFINITY;
     dl_q[qt] = q < S ? dsum : 0.f;
     if (g == 0 && q < S) delta[((int64_t)b * H + h) * S + q] = dsum;
-    // SM: Q is the stationary operand of the score product and is used for nothing else here: it carries scale * log2 e
-    if constexpr (SM) {
+    // Q is the stationary operand of the score product and is used for nothing else here: it carries scale * log2 e
 #pragma unroll
-      for (int ks = 0; ks < KS; ks++) qf[qt][ks] = scale_frag(qf[qt][ks], sc);
-    }
+    for (int ks = 0; ks < KS; ks++) qf[qt][ks] = scale_frag(qf[qt][ks], sc);
   }
   f32x4_t dqacc[QW][DT];
 #pragma unroll
@@ -639,13 +631,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
     for (int dt = 0; dt < DT; dt++) dqacc[qt][dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
   f32x4_t ndl4[QW];   // -delta[q] of this lane's query, four times: the seed of every dP accumulator block
-  f32x4_t nls4[QW];   // SM: -lse2[q] four times: the seed of every score accumulator block (padded queries: -inf -> P = 0)
+  f32x4_t nls4[QW];   // -lse2[q] four times: the seed of every score accumulator block (padded queries: -inf -> P = 0)
 #pragma unroll
   for (int qt = 0; qt < QW; qt++) {
     ndl4[qt] = (f32x4_t){-dl_q[qt], -dl_q[qt], -dl_q[qt], -dl_q[qt]};
-    nls4[qt] = SM ? (f32x4_t){-lse_q[qt], -lse_q[qt], -lse_q[qt], -lse_q[qt]} : (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    nls4[qt] = (f32x4_t){-lse_q[qt], -lse_q[qt], -lse_q[qt], -lse_q[qt]};
   }
-  const f32x2_t sc2 = {sc, sc};
   const int nt = (S + 63) / 64;
   const bool wave_live = qb * (64 * QW) + __builtin_amdgcn_readfirstlane(w) * (16 * QW) < S;   // wave-uniform
   const TileDma<HDP, 256> dma(tid, hd);
@@ -671,7 +662,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
     nxt_off = nxt_off + BUFB == RINGB ? 0 : nxt_off + BUFB;
     // Two halves of the 64-key tile (c = 0, 1: keys 32c .. 32c+31 = the contraction chunk of one dQ MFMA): S^T / dP^T / dS^T of a half
     // for all QW query tiles, then its dQ MFMAs.  Per accumulator the same operations in the same order as the round-4 form (all
-    // four key blocks first, then both halves): bit-identical; only one half's scores are live, which is what lets QW = 4 fit.
+    // four key blocks first, then both halves): bit-identical; only one half's scores are live.
     // round 5: a wave all of whose queries lie beyond S skips the tile's arithmetic (it stores nothing), and a half all of whose KEYS are
     // padded is skipped by every wave (its dS is set to zero below: it would add zeros to every dQ accumulator)
     if (!wave_live) continue;
@@ -683,7 +674,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
       for (int qt = 0; qt < QW; qt++)
 #pragma unroll
         for (int k2 = 0; k2 < 2; k2++) {
-          sacc[qt][k2] = nls4[qt];    // zeros, or (SM) -lse2[q]: s - lse comes out of the matrix pipe
+          sacc[qt][k2] = nls4[qt];    // the score accumulators start at -lse2[q]: s - lse comes out of the matrix pipe
           dpacc[qt][k2] = ndl4[qt];   // the dP accumulators start at -delta[q]: dP - delta comes out of the matrix pipe
         }
 #pragma unroll
@@ -702,16 +693,13 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
       // dS^T = P^T (dP^T - delta)
 #pragma unroll
       for (int qt = 0; qt < QW; qt++) {
-        const f32x2_t nl = {-lse_q[qt], -lse_q[qt]};
 #pragma unroll
         for (int k2 = 0; k2 < 2; k2++)
 #pragma unroll
-          for (int hf = 0; hf < 2; hf++) {   // 2-vectors: v_pk_fma_f32 / v_pk_mul_f32
+          for (int hf = 0; hf < 2; hf++) {   // 2-vectors: v_pk_mul_f32
             const f32x2_t sv = {sacc[qt][k2][2 * hf], sacc[qt][k2][2 * hf + 1]};
             const f32x2_t dpv = {dpacc[qt][k2][2 * hf], dpacc[qt][k2][2 * hf + 1]};
-            f32x2_t a = sv;
-            if constexpr (!SM) a = __builtin_elementwise_fma(sv, sc2, nl);
-            const f32x2_t e = {__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1])};
+            const f32x2_t e = {__builtin_amdgcn_exp2f(sv[0]), __builtin_amdgcn_exp2f(sv[1])};
             const f32x2_t ds = e * dpv;
             sacc[qt][k2][2 * hf] = ds[0];
             sacc[qt][k2][2 * hf + 1] = ds[1];
@@ -755,9 +743,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
     for (int dt = 0; dt < DT; dt++)
 #pragma unroll
       for (int r = 0; r < 4; r++) {
-        float a = dqacc[0][dt][r] + dqacc[1][dt][r];
-        if constexpr (QW == 4) a = a + dqacc[2][dt][r] + dqacc[3][dt][r];
-        cq[dt][r] = row16_sum(a);
+        cq[dt][r] = row16_sum(dqacc[0][dt][r] + dqacc[1][dt][r]);
       }
     lgkm_barrier();   // every wave is done with the {K, V} ring: its first 4 x HDP floats become the combine buffer
     float* red = (float*)smem;
@@ -842,10 +828,9 @@ extern "C" int vj_attn_fwd_segs(const void* qkv, void* o, float* lse2, const vj_
   // scale < 0: the q part of qkv ALREADY carries |scale| * log2(e) (the qkv GEMM applied it before its bf16 rounding, epilogue 4
   // of vj_gemm_bf16_nt): the kernels' own factor becomes 1 (scale_frag(x, 1) is the identity)
   const float sc = scale < 0.f ? 1.0f : scale * LOG2E;
-  // row sums from the matrix pipe: head_dim 24 on the V image's pad column (RS = 1), the other head sizes from an all-ones operand (RS = 2);
-  // the vector-add form (RS = 0) of round 3 is no longer instantiated (profiles/r04_abab_rowsums.md)
-#define VJ_FWD_SM(HDPV, NB, RSV)                                                                                      \
-  hipLaunchKernelGGL((attn_fwd_sm_kernel<HDPV, 2, NB, RSV>), dim3((unsigned)nblk), dim3(256), 0, stream,               \
+  // row sums from the matrix pipe: head_dim 24 on the V image's pad column (RS = 1), the other head sizes from an all-ones operand (RS = 2)
+#define VJ_FWD_SM(HDPV, NB, RSV)                                                                                       \
+  hipLaunchKernelGGL((attn_fwd_sm_kernel<HDPV, NB, RSV>), dim3((unsigned)nblk), dim3(256), 0, stream,                  \
                      (const bf16_t*)qkv, (bf16_t*)o, lse2, sg, (int)H, (int)hd, sc)
   switch (pick_hdp(hd)) {
     case 32:
@@ -882,13 +867,12 @@ extern "C" int64_t vj_attn_bwd_segs_ws_bytes(const vj_seg_t* segs, int64_t n_seg
 }
 
 // dK/dV tiling: 16-key tiles per wave (32 keys at head_dim <= 32: every Q / dO fragment and transposed read serves two key tiles; 64 keys per
-// wave and 64 queries per wave in the dQ kernel were options in round 5: -0.09 / +0.23 ms per step, profiles/r05_attn_tiles.md)
+// wave, and 64 queries per wave in the dQ kernel, were tried in round 5: -0.09 / +0.23 ms per step, profiles/r05_attn_tiles.md)
 static int dkdv_kt(int64_t hd) { return pick_hdp(hd) == 32 ? 2 : 1; }
-static int dq_qw(int64_t) { return 2; }
 // rows of the column-partial matrices vj_attn_bwd_colsum writes for one [B, S] segment: colq [rows_q][H*hd], colkv [rows_kv][2*H*hd]
 extern "C" int vj_attn_bwd_colsum_rows(int64_t B, int64_t S, int64_t hd, int64_t* rows_q, int64_t* rows_kv) {
   VJ_CHECK_ARG(rows_q != nullptr && rows_kv != nullptr && hd % 8 == 0 && pick_hdp(hd) != 0, "vj_attn_bwd_colsum_rows: bad arguments");
-  *rows_q = B * cdiv64(S, 64 * dq_qw(hd));
+  *rows_q = B * cdiv64(S, 128);   // the dQ kernel: 128 queries per workgroup
   *rows_kv = B * cdiv64(S, 64 * dkdv_kt(hd));
   return 0;
 }
@@ -904,8 +888,7 @@ extern "C" int vj_attn_bwd_segs(const void* qkv, const void* o, const void* dout
   const int kt = dkdv_kt(hd);
   AttnSegs sq, sk;
   int64_t gq = 0, gk = 0;
-  const int qw = dq_qw(hd);
-  if (int rc = make_segs(segs, n_segs, H, 64 * qw, &sq, &gq, "vj_attn_bwd")) return rc;
+  if (int rc = make_segs(segs, n_segs, H, 128, &sq, &gq, "vj_attn_bwd")) return rc;
   if (int rc = make_segs(segs, n_segs, H, 64 * kt, &sk, &gk, "vj_attn_bwd")) return rc;
   if (gq == 0) return 0;
   int64_t rows_end = 0;   // the delta workspace mirrors lse2: H floats per token row up to the last row of the list
@@ -921,15 +904,15 @@ extern "C" int vj_attn_bwd_segs(const void* qkv, const void* o, const void* dout
   const float sc = pre ? 1.0f : sabs * LOG2E;
   const float kscale = pre ? 1.0f / LOG2E : sabs;
   // dQ first: it also produces delta[b,h,s] = dO . O for the dK/dV kernel behind it on the same stream.
-  // dK/dV: KTV 16-key tiles per wave (option attn_dkdv_kt: 0 = per head-dim class, 1 / 2 forced)
-#define VJ_BWD_LAUNCH(HDPV, KTV)                                                                                   \
-  do {                                                                                                             \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<HDPV, true, 2>), dim3((unsigned)gq), dim3(256), 0, stream,               \
+  // dK/dV: KTV = dkdv_kt(hd) 16-key tiles per wave
+#define VJ_BWD_LAUNCH(HDPV, KTV)                                                                                    \
+  do {                                                                                                              \
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<HDPV>), dim3((unsigned)gq), dim3(256), 0, stream,                        \
                        (const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)dout, lse2, delta, (bf16_t*)dqkv, sq,   \
-                       (int)H, (int)hd, sc, sabs, colq);                                                           \
-    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<HDPV, KTV, true>), dim3((unsigned)gk), dim3(256), 0, stream,           \
+                       (int)H, (int)hd, sc, sabs, colq);                                                            \
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<HDPV, KTV>), dim3((unsigned)gk), dim3(256), 0, stream,                 \
                        (const bf16_t*)qkv, (const bf16_t*)dout, lse2, delta, (bf16_t*)dqkv, sk, (int)H, (int)hd,    \
-                       sc, kscale, colkv);                                                                         \
+                       sc, kscale, colkv);                                                                          \
   } while (0)
   switch (pick_hdp(hd)) {
     case 32: VJ_BWD_LAUNCH(32, 2); break;

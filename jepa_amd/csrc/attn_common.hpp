@@ -1,5 +1,5 @@
-// Shared pieces of the attention kernels (attention.hip: forward + the two-kernel backward; attention_bwd_fused.hip: the one-pass
-// backward of round 6): the swizzled row-major tile image, transposed fragment reads, segment tables.
+// Shared pieces of the attention kernels (attention.hip: forward + the two-kernel backward): the swizzled row-major tile image,
+// transposed fragment reads, segment tables.
 #pragma once
 #include "common.hpp"
 #include "lds_pipe.hpp"
@@ -8,21 +8,16 @@
 #include <type_traits>
 #include <cstdlib>
 
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-
-
 __device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
   typedef __bf16 bf2_t __attribute__((ext_vector_type(2)));
   bf2_t v = {(__bf16)lo, (__bf16)hi};
   return __builtin_bit_cast(uint32_t, v);
 }
 
-#define DEFER_LOG2 5.0f  // forward softmax: rescale O only when a row max grows by more than 2^5
-
-// ---- round 4: "seeded" soft-max (template parameter SM = 1; SM = 0 keeps the round-3 arithmetic for A/B) ----------------
+// ---- round 4: "seeded" soft-max (the only form of the three kernels; the round-3 arithmetic it was measured against is gone) --------
 // The attention kernels are bound by vector-instruction issue and the matrix and vector pipes of a SIMD add
 // (profiles/r03_valu_mfma_probe.md), so only REMOVING vector instructions per score helps.  Per score the round-3 kernels
-// spend: 1/2 v_pk_fma (s*sc - m), 1 v_exp, 1/2 v_max3 (forward), 1/2 v_pk_add (row sum), 1/2 v_cvt_pk.  With SM = 1:
+// spend: 1/2 v_pk_fma (s*sc - m), 1 v_exp, 1/2 v_max3 (forward), 1/2 v_pk_add (row sum), 1/2 v_cvt_pk.  Seeded:
 //   * the soft-max scale scale*log2(e) is folded into the STATIONARY operand of the score product (Q in the forward and in
 //     dQ, K in dK/dV), once per workgroup: bf16(c * x) -- one more bf16 rounding of that operand;
 //   * the score accumulators START at -m_run (forward) / -lse2[q] (backward), so the MFMA delivers s - m and v_exp_f32
@@ -34,7 +29,7 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
 //     + two cross-lane exchanges).  OR >= max for unsigned integers, so "bit clear" PROVES every P < 2 (inf / NaN have the
 //     bit set and take the slow path, which computes the exact maximum and re-bases exactly like the round-3 code);
 //   * head_dim 24 (the predictor; 32-wide class): column 24 of the V image holds 1.0, so the P.V MFMA accumulates the row
-//     sum of the bf16-rounded P in output column 24 -- the row sums leave the vector pipe too (template parameter PSUM).
+//     sum of the bf16-rounded P in output column 24 -- the row sums leave the vector pipe too (the forward kernel's RS = 1).
 #define SM_HEADROOM 5.0f
 __device__ __forceinline__ bf16x8_t scale_frag(bf16x8_t f, float c) {
   u32x4_t w = __builtin_bit_cast(u32x4_t, f);
@@ -204,9 +199,3 @@ __device__ __forceinline__ int attn_seg_of(const AttnSegs& sg, int& logical) {
   logical -= si > 0 ? sg.blk_end[si - 1] : 0;
   return si;
 }
-
-__device__ __forceinline__ int xcd_remap(int bid, int nblk) {
-  const int qx = nblk >> 3, rx = nblk & 7, xcd = bid & 7, pos = bid >> 3;
-  return (xcd < rx ? xcd * (qx + 1) : rx * (qx + 1) + (xcd - rx) * qx) + pos;
-}
-

@@ -59,90 +59,22 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
-// erf-GELU (nn.GELU() default, reference modules.py:32) and its derivative.  erf by Abramowitz-Stegun 7.1.26
-// (|abs err| <= 1.5e-7, far below the bf16 rounding of the result): one v_rcp + one v_exp + 6 FMAs instead of
-// libm's ~40-instruction erff -- the fc1 epilogue applies this to every element of the 4D-wide hidden layer.
-// The exponential exp(-x^2/2) is shared between erf(x/sqrt2) and the Gaussian term of the derivative.
-__device__ __forceinline__ void erf_core(float x, float& erf_v, float& gauss) {
-  const float z = fabsf(x) * 0.70710678118654752f;          // |x|/sqrt(2)
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
-  gauss = __expf(-z * z);                                     // exp(-x^2/2)
-  float p = fmaf(1.061405429f, t, -1.453152027f);
-  p = fmaf(p, t, 1.421413741f);
-  p = fmaf(p, t, -0.284496736f);
-  p = fmaf(p, t, 0.254829592f);
-  const float e = 1.0f - p * t * gauss;
-  erf_v = copysignf(e, x);
-}
-__device__ __forceinline__ float gelu_f(float x) {
-  float e, g;
-  erf_core(x, e, g);
-  return 0.5f * x * (1.0f + e);
-}
-__device__ __forceinline__ float dgelu_f(float x) {
-  float e, g;
-  erf_core(x, e, g);
-  return 0.5f * (1.0f + e) + x * 0.3989422804014327f * g;
-}
-
-// ---- 2-wide versions for the GEMM epilogues: the polynomial, the products and the final combination issue as
-// v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 (two elements per instruction); only rcp / exp2 / the sign handling stay
-// scalar.  q = 0.5 * erfc(|x|/sqrt2) = 0.5 * poly(t) * t * exp(-x^2/2) (same A-S 7.1.26 coefficients, halved).
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void half_erfc2(f32x2_t x, f32x2_t& q, f32x2_t& gauss) {
-  const float k = 0.3275911f * 0.70710678118654752f;
-  f32x2_t t = {__builtin_amdgcn_rcpf(fmaf(k, fabsf(x[0]), 1.0f)), __builtin_amdgcn_rcpf(fmaf(k, fabsf(x[1]), 1.0f))};
-  const f32x2_t c = {-0.72134752044448170f, -0.72134752044448170f};   // -0.5 * log2(e)
-  const f32x2_t a = (x * c) * x;
-  gauss = (f32x2_t){__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1])};   // exp(-x^2/2)
-  const f32x2_t c5 = {0.5f * 1.061405429f, 0.5f * 1.061405429f}, c4 = {0.5f * -1.453152027f, 0.5f * -1.453152027f},
-                 c3 = {0.5f * 1.421413741f, 0.5f * 1.421413741f}, c2 = {0.5f * -0.284496736f, 0.5f * -0.284496736f},
-                 c1 = {0.5f * 0.254829592f, 0.5f * 0.254829592f};
-  f32x2_t p = __builtin_elementwise_fma(c5, t, c4);
-  p = __builtin_elementwise_fma(p, t, c3);
-  p = __builtin_elementwise_fma(p, t, c2);
-  p = __builtin_elementwise_fma(p, t, c1);
-  q = (p * t) * gauss;
-}
-// relu on the bit pattern: negative floats are negative integers (one v_max_i32; fmaxf() on a value that was assembled
-// from bits costs a second, canonicalising v_max_f32).  NaN passes through or becomes 0 -- the callers' inputs are finite.
-__device__ __forceinline__ float relu_bits(float x) {
-  const int b = __float_as_int(x);
-  return __int_as_float(b > 0 ? b : 0);
-}
-// gelu(x) = x * Phi(x) = max(x, 0) - |x * q|   (q = 0.5 erfc(|x|/sqrt2) >= 0; relative accuracy is kept in the negative tail)
-// (a single v_fma_f32 with -|x| as a source modifier would save half an instruction per element, but hipcc packs the two
-//  FMAs into a v_pk_fma_f32, which has no |x| modifier, and forcing the scalar form through inline assembly makes the
-//  one-pass epilogue of gemm8.hip spill 140 VGPRs)
-__device__ __forceinline__ f32x2_t gelu2(f32x2_t x) {
-  f32x2_t q, g;
-  half_erfc2(x, q, g);
-  const f32x2_t h = x * q;
-  return (f32x2_t){relu_bits(x[0]) - fabsf(h[0]), relu_bits(x[1]) - fabsf(h[1])};
-}
-// gelu(x) AND gelu'(x) from one evaluation of the erfc core: the fc1 epilogue of a layer that will run backward stores
-// gelu'(u) (bf16) instead of the pre-activation u, and the fc2 dgrad epilogue only multiplies by it -- the backward never
-// re-evaluates exp / rcp / the polynomial (u has no other consumer)
-__device__ __forceinline__ void gelu_dgelu2(f32x2_t x, f32x2_t& y, f32x2_t& d) {
-  f32x2_t q, g;
-  half_erfc2(x, q, g);
-  const f32x2_t h = x * q;
-  y = (f32x2_t){relu_bits(x[0]) - fabsf(h[0]), relu_bits(x[1]) - fabsf(h[1])};   // = gelu2(x), bit for bit
-  const f32x2_t half = {0.5f, 0.5f}, a = half - q;
-  const f32x2_t phi = half + (f32x2_t){copysignf(a[0], x[0]), copysignf(a[1], x[1])};
-  const f32x2_t c = {0.3989422804014327f, 0.3989422804014327f};
-  d = __builtin_elementwise_fma(x * c, g, phi);                                    // = dgelu2(x), bit for bit
-}
-// ---- round 4: q = Phi(-|x|) without the reciprocal (option gelu_poly, default) --------------------------------------------
+// erf-GELU (nn.GELU() default, reference modules.py:32) and its derivative, 2-wide for the GEMM epilogues: the polynomial, the products
+// and the final combination issue as v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 (two elements per instruction); only exp2 and the sign
+// handling stay scalar.  The fc1 epilogue of a layer that will run backward stores gelu'(u) (bf16) instead of the pre-activation u, and
+// the fc2 dgrad epilogue only multiplies by it -- the backward never re-evaluates exp / the polynomial (u has no other consumer).
+// q = Phi(-|x|) is exp2 of a polynomial.  Rounds 1-3 took it from erf by Abramowitz-Stegun 7.1.26 (one v_rcp + one v_exp + 4 FMAs +
+// 3 multiplies, relu on the bit pattern); round 4 replaced that form and round 6 removed its run-time switch (docs/history/,
+// profiles/r04_abab_gelu_poly.md).
 // log2 Phi(-a) is a smooth, nearly quadratic function of a >= 0 (-1 at 0, ~ -a^2 log2(e)/2 - log2(a sqrt(2 pi)) far out), so
 // q(a) = exp2(L(a)) with a degree-6 minimax polynomial L on [0, 5] (Lawson iteration, max |dL| 1.8e-5, i.e. q to 1.3e-5
-// RELATIVE over the whole range, tail included) replaces A-S 7.1.26's v_rcp + 4 FMAs + 3 multiplies by 6 FMAs; the one v_exp
-// stays.  a = min(|x|, 5) is ONE instruction (v_min_f32 with the |x| source modifier) and is used for the product a * q as
+// RELATIVE over the whole range, tail included) needs 6 FMAs and one v_exp, no reciprocal.
+// a = min(|x|, 5) is ONE instruction (v_min_f32 with the |x| source modifier) and is used for the product a * q as
 // well: beyond 5 the result is relu(x) - 5 q(5) = relu(x) - 1.4e-6 (exact: relu(x) - |x| Phi(-|x|), at most 1.4e-6 there).
 // Against the correctly rounded bf16 erf-GELU over ALL finite bf16 inputs x > -5: 5 of 20712 results differ (by one bf16 ulp);
 // the A-S form: 22 (tests/test_gelu_poly.py enumerates them on the CPU with this arithmetic).  relu(x) is taken as
-// 0.5 * (x + |x|): exact for finite x, and a NaN of EITHER sign propagates (relu_bits drops a negative-signed NaN, which
-// the A-S form only survives because its reciprocal carries the NaN into q).
+// 0.5 * (x + |x|): exact for finite x, and a NaN of EITHER sign propagates.
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
 // x + |x| = 2 relu(x) as ONE v_add_f32 with the |x| source modifier (hipcc turns the C expression into v_and + a packed add);
 // exact for |x| < 2^127 (no cancellation error for negative x, unlike 0.5 x + 0.5 |x| - ...), +inf above; a NaN of either sign stays a NaN
 __device__ __forceinline__ float twice_relu(float x) {
@@ -188,14 +120,12 @@ __device__ __forceinline__ void gelu_dgelu2_lp(f32x2_t x, f32x2_t& y, f32x2_t& d
   const f32x2_t k = {0.3989422804014327f, 0.3989422804014327f};
   d = __builtin_elementwise_fma(x * k, g, phi);
 }
-// gelu'(x) = Phi(x) + x * pdf(x),  Phi(x) = 0.5 + copysign(0.5 - q, x)
-__device__ __forceinline__ f32x2_t dgelu2(f32x2_t x) {
-  f32x2_t q, g;
-  half_erfc2(x, q, g);
-  const f32x2_t half = {0.5f, 0.5f}, a = half - q;
-  const f32x2_t phi = half + (f32x2_t){copysignf(a[0], x[0]), copysignf(a[1], x[1])};
-  const f32x2_t c = {0.3989422804014327f, 0.3989422804014327f};
-  return __builtin_elementwise_fma(x * c, g, phi);
+
+// XCD-aware band mapping (bijective for any grid size): workgroup `bid` of `nblk` -> logical index such that each XCD (private L2;
+// hardware dispatches workgroup b to XCD b % 8) works on a contiguous band of tiles (GEMM) or of (sample, head, block) items (attention).
+__device__ __forceinline__ int xcd_logical(int bid, int nblk) {
+  const int qx = nblk >> 3, rx = nblk & 7, xcd = bid & 7, pos = bid >> 3;
+  return (xcd < rx ? xcd * (qx + 1) : rx * (qx + 1) + (xcd - rx) * qx) + pos;
 }
 
 // ---- per-device one-time setup ------------------------------------------------------------------------------------

@@ -35,7 +35,7 @@ struct GemmArgs {   // every member has a default: a launcher sets what it means
   const float* lnf_rs = nullptr;   // [M][2] fp32, nullable (null: plain epilogue)
   const float* lnf_c = nullptr;    // [N] fp32
   int half_tiles = 0;    // persistent kernel: N % 256 == 128 and the shifted last column tile computes its own 128 columns only (gemm8p.hip)
-  int epi_pre = 0;       // persistent kernel: form of the epilogue (option gemm_epi_pre: 4 = pipelined passes, 0 = straight passes; PRE below)
+  int epi_pre = 0;       // persistent kernel: form of the epilogue (option gemm_epi_pre: 4 = pipelined passes, 0 = straight passes; EF_PIPE below)
 };
 static_assert(std::is_trivially_copyable_v<GemmArgs> && sizeof(GemmArgs) == 216, "GemmArgs is a kernel argument: its layout is part of every GEMM kernel");
 
@@ -55,6 +55,20 @@ static inline int with_epilogue(int epilogue, void* ws, int64_t ws_bytes, F&& f)
   }
 }
 
+// Variant of a fused epilogue: one flag word, the template argument F of gemm_epilogue_impl / gemm_epilogue_staged.  Every flag is
+// workgroup-uniform (wave-uniform for EF_EDGE / EF_QS) and resolved by the caller-side switch, so that each variant is branch-free inside.
+enum : unsigned {
+  EF_OPT = 1,    // the nullable operand is there: residual (EPI_BF16), aux_out = write the saved gelu'(u) too (EPI_GELU), split-K partials
+                 // into ws[slice] (EPI_F32); EPI_DGELU always has its operand (aux_in) and is always launched with EF_OPT
+  EF_EDGE = 2,   // the wave tile crosses M or N: load addresses are clamped, stores predicated (interior tiles carry no predicates at all)
+  EF_CSUM = 4,   // staged, EPI_DGELU on the persistent kernel: also write the fp32 column sums of the output tile to p.colpart (see below)
+  EF_QS = 8,     // EPI_BF16 without residual: this wave tile holds q columns of a qkv projection, columns n < qcols are scaled by qscale
+  EF_LNF = 16,   // LayerNorm folded into the GEMM (GemmArgs::lnf_rs / lnf_c): bf16 / GELU epilogue, no residual, no saved derivative
+  EF_PIPE = 32,  // staged, persistent kernel only: software-pipelined passes, the row operand as row-major pieces (see below); else straight passes
+  EF_NB = 64,    // staged: the launch has no bias (resolved by the caller): no bias registers and no `+ bias` instruction (see below)
+  EF_BETA = 128, // direct, EPI_F32 without split-K: accumulate beta * C (not used on the training path: every wgrad overwrites)
+};
+
 // Fused epilogue.  acc[i][j] comes from MFMA 16x16x32 issued with swapped operands (D = Bfrag x Afrag): lane
 // (g = lane>>4, r = lane&15) owns row m = .. + i*16 + r and the 4 consecutive columns n = .. + j*16 + 4g + {0..3}.
 //
@@ -62,12 +76,14 @@ static inline int with_epilogue(int epilogue, void* ws, int64_t ws_bytes, F&& f)
 // wait-count insertion falls back to `s_waitcnt vmcnt(0)` -- i.e. "drain every store issued so far" -- at each use of a
 // loaded value once control flow separates the load from the use.  So there are no `continue`s and no per-block
 // branches here: edge rows / columns are handled by clamping load addresses and predicating the stores only, the
-// nullable operands are resolved once by the caller-side variant switch (HAS_OPT), the bias is complete before the
+// nullable operands are resolved once by the caller-side variant switch (EF_OPT), the bias is complete before the
 // first row (one explicit wait), and the row operands (residual / saved pre-activation) are fetched one row-block ahead
 // so that a row's stores stay in flight while the next row is computed.
-template <int EPI, int FM, int FN, bool HAS_OPT, bool EDGE, bool BETA = false, bool QS = false, bool LP = false, bool LNF = false>
+template <int EPI, int FM, int FN, unsigned F>
 __device__ __forceinline__ void gemm_epilogue_impl(const GemmArgs& p, f32x4_t (&acc)[FM][FN], int64_t m_base,
                                                    int64_t n_base, int frow, int fg, int slice) {
+  constexpr bool HAS_OPT = F & EF_OPT, EDGE = F & EF_EDGE, BETA = F & EF_BETA, QS = F & EF_QS, LNF = F & EF_LNF;
+  static_assert(!(F & (EF_CSUM | EF_PIPE | EF_NB)), "column sums, pipelined passes, no-bias form: staged epilogue only");
   static_assert(!QS || (EPI == EPI_BF16 && !HAS_OPT), "column scale: the qkv projection (bf16 output, no residual)");
   static_assert(!LNF || ((EPI == EPI_BF16 || EPI == EPI_GELU) && !HAS_OPT), "LayerNorm fold: bf16 / GELU epilogue, no residual, no saved derivative");
   const int64_t ncol0 = n_base + fg * 4;   // this lane's first column; tile j adds j*16
@@ -122,7 +138,7 @@ __device__ __forceinline__ void gemm_epilogue_impl(const GemmArgs& p, f32x4_t (&
           o.y *= p.alpha;
           o.z *= p.alpha;
           o.w *= p.alpha;
-          if constexpr (BETA) {   // accumulate into C (not used on the training path: every wgrad overwrites)
+          if constexpr (BETA) {
             const float4 c0 = *(const float4*)(c32 + ncl[j]);
             o.x += p.beta * c0.x;
             o.y += p.beta * c0.y;
@@ -191,23 +207,15 @@ __device__ __forceinline__ void gemm_epilogue_impl(const GemmArgs& p, f32x4_t (&
           // GELU (and, for a layer that will run backward, gelu') of the bf16-ROUNDED pre-activation
           if constexpr (HAS_OPT) {
             f32x2_t d01, d23;
-            if constexpr (LP) {
-              gelu_dgelu2_lp((f32x2_t){bf_lo(u[0]), bf_hi(u[0])}, v01, d01);
-              gelu_dgelu2_lp((f32x2_t){bf_lo(u[1]), bf_hi(u[1])}, v23, d23);
-            } else {
-              gelu_dgelu2((f32x2_t){bf_lo(u[0]), bf_hi(u[0])}, v01, d01);
-              gelu_dgelu2((f32x2_t){bf_lo(u[1]), bf_hi(u[1])}, v23, d23);
-            }
+            gelu_dgelu2_lp((f32x2_t){bf_lo(u[0]), bf_hi(u[0])}, v01, d01);
+            gelu_dgelu2_lp((f32x2_t){bf_lo(u[1]), bf_hi(u[1])}, v23, d23);
             u32x2_t dw;
             dw[0] = pack_bf2(d01[0], d01[1]);
             dw[1] = pack_bf2(d23[0], d23[1]);
             if (mok && cok[j]) *(u32x2_t*)(auxo + ncl[j]) = dw;
-          } else if constexpr (LP) {
+          } else {
             v01 = gelu2_lp((f32x2_t){bf_lo(u[0]), bf_hi(u[0])});
             v23 = gelu2_lp((f32x2_t){bf_lo(u[1]), bf_hi(u[1])});
-          } else {
-            v01 = gelu2((f32x2_t){bf_lo(u[0]), bf_hi(u[0])});
-            v23 = gelu2((f32x2_t){bf_lo(u[1]), bf_hi(u[1])});
           }
         } else if constexpr (EPI == EPI_DGELU) {
           const u32x2_t u = opnd[i & 1][j];   // saved gelu'(u)
@@ -234,25 +242,27 @@ __device__ __forceinline__ void gemm_epilogue_impl(const GemmArgs& p, f32x4_t (&
 // swizzled by (row >> 1) & 7: conflict-free reads, 2-way writes that hide under the ds_write data transfer) and reads
 // it back row-major: one ds_read_b128 + one 16-byte store per lane, eight complete 128-byte lines per instruction.
 // The arithmetic (bias, residual, GELU) stays in the MFMA layout and is identical to gemm_epilogue_impl.
-// CSUM (EPI_DGELU only): the wave also sums its 128 x 64 output tile over the rows (fp32 values before the bf16 rounding;
+// EF_CSUM (EPI_DGELU only): the wave also sums its 128 x 64 output tile over the rows (fp32 values before the bf16 rounding;
 // rows below `row_lo` -- the part of a SHIFTED edge tile that belongs to its neighbour -- are left out) and writes the 64
 // column sums to p.colpart[slot][n_base ..]: du = dY of fc1 is produced here, so fc1's bias gradient costs 64 packed FMAs + 64
 // DPP adds per wave tile instead of a second pass over du (colsum_bf16_kernel: 84 MB per ViT-L context block).
-// PRE (round 5, persistent kernel only): 0 = straight passes -- the row operand (residual / saved gelu') of block i + 1 is requested while
-// block i is computed, every pass is {eight staging writes, four times {read back, wait, store}}; 4 (default) = the row operand as
-// sixteen row-major 16-byte loads issued before anything else (eight full 128-byte lines per instruction, parked in the staging area pass
+// EF_PIPE (round 5, persistent kernel only; option gemm_epi_pre, the kernels' PRE: 0 = clear, 4 = set, the default).  Clear = straight passes
+// -- the row operand (residual / saved gelu') of block i + 1 is requested while block i is computed, every pass is {eight staging writes,
+// four times {read back, wait, store}}; set = the row operand as sixteen row-major 16-byte loads issued before anything else (eight full 128-byte lines per instruction, parked in the staging area pass
 // by pass and read back in the MFMA layout -- the mirror image of the output path) and software-PIPELINED passes (see the pass loop).
 // Same values, same arithmetic: bit-identical outputs (profiles/r05_epi_pipeline.md; the intermediate forms 1 - 3 and the two
 // diagnostic copies of round 5 are recorded there).
-// NB: the launch has no bias (workgroup-uniform, resolved by the caller -- every dgrad GEMM): no bias registers (the dGELU epilogue with all its
-// row operand in flight (PRE) and sixteen column-sum accumulators is otherwise 4 VGPRs over the budget, and hipcc's spill lands between the
+// EF_NB: the launch has no bias (workgroup-uniform, resolved by the caller -- every dgrad GEMM): no bias registers (the dGELU epilogue with all its
+// row operand in flight (EF_PIPE) and sixteen column-sum accumulators is otherwise 4 VGPRs over the budget, and hipcc's spill lands between the
 // operand loads behind a vmcnt(0)) and no `+ bias` instruction (64 of a plain epilogue's ~200 vector instructions per wave tile).  Dropping
 // `+ 0.0f` keeps the bits: an accumulator that starts at +0 and is only ever added to cannot hold -0 (x + (-x) and (+0) + (-0) are +0 in
 // round-to-nearest), so there is no -0 for `+ 0.0f` to turn into +0.
-template <int EPI, bool HAS_OPT, bool EDGE, int IPP, bool CSUM = false, bool QS = false, bool LP = false, bool LNF = false, int PRE = 0, bool NB = false>
+template <int EPI, int IPP, unsigned F>
 __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs& p, f32x4_t (&acc)[8][4], int64_t m_base,
                                                      int64_t n_base, int frow, int fg, int lane, char* stage,
                                                      int64_t row_lo = 0, int slot = 0) {
+  constexpr bool HAS_OPT = F & EF_OPT, EDGE = F & EF_EDGE, CSUM = F & EF_CSUM, QS = F & EF_QS, LNF = F & EF_LNF, PIPE = F & EF_PIPE, NB = F & EF_NB;
+  static_assert(!(F & EF_BETA), "beta * C: direct fp32 epilogue only");
   // IPP = 16-row blocks per pass: 8 -> the whole wave tile in one 16 KB pass (stage = 16 KB per wave, the dead operand
   // ring of the one-tile-per-workgroup kernel); 2 -> four 4 KB passes (persistent kernel: the ring already holds the
   // next tile's first parts, the staging area is a separate 32 KB).
@@ -294,10 +304,8 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs& p, f32x4_t 
     }
   }
   constexpr bool HAS_OPND = (EPI == EPI_DGELU) || (EPI == EPI_BF16 && HAS_OPT);
-  constexpr bool PIPE = PRE >= 4;                 // pipelined passes (also for epilogues without a row operand)
-  constexpr bool PRM = HAS_OPND && PIPE;          // row operand as row-major pieces through the staging area
-  static_assert(PRE == 0 || PRE == 4, "epilogue forms: straight (0) or pipelined (4)");
-  static_assert(PRE == 0 || (IPP == 2 && !EDGE), "pipelined passes: interior tiles of the persistent kernel");
+  constexpr bool PRM = HAS_OPND && PIPE;          // row operand as row-major pieces through the staging area (PIPE alone: epilogues without one)
+  static_assert(!PIPE || (IPP == 2 && !EDGE), "pipelined passes: interior tiles of the persistent kernel");
   const bf16_t* opnd_p = (EPI == EPI_DGELU) ? p.aux_in : p.res;
   const int64_t opnd_ld = (EPI == EPI_DGELU) ? p.ldaux : p.ldr;
   const int rrow = lane >> 3, rch = lane & 7;   // row-major side: 8 lanes per 128-byte row, 8 rows per instruction
@@ -405,21 +413,13 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs& p, f32x4_t 
       // GELU (and, for a layer that will run backward, gelu') of the bf16-ROUNDED pre-activation
       if constexpr (TWO_OUT) {
         f32x2_t d01, d23;
-        if constexpr (LP) {
-          gelu_dgelu2_lp((f32x2_t){bf_lo(w[0]), bf_hi(w[0])}, v01, d01);
-          gelu_dgelu2_lp((f32x2_t){bf_lo(w[1]), bf_hi(w[1])}, v23, d23);
-        } else {
-          gelu_dgelu2((f32x2_t){bf_lo(w[0]), bf_hi(w[0])}, v01, d01);
-          gelu_dgelu2((f32x2_t){bf_lo(w[1]), bf_hi(w[1])}, v23, d23);
-        }
+        gelu_dgelu2_lp((f32x2_t){bf_lo(w[0]), bf_hi(w[0])}, v01, d01);
+        gelu_dgelu2_lp((f32x2_t){bf_lo(w[1]), bf_hi(w[1])}, v23, d23);
         dw[0] = pack_bf2(d01[0], d01[1]);
         dw[1] = pack_bf2(d23[0], d23[1]);
-      } else if constexpr (LP) {
+      } else {
         v01 = gelu2_lp((f32x2_t){bf_lo(w[0]), bf_hi(w[0])});
         v23 = gelu2_lp((f32x2_t){bf_lo(w[1]), bf_hi(w[1])});
-      } else {
-        v01 = gelu2((f32x2_t){bf_lo(w[0]), bf_hi(w[0])});
-        v23 = gelu2((f32x2_t){bf_lo(w[1]), bf_hi(w[1])});
       }
     } else if constexpr (EPI == EPI_DGELU) {
       v01 *= (f32x2_t){bf_lo(u[0]), bf_hi(u[0])};   // u = saved gelu'(u)
@@ -468,7 +468,7 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs& p, f32x4_t 
       flush((bf16_t*)p.C, p.ldc, ps * RPP * 16, TWO_OUT ? RPP : 0);
     }
   } else {
-    // PIPELINED passes (PRE 4).  The straight form above is, per wave, a chain of exposed LDS round trips: eight writes, then four times
+    // PIPELINED passes (EF_PIPE).  The straight form above is, per wave, a chain of exposed LDS round trips: eight writes, then four times
     // {ds_read_b128, s_waitcnt lgkmcnt(0), global_store} (hipcc keeps the source order), then the next pass's arithmetic -- sixteen serialised
     // round trips per wave tile on an LDS that all eight waves use at once; the phase stamps (tools/gemm_stamps.py) put 2.9 ... 3.5 us of a
     // 25 us K = 1024 tile into an epilogue whose LDS, store and vector work are ~1 us each.  Here a pass is
@@ -615,14 +615,15 @@ __device__ __forceinline__ bool gemm_epilogue_try_staged(const GemmArgs& p, f32x
     else if constexpr (EPI == EPI_BF16) opt = p.res != nullptr;
     else opt = true;
     const bool edge = __builtin_amdgcn_readfirstlane((m_base + 128 > p.M) || (n_base + 64 > p.N));
-    constexpr int XP = (PRE >= 4 && IPP == 2) ? PRE : 0;   // pipelined passes: every interior variant of the persistent kernel
+    static_assert(PRE == 0 || PRE == 4, "epilogue forms: straight (0) or pipelined (4)");
+    constexpr unsigned XP = (PRE == 4 && IPP == 2) ? EF_PIPE : 0;   // pipelined passes: every interior variant of the persistent kernel
     if constexpr (EPI == EPI_DGELU && IPP == 2) {   // persistent kernel (every tile interior): optional fused column sums
       if (p.colpart != nullptr && !edge) {
         if constexpr (PRE != 0) {   // (a dgrad GEMM has no bias; with one, the kernel that keeps bias registers)
-          if (p.bias == nullptr) gemm_epilogue_staged<EPI, true, false, IPP, true, false, false, false, PRE, true>(p, acc, m_base, n_base, frow, fg, lane, stage, row_lo, slot);
-          else gemm_epilogue_staged<EPI, true, false, IPP, true>(p, acc, m_base, n_base, frow, fg, lane, stage, row_lo, slot);
+          if (p.bias == nullptr) gemm_epilogue_staged<EPI, IPP, EF_OPT | EF_CSUM | EF_PIPE | EF_NB>(p, acc, m_base, n_base, frow, fg, lane, stage, row_lo, slot);
+          else gemm_epilogue_staged<EPI, IPP, EF_OPT | EF_CSUM>(p, acc, m_base, n_base, frow, fg, lane, stage, row_lo, slot);
         } else {
-          gemm_epilogue_staged<EPI, true, false, IPP, true>(p, acc, m_base, n_base, frow, fg, lane, stage, row_lo, slot);
+          gemm_epilogue_staged<EPI, IPP, EF_OPT | EF_CSUM>(p, acc, m_base, n_base, frow, fg, lane, stage, row_lo, slot);
         }
         return true;
       }
@@ -633,11 +634,11 @@ __device__ __forceinline__ bool gemm_epilogue_try_staged(const GemmArgs& p, f32x
       if (opt && !edge && (EPI == EPI_DGELU ? p.bias == nullptr : p.lnf_rs == nullptr)) {
         if constexpr (EPI == EPI_BF16) {   // (pipelined form: a residual GEMM without a bias -- the dgrad that adds the skip path's gradient)
           if (p.bias == nullptr) {
-            gemm_epilogue_staged<EPI, true, false, IPP, false, false, false, false, PRE, true>(p, acc, m_base, n_base, frow, fg, lane, stage);
+            gemm_epilogue_staged<EPI, IPP, EF_OPT | EF_PIPE | EF_NB>(p, acc, m_base, n_base, frow, fg, lane, stage);
             return true;
           }
         }
-        gemm_epilogue_staged<EPI, true, false, IPP, false, false, false, false, PRE, EPI == EPI_DGELU>(p, acc, m_base, n_base, frow, fg, lane, stage);
+        gemm_epilogue_staged<EPI, IPP, EF_OPT | EF_PIPE | (EPI == EPI_DGELU ? EF_NB : 0)>(p, acc, m_base, n_base, frow, fg, lane, stage);
         return true;
       }
     }
@@ -645,49 +646,49 @@ __device__ __forceinline__ bool gemm_epilogue_try_staged(const GemmArgs& p, f32x
       if (p.lnf_rs != nullptr) {   // LayerNorm folded into this GEMM (workgroup-uniform; the launcher guarantees: no residual / aux_out)
         if constexpr (EPI == EPI_BF16) {
           if (p.qscale != 0.f && n_base < p.qcols) {
-            if (edge) gemm_epilogue_staged<EPI, false, true, IPP, false, true, false, true>(p, acc, m_base, n_base, frow, fg, lane, stage);
-            else gemm_epilogue_staged<EPI, false, false, IPP, false, true, false, true, XP>(p, acc, m_base, n_base, frow, fg, lane, stage);
+            if (edge) gemm_epilogue_staged<EPI, IPP, EF_EDGE | EF_QS | EF_LNF>(p, acc, m_base, n_base, frow, fg, lane, stage);
+            else gemm_epilogue_staged<EPI, IPP, EF_QS | EF_LNF | XP>(p, acc, m_base, n_base, frow, fg, lane, stage);
           } else {
-            if (edge) gemm_epilogue_staged<EPI, false, true, IPP, false, false, false, true>(p, acc, m_base, n_base, frow, fg, lane, stage);
-            else gemm_epilogue_staged<EPI, false, false, IPP, false, false, false, true, XP>(p, acc, m_base, n_base, frow, fg, lane, stage);
+            if (edge) gemm_epilogue_staged<EPI, IPP, EF_EDGE | EF_LNF>(p, acc, m_base, n_base, frow, fg, lane, stage);
+            else gemm_epilogue_staged<EPI, IPP, EF_LNF | XP>(p, acc, m_base, n_base, frow, fg, lane, stage);
           }
         } else {
-          if (edge) gemm_epilogue_staged<EPI, false, true, IPP, false, false, true, true>(p, acc, m_base, n_base, frow, fg, lane, stage);
-          else gemm_epilogue_staged<EPI, false, false, IPP, false, false, true, true, XP>(p, acc, m_base, n_base, frow, fg, lane, stage);
+          if (edge) gemm_epilogue_staged<EPI, IPP, EF_EDGE | EF_LNF>(p, acc, m_base, n_base, frow, fg, lane, stage);
+          else gemm_epilogue_staged<EPI, IPP, EF_LNF | XP>(p, acc, m_base, n_base, frow, fg, lane, stage);
         }
         return true;
       }
     }
     if constexpr (EPI == EPI_BF16) {
       if (p.qscale != 0.f && n_base < p.qcols) {   // wave tiles that hold q columns only (the launcher guarantees: no residual)
-        if (edge) gemm_epilogue_staged<EPI, false, true, IPP, false, true>(p, acc, m_base, n_base, frow, fg, lane, stage);
-        else gemm_epilogue_staged<EPI, false, false, IPP, false, true, false, false, XP>(p, acc, m_base, n_base, frow, fg, lane, stage);
+        if (edge) gemm_epilogue_staged<EPI, IPP, EF_EDGE | EF_QS>(p, acc, m_base, n_base, frow, fg, lane, stage);
+        else gemm_epilogue_staged<EPI, IPP, EF_QS | XP>(p, acc, m_base, n_base, frow, fg, lane, stage);
         return true;
       }
     }
-    if constexpr (EPI == EPI_GELU) {   // GELU: Phi(-|x|) as exp2 of a degree-6 polynomial (LP = true; the Abramowitz-Stegun form of rounds 1-3 is gone)
+    if constexpr (EPI == EPI_GELU) {
       if (opt) {
-        if (edge) gemm_epilogue_staged<EPI, true, true, IPP, false, false, true>(p, acc, m_base, n_base, frow, fg, lane, stage);
-        else gemm_epilogue_staged<EPI, true, false, IPP, false, false, true, false, XP>(p, acc, m_base, n_base, frow, fg, lane, stage);
+        if (edge) gemm_epilogue_staged<EPI, IPP, EF_OPT | EF_EDGE>(p, acc, m_base, n_base, frow, fg, lane, stage);
+        else gemm_epilogue_staged<EPI, IPP, EF_OPT | XP>(p, acc, m_base, n_base, frow, fg, lane, stage);
       } else {
-        if (edge) gemm_epilogue_staged<EPI, false, true, IPP, false, false, true>(p, acc, m_base, n_base, frow, fg, lane, stage);
-        else gemm_epilogue_staged<EPI, false, false, IPP, false, false, true, false, XP>(p, acc, m_base, n_base, frow, fg, lane, stage);
+        if (edge) gemm_epilogue_staged<EPI, IPP, EF_EDGE>(p, acc, m_base, n_base, frow, fg, lane, stage);
+        else gemm_epilogue_staged<EPI, IPP, XP>(p, acc, m_base, n_base, frow, fg, lane, stage);
       }
       return true;
     } else if (opt) {
-      if (edge) gemm_epilogue_staged<EPI, true, true, IPP>(p, acc, m_base, n_base, frow, fg, lane, stage);
-      else gemm_epilogue_staged<EPI, true, false, IPP, false, false, false, false, EPI == EPI_DGELU ? 0 : XP>(p, acc, m_base, n_base, frow, fg, lane, stage);   // (dGELU WITH a bias: the straight form)
+      if (edge) gemm_epilogue_staged<EPI, IPP, EF_OPT | EF_EDGE>(p, acc, m_base, n_base, frow, fg, lane, stage);
+      else gemm_epilogue_staged<EPI, IPP, EF_OPT | (EPI == EPI_DGELU ? 0 : XP)>(p, acc, m_base, n_base, frow, fg, lane, stage);   // (dGELU WITH a bias: the straight form)
     } else if constexpr (EPI != EPI_DGELU) {
       if (edge) {
-        gemm_epilogue_staged<EPI, false, true, IPP>(p, acc, m_base, n_base, frow, fg, lane, stage);
+        gemm_epilogue_staged<EPI, IPP, EF_EDGE>(p, acc, m_base, n_base, frow, fg, lane, stage);
       } else {
-        if constexpr (EPI == EPI_BF16 && XP >= 4) {   // (pipelined form: plain dgrad GEMMs have no bias)
+        if constexpr (EPI == EPI_BF16 && XP != 0) {   // (pipelined form: plain dgrad GEMMs have no bias)
           if (p.bias == nullptr) {
-            gemm_epilogue_staged<EPI, false, false, IPP, false, false, false, false, XP, true>(p, acc, m_base, n_base, frow, fg, lane, stage);
+            gemm_epilogue_staged<EPI, IPP, XP | EF_NB>(p, acc, m_base, n_base, frow, fg, lane, stage);
             return true;
           }
         }
-        gemm_epilogue_staged<EPI, false, false, IPP, false, false, false, false, XP>(p, acc, m_base, n_base, frow, fg, lane, stage);
+        gemm_epilogue_staged<EPI, IPP, XP>(p, acc, m_base, n_base, frow, fg, lane, stage);
       }
     }
     return true;
@@ -708,40 +709,40 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x4_t (&acc)[
   if constexpr (ALLOW_LNF && (EPI == EPI_BF16 || EPI == EPI_GELU)) {
     if (p.lnf_rs != nullptr) {   // LayerNorm folded into this GEMM (the launcher guarantees: no residual / aux_out); always the predicated form
       if constexpr (EPI == EPI_BF16) {
-        if (p.qscale != 0.f && n_base < p.qcols) gemm_epilogue_impl<EPI, FM, FN, false, true, false, true, false, true>(p, acc, m_base, n_base, frow, fg, slice);
-        else gemm_epilogue_impl<EPI, FM, FN, false, true, false, false, false, true>(p, acc, m_base, n_base, frow, fg, slice);
+        if (p.qscale != 0.f && n_base < p.qcols) gemm_epilogue_impl<EPI, FM, FN, EF_EDGE | EF_QS | EF_LNF>(p, acc, m_base, n_base, frow, fg, slice);
+        else gemm_epilogue_impl<EPI, FM, FN, EF_EDGE | EF_LNF>(p, acc, m_base, n_base, frow, fg, slice);
       } else {
-        gemm_epilogue_impl<EPI, FM, FN, false, true, false, false, true, true>(p, acc, m_base, n_base, frow, fg, slice);
+        gemm_epilogue_impl<EPI, FM, FN, EF_EDGE | EF_LNF>(p, acc, m_base, n_base, frow, fg, slice);
       }
       return;
     }
   }
   if constexpr (EPI == EPI_BF16) {
     if (p.qscale != 0.f && n_base < p.qcols) {   // wave tiles that hold q columns only (the launcher guarantees: no residual)
-      if (edge) gemm_epilogue_impl<EPI, FM, FN, false, true, false, true>(p, acc, m_base, n_base, frow, fg, slice);
-      else gemm_epilogue_impl<EPI, FM, FN, false, false, false, true>(p, acc, m_base, n_base, frow, fg, slice);
+      if (edge) gemm_epilogue_impl<EPI, FM, FN, EF_EDGE | EF_QS>(p, acc, m_base, n_base, frow, fg, slice);
+      else gemm_epilogue_impl<EPI, FM, FN, EF_QS>(p, acc, m_base, n_base, frow, fg, slice);
       return;
     }
   }
-  if constexpr (EPI == EPI_GELU) {   // (LP = true: the polynomial form, the only one since round 6)
+  if constexpr (EPI == EPI_GELU) {
     if (opt) {
-      if (edge) gemm_epilogue_impl<EPI, FM, FN, true, true, false, false, true>(p, acc, m_base, n_base, frow, fg, slice);
-      else gemm_epilogue_impl<EPI, FM, FN, true, false, false, false, true>(p, acc, m_base, n_base, frow, fg, slice);
+      if (edge) gemm_epilogue_impl<EPI, FM, FN, EF_OPT | EF_EDGE>(p, acc, m_base, n_base, frow, fg, slice);
+      else gemm_epilogue_impl<EPI, FM, FN, EF_OPT>(p, acc, m_base, n_base, frow, fg, slice);
     } else {
-      if (edge) gemm_epilogue_impl<EPI, FM, FN, false, true, false, false, true>(p, acc, m_base, n_base, frow, fg, slice);
-      else gemm_epilogue_impl<EPI, FM, FN, false, false, false, false, true>(p, acc, m_base, n_base, frow, fg, slice);
+      if (edge) gemm_epilogue_impl<EPI, FM, FN, EF_EDGE>(p, acc, m_base, n_base, frow, fg, slice);
+      else gemm_epilogue_impl<EPI, FM, FN, 0u>(p, acc, m_base, n_base, frow, fg, slice);
     }
     return;
   } else if (opt) {
-    if (edge) gemm_epilogue_impl<EPI, FM, FN, true, true>(p, acc, m_base, n_base, frow, fg, slice);
-    else gemm_epilogue_impl<EPI, FM, FN, true, false>(p, acc, m_base, n_base, frow, fg, slice);
+    if (edge) gemm_epilogue_impl<EPI, FM, FN, EF_OPT | EF_EDGE>(p, acc, m_base, n_base, frow, fg, slice);
+    else gemm_epilogue_impl<EPI, FM, FN, EF_OPT>(p, acc, m_base, n_base, frow, fg, slice);
   } else if constexpr (EPI == EPI_F32) {
-    if (p.beta != 0.f) gemm_epilogue_impl<EPI, FM, FN, false, true, true>(p, acc, m_base, n_base, frow, fg, slice);
-    else if (edge) gemm_epilogue_impl<EPI, FM, FN, false, true>(p, acc, m_base, n_base, frow, fg, slice);
-    else gemm_epilogue_impl<EPI, FM, FN, false, false>(p, acc, m_base, n_base, frow, fg, slice);
+    if (p.beta != 0.f) gemm_epilogue_impl<EPI, FM, FN, EF_EDGE | EF_BETA>(p, acc, m_base, n_base, frow, fg, slice);
+    else if (edge) gemm_epilogue_impl<EPI, FM, FN, EF_EDGE>(p, acc, m_base, n_base, frow, fg, slice);
+    else gemm_epilogue_impl<EPI, FM, FN, 0u>(p, acc, m_base, n_base, frow, fg, slice);
   } else if constexpr (EPI != EPI_DGELU) {
-    if (edge) gemm_epilogue_impl<EPI, FM, FN, false, true>(p, acc, m_base, n_base, frow, fg, slice);
-    else gemm_epilogue_impl<EPI, FM, FN, false, false>(p, acc, m_base, n_base, frow, fg, slice);
+    if (edge) gemm_epilogue_impl<EPI, FM, FN, EF_EDGE>(p, acc, m_base, n_base, frow, fg, slice);
+    else gemm_epilogue_impl<EPI, FM, FN, 0u>(p, acc, m_base, n_base, frow, fg, slice);
   }
 }
 
@@ -777,12 +778,7 @@ static inline int pick_splitk(int64_t tiles, int nk, int slots, double us_per_kt
 void vj_splitk_finish_plan(int nk, int& splitk, int& ktiles_per);
 int vj_splitk_reduce(const GemmArgs& b, hipStream_t stream);
 
-// XCD-aware, grouped tile mapping (bijective for any grid size): workgroup `bid` of `nblk` -> logical tile index such
-// that each XCD (private L2; hardware dispatches workgroup b to XCD b % 8) works on a contiguous band of tiles.
-__device__ __forceinline__ int xcd_logical(int bid, int nblk) {
-  const int qx = nblk >> 3, rx = nblk & 7, xcd = bid & 7, pos = bid >> 3;
-  return (xcd < rx ? xcd * (qx + 1) : rx * (qx + 1) + (xcd - rx) * qx) + pos;
-}
+// Grouped tile mapping of the logical tile index (xcd_logical, common.hpp):
 // GM row-tiles form a group that sweeps all column tiles (keeps the A panel hot in L2)
 // raster (persistent kernel only, option gemm_raster): bits 0-7 = group size G (0 -> 8); bit 8 clear = G ROW tiles sweep all column tiles,
 // row tile fastest (the default: 32 consecutive tiles = 8 rows x 4 columns, the A panels are revisited column step after column step);

@@ -233,7 +233,7 @@ extern "C" int vj_ln_fold_weights(const float* W, const float* b, const float* g
 // separate read of dY each (the transpose-free weight-gradient route has no transpose pass to fold them into).
 // ---------------------------------------------------------------------------------------------
 #define LN_BWD_MAX_BLOCKS 1024
-template <int NCH, bool CS, bool PF = true>
+template <int NCH, bool CS>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
                                                             const float* __restrict__ gamma,
                                                             const float* __restrict__ mean_in,
@@ -286,9 +286,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __rest
   };
 #pragma unroll
   for (int i = 0; i < NCH; i++) nx[i] = nd[i] = nr[i] = (u32x4_t){0u, 0u, 0u, 0u};
-  if (PF && rbeg + wv < rend) request(rbeg + wv);
+  if (rbeg + wv < rend) request(rbeg + wv);
   for (int64_t r = rbeg + wv; r < rend; r += 4) {
-    if constexpr (!PF) request(r);   // option ln_bwd_prefetch = 0 (A/B): the row is requested when it is needed
     u32x4_t cx[NCH], cd[NCH], cr[NCH];
 #pragma unroll
     for (int i = 0; i < NCH; i++) {
@@ -297,7 +296,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __rest
       cr[i] = nr[i];
     }
     const float mean = nmean, rstd = nrstd;
-    if (PF && r + 4 < rend) request(r + 4);
+    if (r + 4 < rend) request(r + 4);
     // (the second pass recomputes xhat and g from the raw chunks -- the same operations on the same operands, hence the same bits --
     //  instead of keeping 16 floats per chunk alive across the two wave reductions: with the prefetch buffers that keeps the
     //  D = 1024 variant at three waves per SIMD, i.e. its 660 workgroups resident in one round)
@@ -387,10 +386,9 @@ int vj_layernorm_bwd_partials(const void* dy_bf16, const void* x_bf16, const flo
   int64_t nb = cdiv64(rows, 16);  // >= 16 rows per workgroup so the column partials amortise
   if (nb > LN_BWD_MAX_BLOCKS) nb = LN_BWD_MAX_BLOCKS;
   if (nb < 1) nb = 1;
-  // (PF = true: the row-ahead prefetch of round 4; its control without the prefetch is no longer instantiated: bit-identical, profiles/r04_ln_bench.txt)
-#define VJ_LNB(NCHV, CSV)                                                                                                     \
-  hipLaunchKernelGGL((layernorm_bwd_kernel<NCHV, CSV, true>), dim3((unsigned)nb), dim3(256), 0, stream, (const bf16_t*)dy_bf16, \
-                     (const bf16_t*)x_bf16, gamma, mean, rstd, (const bf16_t*)dres_bf16, (bf16_t*)dx_bf16, (float*)ws,         \
+#define VJ_LNB(NCHV, CSV)                                                                                               \
+  hipLaunchKernelGGL((layernorm_bwd_kernel<NCHV, CSV>), dim3((unsigned)nb), dim3(256), 0, stream, (const bf16_t*)dy_bf16, \
+                     (const bf16_t*)x_bf16, gamma, mean, rstd, (const bf16_t*)dres_bf16, (bf16_t*)dx_bf16, (float*)ws,   \
                      rows, (int)D)
   if (cs) {
     if (D <= 512) VJ_LNB(1, true);

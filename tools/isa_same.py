@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
 """CPU: is the gfx950 device code of the working tree the same as that of a git revision?
 
-    python tools/isa_same.py [rev]          (default HEAD)
+    python tools/isa_same.py [rev] [--sub PATTERN REPLACEMENT]...          (default HEAD)
 
 Every jepa_amd/csrc/*.hip of the revision (extracted with `git archive` into a temporary directory) and of the working tree is
 compiled device-only to assembly with the flags of jepa_amd/build.py, as tests/test_build_no_spills.py does; lines that contain
 `__hip_cuid_` (a hash of the source text) are dropped and the rest is compared per file.  The gate of a refactor of csrc/:
-instructions, register counts, LDS sizes, kernel names and kernel-argument sizes must not move.  Exit status 1 on any difference."""
+instructions, register counts, LDS sizes, kernel names and kernel-argument sizes must not move.  Exit status 1 on any difference.
+A kernel that lost a template parameter has a new mangled name and nothing else: each --sub (a regular expression and its replacement,
+re.sub) is applied to the REVISION's assembly before the comparison, and is printed with the number of replacements it made."""
 import concurrent.futures
 import difflib
 import io
 import os
+import re
 import subprocess
 import sys
 import tarfile
@@ -30,7 +33,7 @@ def asm(src):
     return [ln for ln in r.stdout.splitlines() if "__hip_cuid_" not in ln]
 
 
-def main(rev):
+def main(rev, subs=()):
     with tempfile.TemporaryDirectory() as tmp:
         tar = subprocess.run(["git", "-C", ROOT, "archive", rev, REL, "include"], capture_output=True, check=True).stdout
         tarfile.open(fileobj=io.BytesIO(tar)).extractall(tmp)
@@ -40,6 +43,13 @@ def main(rev):
         with concurrent.futures.ThreadPoolExecutor(max_workers=8) as ex:
             outs = list(ex.map(lambda p: asm(p) if os.path.exists(p) else None, jobs))
     bad = 0
+    for pat, repl in subs:
+        hits = 0
+        for old in outs[0::2]:
+            for k, ln in enumerate(old or ()):
+                old[k], c = re.subn(pat, repl, ln)
+                hits += c
+        print(f"--sub {pat} -> {repl}: {hits} replacements in the assembly of {rev}")
     for i, n in enumerate(names):
         old, new = outs[2 * i], outs[2 * i + 1]
         same = old == new
@@ -52,4 +62,9 @@ def main(rev):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1] if len(sys.argv) > 1 else "HEAD"))
+    argv, subs = sys.argv[1:], []
+    while "--sub" in argv:
+        k = argv.index("--sub")
+        subs.append((argv[k + 1], argv[k + 2]))
+        del argv[k:k + 3]
+    sys.exit(main(argv[0] if argv else "HEAD", subs))
