@@ -54,6 +54,27 @@ int vj_tubelet_pack(const float* clips, void* out_bf16, const int64_t* idx, int6
 int vj_add_pos(void* x_bf16, const float* pos, const int64_t* idx, int64_t B, int64_t K, int64_t D,
                vj_stream_t stream);
 
+/* ---- still-image front end of the video encoder and position-table interpolation ------------------------------
+ * input.unsqueeze(2).repeat(1, 1, frames_per_clip, 1, 1) + patch_embed    evals/image_classification_frozen/eval.py:452-455
+ * fp32 images [B,C,H,W] -> the bf16 A operand [B,K,C*tub*p*p] of the patch-embed GEMM for the gh*gw DISTINCT tubelets of
+ * the repeated clip (element order c,dt,dh,dw; each pixel read once, written to the `tubelet` dt slices).  idx (nullable,
+ * [B,K]): row k of image b is cell idx[b,k] % (gh*gw), so both spatial indices and indices into the (t,h,w) grid of the
+ * repeated clip are accepted; NULL packs K = gh*gw cells in (h,w) order.  Rows are bit-identical to vj_tubelet_pack's on
+ * the materialised clip. */
+int vj_image_pack(const float* images, void* out_bf16, const int64_t* idx, int64_t B, int64_t C, int64_t H, int64_t W,
+                  int64_t tubelet, int64_t patch, int64_t K, vj_stream_t stream);
+/* x += pos_embed (vision_transformer.py:172-174) for the repeated clip of a still image: y bf16 [B,S,D] holds the patch
+ * embedding of the S = gh*gw distinct tubelets, pos fp32 [Gt*S,D], out bf16 [B,Gt*S,D]:
+ * out[b, t*S+s, :] = bf16(float(y[b,s,:]) + pos[t*S+s, :]).  Same fp32 add and single rounding as vj_add_pos. */
+int vj_add_pos_bcast(const void* y_bf16, const float* pos, void* out_bf16, int64_t B, int64_t S, int64_t Gt, int64_t D,
+                     vj_stream_t stream);
+/* nn.functional.interpolate(pos_embed [1,D,Nt,Nh,Nw], scale_factor=(T/N_t, H/N_h, W/N_w), mode='trilinear')
+ *                                                                         src/models/vision_transformer.py:221-227
+ * on the token-major table: fp32 [Nt,Nh,Nw,D] -> [To,Ho,Wo,D].  align_corners=False with the scale factors given (the
+ * source coordinate uses float(1/scale), not in/out); To,Ho,Wo must equal floor(in * scale) computed in double. */
+int vj_pos_interp3d(const float* table, float* out, int64_t Nt, int64_t Nh, int64_t Nw, int64_t D, double scale_t,
+                    double scale_h, double scale_w, int64_t To, int64_t Ho, int64_t Wo, vj_stream_t stream);
+
 /* ---- LayerNorm ----------------------------------------------------------------------------------------------
  * nn.LayerNorm(eps=1e-6) (modules.py:97,106,115,119; vision_transformer.py:193; predictor.py:233).
  * bf16 in/out, fp32 statistics; mean/rstd (nullable pair) are saved for the backward. */

@@ -183,6 +183,183 @@ extern "C" int vj_add_pos(void* x_bf16, const float* pos, const int64_t* idx, in
 }
 
 // ---------------------------------------------------------------------------------------------
+// image_pack: fp32 still images [B,C,H,W] -> bf16 patch rows [B,K,C*tub*p*p] of the clip that repeats the image along
+// time (input.unsqueeze(2).repeat(1,1,T,1,1), evals/image_classification_frozen/eval.py:452-455).  All tubelets of one
+// spatial cell of that clip are the same row, so only the gh*gw distinct ones are packed (idx == NULL: K = gh*gw, row k
+// is cell k).  With idx, row k of image b is cell idx[b,k] % (gh*gw): an index into the (t,h,w) grid of the repeated clip
+// names the same pixels as its spatial part.  Element order (c,dt,dh,dw) as tubelet_pack; every pixel is read ONCE and
+// its bf16 rounding is written to the `tub` dt slices.  Same fp32 -> bf16 rounding of the same pixels as tubelet_pack on
+// the repeated clip: the rows are bit-identical to that kernel's.  8 pixels per thread.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void image_pack_kernel(const float* __restrict__ images, bf16_t* __restrict__ out,
+                                                         const int64_t* __restrict__ idx, int64_t B, int C, int H, int W,
+                                                         int tub, int p, int64_t K) {
+  const int gh = H / p, gw = W / p;
+  const int kdim = C * tub * p * p;
+  const int cpr = C * p * p / 8;  // 16-byte input chunks per row (one dt slice)
+  const int64_t cells = (int64_t)gh * gw;
+  const int64_t total = B * K * cpr;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < total; q += (int64_t)gridDim.x * 256) {
+    const int64_t row = q / cpr;
+    const int e = (int)(q - row * cpr) * 8;   // offset inside the (c,dh,dw) slice
+    const int64_t b = row / K;
+    const int64_t n = (idx ? idx[row] : (row - b * K)) % cells;
+    const int wq = (int)(n % gw), hq = (int)(n / gw);
+    const int dw = e % p, dh = (e / p) % p, c = e / (p * p);
+    const float* s = images + (((b * C + c) * H + (hq * p + dh)) * (int64_t)W + wq * p + dw);
+    const float4 lo = *(const float4*)s;
+    const float4 hi = *(const float4*)(s + 4);
+    u32x4_t o;
+    o[0] = pack_bf2(lo.x, lo.y);
+    o[1] = pack_bf2(lo.z, lo.w);
+    o[2] = pack_bf2(hi.x, hi.y);
+    o[3] = pack_bf2(hi.z, hi.w);
+    bf16_t* d = out + row * kdim + ((int64_t)c * tub * p + dh) * p + dw;
+    for (int dt = 0; dt < tub; dt++) *(u32x4_t*)(d + (int64_t)dt * p * p) = o;
+  }
+}
+
+extern "C" int vj_image_pack(const float* images, void* out_bf16, const int64_t* idx, int64_t B, int64_t C, int64_t H,
+                             int64_t W, int64_t tubelet, int64_t patch, int64_t K, hipStream_t stream) {
+  VJ_CHECK_ARG(B >= 0 && K >= 0 && C > 0 && H > 0 && W > 0 && tubelet > 0 && patch > 0,
+               "vj_image_pack: bad dims B=%ld K=%ld C=%ld H=%ld W=%ld tubelet=%ld patch=%ld", (long)B, (long)K, (long)C,
+               (long)H, (long)W, (long)tubelet, (long)patch);
+  VJ_CHECK_ARG(patch % 8 == 0, "vj_image_pack: patch (%ld) must be a multiple of 8", (long)patch);
+  VJ_CHECK_ARG(H % patch == 0 && W % patch == 0, "vj_image_pack: image %ldx%ld not divisible into tubelets of patch %ld",
+               (long)H, (long)W, (long)patch);
+  VJ_CHECK_ARG(idx != nullptr || K == (H / patch) * (W / patch), "vj_image_pack: K=%ld must be gh*gw=%ld without idx", (long)K,
+               (long)((H / patch) * (W / patch)));
+  VJ_CHECK_ARG(C * tubelet * patch * patch < (1ll << 31), "vj_image_pack: row too long");
+  if (B * K == 0) return 0;
+  const int64_t total = B * K * (C * patch * patch / 8);
+  int64_t g = cdiv64(total, 256);
+  if (g > 256 * 32) g = 256 * 32;
+  hipLaunchKernelGGL(image_pack_kernel, dim3((int)g), dim3(256), 0, stream, images, (bf16_t*)out_bf16, idx, B, (int)C, (int)H,
+                     (int)W, (int)tubelet, (int)patch, K);
+  VJ_LAUNCH_CHECK("vj_image_pack");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// add_pos_bcast: out[b, t*S + s, :] = bf16(float(y[b,s,:]) + pos[t*S + s, :]), t < Gt.  y = patch embedding of the S
+// distinct tubelets of a still image; the Gt temporal slices of the repeated clip share it and differ only in their
+// position rows.  The add is add_pos_kernel's (fp32, one rounding), so out equals add_pos on the Gt-fold repeated rows
+// bit for bit.  One wave per (b,s): y is read once, Gt position rows are read and Gt output rows written.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void add_pos_bcast_kernel(const bf16_t* __restrict__ y, const float* __restrict__ pos,
+                                                            bf16_t* __restrict__ out, int64_t rows, int64_t S, int64_t Gt,
+                                                            int D) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  for (int64_t r = wave; r < rows; r += nw) {
+    const int64_t b = r / S, s = r - b * S;
+    const bf16_t* yp = y + r * D;
+    for (int c = lane * 8; c < D; c += 512) {
+      const u32x4_t v = *(const u32x4_t*)(yp + c);
+      for (int64_t t = 0; t < Gt; t++) {
+        const float* pp = pos + (t * S + s) * D + c;
+        const float4 p0 = *(const float4*)pp;
+        const float4 p1 = *(const float4*)(pp + 4);
+        u32x4_t o;
+        o[0] = pack_bf2(bf_lo(v[0]) + p0.x, bf_hi(v[0]) + p0.y);
+        o[1] = pack_bf2(bf_lo(v[1]) + p0.z, bf_hi(v[1]) + p0.w);
+        o[2] = pack_bf2(bf_lo(v[2]) + p1.x, bf_hi(v[2]) + p1.y);
+        o[3] = pack_bf2(bf_lo(v[3]) + p1.z, bf_hi(v[3]) + p1.w);
+        *(u32x4_t*)(out + ((b * Gt + t) * S + s) * D + c) = o;
+      }
+    }
+  }
+}
+
+extern "C" int vj_add_pos_bcast(const void* y_bf16, const float* pos, void* out_bf16, int64_t B, int64_t S, int64_t Gt,
+                                int64_t D, hipStream_t stream) {
+  VJ_CHECK_ARG(B >= 0 && S >= 0 && Gt >= 0 && D > 0, "vj_add_pos_bcast: bad dims B=%ld S=%ld Gt=%ld D=%ld", (long)B, (long)S,
+               (long)Gt, (long)D);
+  VJ_CHECK_ARG(D % 8 == 0, "vj_add_pos_bcast: D=%ld must be a multiple of 8", (long)D);
+  const int64_t rows = B * S;
+  if (rows * Gt == 0) return 0;
+  hipLaunchKernelGGL(add_pos_bcast_kernel, dim3(rows_grid(rows)), dim3(256), 0, stream, (const bf16_t*)y_bf16, pos,
+                     (bf16_t*)out_bf16, rows, S, Gt, (int)D);
+  VJ_LAUNCH_CHECK("vj_add_pos_bcast");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// pos_interp3d: fp32 table [Nt,Nh,Nw,D] -> [To,Ho,Wo,D], the trilinear F.interpolate(scale_factor=(st,sh,sw)) of
+// interpolate_pos_encoding (src/models/vision_transformer.py:197-228) on the channels-last view it permutes to and from.
+// align_corners=False with the scale factor GIVEN: per axis src = (dst + 0.5) * r - 0.5 clamped below at 0, with
+// r = float(1 / scale) (not in/out); i0 = int(src), i1 = i0 + (i0 < in - 1), weights src - i0 and 1 - (src - i0).  The
+// products and differences of the coordinate are kept unfused so they round as the plain expression does.  One thread
+// per 4 output floats; the 8 corner rows are 16-byte loads.
+// ---------------------------------------------------------------------------------------------
+struct InterpAxis {
+  int i0, i1;
+  float w0, w1;
+};
+
+__device__ __forceinline__ InterpAxis interp_axis(int dst, float r, int in) {
+  float src = __fsub_rn(__fmul_rn(r, (float)dst + 0.5f), 0.5f);
+  if (src < 0.f) src = 0.f;
+  int i0 = (int)src;
+  if (i0 > in - 1) i0 = in - 1;
+  float l = src - (float)i0;
+  l = l < 0.f ? 0.f : (l > 1.f ? 1.f : l);
+  InterpAxis a;
+  a.i0 = i0;
+  a.i1 = i0 + (i0 < in - 1 ? 1 : 0);
+  a.w1 = l;
+  a.w0 = 1.f - l;
+  return a;
+}
+
+__global__ __launch_bounds__(256) void pos_interp3d_kernel(const float* __restrict__ in, float* __restrict__ out, int Nt,
+                                                           int Nh, int Nw, int D, float rt, float rh, float rw, int To,
+                                                           int Ho, int Wo) {
+  const int dv = D / 4;
+  const int64_t total = (int64_t)To * Ho * Wo * dv;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < total; q += (int64_t)gridDim.x * 256) {
+    const int64_t cell = q / dv;
+    const int c = (int)(q - cell * dv) * 4;
+    const int w = (int)(cell % Wo), h = (int)((cell / Wo) % Ho), t = (int)(cell / ((int64_t)Wo * Ho));
+    const InterpAxis at = interp_axis(t, rt, Nt), ah = interp_axis(h, rh, Nh), aw = interp_axis(w, rw, Nw);
+    float4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const int ti = (k & 4) ? at.i1 : at.i0, hi = (k & 2) ? ah.i1 : ah.i0, wi = (k & 1) ? aw.i1 : aw.i0;
+      const float wt = ((k & 4) ? at.w1 : at.w0) * ((k & 2) ? ah.w1 : ah.w0) * ((k & 1) ? aw.w1 : aw.w0);
+      const float4 v = *(const float4*)(in + (((int64_t)ti * Nh + hi) * Nw + wi) * D + c);
+      acc.x += wt * v.x;
+      acc.y += wt * v.y;
+      acc.z += wt * v.z;
+      acc.w += wt * v.w;
+    }
+    *(float4*)(out + cell * D + c) = acc;
+  }
+}
+
+extern "C" int vj_pos_interp3d(const float* table, float* out, int64_t Nt, int64_t Nh, int64_t Nw, int64_t D, double scale_t,
+                               double scale_h, double scale_w, int64_t To, int64_t Ho, int64_t Wo, hipStream_t stream) {
+  VJ_CHECK_ARG(Nt > 0 && Nh > 0 && Nw > 0 && D > 0 && Nt < (1 << 20) && Nh < (1 << 20) && Nw < (1 << 20),
+               "vj_pos_interp3d: bad table dims %ldx%ldx%ldx%ld", (long)Nt, (long)Nh, (long)Nw, (long)D);
+  VJ_CHECK_ARG(D % 4 == 0, "vj_pos_interp3d: D=%ld must be a multiple of 4", (long)D);
+  VJ_CHECK_ARG(scale_t > 0.0 && scale_h > 0.0 && scale_w > 0.0, "vj_pos_interp3d: scale factors must be positive");
+  VJ_CHECK_ARG(To > 0 && Ho > 0 && Wo > 0 && To < (1 << 20) && Ho < (1 << 20) && Wo < (1 << 20),
+               "vj_pos_interp3d: non-positive output grid %ldx%ldx%ld", (long)To, (long)Ho, (long)Wo);
+  // F.interpolate's output extent for a given scale factor: floor(in * scale) in double
+  VJ_CHECK_ARG(To == (int64_t)floor((double)Nt * scale_t) && Ho == (int64_t)floor((double)Nh * scale_h) &&
+                   Wo == (int64_t)floor((double)Nw * scale_w),
+               "vj_pos_interp3d: output grid %ldx%ldx%ld is not floor(in * scale)", (long)To, (long)Ho, (long)Wo);
+  const int64_t total = To * Ho * Wo * (D / 4);
+  int64_t g = cdiv64(total, 256);
+  if (g > 256 * 32) g = 256 * 32;
+  hipLaunchKernelGGL(pos_interp3d_kernel, dim3((int)g), dim3(256), 0, stream, table, out, (int)Nt, (int)Nh, (int)Nw, (int)D,
+                     (float)(1.0 / scale_t), (float)(1.0 / scale_h), (float)(1.0 / scale_w), (int)To, (int)Ho, (int)Wo);
+  VJ_LAUNCH_CHECK("vj_pos_interp3d");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // pred_assemble_fwd: out[b, j, :] = j < Ke ? e[b,j,:] + pos[idx_e[b,j]] : tok[:] + pos[idx_p[b,j-Ke]]
 //   e  = predictor_embed(z)   bf16 [B,Ke,Dp]     (predictor.py:194-200)
 //   tok = mask_tokens[i]      fp32 [Dp]          (predictor.py:207-217)

@@ -323,17 +323,37 @@ def _wait_gates(gates, chained):
 
 
 def encoder_forward(ew: EncoderW, clips, masks: Optional[List[torch.Tensor]], save: bool, final_norm=True, ws_tag=None,
-                    gemm_flags=0, gates=None):
-    """clips fp32 [B,3,T,H,W]; masks: None (all N tokens) or a list of int64 [B,K_i] index tensors.
+                    gemm_flags=0, gates=None, pos=None):
+    """clips fp32 [B,3,T,H,W], or still images [B,3,H,W] standing for the clip that repeats each image along time; masks:
+    None (all N tokens) or a list of int64 [B,K_i] index tensors.  pos (fp32 [N, D], default ew.pos): the position table of
+    the input's token grid (gt, gh, gw), N = gt*gh*gw; the grid is taken from the input (and, for a still image, gt from N).
     Returns (out [sum_i B*K_i, D] bf16, segs, saved).  With final_norm=False the last residual stream is returned
-    (the target path fuses the final norm into vj_target_rows).  gates: see _wait_gates."""
+    (the target path fuses the final norm into vj_target_rows).  gates: see _wait_gates.
+
+    Still images: only the gh*gw distinct tubelets are packed and embedded (vj_image_pack, a GEMM on B*gh*gw rows) and the gt
+    temporal slices differ only in their position rows (vj_add_pos_bcast); with masks, the kept rows are packed one by one
+    (vj_image_pack with idx) and go through the same GEMM and vj_add_pos as a clip's.  Both equal the materialised repeated
+    clip bit for bit: the packed rows hold the same bf16 pixels, the NT GEMM accumulates a row's dot product in the same K
+    order in every execution form, and the position add is the same single fp32 rounding."""
     B = clips.shape[0]
     D = ew.patch.w.shape[0]
     kdim = ew.patch.w.shape[1]
-    N = ew.pos.shape[0]
+    pos = ew.pos if pos is None else pos
+    N = pos.shape[0]
+    still = clips.dim() == 4
+    cells = (clips.shape[-2] // ew.patch_size) * (clips.shape[-1] // ew.patch_size)
+    if still:
+        if save:
+            raise ValueError("encoder_forward: still-image input is a frozen (save=False) path")
+        if cells == 0 or N % cells != 0:
+            raise ValueError(f"encoder_forward: position table of {N} rows does not fit images of {cells} cells")
+    elif (clips.shape[2] // ew.tubelet) * cells != N:
+        raise ValueError(f"encoder_forward: position table of {N} rows does not fit the input's token grid "
+                         f"{clips.shape[2] // ew.tubelet}x{clips.shape[-2] // ew.patch_size}x{clips.shape[-1] // ew.patch_size}")
+    pack = ops.image_pack if still else ops.tubelet_pack
     if masks is None:
         segs = [Seg(0, B, N)]
-        tok = ops.tubelet_pack(clips, ew.tubelet, ew.patch_size)
+        tok = pack(clips, ew.tubelet, ew.patch_size)
     else:
         segs, r = [], 0
         for m in masks:
@@ -341,12 +361,15 @@ def encoder_forward(ew: EncoderW, clips, masks: Optional[List[torch.Tensor]], sa
             r += B * m.shape[1]
         tok = torch.empty((r, kdim), dtype=torch.bfloat16, device=clips.device)
         for sg, m in zip(segs, masks):
-            ops.tubelet_pack(clips, ew.tubelet, ew.patch_size, idx=m, out=_rows(tok, sg))
+            pack(clips, ew.tubelet, ew.patch_size, idx=m, out=_rows(tok, sg))
     chained = ws_tag is not None and USE_C_CHAIN
     _wait_gates(gates, chained)
     x = ops.gemm_nt(tok, ew.patch.w, bias=ew.patch.b, flags=(gemm_flags & 0xffff if not gemm_flags >> 16 else 0) or None)
-    for i, sg in enumerate(segs):
-        ops.add_pos(_rows(x, sg), ew.pos, sg.B, sg.S, idx=None if masks is None else masks[i])
+    if still and masks is None:
+        x = ops.add_pos_bcast(x, pos, B, cells, N // cells)
+    else:
+        for i, sg in enumerate(segs):
+            ops.add_pos(_rows(x, sg), pos, sg.B, sg.S, idx=None if masks is None else masks[i])
     if chained:    # ws_tag: the caller owns one workspace per trunk (engine/chain.py)
         x, saved_blocks = chain.blocks_forward(x, ew, segs, save, ws_tag, LN_EPS, gemm_flags=gemm_flags, gates=gates)
     else:

@@ -18,6 +18,7 @@ P = ctypes.c_void_p
 I64 = ctypes.c_int64
 I32 = ctypes.c_int
 F32 = ctypes.c_float
+F64 = ctypes.c_double
 
 
 
@@ -59,6 +60,9 @@ SIGNATURES = {
     "vj_copy_rows": (I32, [P, P, I64, I64, I64, I64, I64, I64, I64, P]),
     "vj_tubelet_pack": (I32, [P, P, P, I64, I64, I64, I64, I64, I64, I64, I64, P]),
     "vj_add_pos": (I32, [P, P, P, I64, I64, I64, P]),
+    "vj_image_pack": (I32, [P, P, P, I64, I64, I64, I64, I64, I64, I64, P]),
+    "vj_add_pos_bcast": (I32, [P, P, P, I64, I64, I64, I64, P]),
+    "vj_pos_interp3d": (I32, [P, P, I64, I64, I64, I64, F64, F64, F64, I64, I64, I64, P]),
     "vj_layernorm_fwd": (I32, [P, P, P, P, P, P, I64, I64, F32, P]),
     "vj_layernorm_bwd_ws_bytes": (I64, [I64]),
     "vj_layernorm_bwd": (I32, [P, P, P, P, P, P, P, P, P, F32, F32, I64, I64, P, I64, P]),

@@ -132,6 +132,50 @@ def add_pos(x, pos, B, K, idx=None, stream=None):
     return x
 
 
+def image_pack(images, tubelet, patch, idx=None, out=None, stream=None):
+    """fp32 images [B,C,H,W] -> bf16 [B*K, C*tubelet*patch*patch]: the patch rows of the clip that repeats each image along time,
+    one per spatial cell (K = gh*gw) or per idx entry (taken modulo gh*gw).  Bit-identical to tubelet_pack of that clip."""
+    lib = load_library()
+    images = _req(images, F32, "images")
+    if images.dim() != 4:
+        raise ValueError(f"image_pack: expected [B,C,H,W], got {tuple(images.shape)}")
+    B, C, H, W = images.shape
+    K = (H // patch) * (W // patch) if idx is None else _req(idx, I64, "idx").shape[1]
+    kdim = C * tubelet * patch * patch
+    if out is None:
+        out = torch.empty((B * K, kdim), dtype=BF16, device=images.device)
+    check(lib.vj_image_pack(_ptr(images), _ptr(out), _ptr(idx), B, C, H, W, tubelet, patch, K, _stream(stream)), "vj_image_pack")
+    return out
+
+
+def add_pos_bcast(y, pos, B, S, Gt, out=None, stream=None):
+    """out[b, t*S+s] = bf16(y[b,s] + pos[t*S+s]), t < Gt; y bf16 [B*S, D], pos fp32 [Gt*S, D] -> bf16 [B*Gt*S, D]."""
+    lib = load_library()
+    _req(y, BF16, "y")
+    _req(pos, F32, "pos")
+    D = y.shape[-1]
+    if y.numel() != B * S * D or pos.numel() != Gt * S * D:
+        raise ValueError(f"add_pos_bcast: y {tuple(y.shape)} / pos {tuple(pos.shape)} do not match B={B} S={S} Gt={Gt}")
+    if out is None:
+        out = torch.empty((B * Gt * S, D), dtype=BF16, device=y.device)
+    check(lib.vj_add_pos_bcast(_ptr(y), _ptr(pos), _ptr(out), B, S, Gt, D, _stream(stream)), "vj_add_pos_bcast")
+    return out
+
+
+def pos_interp3d(table, scale_factor, stream=None):
+    """Trilinear F.interpolate(scale_factor=..., align_corners=False) of an fp32 position table [Nt,Nh,Nw,D] along its three grid
+    axes -> [floor(Nt*st), floor(Nh*sh), floor(Nw*sw), D]."""
+    import math
+    lib = load_library()
+    _req(table, F32, "table")
+    Nt, Nh, Nw, D = table.shape
+    st, sh, sw = (float(s) for s in scale_factor)
+    To, Ho, Wo = (int(math.floor(float(n) * s)) for n, s in ((Nt, st), (Nh, sh), (Nw, sw)))
+    out = torch.empty((max(To, 0), max(Ho, 0), max(Wo, 0), D), dtype=F32, device=table.device)
+    check(lib.vj_pos_interp3d(_ptr(table), _ptr(out), Nt, Nh, Nw, D, st, sh, sw, To, Ho, Wo, _stream(stream)), "vj_pos_interp3d")
+    return out
+
+
 # ---------------------------------------------------------------- layernorm
 def layernorm_fwd(x, gamma, beta, eps, save_stats=True, out=None, stream=None):
     lib = load_library()

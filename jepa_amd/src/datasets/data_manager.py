@@ -67,6 +67,37 @@ class SyntheticVideoClassification(torch.utils.data.Dataset):
         return clips, label, indices
 
 
+class SyntheticImageClassification(torch.utils.data.Dataset):
+    """Seeded labelled images for the frozen image-classification eval, in the item layout of the reference's image datasets
+    under its eval transform (evals/image_classification_frozen/eval.py:286, 404-409): (fp32 [3,H,W], label).
+
+    Item i depends on (seed, i) alone: its label is uniform in [0, num_classes) and the image is N(0,1) noise plus the pattern of
+    its class.  A class's pattern (a plane wave per channel whose frequency, phase and amplitude are drawn from
+    (pattern_seed, label)) does not depend on `seed`, so the training and validation splits share their classes, as in
+    SyntheticVideoClassification.  Item and pattern generators are seeded from disjoint ranges."""
+
+    def __init__(self, length, num_classes, crop_size, seed=0, signal=1.0, pattern_seed=0):
+        self.length, self.num_classes, self.crop, self.seed, self.signal = length, num_classes, crop_size, seed, signal
+        self.pattern_seed = pattern_seed
+
+    def __len__(self):
+        return self.length
+
+    def _pattern(self, label):
+        g = torch.Generator().manual_seed((1 << 62) + self.pattern_seed * 1_000_003 + label)   # items use seeds < 2^62
+        f = 1.0 + 3.0 * torch.rand(3, 2, generator=g)                  # cycles per image along (h, w), per channel
+        phase = 6.283185307179586 * torch.rand(3, generator=g)
+        amp = self.signal * (0.5 + torch.rand(3, generator=g))
+        s = torch.arange(self.crop, dtype=torch.float32) / self.crop
+        arg = f[:, 0, None, None] * s[None, :, None] + f[:, 1, None, None] * s[None, None, :]
+        return amp[:, None, None] * torch.cos(6.283185307179586 * arg + phase[:, None, None])
+
+    def __getitem__(self, i):
+        g = torch.Generator().manual_seed((self.seed * 1_000_003 + i) % (1 << 62))
+        label = int(torch.randint(0, self.num_classes, (1,), generator=g))
+        return torch.randn(3, self.crop, self.crop, generator=g) + self._pattern(label), label
+
+
 def init_data(batch_size, transform=None, shared_transform=None, data='ImageNet', collator=None, pin_mem=True,
               num_workers=8, world_size=1, rank=0, root_path=None, image_folder=None, training=True, copy_data=False,
               drop_last=True, tokenize_txt=True, subset_file=None, clip_len=8, frame_sample_rate=2, duration=None,

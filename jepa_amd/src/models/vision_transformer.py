@@ -84,12 +84,49 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
     def no_weight_decay(self):
         return {}
 
+    def _apply(self, fn, *args, **kwargs):
+        self.__dict__.pop("_pos_interp_cache", None)    # .to() / .cuda() / .float(): interpolated tables follow pos_embed
+        return super()._apply(fn, *args, **kwargs)
+
+    def _input_size(self, x):
+        """(T, H, W) of the clip an input stands for: a 4-D [B,C,H,W] still image is its repetition over num_frames frames."""
+        if x.dim() == 4:
+            return self.num_frames, x.shape[2], x.shape[3]
+        if x.dim() != 5:
+            raise ValueError(f"expected clips [B,C,T,H,W] or still images [B,C,H,W], got {tuple(x.shape)}")
+        return x.shape[2], x.shape[3], x.shape[4]
+
     def interpolate_pos_encoding(self, x, pos_embed):
-        _, _, T, H, W = x.shape
+        """The position table of x's token grid (reference: vision_transformer.py:197-228): the parameter itself at the native
+        size, otherwise its trilinear interpolation [1, T'*H'*W', D] in fp32 (vj_pos_interp3d), computed once per (T, H, W) and
+        kept until pos_embed is reloaded or moved."""
+        T, H, W = self._input_size(x)
         if H == self.input_size and W == self.input_size and T == self.num_frames:
             return pos_embed
-        raise NotImplementedError("pos-embed interpolation (non-native resolution) is an eval-time feature; the "
-                                  "pretraining step always runs at the native clip size")
+        if T % self.tubelet_size or H % self.patch_size or W % self.patch_size or min(T, H, W) <= 0:
+            raise ValueError(f"input of {T}x{H}x{W} is not divisible into tubelets of {self.tubelet_size}x{self.patch_size}x"
+                             f"{self.patch_size}")
+        hipmodule.require_gpu(pos_embed, "VisionTransformer.interpolate_pos_encoding")
+        grid = (T // self.tubelet_size, H // self.patch_size, W // self.patch_size)
+        stamp = (pos_embed.data_ptr(), pos_embed._version, pos_embed.device)
+        cache = self.__dict__.setdefault("_pos_interp_cache", {})
+        if cache.get("stamp") != stamp:     # load_state_dict bumps the version, .to() moves the storage
+            cache.clear()
+            cache["stamp"] = stamp
+        table = cache.get(grid)
+        if table is None:
+            from ...hip import ops
+            N_t = self.num_frames // self.tubelet_size
+            N_h = N_w = self.input_size // self.patch_size
+            dim = pos_embed.shape[-1]
+            assert N_h * N_w * N_t == pos_embed.shape[1], 'Positional embedding initialized incorrectly'
+            scale_factor = (grid[0] / N_t, grid[1] / N_h, grid[2] / N_w)
+            src = pos_embed.detach().to(torch.float32).contiguous().view(N_t, N_h, N_w, dim)
+            out = ops.pos_interp3d(src, scale_factor)
+            if tuple(out.shape[:3]) != grid:
+                raise ValueError(f"interpolated position table has grid {tuple(out.shape[:3])}, the input has {grid}")
+            table = cache[grid] = out.view(1, -1, dim)
+        return table
 
     # ---- compute ------------------------------------------------------------------------------------------
     def _hip_views(self, train):
@@ -106,22 +143,34 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
 
     def forward_masks(self, x, masks):
         """All masks through one fused chain; returns a list with one [B, K_i, D] tensor per mask."""
-        out, segs = self._run(x, masks)
+        out, segs = self._run(x, masks, self._pos_table(x))
         B = x.shape[0]
         return [out[s.row0:s.row0 + s.rows].view(B, s.S, self.embed_dim) for s in segs]
 
+    def _pos_table(self, x):
+        """None at the native clip size (the arena's table is used), otherwise the fp32 [N', D] table of x's token grid.  Still
+        images and off-native sizes are frozen-path features: with gradients enabled they raise."""
+        T, H, W = self._input_size(x)
+        native = H == self.input_size and W == self.input_size and T == self.num_frames
+        if (x.dim() == 4 or not native) and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError("still-image [B,C,H,W] and off-native-size inputs run on the frozen / no-grad path only "
+                                      "(torch.no_grad() or parameters with requires_grad=False); with gradients enabled the "
+                                      "encoder runs at its native clip size, as the pretraining step does")
+        pos = self.interpolate_pos_encoding(x, self.pos_embed)
+        return None if pos is self.pos_embed else pos.view(-1, self.embed_dim)
+
     def forward(self, x, masks=None):
-        """x: fp32 clips [B,3,T,H,W] on the GPU; masks: None, an index tensor, or a list of [B,K] index tensors."""
+        """x: fp32 clips [B,3,T,H,W] on the GPU, or still images [B,3,H,W] standing for the clip of num_frames repetitions
+        (the forward pre-hook of evals/image_classification_frozen/eval.py:452-455); masks: None, an index tensor, or a list
+        of [B,K] index tensors addressing the input's token grid."""
         if masks is not None and not isinstance(masks, list):
             masks = [masks]
-        self.interpolate_pos_encoding(x, self.pos_embed)
-        outs = self.forward_masks(x, masks) if masks is not None else None
-        if masks is None:
-            out, segs = self._run(x, None)
-            return out.view(x.shape[0], self.num_patches, self.embed_dim)
-        return torch.cat(outs, dim=0)
+        if masks is not None:
+            return torch.cat(self.forward_masks(x, masks), dim=0)
+        out, segs = self._run(x, None, self._pos_table(x))
+        return out.view(x.shape[0], segs[0].S, self.embed_dim)
 
-    def _run(self, x, masks):
+    def _run(self, x, masks, pos=None):
         hipmodule.require_gpu(x, "VisionTransformer.forward")
         x = x.contiguous().float()
         if masks is not None:
@@ -139,7 +188,7 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
             import weakref
             from ...engine.chain import Workspace
             self.__dict__["_hip_ws_finalizer"] = weakref.finalize(self, Workspace.release, tag)
-        out, segs, _ = encoder_forward(ew, x, masks, save=False, ws_tag=tag, gemm_flags=flags)
+        out, segs, _ = encoder_forward(ew, x, masks, save=False, ws_tag=tag, gemm_flags=flags, pos=pos)
         return out, segs
 
 

@@ -3,7 +3,13 @@
 shipped eval config with random weights, B = 4 as in the configs.  Reports the frozen forward (clips/s), the probe (ms for the
 training step -- forward, backward, clip_grad_norm_, AdamW -- and for the validation forward over every view), the whole
 run_one_epoch iteration and the peak memory.  One JSON line per config.
-python tools/eval_bench.py [--configs vitl16_k400_16x8x3 vith16_384_k400_16x8x3] [--reps 3]"""
+python tools/eval_bench.py [--configs vitl16_k400_16x8x3 vith16_384_k400_16x8x3] [--reps 3]
+
+--image: the frozen image-classification eval (jepa_amd/evals/image_classification_frozen) in the in1k setup (batch 16, 1000 classes)
+for ViT-L/16-224 and ViT-H/16-384: frozen images/s, probe ms, one training and one validation iteration, peak memory; the still-image
+path against the only route there was before it (the ATen repeat to 16 frames, timed, followed by the 5-D forward), the two arms
+taking turns inside this process in both orders (as tools/abab.py does for the step); and vj_pos_interp3d once per new size.
+python tools/eval_bench.py --image [--image-configs vitl16_in1k vith16_384_in1k] [--rounds 4] [--reps 3]"""
 import argparse
 import json
 import os
@@ -90,11 +96,125 @@ def bench(name, reps, B=4):
                 max_clips_per_call=enc.max_clips_per_call)
 
 
+IMAGE_CONFIGS = {"vitl16_in1k": ("vit_large", 224, 1000), "vith16_in1k": ("vit_huge", 224, 1000),
+                 "vith16_384_in1k": ("vit_huge", 384, 1000)}
+# (model, native token grid) -> token grids to interpolate the position table to
+INTERP_CASES = [("vit_large", 1024, (8, 14, 14), (8, 24, 24)), ("vit_huge", 1280, (8, 24, 24), (8, 14, 14)),
+                ("vit_huge", 1280, (8, 24, 24), (16, 24, 24))]
+
+
+def bench_image(name, reps, rounds, B=16, frames=16):
+    import statistics
+    from jepa_amd.evals.image_classification_frozen import eval as IE
+    model_name, res, C = IMAGE_CONFIGS[name]
+    dev = "cuda"
+    torch.manual_seed(0)
+    enc = vit.__dict__[model_name](img_size=res, patch_size=16, num_frames=frames, tubelet_size=2, uniform_power=True).to(dev).eval()
+    for p in enc.parameters():
+        p.requires_grad = False
+    clf = AttentiveClassifier(embed_dim=enc.embed_dim, num_heads=enc.num_heads, depth=1, num_classes=C).to(dev)
+    opt, scaler, sched, wd_sched = IE.init_opt(clf, iterations_per_epoch=1, start_lr=1e-4, ref_lr=1e-4, warmup=0, num_epochs=10 ** 6,
+                                               wd=0.01)
+    images = torch.randn(B, 3, res, res, device=dev)
+    labels = torch.randint(0, C, (B,))
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+
+    def still():
+        with torch.no_grad():
+            return enc(images)
+
+    def repeated():      # the route before the still-image front end: the repeated fp32 clip through ATen, then the 5-D forward
+        with torch.no_grad():
+            return enc(images.unsqueeze(2).repeat(1, 1, frames, 1, 1))
+
+    arms = {"still": still, "repeat": repeated}
+    peak = {}
+    for arm, fn in arms.items():    # warm-up (workspace growth, code load) and the peak memory of each route on its own
+        torch.cuda.reset_peak_memory_stats()
+        fn()
+        torch.cuda.synchronize()
+        peak[arm] = round((torch.cuda.max_memory_allocated() - base) / 2 ** 30, 3)
+    ms = {arm: [] for arm in arms}
+    for r in range(rounds):
+        for arm in (("still", "repeat") if r % 2 == 0 else ("repeat", "still")):
+            ms[arm].append(timed(arms[arm], reps))
+    mean = {arm: statistics.mean(v) for arm, v in ms.items()}
+    spread = {arm: max(v) - min(v) for arm, v in ms.items()}
+    feats = still()
+    crit = torch.nn.CrossEntropyLoss()
+    lab = labels.to(dev)
+
+    def probe_train():
+        loss = crit(clf(feats), lab)
+        loss.backward()
+        torch.nn.utils.clip_grad_norm_(clf.parameters(), 1.0)
+        opt.step()
+        opt.zero_grad()
+
+    def probe_val():
+        with torch.no_grad():
+            return clf(feats)
+
+    torch.cuda.reset_peak_memory_stats()
+    t_probe_train = timed(probe_train, reps)
+    t_probe_val = timed(probe_val, reps)
+    del feats
+    it_train = timed(lambda: IE.run_one_epoch(dev, True, enc, clf, scaler, opt, sched, wd_sched, [(images, labels)], False), reps)
+    it_val = timed(lambda: IE.run_one_epoch(dev, False, enc, clf, scaler, opt, sched, wd_sched, [(images, labels)], False), reps)
+    torch.cuda.synchronize()
+    return dict(config=name, batch=B, tokens_per_image=enc.num_patches, rounds=rounds, reps=reps,
+                still_ms_rounds=[round(v, 3) for v in ms["still"]], repeat_ms_rounds=[round(v, 3) for v in ms["repeat"]],
+                still_ms_mean=round(mean["still"], 3), repeat_ms_mean=round(mean["repeat"], 3),
+                still_ms_spread=round(spread["still"], 3), repeat_ms_spread=round(spread["repeat"], 3),
+                still_minus_repeat_ms=round(mean["still"] - mean["repeat"], 3),
+                still_not_slower_than_repeat_plus_its_spread=bool(mean["still"] <= mean["repeat"] + spread["repeat"]),
+                frozen_images_per_s=round(B / mean["still"] * 1e3, 1), frozen_images_per_s_repeat=round(B / mean["repeat"] * 1e3, 1),
+                probe_train_step_ms=round(t_probe_train, 3), probe_val_ms=round(t_probe_val, 3),
+                train_iteration_ms=round(it_train, 2), val_iteration_ms=round(it_val, 2),
+                peak_mem_gib_forward_still=peak["still"], peak_mem_gib_forward_repeat=peak["repeat"],
+                peak_mem_gib_iterations=round((torch.cuda.max_memory_allocated() - base) / 2 ** 30, 3))
+
+
+def bench_interp():
+    """vj_pos_interp3d, one launch per new size (the table is cached afterwards), timed by events after an unrelated warm-up launch."""
+    from jepa_amd.hip import ops
+    from jepa_amd.src.models.utils.pos_embs import get_3d_sincos_pos_embed
+    dev = "cuda"
+    warm = torch.zeros(2, 2, 2, 64, device=dev)
+    ops.pos_interp3d(warm, (2.0, 2.0, 2.0))
+    torch.cuda.synchronize()
+    out = []
+    for model, D, src, dst in INTERP_CASES:
+        table = torch.from_numpy(get_3d_sincos_pos_embed(D, src[1], src[0], cls_token=False, uniform_power=True)).float().to(dev)
+        table = table.view(*src, D)
+        scale = tuple(d / s for d, s in zip(dst, src))
+        torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        o = ops.pos_interp3d(table, scale)
+        e.record()
+        torch.cuda.synchronize()
+        out.append(dict(model=model, D=D, src_grid=list(src), dst_grid=list(dst), first_call_us=round(s.elapsed_time(e) * 1e3, 1),
+                        repeat_call_us=round(timed(lambda: ops.pos_interp3d(table, scale), 20) * 1e3, 1),
+                        out_mib=round(o.numel() * 4 / 2 ** 20, 2)))
+    return dict(pos_interp3d=out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--image", action="store_true", help="the image-classification eval instead of the video one")
+    ap.add_argument("--image-configs", nargs="*", default=["vitl16_in1k", "vith16_384_in1k"], choices=sorted(IMAGE_CONFIGS))
+    ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--configs", nargs="*", default=["vitl16_k400_16x8x3", "vith16_384_k400_16x8x3"], choices=sorted(CONFIGS))
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
+    if a.image:
+        for name in a.image_configs:
+            print(json.dumps(bench_image(name, a.reps, a.rounds)), flush=True)
+            torch.cuda.empty_cache()
+        print(json.dumps(bench_interp()), flush=True)
+        return
     for name in a.configs:
         print(json.dumps(bench(name, a.reps)), flush=True)
         torch.cuda.empty_cache()
