@@ -54,6 +54,22 @@ int vj_tubelet_pack(const float* clips, void* out_bf16, const int64_t* idx, int6
 int vj_add_pos(void* x_bf16, const float* pos, const int64_t* idx, int64_t B, int64_t K, int64_t D,
                vj_stream_t stream);
 
+/* ---- device-side clip augmentation: decoded uint8 frames -> model-ready fp32 clips -----------------------------
+ * VideoTransform.__call__ / _tensor_normalize_inplace                       app/vjepa/transforms.py:86-115,138-153
+ * random_resized_crop[_with_shift] / horizontal_flip        src/datasets/utils/video/transforms.py:160-192,545-622
+ * The random draws stay on the host (jepa_amd/app/vjepa/transforms.py); this is the pixel work: per-frame crop box, bilinear
+ * resize to S x S (align_corners=False, fused source coordinate), flip(-1) of the clip, (x - mean) / std.
+ *   frames  flat uint8 buffer of frames_bytes bytes holding clip after clip, each [T,Hs,Ws,3] interleaved RGB
+ *   desc    int64 [B,4] = (byte offset of the clip in frames, Hs, Ws, flip flag)
+ *   boxes   int32 [B,T,4] = (i, j, h, w): top, left, height, width of each frame's crop; 16-byte aligned
+ *   out     fp32 [B,3,T,S,S] (what vj_tubelet_pack takes), S % 4 == 0
+ *   mean_*, std_* in 0..255 units (the reference multiplies its ImageNet constants by 255).
+ * Callers validate desc / boxes on the host before copying them (RawClipBatch.validate); the kernel itself clamps every source
+ * row and column into the frame and writes zeros for a clip whose extent leaves the buffer.  B == 0 launches nothing. */
+int vj_clip_transform(const uint8_t* frames, int64_t frames_bytes, const int64_t* desc, const int32_t* boxes, float* out,
+                      int64_t B, int64_t T, int64_t S, float mean_r, float mean_g, float mean_b, float std_r, float std_g,
+                      float std_b, vj_stream_t stream);
+
 /* ---- still-image front end of the video encoder and position-table interpolation ------------------------------
  * input.unsqueeze(2).repeat(1, 1, frames_per_clip, 1, 1) + patch_embed    evals/image_classification_frozen/eval.py:452-455
  * fp32 images [B,C,H,W] -> the bf16 A operand [B,K,C*tub*p*p] of the patch-embed GEMM for the gh*gw DISTINCT tubelets of

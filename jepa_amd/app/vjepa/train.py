@@ -10,6 +10,7 @@ overlapped with backward) instead of autocast + DDP + torch.optim.AdamW + a per-
 """
 import copy
 import os
+import random
 import time
 
 import numpy as np
@@ -23,6 +24,7 @@ from ...src.masks.multiblock3d import MaskCollator as MB3DMaskCollator
 from ...src.masks.random_tube import MaskCollator as TubeMaskCollator
 from ...src.utils.distributed import AllReduce, init_distributed
 from ...src.utils.logging import AverageMeter, CSVLogger, adamw_logger, get_logger, gpu_timer, grad_logger
+from .transforms import make_transforms
 from .utils import init_opt, init_video_model, load_checkpoint
 
 log_timings = True
@@ -105,6 +107,9 @@ def main(args, resume_preempt=False):
 
     np.random.seed(seed)
     torch.manual_seed(seed)
+    # the crop draws use Python's `random`, which the reference leaves unseeded: loader workers are seeded by the DataLoader from
+    # torch's generator either way, this makes the num_workers = 0 stream reproducible as well
+    random.seed(seed)
     try:
         mp.set_start_method('spawn')
     except Exception:
@@ -142,10 +147,24 @@ def main(args, resume_preempt=False):
     mask_collator = collator_cls(crop_size=cfg.crop_size, num_frames=cfg.num_frames, patch_size=cfg.patch_size,
                                  tubelet_size=cfg.tubelet_size, cfgs_mask=cfgs_mask)
 
+    # data_aug with the reference's defaults (train.py:126-131); the transform only DRAWS on the host (boxes, flip) -- the pixel
+    # work is vj_clip_transform on the prefetcher's copy stream.  The synthetic fp32 stream has no frames to augment.
+    cfgs_data_aug = args.get('data_aug') or {}
+    transform = None
+    if str(cfg.dataset_type).lower() != 'synthetic':
+        transform = make_transforms(
+            random_horizontal_flip=True,
+            random_resize_aspect_ratio=cfgs_data_aug.get('random_resize_aspect_ratio', [3/4, 4/3]),
+            random_resize_scale=cfgs_data_aug.get('random_resize_scale', [0.3, 1.0]),
+            reprob=cfgs_data_aug.get('reprob', 0.),
+            auto_augment=cfgs_data_aug.get('auto_augment', False),
+            motion_shift=cfgs_data_aug.get('motion_shift', False),
+            crop_size=cfg.crop_size)
+
     (unsupervised_loader, unsupervised_sampler) = init_data(
         data=cfg.dataset_type, root_path=cfg.dataset_paths, batch_size=batch_size, training=True, clip_len=cfg.num_frames,
         frame_sample_rate=cfg.sampling_rate, filter_short_videos=cfg.filter_short_videos, decode_one_clip=cfg.decode_one_clip,
-        duration=cfg.duration, num_clips=cfg.num_clips, transform=None, datasets_weights=cfg.datasets_weights,
+        duration=cfg.duration, num_clips=cfg.num_clips, transform=transform, datasets_weights=cfg.datasets_weights,
         collator=mask_collator, num_workers=cfg.num_workers, world_size=world_size, pin_mem=cfg.pin_mem, rank=rank,
         log_dir=None, crop_size=cfg.crop_size)
     try:

@@ -146,6 +146,114 @@ extern "C" int vj_tubelet_pack(const float* clips, void* out_bf16, const int64_t
 }
 
 // ---------------------------------------------------------------------------------------------
+// clip_transform: decoded uint8 frames -> model-ready fp32 clips [B,3,T,S,S]: per-frame crop box (i,j,h,w), bilinear resize
+// of the crop to S x S (F.interpolate(mode='bilinear', align_corners=False)), horizontal flip of the whole clip, then
+// (x - mean) / std with mean / std in 0..255 units.  Source clip b is [T,Hs,Ws,3] (interleaved RGB) at byte `off` of one flat
+// buffer; desc[b] = {off, Hs, Ws, flip}.  Per axis: scale = (float)h / S, c = max(fma(scale, dst + 0.5, -0.5), 0) -- the FUSED
+// form is the one that reproduces the CPU reference (a separately rounded product moves a coordinate near 1000 by one ulp,
+// 1.3e-4 after a 255-step) --, i0 = min((int)c, h - 1), i1 = min(i0 + 1, h - 1), weights 1 - l and l with l = c - i0; rows are
+// blended last: wy0 * (wx0 * p00 + wx1 * p01) + wy1 * (wx0 * p10 + wx1 * p11).  A flipped clip takes output column x from
+// S - 1 - x.  One thread per 4 consecutive output pixels of one (b,t,y): three 16-byte stores, one per channel plane; source
+// bytes come through the cache (neighbouring outputs share them).  Every source row / column is clamped into the frame and a
+// clip whose extent does not lie inside the buffer is written as zeros, whatever the descriptor says: nothing outside
+// [frames, frames + frames_bytes) is ever read.
+// ---------------------------------------------------------------------------------------------
+struct ClipAxis {
+  int i0, i1;
+  float w0, w1;
+};
+
+__device__ __forceinline__ ClipAxis clip_axis(int dst, float scale, int org, int len, int lim) {
+  const float c = fmaxf(fmaf(scale, (float)dst + 0.5f, -0.5f), 0.f);
+  int i0 = (int)c;
+  if (i0 > len - 1) i0 = len - 1;
+  const int i1 = i0 + 1 < len ? i0 + 1 : len - 1;
+  const float l = fminf(fmaxf(c - (float)i0, 0.f), 1.f);
+  ClipAxis a;
+  a.i0 = min(max(org + i0, 0), lim - 1);
+  a.i1 = min(max(org + i1, 0), lim - 1);
+  a.w0 = 1.f - l;
+  a.w1 = l;
+  return a;
+}
+
+struct ClipNorm {
+  float mean[3], std[3];
+};
+
+__global__ __launch_bounds__(256) void clip_transform_kernel(const uint8_t* __restrict__ frames, int64_t frames_bytes,
+                                                             const int64_t* __restrict__ desc,
+                                                             const int4* __restrict__ boxes, float* __restrict__ out,
+                                                             int64_t B, int T, int S, ClipNorm nm) {
+  const uint32_t qpr = (uint32_t)S / 4;  // 16-byte output chunks per row
+  const uint32_t total = (uint32_t)B * T * S * qpr;   // < 2^31 (checked by the launcher): 32-bit index arithmetic
+  const int64_t plane = (int64_t)T * S * S;
+  for (uint32_t q = blockIdx.x * 256u + threadIdx.x; q < total; q += gridDim.x * 256u) {
+    const uint32_t r = q / qpr;   // (b,t,y)
+    const int xq = (int)(q - r * qpr) * 4;
+    const uint32_t bt = r / (uint32_t)S;
+    const int y = (int)(r - bt * (uint32_t)S);
+    const int64_t b = bt / (uint32_t)T;
+    const int t = (int)(bt - (uint32_t)b * (uint32_t)T);
+    const int64_t off = desc[b * 4 + 0], Hs = desc[b * 4 + 1], Ws = desc[b * 4 + 2];
+    const bool flip = desc[b * 4 + 3] != 0;
+    const int4 box = boxes[bt];  // (i, j, h, w)
+    float* o = out + ((b * 3 * T + t) * S + y) * (int64_t)S + xq;
+    float4 res[3];
+    const bool ok = off >= 0 && Hs > 0 && Ws > 0 && Hs < (1 << 20) && Ws < (1 << 20) && box.z > 0 && box.w > 0 &&
+                    off <= frames_bytes && (int64_t)T * Hs * Ws * 3 <= frames_bytes - off;
+    if (ok) {
+      const uint8_t* f = frames + off + (int64_t)t * Hs * Ws * 3;
+      const ClipAxis ay = clip_axis(y, (float)box.z / (float)S, box.x, box.z, (int)Hs);
+      const uint8_t* r0 = f + (int64_t)ay.i0 * Ws * 3;
+      const uint8_t* r1 = f + (int64_t)ay.i1 * Ws * 3;
+      const float sx = (float)box.w / (float)S;
+      float v[3][4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int x = flip ? S - 1 - (xq + k) : xq + k;
+        const ClipAxis ax = clip_axis(x, sx, box.y, box.w, (int)Ws);
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+          const float p00 = (float)r0[ax.i0 * 3 + c], p01 = (float)r0[ax.i1 * 3 + c];
+          const float p10 = (float)r1[ax.i0 * 3 + c], p11 = (float)r1[ax.i1 * 3 + c];
+          const float top = ax.w0 * p00 + ax.w1 * p01, bot = ax.w0 * p10 + ax.w1 * p11;
+          v[c][k] = (ay.w0 * top + ay.w1 * bot - nm.mean[c]) / nm.std[c];
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; c++) res[c] = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; c++) res[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) *(float4*)(o + c * plane) = res[c];
+  }
+}
+
+extern "C" int vj_clip_transform(const uint8_t* frames, int64_t frames_bytes, const int64_t* desc, const int32_t* boxes,
+                                 float* out, int64_t B, int64_t T, int64_t S, float mean_r, float mean_g, float mean_b,
+                                 float std_r, float std_g, float std_b, hipStream_t stream) {
+  VJ_CHECK_ARG(B >= 0 && T > 0 && S > 0 && frames_bytes >= 0 && T < (1 << 20) && S < (1 << 20),
+               "vj_clip_transform: bad dims B=%ld T=%ld S=%ld frames_bytes=%ld", (long)B, (long)T, (long)S, (long)frames_bytes);
+  VJ_CHECK_ARG(S % 4 == 0, "vj_clip_transform: S=%ld must be a multiple of 4", (long)S);
+  VJ_CHECK_ARG(std_r != 0.f && std_g != 0.f && std_b != 0.f, "vj_clip_transform: std must be non-zero");
+  if (B == 0) return 0;
+  VJ_CHECK_ARG(frames != nullptr && desc != nullptr && boxes != nullptr && out != nullptr, "vj_clip_transform: null pointer");
+  VJ_CHECK_ARG(((uintptr_t)out % 16 == 0) && ((uintptr_t)boxes % 16 == 0), "vj_clip_transform: out and boxes must be 16-byte aligned");
+  const int64_t total = B * T * S * (S / 4);
+  VJ_CHECK_ARG(B < (1ll << 31) && total < (1ll << 31), "vj_clip_transform: batch too large (B=%ld)", (long)B);
+  int64_t g = cdiv64(total, 256);
+  if (g > 256 * 32) g = 256 * 32;
+  ClipNorm nm = {{mean_r, mean_g, mean_b}, {std_r, std_g, std_b}};
+  hipLaunchKernelGGL(clip_transform_kernel, dim3((int)g), dim3(256), 0, stream, frames, frames_bytes, desc, (const int4*)boxes,
+                     out, B, (int)T, (int)S, nm);
+  VJ_LAUNCH_CHECK("vj_clip_transform");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // add_pos: x[b,k,:] (bf16) += pos[idx ? idx[b,k] : k, :] (fp32), fp32 add, one rounding.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void add_pos_kernel(bf16_t* __restrict__ x, const float* __restrict__ pos,

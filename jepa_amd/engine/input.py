@@ -15,9 +15,17 @@ before the host memcpy of batch k+depth into a slot's pinned buffer, the host wa
 slot's previous H2D copy (batch k) -- normally long complete, so the wait is free, but without it a host that runs more
 than `depth` steps ahead of the GPU (loss read every N steps, pageable loader tensors) would overwrite pixels a DMA has
 not read yet.  The fp32 -> bf16 cast stays fused in `vj_tubelet_pack` (the copy moves the loader's fp32 pixels verbatim).
+
+A clip entry may also be a `RawClipBatch` (app/vjepa/transforms.py: decoded uint8 frames of varying source size in one flat
+buffer + descriptor and box tables).  Then the uint8 bytes and the two small tables are what crosses PCIe (3 bytes per SOURCE
+pixel instead of 12 per output pixel: 0.38 x the fp32 clip for 240x320 sources at 224x224), and `vj_clip_transform` runs on the
+copy stream, after the copies, into the slot's fp32 [B,3,T,S,S] buffer; `ready` is recorded after it, so `next()` hands out the same tensors as for fp32 batches.
+The flat buffer changes size from batch to batch: its pinned and device staging buffers only ever grow.
 """
 import torch
 
+from ..app.vjepa.transforms import RawClipBatch
+from ..hip import ops
 from ..src.utils.tensors import repeat_interleave_batch
 
 
@@ -56,6 +64,39 @@ class DevicePrefetcher:
         self.bytes_copied += t.numel() * t.element_size()
         return dev
 
+    # -- a flat byte buffer whose length changes from batch to batch: staging buffers grow (x1.25) and are never shrunk
+    def _stage_flat(self, slot, key, t):
+        n = t.numel()
+        host, dev = self._host[slot].get(key), self._dev[slot].get(key)
+        if dev is None or dev.numel() < n:
+            dev = torch.empty(max(n + n // 4, 1), dtype=t.dtype, device=self.device)
+            self._dev[slot][key] = dev
+        if t.is_pinned():
+            src = t
+        else:
+            if host is None or host.numel() < n:
+                host = torch.empty(max(n + n // 4, 1), dtype=t.dtype, pin_memory=True)
+                self._host[slot][key] = host
+            host[:n].copy_(t)
+            src = host[:n]
+        dev[:n].copy_(src, non_blocking=True)
+        self.bytes_copied += n * t.element_size()
+        return dev[:n]
+
+    # -- uint8 frames + tables through staging, then the augmentation kernel into the slot's fp32 clip buffer
+    def _stage_raw(self, slot, i, raw):
+        raw.validate()                                 # on the host, before anything is copied
+        frames = self._stage_flat(slot, ("raw", i), raw.frames)
+        desc = self._stage(slot, ("desc", i), raw.desc)
+        boxes = self._stage(slot, ("boxes", i), raw.boxes)
+        shape = (len(raw), 3, raw.num_frames, raw.crop_size, raw.crop_size)
+        out = self._dev[slot].get(("clip", i))
+        if out is None or tuple(out.shape) != shape or out.dtype != torch.float32:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+            self._dev[slot][("clip", i)] = out
+        return ops.clip_transform(frames, desc, boxes, raw.crop_size, raw.mean, raw.std, out=out,
+                                  stream=self.copy_stream.cuda_stream)
+
     def _launch(self):
         clip_list, masks_enc, masks_pred = self.fetch()
         slot = self._slot
@@ -65,7 +106,8 @@ class DevicePrefetcher:
         with torch.cuda.stream(self.copy_stream):
             if self._free_ev[slot] is not None:
                 self.copy_stream.wait_event(self._free_ev[slot])
-            clips = [self._stage(slot, ("clip", i), u) for i, u in enumerate(clip_list)]
+            clips = [self._stage_raw(slot, i, u) if isinstance(u, RawClipBatch) else self._stage(slot, ("clip", i), u)
+                     for i, u in enumerate(clip_list)]
             me = [self._stage(slot, ("me", i), m) for i, m in enumerate(masks_enc)]
             mp = [self._stage(slot, ("mp", i), m) for i, m in enumerate(masks_pred)]
             ready = torch.cuda.Event()

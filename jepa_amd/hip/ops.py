@@ -148,6 +148,34 @@ def image_pack(images, tubelet, patch, idx=None, out=None, stream=None):
     return out
 
 
+def clip_transform(frames, desc, boxes, S, mean, std, out=None, stream=None):
+    """Decoded uint8 frames -> fp32 clips [B,3,T,S,S]: per-frame crop + bilinear resize to S x S, clip flip, (x - mean) / std.
+    frames: flat uint8 buffer of [T,Hs,Ws,3] clips; desc int64 [B,4] = (byte offset, Hs, Ws, flip); boxes int32 [B,T,4] =
+    (i, j, h, w); mean / std: three floats each in 0..255 units.  The tables must have been validated on the host
+    (jepa_amd.app.vjepa.transforms.RawClipBatch.validate) before they were copied to the device."""
+    lib = load_library()
+    _req(frames, torch.uint8, "frames")
+    _req(desc, I64, "desc")
+    _req(boxes, torch.int32, "boxes")
+    if frames.dim() != 1 or desc.dim() != 2 or desc.shape[1] != 4 or boxes.dim() != 3 or boxes.shape[2] != 4 \
+            or boxes.shape[0] != desc.shape[0]:
+        raise ValueError(f"clip_transform: frames {tuple(frames.shape)} / desc {tuple(desc.shape)} / boxes {tuple(boxes.shape)}: "
+                         "expected [nbytes], [B,4], [B,T,4]")
+    B, T = boxes.shape[0], boxes.shape[1]
+    mean, std = [float(m) for m in mean], [float(v) for v in std]
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("clip_transform: mean and std take three values each")
+    if out is None:
+        out = torch.empty((B, 3, T, S, S), dtype=F32, device=frames.device)
+    else:
+        _req(out, F32, "out")
+        if tuple(out.shape) != (B, 3, T, S, S):
+            raise ValueError(f"clip_transform: out {tuple(out.shape)} is not {(B, 3, T, S, S)}")
+    check(lib.vj_clip_transform(_ptr(frames), frames.numel(), _ptr(desc), _ptr(boxes), _ptr(out), B, T, S, *mean, *std,
+                                _stream(stream)), "vj_clip_transform")
+    return out
+
+
 def add_pos_bcast(y, pos, B, S, Gt, out=None, stream=None):
     """out[b, t*S+s] = bf16(y[b,s] + pos[t*S+s]), t < Gt; y bf16 [B*S, D], pos fp32 [Gt*S, D] -> bf16 [B*Gt*S, D]."""
     lib = load_library()

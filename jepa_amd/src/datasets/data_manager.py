@@ -3,8 +3,11 @@
 The reference's CPU video pipeline (decord decode, clip sampling, augmentation: src/datasets/video_dataset.py,
 app/vjepa/transforms.py) sits OUTSIDE the accelerated hot path and needs packages that are not part of this
 image; `data='synthetic'` provides the seeded synthetic clip stream used by BASELINE.json's configs and the
-tests.  Any real dataset type raises with an explanation instead of silently degrading.
+tests, and `data='synthetic_frames'` seeded uint8 [T,H,W,3] frame buffers of varying size that go through `transform`
+(app/vjepa/transforms.py) the way decoded video does.  Any real dataset type raises with an explanation instead of
+silently degrading.
 """
+import numpy as np
 import torch
 
 
@@ -23,6 +26,40 @@ class SyntheticClips(torch.utils.data.Dataset):
         clips = [torch.randn(3, self.num_frames, self.crop_size, self.crop_size, generator=g)
                  for _ in range(self.num_clips)]
         return clips, 0, [torch.arange(self.num_frames) for _ in range(self.num_clips)]
+
+
+class SyntheticFrames(torch.utils.data.Dataset):
+    """Seeded uint8 frame buffers in the item layout of the reference's VideoDataset (video_dataset.py:156-184):
+    ([transform(clip[T,Hs,Ws,3] uint8)] * num_clips, label, [frame indices]).  The source size of item i is
+    SIZES[(seed + i) % len(SIZES)]: square, non-square, smaller and larger than the usual crops.  Frames depend on (seed, i)
+    alone: a smooth pattern that drifts over time plus noise, so that crops of one clip are correlated like video."""
+
+    SIZES = ((96, 128), (120, 90), (64, 64), (144, 256), (48, 56), (100, 400))
+
+    def __init__(self, length, num_frames, num_clips=1, transform=None, seed=1234):
+        self.length, self.num_frames, self.num_clips, self.transform, self.seed = length, num_frames, num_clips, transform, seed
+
+    def __len__(self):
+        return self.length
+
+    def source_size(self, i):
+        return self.SIZES[(self.seed + i) % len(self.SIZES)]
+
+    def __getitem__(self, i):
+        H, W = self.source_size(i)
+        g = torch.Generator().manual_seed(self.seed + i)
+        clips = []
+        for _ in range(self.num_clips):
+            f = 1.0 + 3.0 * torch.rand(3, 3, generator=g)
+            t = torch.arange(self.num_frames, dtype=torch.float32)[:, None, None, None] / self.num_frames
+            y = torch.arange(H, dtype=torch.float32)[None, :, None, None] / H
+            x = torch.arange(W, dtype=torch.float32)[None, None, :, None] / W
+            wave = torch.cos(6.283185307179586 * (f[0] * t + f[1] * y + f[2] * x))
+            noise = torch.randn(self.num_frames, H, W, 3, generator=g)
+            clips.append((127.5 + 90.0 * wave + 20.0 * noise).clamp_(0, 255).to(torch.uint8).numpy())
+        if self.transform is not None:
+            clips = [self.transform(c) for c in clips]
+        return clips, 0, [np.arange(self.num_frames) for _ in range(self.num_clips)]
 
 
 class SyntheticVideoClassification(torch.utils.data.Dataset):
@@ -104,13 +141,22 @@ def init_data(batch_size, transform=None, shared_transform=None, data='ImageNet'
               num_clips=1, random_clip_sampling=True, allow_clip_overlap=False, filter_short_videos=False,
               filter_long_videos=int(1e9), decode_one_clip=True, datasets_weights=None, persistent_workers=False,
               repeat_wds=False, ipe=300, log_dir=None, crop_size=224, synthetic_length=None):
-    if str(data).lower() != 'synthetic':
+    kind = str(data).lower()
+    if kind not in ('synthetic', 'synthetic_frames'):
         raise NotImplementedError(
-            f"dataset_type={data!r}: the reference's decord/torchvision CPU video pipeline is outside the "
-            "accelerated V-JEPA step and its dependencies are not available here; use dataset_type: synthetic, "
-            "or assign your own loader factory to jepa_amd.app.vjepa.train.init_data")
+            f"dataset_type={data!r}: the reference's decord video decoding needs packages that are not available here. "
+            "The augmentation is: `transform` (jepa_amd.app.vjepa.transforms.make_transforms) takes a uint8 [T,H,W,3] "
+            "buffer per clip and the device does the pixel work, so a loader that yields such buffers through `transform` "
+            "in the VideoDataset item layout is all that is needed -- the reference's src/datasets/video_dataset.py does, "
+            "unchanged.  Assign its factory to jepa_amd.app.vjepa.train.init_data, or use dataset_type: synthetic / "
+            "synthetic_frames")
     length = synthetic_length if synthetic_length is not None else batch_size * world_size * ipe
-    dataset = SyntheticClips(length, clip_len, crop_size, num_clips=num_clips)
+    if kind == 'synthetic_frames':
+        if transform is None:
+            raise ValueError("dataset_type: synthetic_frames needs the clip transform (app/vjepa/transforms.py make_transforms)")
+        dataset = SyntheticFrames(length, clip_len, num_clips=num_clips, transform=transform)
+    else:
+        dataset = SyntheticClips(length, clip_len, crop_size, num_clips=num_clips)
     sampler = torch.utils.data.distributed.DistributedSampler(dataset, num_replicas=world_size, rank=rank, shuffle=True)
     loader = torch.utils.data.DataLoader(dataset, collate_fn=collator, sampler=sampler, batch_size=batch_size,
                                          drop_last=drop_last, pin_memory=pin_mem, num_workers=num_workers,
