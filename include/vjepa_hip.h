@@ -91,6 +91,25 @@ int vj_add_pos_bcast(const void* y_bf16, const float* pos, void* out_bf16, int64
 int vj_pos_interp3d(const float* table, float* out, int64_t Nt, int64_t Nh, int64_t Nw, int64_t D, double scale_t,
                     double scale_h, double scale_w, int64_t To, int64_t Ho, int64_t Wo, vj_stream_t stream);
 
+/* ---- image (num_frames = 1) encoders ---------------------------------------------------------------------------
+ * The 2-D PatchEmbed (Conv2d, src/models/utils/patch_embed.py:11-28) is vj_tubelet_pack on the image viewed as [B,C,1,H,W]
+ * with tubelet = 1, the patch-embed GEMM with K = C*p*p and vj_add_pos.
+ * nn.functional.interpolate(pos_embed [1,D,Nh,Nw], scale_factor=sqrt(npatch / N), mode='bicubic')
+ *                                                                         src/models/vision_transformer.py:238-245
+ * on the token-major table: fp32 [Nh,Nw,D] -> [Ho,Wo,D].  align_corners=False with the scale factor given: the source
+ * coordinate (dst + 0.5) * float(1/scale) - 0.5 is not clamped at zero, the four taps per axis are clamped into the table
+ * and weighted by the cubic convolution with A = -0.75, fp32 accumulation.  Ho, Wo must equal floor(in * scale) computed in
+ * double; table and out 16-byte aligned, D % 4 == 0. */
+int vj_pos_interp2d_bicubic(const float* table, float* out, int64_t Nh, int64_t Nw, int64_t D, double scale, int64_t Ho,
+                            int64_t Wo, vj_stream_t stream);
+/* FrameAggregation's temporal position embedding: o += pos_embed[clip_indices] repeated over the N tokens of each frame
+ *                                                                         evals/video_classification_frozen/utils.py:74-80
+ * x bf16 [B, F*N, D], pos fp32 [max_frames, D], idx int64 [B,F] (the segments' clip_indices concatenated along time):
+ * x[b, f*N+n, :] = bf16(float(x[b, f*N+n, :]) + pos[idx[b,f], :]).  Same fp32 add and single rounding as vj_add_pos.  The
+ * caller validates 0 <= idx < max_frames on the host before copying idx; the kernel clamps it all the same.  D % 8 == 0; x and pos 16-byte aligned. */
+int vj_add_pos_frames(void* x_bf16, const float* pos, const int64_t* idx, int64_t B, int64_t F, int64_t N, int64_t D,
+                      int64_t max_frames, vj_stream_t stream);
+
 /* ---- LayerNorm ----------------------------------------------------------------------------------------------
  * nn.LayerNorm(eps=1e-6) (modules.py:97,106,115,119; vision_transformer.py:193; predictor.py:233).
  * bf16 in/out, fp32 statistics; mean/rstd (nullable pair) are saved for the backward. */

@@ -468,6 +468,144 @@ extern "C" int vj_pos_interp3d(const float* table, float* out, int64_t Nt, int64
 }
 
 // ---------------------------------------------------------------------------------------------
+// pos_interp2d_bicubic: fp32 table [Nh,Nw,D] -> [Ho,Wo,D], the bicubic F.interpolate(scale_factor=s) of the image branch of
+// interpolate_pos_encoding (src/models/vision_transformer.py:230-246) on the channels-last view it permutes to and from.
+// align_corners=False with the scale factor GIVEN: per axis src = (dst + 0.5) * r - 0.5 with r = float(1 / scale), NOT
+// clamped at zero (only the linear modes clamp); i = floor(src), t = src - i; the four taps i-1 .. i+2 are clamped into
+// [0, in-1] and weighted by the cubic convolution with A = -0.75:
+//   w0 = ((A(t+1) - 5A)(t+1) + 8A)(t+1) - 4A,  w1 = ((A+2)t - (A+3))t^2 + 1,  w2 = w1(1-t),  w3 = w0(1-t).
+// Rows are blended last, each an fp32 sum of its four columns.  One thread per 4 output floats; the 16 taps are 16-byte loads.
+// ---------------------------------------------------------------------------------------------
+struct CubicAxis {
+  int i[4];
+  float w[4];
+};
+
+__device__ __forceinline__ float cubic_near(float x) {   // |x| <= 1
+  const float A = -0.75f;
+  return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f;
+}
+
+__device__ __forceinline__ float cubic_far(float x) {   // 1 < |x| < 2
+  const float A = -0.75f;
+  return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A;
+}
+
+__device__ __forceinline__ CubicAxis cubic_axis(int dst, float r, int in) {
+  const float src = __fsub_rn(__fmul_rn(r, (float)dst + 0.5f), 0.5f);
+  int i0 = (int)floorf(src);
+  if (i0 > in - 1) i0 = in - 1;
+  float t = src - (float)i0;
+  t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
+  CubicAxis a;
+#pragma unroll
+  for (int k = 0; k < 4; k++) a.i[k] = min(max(i0 - 1 + k, 0), in - 1);
+  a.w[0] = cubic_far(t + 1.f);
+  a.w[1] = cubic_near(t);
+  a.w[2] = cubic_near(1.f - t);
+  a.w[3] = cubic_far((1.f - t) + 1.f);
+  return a;
+}
+
+__global__ __launch_bounds__(256) void pos_interp2d_bicubic_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                                   int Nh, int Nw, int D, float r, int Ho, int Wo) {
+  const int dv = D / 4;
+  const int64_t total = (int64_t)Ho * Wo * dv;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < total; q += (int64_t)gridDim.x * 256) {
+    const int64_t cell = q / dv;
+    const int c = (int)(q - cell * dv) * 4;
+    const int w = (int)(cell % Wo), h = (int)(cell / Wo);
+    const CubicAxis ah = cubic_axis(h, r, Nh), aw = cubic_axis(w, r, Nw);
+    float4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const float* row = in + (int64_t)ah.i[j] * Nw * D + c;
+      float4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const float4 v = *(const float4*)(row + (int64_t)aw.i[k] * D);
+        s.x += aw.w[k] * v.x;
+        s.y += aw.w[k] * v.y;
+        s.z += aw.w[k] * v.z;
+        s.w += aw.w[k] * v.w;
+      }
+      acc.x += ah.w[j] * s.x;
+      acc.y += ah.w[j] * s.y;
+      acc.z += ah.w[j] * s.z;
+      acc.w += ah.w[j] * s.w;
+    }
+    *(float4*)(out + cell * D + c) = acc;
+  }
+}
+
+extern "C" int vj_pos_interp2d_bicubic(const float* table, float* out, int64_t Nh, int64_t Nw, int64_t D, double scale,
+                                       int64_t Ho, int64_t Wo, hipStream_t stream) {
+  VJ_CHECK_ARG(Nh > 0 && Nw > 0 && D > 0 && Nh < (1 << 20) && Nw < (1 << 20), "vj_pos_interp2d_bicubic: bad table dims %ldx%ldx%ld",
+               (long)Nh, (long)Nw, (long)D);
+  VJ_CHECK_ARG(D % 4 == 0, "vj_pos_interp2d_bicubic: D=%ld must be a multiple of 4", (long)D);
+  VJ_CHECK_ARG(scale > 0.0, "vj_pos_interp2d_bicubic: the scale factor must be positive");
+  VJ_CHECK_ARG(Ho > 0 && Wo > 0 && Ho < (1 << 20) && Wo < (1 << 20), "vj_pos_interp2d_bicubic: non-positive output grid %ldx%ld",
+               (long)Ho, (long)Wo);
+  // F.interpolate's output extent for a given scale factor: floor(in * scale) in double
+  VJ_CHECK_ARG(Ho == (int64_t)floor((double)Nh * scale) && Wo == (int64_t)floor((double)Nw * scale),
+               "vj_pos_interp2d_bicubic: output grid %ldx%ld is not floor(in * scale)", (long)Ho, (long)Wo);
+  VJ_CHECK_ARG(table != nullptr && out != nullptr, "vj_pos_interp2d_bicubic: null pointer");
+  VJ_CHECK_ARG(((uintptr_t)table | (uintptr_t)out) % 16 == 0, "vj_pos_interp2d_bicubic: table and out must be 16-byte aligned");
+  const int64_t total = Ho * Wo * (D / 4);
+  int64_t g = cdiv64(total, 256);
+  if (g > 256 * 32) g = 256 * 32;
+  hipLaunchKernelGGL(pos_interp2d_bicubic_kernel, dim3((int)g), dim3(256), 0, stream, table, out, (int)Nh, (int)Nw, (int)D,
+                     (float)(1.0 / scale), (int)Ho, (int)Wo);
+  VJ_LAUNCH_CHECK("vj_pos_interp2d_bicubic");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// add_pos_frames: x[b, f*N + n, :] (bf16) += pos[idx[b,f], :] (fp32), the temporal position embedding of FrameAggregation
+// (evals/video_classification_frozen/utils.py:74-80): every token of frame f of sample b takes the table row of that frame's
+// index.  add_pos_kernel's add (fp32, one rounding).  One wave per token row; idx values were validated on the host and are
+// clamped into [0, max_frames) here all the same, so no row outside the table is ever read.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void add_pos_frames_kernel(bf16_t* __restrict__ x, const float* __restrict__ pos,
+                                                             const int64_t* __restrict__ idx, int64_t rows, int64_t N, int D,
+                                                             int64_t max_frames) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  for (int64_t r = wave; r < rows; r += nw) {
+    int64_t n = idx[r / N];   // rows = B*F*N, idx is [B,F]: row r belongs to frame r / N
+    n = n < 0 ? 0 : (n > max_frames - 1 ? max_frames - 1 : n);
+    bf16_t* xp = x + r * D;
+    const float* pp = pos + n * D;
+    for (int c = lane * 8; c < D; c += 512) {
+      u32x4_t v = *(u32x4_t*)(xp + c);
+      const float4 p0 = *(const float4*)(pp + c);
+      const float4 p1 = *(const float4*)(pp + c + 4);
+      v[0] = pack_bf2(bf_lo(v[0]) + p0.x, bf_hi(v[0]) + p0.y);
+      v[1] = pack_bf2(bf_lo(v[1]) + p0.z, bf_hi(v[1]) + p0.w);
+      v[2] = pack_bf2(bf_lo(v[2]) + p1.x, bf_hi(v[2]) + p1.y);
+      v[3] = pack_bf2(bf_lo(v[3]) + p1.z, bf_hi(v[3]) + p1.w);
+      *(u32x4_t*)(xp + c) = v;
+    }
+  }
+}
+
+extern "C" int vj_add_pos_frames(void* x_bf16, const float* pos, const int64_t* idx, int64_t B, int64_t F, int64_t N, int64_t D,
+                                 int64_t max_frames, hipStream_t stream) {
+  VJ_CHECK_ARG(B >= 0 && F >= 0 && N >= 0 && D > 0 && max_frames > 0, "vj_add_pos_frames: bad dims B=%ld F=%ld N=%ld D=%ld max_frames=%ld",
+               (long)B, (long)F, (long)N, (long)D, (long)max_frames);
+  VJ_CHECK_ARG(D % 8 == 0, "vj_add_pos_frames: D=%ld must be a multiple of 8", (long)D);
+  const int64_t rows = B * F * N;
+  if (rows == 0) return 0;
+  VJ_CHECK_ARG(x_bf16 != nullptr && pos != nullptr && idx != nullptr, "vj_add_pos_frames: null pointer");
+  VJ_CHECK_ARG(((uintptr_t)x_bf16 | (uintptr_t)pos) % 16 == 0, "vj_add_pos_frames: x and pos must be 16-byte aligned");
+  hipLaunchKernelGGL(add_pos_frames_kernel, dim3(rows_grid(rows)), dim3(256), 0, stream, (bf16_t*)x_bf16, pos, idx, rows, N,
+                     (int)D, max_frames);
+  VJ_LAUNCH_CHECK("vj_add_pos_frames");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // pred_assemble_fwd: out[b, j, :] = j < Ke ? e[b,j,:] + pos[idx_e[b,j]] : tok[:] + pos[idx_p[b,j-Ke]]
 //   e  = predictor_embed(z)   bf16 [B,Ke,Dp]     (predictor.py:194-200)
 //   tok = mask_tokens[i]      fp32 [Dp]          (predictor.py:207-217)

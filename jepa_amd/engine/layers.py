@@ -322,9 +322,46 @@ def _wait_gates(gates, chained):
             cur.wait_event(ev)
 
 
+def _image_model_tokens(ew: EncoderW, clips, masks, N, kdim):
+    """Patch rows of the image model's input (tok bf16 [rows, 3*p*p], segs): images [B,3,H,W], or frames given as one clip tensor
+    [B,3,T,H,W] or a list of such tensors of one frame size.  vj_tubelet_pack with tubelet 1 emits a clip's rows in (b,t,h,w) order,
+    which is frame-major: every frame becomes its own sequence of N tokens, the frames of a list following one another part by part,
+    and no [B*T,3,H,W] copy of the pixels is made.  Masks address one image's token grid and go with images only.  The shapes were
+    validated by VisionTransformer.forward / forward_frames; this only packs."""
+    parts = list(clips) if isinstance(clips, (list, tuple)) else [clips]
+    parts = [c.unsqueeze(2) if c.dim() == 4 else c for c in parts]      # a view: an image is its own one-frame clip
+    p = ew.patch_size
+    if (parts[0].shape[-2] // p) * (parts[0].shape[-1] // p) != N:     # the callers checked that the parts share one frame size
+        raise ValueError(f"encoder_forward: position table of {N} rows does not fit images of "
+                         f"{parts[0].shape[-2] // p}x{parts[0].shape[-1] // p} cells")
+    frames = [c.shape[0] * c.shape[2] for c in parts]
+    if masks is None:
+        segs = [Seg(0, sum(frames), N)]
+        if len(parts) == 1:
+            return ops.tubelet_pack(parts[0], 1, p), segs
+        tok = torch.empty((sum(frames) * N, kdim), dtype=torch.bfloat16, device=parts[0].device)
+        r = 0
+        for c, f in zip(parts, frames):
+            ops.tubelet_pack(c, 1, p, out=tok[r:r + f * N])
+            r += f * N
+        return tok, segs
+    if len(parts) != 1 or parts[0].shape[2] != 1:
+        raise ValueError("encoder_forward: masks address one image's token grid; frames [B,C,T,H,W] take none")
+    B = parts[0].shape[0]
+    segs, r = [], 0
+    for m in masks:
+        segs.append(Seg(r, B, m.shape[1]))
+        r += B * m.shape[1]
+    tok = torch.empty((r, kdim), dtype=torch.bfloat16, device=parts[0].device)
+    for sg, m in zip(segs, masks):
+        ops.tubelet_pack(parts[0], 1, p, idx=m, out=_rows(tok, sg))
+    return tok, segs
+
+
 def encoder_forward(ew: EncoderW, clips, masks: Optional[List[torch.Tensor]], save: bool, final_norm=True, ws_tag=None,
                     gemm_flags=0, gates=None, pos=None):
-    """clips fp32 [B,3,T,H,W], or still images [B,3,H,W] standing for the clip that repeats each image along time; masks:
+    """clips fp32 [B,3,T,H,W], or still images [B,3,H,W] standing for the clip that repeats each image along time; for the image
+    model (ew.image) images [B,3,H,W], or frames [B,3,T,H,W] (or a list of such clips) each encoded on its own (_image_model_tokens); masks:
     None (all N tokens) or a list of int64 [B,K_i] index tensors.  pos (fp32 [N, D], default ew.pos): the position table of
     the input's token grid (gt, gh, gw), N = gt*gh*gw; the grid is taken from the input (and, for a still image, gt from N).
     Returns (out [sum_i B*K_i, D] bf16, segs, saved).  With final_norm=False the last residual stream is returned
@@ -335,33 +372,39 @@ def encoder_forward(ew: EncoderW, clips, masks: Optional[List[torch.Tensor]], sa
     (vj_image_pack with idx) and go through the same GEMM and vj_add_pos as a clip's.  Both equal the materialised repeated
     clip bit for bit: the packed rows hold the same bf16 pixels, the NT GEMM accumulates a row's dot product in the same K
     order in every execution form, and the position add is the same single fp32 rounding."""
-    B = clips.shape[0]
     D = ew.patch.w.shape[0]
     kdim = ew.patch.w.shape[1]
     pos = ew.pos if pos is None else pos
     N = pos.shape[0]
-    still = clips.dim() == 4
-    cells = (clips.shape[-2] // ew.patch_size) * (clips.shape[-1] // ew.patch_size)
-    if still:
+    if ew.image:
         if save:
-            raise ValueError("encoder_forward: still-image input is a frozen (save=False) path")
-        if cells == 0 or N % cells != 0:
-            raise ValueError(f"encoder_forward: position table of {N} rows does not fit images of {cells} cells")
-    elif (clips.shape[2] // ew.tubelet) * cells != N:
-        raise ValueError(f"encoder_forward: position table of {N} rows does not fit the input's token grid "
-                         f"{clips.shape[2] // ew.tubelet}x{clips.shape[-2] // ew.patch_size}x{clips.shape[-1] // ew.patch_size}")
-    pack = ops.image_pack if still else ops.tubelet_pack
-    if masks is None:
-        segs = [Seg(0, B, N)]
-        tok = pack(clips, ew.tubelet, ew.patch_size)
+            raise ValueError("encoder_forward: the image model is a frozen (save=False) path")
+        still = False
+        tok, segs = _image_model_tokens(ew, clips, masks, N, kdim)
     else:
-        segs, r = [], 0
-        for m in masks:
-            segs.append(Seg(r, B, m.shape[1]))
-            r += B * m.shape[1]
-        tok = torch.empty((r, kdim), dtype=torch.bfloat16, device=clips.device)
-        for sg, m in zip(segs, masks):
-            pack(clips, ew.tubelet, ew.patch_size, idx=m, out=_rows(tok, sg))
+        B = clips.shape[0]
+        still = clips.dim() == 4
+        cells = (clips.shape[-2] // ew.patch_size) * (clips.shape[-1] // ew.patch_size)
+        if still:
+            if save:
+                raise ValueError("encoder_forward: still-image input is a frozen (save=False) path")
+            if cells == 0 or N % cells != 0:
+                raise ValueError(f"encoder_forward: position table of {N} rows does not fit images of {cells} cells")
+        elif (clips.shape[2] // ew.tubelet) * cells != N:
+            raise ValueError(f"encoder_forward: position table of {N} rows does not fit the input's token grid "
+                             f"{clips.shape[2] // ew.tubelet}x{clips.shape[-2] // ew.patch_size}x{clips.shape[-1] // ew.patch_size}")
+        pack = ops.image_pack if still else ops.tubelet_pack
+        if masks is None:
+            segs = [Seg(0, B, N)]
+            tok = pack(clips, ew.tubelet, ew.patch_size)
+        else:
+            segs, r = [], 0
+            for m in masks:
+                segs.append(Seg(r, B, m.shape[1]))
+                r += B * m.shape[1]
+            tok = torch.empty((r, kdim), dtype=torch.bfloat16, device=clips.device)
+            for sg, m in zip(segs, masks):
+                pack(clips, ew.tubelet, ew.patch_size, idx=m, out=_rows(tok, sg))
     chained = ws_tag is not None and USE_C_CHAIN
     _wait_gates(gates, chained)
     x = ops.gemm_nt(tok, ew.patch.w, bias=ew.patch.b, flags=(gemm_flags & 0xffff if not gemm_flags >> 16 else 0) or None)

@@ -153,6 +153,8 @@ class Trainer:
                  micro_batch=None, overlap_update=False):
         self.encoder, self.predictor, self.target_encoder = encoder, predictor, target_encoder
         self.vit, self.pred, self.tvit = encoder.backbone, predictor.backbone, target_encoder.backbone
+        if not (self.vit.is_video and self.tvit.is_video):
+            raise NotImplementedError("the pretraining step is video-only: image (num_frames=1) encoders run on the frozen-eval path")
         self.device = torch.device(device) if device is not None else next(encoder.parameters()).device
         if self.device.type != "cuda":
             raise ValueError("jepa_amd.Trainer needs a GPU device: the step runs in libvjepa_hip.so only")

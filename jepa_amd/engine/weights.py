@@ -88,13 +88,14 @@ class FoldW:
 
 @dataclass
 class EncoderW:
-    patch: LinearW                        # Conv3d weight viewed [D, C*tub*p*p]
+    patch: LinearW                        # Conv3d weight viewed [D, C*tub*p*p] (image model: Conv2d, [D, C*p*p])
     pos: torch.Tensor                     # fp32 [N, D]
     blocks: List[BlockW]
     norm: NormW
     heads: int = 1
     tubelet: int = 2
     patch_size: int = 16
+    image: bool = False                   # the 2-D image ViT (num_frames = 1): tubelet is 1 and every frame is its own sequence
     folds: Optional[List[FoldW]] = None   # set (EMA target encoder, option ln_fold): the forward takes vj_blocks_fwd_lnfold
 
 
@@ -226,8 +227,8 @@ def encoder_views(arena, prefix, vit, pos, train):
     D = vit.embed_dim
     return EncoderW(patch=_lin(arena, prefix + "patch_embed.proj", train, (D, -1)), pos=pos,
                     blocks=[_block(arena, f"{prefix}blocks.{i}.", train) for i in range(len(vit.blocks))],
-                    norm=_norm(arena, prefix + "norm", train), heads=vit.num_heads, tubelet=vit.tubelet_size,
-                    patch_size=vit.patch_size)
+                    norm=_norm(arena, prefix + "norm", train), heads=vit.num_heads,
+                    tubelet=vit.tubelet_size if vit.is_video else 1, patch_size=vit.patch_size, image=not vit.is_video)
 
 
 def predictor_views(arena, prefix, pred, pos, train):

@@ -6,11 +6,14 @@
 
 Same config keys, probe (AttentiveClassifier on all tokens of the frozen encoder), optimizer groups, schedules, loss and accuracy
 arithmetic, CSV columns, checkpoint dictionary and folder / file names.  Differences from the reference:
-  - the encoder is the VIDEO ViT (`pretrain.frames_per_clip` > 1, as in every shipped image config) and takes the [B,C,H,W] batch
+  - with `pretrain.frames_per_clip` > 1 (every shipped image config) the encoder is the VIDEO ViT and takes the [B,C,H,W] batch
     itself: the reference's forward pre-hook that repeats every image `frames_per_clip` times (eval.py:451-457) is not registered
     and the repeated clip is never materialised (vj_image_pack / vj_add_pos_bcast, bit-identical to feeding the repeated clip).
     `data.resolution` may differ from the checkpoint's: the position table is interpolated (vj_pos_interp3d) when the model is
     called at another size than it was built for, and load_pretrained keeps the model's own table when the shapes differ.
+  - with `pretrain.frames_per_clip` == 1 (the reference's default) the encoder is the 2-D image ViT, fed the [B,C,H,W] batch as the
+    reference feeds it (no pre-hook is registered there, eval.py:451); its table is interpolated bicubically at other square sizes
+    (vj_pos_interp2d_bicubic).
   - bf16 compute, `use_bfloat16`, `use_silu` and the DistributedDataParallel wrapping are handled exactly as in the video eval
     (..video_classification_frozen.eval, whose load_checkpoint, load_pretrained, init_model and init_opt are these files' too).
   - there are no real image datasets: `data.dataset_name` must be `synthetic` (seeded labelled images,
@@ -18,7 +21,6 @@ arithmetic, CSV columns, checkpoint dictionary and folder / file names.  Differe
     batches) and `data.num_workers` (default 0).
   - one encoder call never holds more images than keep fc1's output below 2^31 elements, counted from the tokens the actual input
     makes (frozen_features).
-  - image (frames_per_clip == 1) encoders are not supported, as in the video eval.
   - `main` returns a small record of the run (per-epoch accuracies, per-iteration training loss and learning rate).
 """
 import os
@@ -107,7 +109,7 @@ def main(args_eval, resume_preempt=False):
     if rank == 0:
         csv_logger = CSVLogger(log_file, ('%d', 'epoch'), ('%.5f', 'loss'), ('%.5f', 'acc'))
 
-    # -- pretrained encoder (frozen): the video ViT, fed [B,C,H,W] directly
+    # -- pretrained encoder (frozen): the video ViT, or the image ViT with frames_per_clip == 1; both are fed [B,C,H,W] directly
     encoder = init_model(crop_size=resolution, device=device, pretrained=pretrained_path, model_name=model_name,
                          patch_size=patch_size, frames_per_clip=frames_per_clip, tubelet_size=tubelet_size,
                          uniform_power=uniform_power, checkpoint_key=checkpoint_key, use_SiLU=use_SiLU, tight_SiLU=tight_SiLU,
@@ -183,7 +185,8 @@ def frozen_features(encoder, imgs):
         return encoder(imgs)
     B = imgs.shape[0]
     frames = encoder.num_frames if imgs.dim() == 4 else imgs.shape[2]
-    tokens = (frames // encoder.tubelet_size) * (imgs.shape[-2] // encoder.patch_size) * (imgs.shape[-1] // encoder.patch_size)
+    depth = frames // encoder.tubelet_size if getattr(encoder, 'is_video', True) else 1     # the image model has no tubelets
+    tokens = depth * (imgs.shape[-2] // encoder.patch_size) * (imgs.shape[-1] // encoder.patch_size)
     cap = max_clips_per_call(_widest(encoder), max(tokens, 1))
     if B <= cap:
         return encoder(imgs)

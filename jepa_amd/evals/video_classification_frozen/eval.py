@@ -14,7 +14,8 @@ arithmetic, CSV columns, checkpoint dictionary and folder / file names.  Differe
     default 8 batches) and `data.num_workers` (default 0).
   - the classifier is wrapped in DistributedDataParallel only when a process group with more than one rank is active; its
     checkpoint keys carry the `module.` prefix either way, so checkpoints move between this package and the reference.
-  - image encoders (FrameAggregation, pretrain.frames_per_clip == 1) are not supported.
+  - with `pretrain.frames_per_clip` == 1 the encoder is the 2-D image ViT under FrameAggregation, which (as in the reference) only
+    has the concatenated form: `optimization.attend_across_segments` must be true.
   - `main` returns a small record of the run (per-epoch accuracies, per-iteration training loss and learning rate).
 """
 import os
@@ -94,6 +95,11 @@ def main(args_eval, resume_preempt=False):
     # -- EXPERIMENT-ID/TAG (optional)
     resume_checkpoint = args_eval.get('resume_checkpoint', False) or resume_preempt
     eval_tag = args_eval.get('tag', None)
+
+    if pretrain_frames_per_clip == 1 and not attend_across_segments:
+        raise ValueError("pretrain.frames_per_clip == 1 needs optimization.attend_across_segments: true: the reference's frame "
+                         "aggregation only has the concatenated form (one [B, S*T*N, D] tensor per view), and the epoch loop of "
+                         "attend_across_segments: false would iterate over the batch dimension of those tensors")
 
     if not torch.cuda.is_available():
         raise RuntimeError("the frozen eval computes on the GPU through libvjepa_hip.so (there is no CPU path)")

@@ -1,4 +1,4 @@
-"""Clip aggregation of the frozen video-classification eval (evals/video_classification_frozen/utils.py:22-159).
+"""Clip and frame aggregation of the frozen video-classification eval (evals/video_classification_frozen/utils.py:22-159).
 
 ClipAggregation keeps the reference's constructor, attributes and forward contract: the input is a list over segments of lists
 over views of [B,C,T,H,W] clips; the output is a list over views of [B, S*N, D] (attend_across_segments) or a list over views of
@@ -10,11 +10,12 @@ import torch
 import torch.nn as nn
 
 from ...hip import ops
+from ...src.models.utils.pos_embs import get_1d_sincos_pos_embed
 
 
 def max_clips_per_call(width, tokens_per_clip):
-    """Clips per encoder call that keep the widest activation (M token rows x `width` columns: fc1's output) below 2^31
-    elements."""
+    """Clips (or frames of an image encoder: tokens_per_clip is then one frame's tokens; with 1, token rows) per encoder call that
+    keep the widest activation (M token rows x `width` columns: fc1's output) below 2^31 elements."""
     return max(1, (2 ** 31 - 1) // (width * tokens_per_clip))
 
 
@@ -26,11 +27,96 @@ def _widest(model):
 
 
 class FrameAggregation(nn.Module):
-    """Image encoders (evals/video_classification_frozen/utils.py:22-81): not supported, as image ViTs are not."""
+    """Process each frame independently and concatenate all tokens (utils.py:23-83), for this package's image (num_frames=1)
+    VisionTransformer.  Like the reference it always returns the concatenated layout: a list over views of [B, S*T*N, D].
+
+    The reference's [B*T,C,H,W] permuted copy of the frames is never made: the image encoder packs the patch rows straight from
+    the [B,C,T,H,W] clips (VisionTransformer.forward_frames), several clips per trunk call, each call small enough that its widest
+    activation stays below 2^31 elements (max_tokens_per_call token rows), and the segments are written into the per-view output
+    by the bit-exact row copy (vj_copy_rows).  The temporal position embedding is one in-place pass per view (vj_add_pos_frames)."""
 
     def __init__(self, model, max_frames=10000, use_pos_embed=False, attend_across_segments=False):
-        raise NotImplementedError("FrameAggregation runs an image (num_frames=1) encoder frame by frame; image ViTs are "
-                                  "outside this package (see jepa_amd/src/models/vision_transformer.py)")
+        from ...src.models.vision_transformer import VisionTransformer
+        if not isinstance(model, VisionTransformer) or model.is_video:
+            raise NotImplementedError("FrameAggregation drives the frames entry of this package's image (num_frames=1) "
+                                      "VisionTransformer (forward_frames); other encoders are not supported")
+        super().__init__()
+        self.model = model
+        self.embed_dim = embed_dim = model.embed_dim
+        self.num_heads = model.num_heads
+        self.attend_across_segments = attend_across_segments
+        # 1D-temporal pos-embedding
+        self.pos_embed = None
+        if use_pos_embed:
+            self.pos_embed = nn.Parameter(torch.zeros(1, max_frames, embed_dim), requires_grad=False)
+            sincos = get_1d_sincos_pos_embed(embed_dim, max_frames)
+            self.pos_embed.data.copy_(torch.from_numpy(sincos).float().unsqueeze(0))
+        # encoder call size in token rows: fc1's output of one call stays below 2^31 elements
+        self.max_tokens_per_call = max_clips_per_call(_widest(model), 1)
+
+    def _pieces(self, x, frames_per_call):
+        """(clips [b,C,t,H,W], view, first sample, first frame of the output) in the reference's order, none above frames_per_call
+        frames: whole (segment, view) tensors where they fit, else runs of samples, else runs of frames of one sample.  Segments
+        follow one another along time, each with its own length, as the reference's torch.cat(x, dim=2) lays them out."""
+        first = 0
+        for xi in x:
+            for j, c in enumerate(xi):
+                B, T = c.shape[0], c.shape[2]
+                if frames_per_call >= T:
+                    step = frames_per_call // T
+                    for b0 in range(0, B, step):
+                        yield c[b0:b0 + step], j, b0, first
+                else:
+                    for b0 in range(B):
+                        for t0 in range(0, T, frames_per_call):
+                            yield c[b0:b0 + 1, :, t0:t0 + frames_per_call], j, b0, first + t0
+            first += xi[0].shape[2]
+
+    def forward(self, x, clip_indices=None):
+        num_views_per_clip = len(x[0])
+        # what the reference's two torch.cat calls require: views of one shape, segments that differ in length only
+        frame = lambda c: (c.dim(),) + tuple(c.shape[:2] + c.shape[3:])      # noqa: E731
+        if x[0][0].dim() != 5 or any(len(xi) != num_views_per_clip or any(c.shape != xi[0].shape for c in xi)
+                                     or frame(xi[0]) != frame(x[0][0]) for xi in x):
+            raise ValueError(f"FrameAggregation: segments of {num_views_per_clip} views of [B,C,T,H,W] clips that differ in T "
+                             f"only are expected, got {[[tuple(c.shape) for c in xi] for xi in x]}")
+        B, C, _, H, W = x[0][0].shape
+        p = self.model.patch_size
+        N, D = (H // p) * (W // p), self.embed_dim
+        F = sum(xi[0].shape[2] for xi in x)
+        device = x[0][0].device
+        idx = None
+        if (self.pos_embed is not None) and (clip_indices is not None):
+            idx = torch.cat([ci.reshape(B, -1) for ci in clip_indices], dim=1).to(torch.int64)   # [B, S*T], shared by all views
+            lo, hi = (int(v) for v in torch.stack([idx.min(), idx.max()]).tolist()) if idx.numel() else (0, 0)
+            if idx.shape[1] != F or lo < 0 or hi >= self.pos_embed.shape[1]:
+                raise ValueError(f"FrameAggregation: clip_indices {tuple(idx.shape)} in [{lo}, {hi}] do not index {F} frames of a "
+                                 f"temporal table of {self.pos_embed.shape[1]} rows")
+            idx = idx.to(device).contiguous()
+        outs = [torch.empty((B, F * N, D), dtype=torch.bfloat16, device=device) for _ in range(num_views_per_clip)]
+        cap = max(1, self.max_tokens_per_call // max(N, 1))     # frames per encoder call
+        call, frames = [], 0
+
+        def flush():
+            feats = self.model.forward_frames([c for c, _, _, _ in call])
+            for (c, j, b0, f0), f in zip(call, feats):
+                n = c.shape[2] * N
+                ops.copy_rows(f, outs[j][b0:b0 + c.shape[0]], c.shape[0], n, 0, F * N, f0 * N, n, D)
+
+        for piece in self._pieces(x, cap):
+            n = piece[0].shape[0] * piece[0].shape[2]
+            if call and frames + n > cap:
+                flush()
+                call, frames = [], 0
+            call.append(piece)
+            frames += n
+        if call:
+            flush()
+        if idx is not None:
+            pos = self.pos_embed.detach()[0].to(device=device, dtype=torch.float32).contiguous()
+            for o in outs:
+                ops.add_pos_frames(o, pos, idx, N)
+        return outs
 
 
 class ClipAggregation(nn.Module):

@@ -204,6 +204,35 @@ def pos_interp3d(table, scale_factor, stream=None):
     return out
 
 
+def pos_interp2d_bicubic(table, scale_factor, stream=None):
+    """Bicubic F.interpolate(scale_factor=s, align_corners=False) of an fp32 position table [Nh,Nw,D] along its two grid axes ->
+    [floor(Nh*s), floor(Nw*s), D]."""
+    import math
+    lib = load_library()
+    _req(table, F32, "table")
+    Nh, Nw, D = table.shape
+    s = float(scale_factor)
+    Ho, Wo = (int(math.floor(float(n) * s)) for n in (Nh, Nw))
+    out = torch.empty((max(Ho, 0), max(Wo, 0), D), dtype=F32, device=table.device)
+    check(lib.vj_pos_interp2d_bicubic(_ptr(table), _ptr(out), Nh, Nw, D, s, Ho, Wo, _stream(stream)), "vj_pos_interp2d_bicubic")
+    return out
+
+
+def add_pos_frames(x, pos, idx, N, stream=None):
+    """x bf16 [B, F*N, D] += pos[idx[b,f]] on the N token rows of frame f (fp32 table [max_frames, D], idx int64 [B,F] already
+    validated against the table on the host); in place."""
+    lib = load_library()
+    _req(x, BF16, "x")
+    _req(pos, F32, "pos")
+    _req(idx, I64, "idx")
+    B, F = idx.shape
+    D = x.shape[-1]
+    if x.numel() != B * F * N * D or pos.dim() != 2 or pos.shape[1] != D:
+        raise ValueError(f"add_pos_frames: x {tuple(x.shape)} / pos {tuple(pos.shape)} do not match idx {tuple(idx.shape)}, N={N}")
+    check(lib.vj_add_pos_frames(_ptr(x), _ptr(pos), _ptr(idx), B, F, N, D, pos.shape[0], _stream(stream)), "vj_add_pos_frames")
+    return x
+
+
 # ---------------------------------------------------------------- layernorm
 def layernorm_fwd(x, gamma, beta, eps, save_stats=True, out=None, stream=None):
     lib = load_library()

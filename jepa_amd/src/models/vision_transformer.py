@@ -1,4 +1,4 @@
-"""Video Vision Transformer with the reference's constructor, factories, attributes and state-dict names
+"""Vision Transformer (video, and image with num_frames=1) with the reference's constructor, factories, attributes and state-dict names
 (src/models/vision_transformer.py:21-307), computing on MI355X through the jepa_amd HIP kernels.
 
     vit = vit_large(img_size=224, patch_size=16, num_frames=16, tubelet_size=2, uniform_power=True)
@@ -8,6 +8,13 @@
 `forward` is differentiable (one autograd node per call whose backward is the hand-written layer chain), but
 the pretraining step (jepa_amd.engine.step.Trainer) bypasses autograd entirely and shares this module's
 parameters through flat arenas.
+
+    img = vit_large(img_size=224, patch_size=16)       # num_frames=1: the 2-D image ViT (Conv2d patch embed, 2-D sincos table)
+    out = img(images)                                  # [B, N, D] from fp32 [B,3,H,W]; frozen / no-grad path only
+
+The image model is the frozen evals' encoder for image-pretrained checkpoints: its position table is interpolated
+bicubically at other square sizes (vj_pos_interp2d_bicubic) and FrameAggregation drives it frame by frame through
+`forward_frames`.
 """
 import math
 from functools import partial
@@ -19,12 +26,12 @@ from ...engine import hipmodule
 from ...engine.layers import encoder_backward, encoder_forward
 from ..utils.tensors import trunc_normal_
 from .utils.modules import Block
-from .utils.patch_embed import PatchEmbed3D
-from .utils.pos_embs import get_3d_sincos_pos_embed
+from .utils.patch_embed import PatchEmbed, PatchEmbed3D
+from .utils.pos_embs import get_2d_sincos_pos_embed, get_3d_sincos_pos_embed
 
 
 class VisionTransformer(nn.Module, hipmodule.HipModule):
-    """ Vision Transformer (video) """
+    """ Vision Transformer """
 
     def __init__(self, img_size=224, patch_size=16, num_frames=1, tubelet_size=2, in_chans=3, embed_dim=768,
                  depth=12, num_heads=12, mlp_ratio=4.0, qkv_bias=True, qk_scale=None, drop_rate=0.0,
@@ -39,16 +46,20 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         self.num_frames = num_frames
         self.tubelet_size = tubelet_size
         self.is_video = num_frames > 1
-        if not self.is_video:
-            raise NotImplementedError("image (num_frames=1) ViTs belong to the frozen-eval path, outside the "
-                                      "V-JEPA pretraining step this package accelerates")
         if in_chans != 3 or not qkv_bias or out_layers is not None:
             raise NotImplementedError("only in_chans=3, qkv_bias=True, out_layers=None (the pretraining setup)")
         grid_size = img_size // patch_size
         grid_depth = num_frames // tubelet_size
-        self.patch_embed = PatchEmbed3D(patch_size=patch_size, tubelet_size=tubelet_size, in_chans=in_chans,
-                                        embed_dim=embed_dim)
-        self.num_patches = grid_depth * grid_size * grid_size
+        if self.is_video:
+            self.patch_embed = PatchEmbed3D(patch_size=patch_size, tubelet_size=tubelet_size, in_chans=in_chans,
+                                            embed_dim=embed_dim)
+            self.num_patches = grid_depth * grid_size * grid_size
+        else:
+            if patch_size % 8:
+                raise ValueError(f"image ViT: patch_size={patch_size} must be a multiple of 8 (the patch rows are packed 8 pixels "
+                                 "at a time, vj_tubelet_pack)")
+            self.patch_embed = PatchEmbed(patch_size=patch_size, in_chans=in_chans, embed_dim=embed_dim)
+            self.num_patches = grid_size * grid_size
         self.uniform_power = uniform_power
         self.pos_embed = nn.Parameter(torch.zeros(1, self.num_patches, embed_dim), requires_grad=False)
         self.blocks = nn.ModuleList([
@@ -57,8 +68,11 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
                   attn_drop=attn_drop_rate, norm_layer=norm_layer) for _ in range(depth)])
         self.norm = norm_layer(embed_dim)
         # ---- weights: sincos table, trunc-normal(0.02) matrices, zero biases, unit norms, depth rescale
-        sincos = get_3d_sincos_pos_embed(embed_dim, grid_size, grid_depth, cls_token=False,
-                                         uniform_power=uniform_power)
+        if self.is_video:
+            sincos = get_3d_sincos_pos_embed(embed_dim, grid_size, grid_depth, cls_token=False,
+                                             uniform_power=uniform_power)
+        else:
+            sincos = get_2d_sincos_pos_embed(embed_dim, grid_size, cls_token=False)
         self.pos_embed.data.copy_(torch.from_numpy(sincos).float().unsqueeze(0))
         self.init_std = init_std
         self.apply(self._init_weights)
@@ -90,6 +104,11 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
 
     def _input_size(self, x):
         """(T, H, W) of the clip an input stands for: a 4-D [B,C,H,W] still image is its repetition over num_frames frames."""
+        if not self.is_video:
+            if x.dim() != 4:
+                raise ValueError(f"the image model (num_frames=1) takes images [B,C,H,W], got {tuple(x.shape)}; frames of a clip "
+                                 "go through FrameAggregation")
+            return 1, x.shape[2], x.shape[3]
         if x.dim() == 4:
             return self.num_frames, x.shape[2], x.shape[3]
         if x.dim() != 5:
@@ -99,8 +118,11 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
     def interpolate_pos_encoding(self, x, pos_embed):
         """The position table of x's token grid (reference: vision_transformer.py:197-228): the parameter itself at the native
         size, otherwise its trilinear interpolation [1, T'*H'*W', D] in fp32 (vj_pos_interp3d), computed once per (T, H, W) and
-        kept until pos_embed is reloaded or moved."""
+        kept until pos_embed is reloaded or moved.  Image model (vision_transformer.py:230-246): bicubic interpolation by
+        scale_factor = sqrt(npatch / N) to the square grid of x (vj_pos_interp2d_bicubic)."""
         T, H, W = self._input_size(x)
+        if not self.is_video:
+            return self._interpolate_image(H, W, pos_embed)
         if H == self.input_size and W == self.input_size and T == self.num_frames:
             return pos_embed
         if T % self.tubelet_size or H % self.patch_size or W % self.patch_size or min(T, H, W) <= 0:
@@ -108,11 +130,7 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
                              f"{self.patch_size}")
         hipmodule.require_gpu(pos_embed, "VisionTransformer.interpolate_pos_encoding")
         grid = (T // self.tubelet_size, H // self.patch_size, W // self.patch_size)
-        stamp = (pos_embed.data_ptr(), pos_embed._version, pos_embed.device)
-        cache = self.__dict__.setdefault("_pos_interp_cache", {})
-        if cache.get("stamp") != stamp:     # load_state_dict bumps the version, .to() moves the storage
-            cache.clear()
-            cache["stamp"] = stamp
+        cache = self._interp_cache(pos_embed)
         table = cache.get(grid)
         if table is None:
             from ...hip import ops
@@ -126,6 +144,38 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
             if tuple(out.shape[:3]) != grid:
                 raise ValueError(f"interpolated position table has grid {tuple(out.shape[:3])}, the input has {grid}")
             table = cache[grid] = out.view(1, -1, dim)
+        return table
+
+    def _interp_cache(self, pos_embed):
+        stamp = (pos_embed.data_ptr(), pos_embed._version, pos_embed.device)
+        cache = self.__dict__.setdefault("_pos_interp_cache", {})
+        if cache.get("stamp") != stamp:     # load_state_dict bumps the version, .to() moves the storage
+            cache.clear()
+            cache["stamp"] = stamp
+        return cache
+
+    def _interpolate_image(self, H, W, pos_embed):
+        if H == self.input_size and W == self.input_size:
+            return pos_embed
+        p = self.patch_size
+        if H % p or W % p or min(H, W) <= 0:
+            raise ValueError(f"input of {H}x{W} is not divisible into patches of {p}x{p}")
+        N, dim = pos_embed.shape[1], pos_embed.shape[-1]
+        side_in = int(math.sqrt(N))
+        npatch = (H // p) * (W // p)
+        scale_factor = math.sqrt(npatch / N)                       # as the reference computes it
+        side = int(math.floor(float(side_in) * scale_factor))      # F.interpolate's output extent for a given scale factor
+        if side * side != npatch or H // p != W // p:
+            # the reference adds its side x side table to the H/p x W/p tokens and fails there (or, when the counts happen to agree,
+            # adds rows of another grid)
+            raise ValueError(f"the interpolated position table is a square {side}x{side} grid, the input has {H // p}x{W // p} patches")
+        hipmodule.require_gpu(pos_embed, "VisionTransformer.interpolate_pos_encoding")
+        cache = self._interp_cache(pos_embed)
+        table = cache.get((H, W))
+        if table is None:
+            from ...hip import ops
+            src = pos_embed.detach().to(torch.float32).contiguous().view(side_in, side_in, dim)
+            table = cache[(H, W)] = ops.pos_interp2d_bicubic(src, scale_factor).view(1, -1, dim)
         return table
 
     # ---- compute ------------------------------------------------------------------------------------------
@@ -151,6 +201,8 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         """None at the native clip size (the arena's table is used), otherwise the fp32 [N', D] table of x's token grid.  Still
         images and off-native sizes are frozen-path features: with gradients enabled they raise."""
         T, H, W = self._input_size(x)
+        if not self.is_video:
+            return self._image_pos_table(H, W)
         native = H == self.input_size and W == self.input_size and T == self.num_frames
         if (x.dim() == 4 or not native) and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise NotImplementedError("still-image [B,C,H,W] and off-native-size inputs run on the frozen / no-grad path only "
@@ -159,10 +211,36 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         pos = self.interpolate_pos_encoding(x, self.pos_embed)
         return None if pos is self.pos_embed else pos.view(-1, self.embed_dim)
 
+    def _image_pos_table(self, H, W):
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError("the image (num_frames=1) encoder runs on the frozen / no-grad path only (torch.no_grad() "
+                                      "or parameters with requires_grad=False)")
+        pos = self._interpolate_image(H, W, self.pos_embed)
+        return None if pos is self.pos_embed else pos.view(-1, self.embed_dim)
+
+    def forward_frames(self, x):
+        """Image model only: fp32 clips [B,3,T,H,W] -> [B, T*N, D], every frame encoded on its own (what FrameAggregation's
+        x.permute(0,2,1,3,4).reshape(B*T,C,H,W) feeds the model, utils.py:62-66, without that copy: vj_tubelet_pack with tubelet 1
+        emits the patch rows of the clip in (b,t,h,w) order, which is frame-major, and the trunk runs on B*T sequences).  A list of
+        clips of one frame size goes through ONE trunk call and comes back as a list of views of its output."""
+        if self.is_video:
+            raise ValueError("forward_frames belongs to the image (num_frames=1) model")
+        parts = list(x) if isinstance(x, (list, tuple)) else [x]
+        for c in parts:
+            if c.dim() != 5 or c.shape[1:2] + c.shape[3:] != parts[0].shape[1:2] + parts[0].shape[3:]:    # the one shape check of the frames route
+                raise ValueError(f"forward_frames expects clips [B,C,T,H,W] of one frame size, got {[tuple(q.shape) for q in parts]}")
+        out, segs = self._run(parts if len(parts) > 1 else parts[0], None, self._image_pos_table(parts[0].shape[3], parts[0].shape[4]))
+        N, views, r = segs[0].S, [], 0
+        for c in parts:
+            rows = c.shape[0] * c.shape[2] * N
+            views.append(out[r:r + rows].view(c.shape[0], c.shape[2] * N, self.embed_dim))
+            r += rows
+        return views if isinstance(x, (list, tuple)) else views[0]
+
     def forward(self, x, masks=None):
         """x: fp32 clips [B,3,T,H,W] on the GPU, or still images [B,3,H,W] standing for the clip of num_frames repetitions
         (the forward pre-hook of evals/image_classification_frozen/eval.py:452-455); masks: None, an index tensor, or a list
-        of [B,K] index tensors addressing the input's token grid."""
+        of [B,K] index tensors addressing the input's token grid.  The image model (num_frames=1) takes fp32 images [B,3,H,W]."""
         if masks is not None and not isinstance(masks, list):
             masks = [masks]
         if masks is not None:
@@ -171,8 +249,13 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         return out.view(x.shape[0], segs[0].S, self.embed_dim)
 
     def _run(self, x, masks, pos=None):
-        hipmodule.require_gpu(x, "VisionTransformer.forward")
-        x = x.contiguous().float()
+        if isinstance(x, list):     # frames of the image model, clip by clip (forward_frames)
+            for c in x:
+                hipmodule.require_gpu(c, "VisionTransformer.forward_frames")
+            x = [c.contiguous().float() for c in x]
+        else:
+            hipmodule.require_gpu(x, "VisionTransformer.forward")
+            x = x.contiguous().float()
         if masks is not None:
             masks = [m.contiguous() for m in masks]
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):

@@ -9,7 +9,14 @@ python tools/eval_bench.py [--configs vitl16_k400_16x8x3 vith16_384_k400_16x8x3]
 for ViT-L/16-224 and ViT-H/16-384: frozen images/s, probe ms, one training and one validation iteration, peak memory; the still-image
 path against the only route there was before it (the ATen repeat to 16 frames, timed, followed by the 5-D forward), the two arms
 taking turns inside this process in both orders (as tools/abab.py does for the step); and vj_pos_interp3d once per new size.
-python tools/eval_bench.py --image [--image-configs vitl16_in1k vith16_384_in1k] [--rounds 4] [--reps 3]"""
+python tools/eval_bench.py --image [--image-configs vitl16_in1k vith16_384_in1k] [--rounds 4] [--reps 3]
+
+--frames: FrameAggregation on the ViT-L/16 image (num_frames=1) model at 224: 2 videos x 8 segments x 3 views x 16 frames = 768 frames
+of 196 tokens.  The direct route (patch rows packed straight from the [B,C,T,H,W] clips) against the reference's route (views
+concatenated along the batch, segments along time, the permuted [B*T,C,H,W] fp32 copy through ATen, then the model) and against the
+direct route with one (segment, view) tensor per trunk call, the arms taking turns inside this process in both orders; frames/s and peak memory of each; the temporal position pass (vj_add_pos_frames);
+and vj_pos_interp2d_bicubic once per new size.
+python tools/eval_bench.py --frames [--rounds 4] [--reps 3]"""
 import argparse
 import json
 import os
@@ -201,14 +208,101 @@ def bench_interp():
     return dict(pos_interp3d=out)
 
 
+def bench_frames(reps, rounds, B=2, S=8, V=3, T=16, res=224, max_frames=1024):
+    import math
+    import statistics
+    from jepa_amd.evals.video_classification_frozen.utils import FrameAggregation
+    from jepa_amd.hip import ops
+    from jepa_amd.src.models.utils.pos_embs import get_2d_sincos_pos_embed
+    dev = "cuda"
+    torch.manual_seed(0)
+    model = vit.vit_large(img_size=res, patch_size=16).to(dev).eval()
+    for p in model.parameters():
+        p.requires_grad = False
+    agg = FrameAggregation(model).to(dev)
+    agg_pos = FrameAggregation(model, max_frames=max_frames, use_pos_embed=True).to(dev)
+    agg_one = FrameAggregation(model).to(dev)
+    agg_one.max_tokens_per_call = B * T * model.num_patches      # one (segment, view) tensor per trunk call: what the batching buys
+    clips = [[torch.randn(B, 3, T, res, res, device=dev) for _ in range(V)] for _ in range(S)]
+    idx = [torch.arange(s * T * 4, (s + 1) * T * 4, 4, device=dev).repeat(B, 1) for s in range(S)]
+    N = model.num_patches
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+
+    def direct():
+        with torch.no_grad():
+            return agg(clips, idx)
+
+    def permuted():     # the reference's FrameAggregation.forward (utils.py:53-72) on this model
+        with torch.no_grad():
+            x = torch.cat([torch.cat(xi, dim=0) for xi in clips], dim=2)
+            b, c, t, h, w = x.size()
+            out = model(x.permute(0, 2, 1, 3, 4).reshape(b * t, c, h, w)).reshape(b, t, N, -1).flatten(1, 2)
+            return [out[i * B:(i + 1) * B] for i in range(V)]
+
+    def per_clip():
+        with torch.no_grad():
+            return agg_one(clips, idx)
+
+    arms = {"direct": direct, "permuted": permuted, "per_clip": per_clip}
+    peak, outs = {}, {}
+    for arm, fn in arms.items():    # warm-up (workspace growth, code load) and the peak memory of each route on its own
+        torch.cuda.reset_peak_memory_stats()
+        outs[arm] = fn()
+        torch.cuda.synchronize()
+        peak[arm] = round((torch.cuda.max_memory_allocated() - base) / 2 ** 30, 3)
+    equal = all(torch.equal(a, b) and torch.equal(a, c) for a, b, c in zip(outs["direct"], outs["permuted"], outs["per_clip"]))
+    del outs
+    ms = {arm: [] for arm in arms}
+    for r in range(rounds):
+        for arm in (("direct", "permuted", "per_clip") if r % 2 == 0 else ("per_clip", "permuted", "direct")):
+            ms[arm].append(timed(arms[arm], reps))
+    mean = {arm: statistics.mean(v) for arm, v in ms.items()}
+    spread = {arm: max(v) - min(v) for arm, v in ms.items()}
+
+    def with_pos():
+        with torch.no_grad():
+            return agg_pos(clips, idx)
+
+    t_pos = timed(with_pos, reps)
+    frames = B * S * V * T
+    # the bicubic table of a new size: one launch (cached afterwards), timed by events after an unrelated warm-up launch
+    ops.pos_interp2d_bicubic(torch.zeros(2, 2, 64, device=dev), 2.0)
+    table = torch.from_numpy(get_2d_sincos_pos_embed(1024, 14, cls_token=False)).float().to(dev).view(14, 14, 1024)
+    scale = math.sqrt(24 * 24 / (14 * 14))
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    ops.pos_interp2d_bicubic(table, scale)
+    e.record()
+    torch.cuda.synchronize()
+    return dict(config="vitl16_image_frames", frames=frames, tokens_per_frame=N, rounds=rounds, reps=reps, outputs_equal=equal,
+                direct_ms_rounds=[round(v, 3) for v in ms["direct"]], permuted_ms_rounds=[round(v, 3) for v in ms["permuted"]],
+                per_clip_ms_rounds=[round(v, 3) for v in ms["per_clip"]], per_clip_ms_mean=round(mean["per_clip"], 3),
+                per_clip_ms_spread=round(spread["per_clip"], 3), peak_mem_gib_per_clip=peak["per_clip"],
+                direct_ms_mean=round(mean["direct"], 3), permuted_ms_mean=round(mean["permuted"], 3),
+                direct_ms_spread=round(spread["direct"], 3), permuted_ms_spread=round(spread["permuted"], 3),
+                direct_minus_permuted_ms=round(mean["direct"] - mean["permuted"], 3),
+                direct_not_slower_than_permuted_plus_its_spread=bool(mean["direct"] <= mean["permuted"] + spread["permuted"]),
+                frames_per_s_direct=round(frames / mean["direct"] * 1e3, 1), frames_per_s_permuted=round(frames / mean["permuted"] * 1e3, 1),
+                peak_mem_gib_direct=peak["direct"], peak_mem_gib_permuted=peak["permuted"],
+                with_temporal_pos_ms=round(t_pos, 3), temporal_pos_extra_ms=round(t_pos - mean["direct"], 3),
+                bicubic_14x14x1024_to_24x24=dict(first_call_us=round(s.elapsed_time(e) * 1e3, 1),
+                                                 repeat_call_us=round(timed(lambda: ops.pos_interp2d_bicubic(table, scale), 20) * 1e3, 1)))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", action="store_true", help="FrameAggregation on the ViT-L/16 image model instead of the video eval")
     ap.add_argument("--image", action="store_true", help="the image-classification eval instead of the video one")
     ap.add_argument("--image-configs", nargs="*", default=["vitl16_in1k", "vith16_384_in1k"], choices=sorted(IMAGE_CONFIGS))
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--configs", nargs="*", default=["vitl16_k400_16x8x3", "vith16_384_k400_16x8x3"], choices=sorted(CONFIGS))
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
+    if a.frames:
+        print(json.dumps(bench_frames(a.reps, a.rounds)), flush=True)
+        return
     if a.image:
         for name in a.image_configs:
             print(json.dumps(bench_image(name, a.reps, a.rounds)), flush=True)
