@@ -366,7 +366,13 @@ typedef void (*vj_layer_cb_t)(void* user, int layer);
 int64_t vj_blocks_fwd_ws_bytes(int64_t M, int64_t D, int64_t Dh, int64_t heads, int64_t n_blocks, int save);
 /* x_out [M,D] bf16 = blocks[n-1](...blocks[0](x_in)) ; x_in must stay valid until the backward has run.
  * gemm_flags: kernel selection for the four Linear GEMMs of every block, as in vj_gemm_bf16_nt (0 = automatic;
- * 0x100 = the two-workgroups-per-CU kernel, the better choice when this stream has the GPU to itself: inference). */
+ * 0x100 = the two-workgroups-per-CU kernel, the better choice when this stream has the GPU to itself: inference).
+ * The fields of gemm_flags: the selection, and the first block it applies to (earlier blocks take the automatic choice). */
+enum {
+  VJ_GEMM_FLAGS_SEL_MASK = 0xffff, /* low 16 bits: kernel selection of vj_gemm_bf16_nt (0: option "gemm_fwd_flags") */
+  VJ_GEMM_FLAGS_FROM_SHIFT = 16,   /* bits 16-23: first block the selection applies to */
+  VJ_GEMM_FLAGS_FROM_MASK = 0xff
+};
 int vj_blocks_fwd(const vj_block_t* blocks, int64_t n_blocks, const void* x_in, void* x_out, int64_t M, int64_t D,
                   int64_t heads, const vj_seg_t* segs, int64_t n_segs, float ln_eps, int save, int gemm_flags, void* ws,
                   int64_t ws_bytes, vj_stream_t stream);
@@ -413,6 +419,12 @@ int64_t vj_blocks_bwd_ws_bytes(int64_t M, int64_t D, int64_t Dh, int64_t heads);
  * With the transpose-free route and option "bias_fuse" (default) the bias gradients of qkv and fc1 come from column partials of
  * the kernels that produce dqkv / du (vj_attn_bwd_colsum, vj_gemm_bf16_nt_dgelu_colsum) and every partial reduction of a block
  * (both LayerNorms', those two) is ONE vj_reduce_segments launch at the end of the block. */
+enum {
+  VJ_BWD_FORCE_TN = 1,           /* flags bit0 */
+  VJ_BWD_LAST_FC2_BIAS_DONE = 2, /* flags bit1 */
+  VJ_BWD_Q_PRESCALED = 4,        /* flags bit2: read only with bit3 */
+  VJ_BWD_Q_PRESCALED_VALID = 8   /* flags bit3 */
+};
 int vj_blocks_bwd(const vj_block_t* blocks, int64_t n_blocks, const void* x_in, const void* dout, void* dx_out, int64_t M,
                   int64_t D, int64_t heads, const vj_seg_t* segs, int64_t n_segs, float alpha, float beta_acc,
                   const void* save_ws, int64_t save_ws_bytes, void* tmp_ws, int64_t tmp_ws_bytes, int flags,

@@ -13,6 +13,7 @@
 // CONSECUTIVE output columns: 8-byte bf16 / 16-byte fp32 epilogue accesses for C, bias, residual and aux.
 // Workgroup ids are remapped so every XCD (private L2) works on a contiguous band of tiles.
 #include "gemm_common.hpp"
+#include "internal.hpp"
 #include "options.hpp"
 #include <cstdlib>
 
@@ -231,9 +232,7 @@ static int launch_gemm(const GemmArgs& a, void* ws, int64_t ws_bytes, hipStream_
 //        ring with counted vmcnt, 3 = 256x256 staggered 8-phase schedule, gemm8.hip / gemm8p.hip); bit 8 = the 4-wave 256x128 kernel with two
 //        workgroups per CU (gemm4w.hip: single-stream inference).  (Register-staged operands, a 256x128 BK32 ring and a persistent form of
 //        the 4-wave kernel existed through round 5; all measured slower in the step: profiles/r03_abab_switches.md, r05_gemm_4wp.md.)
-int vj_gemm_launch_8phase(const GemmArgs& a, int epilogue, void* ws, int64_t ws_bytes, hipStream_t stream);  // gemm8.hip
-int vj_gemm_launch_4w(const GemmArgs& a, int epilogue, void* ws, int64_t ws_bytes, hipStream_t stream);      // gemm4w.hip
-int vj_gemm_launch_8phase_persist(const GemmArgs& a, int epilogue, hipStream_t stream);                        // gemm8p.hip (VJ_PERSIST_NA: n/a)
+//        The launchers behind the selection (gemm8.hip, gemm4w.hip, gemm8p.hip) are declared in internal.hpp.
 
 extern "C" int64_t vj_gemm_colsum_rows(int64_t M) { return 2 * cdiv64(M, 256); }   // rows of colpart: (row tile, wave row) slots
 

@@ -20,6 +20,7 @@
 // Hazards: a part is read only after a barrier that follows every thread's counted wait for it; a slot is re-filled at
 // least two barriers after the section that read it last (see the slot arithmetic next to issue_part4).
 #include "gemm_common.hpp"
+#include "internal.hpp"
 #include <type_traits>
 #include <cstdlib>
 

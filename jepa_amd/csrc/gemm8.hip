@@ -14,6 +14,7 @@
 // Hazards: part q is read only after a barrier that follows every thread's vmcnt for it (end of L(q-1)); its slot is
 // re-filled by part q+8 issued in L(q+4), >= 7 barrier intervals after the last read.
 #include "gemm_common.hpp"
+#include "internal.hpp"
 
 #define P8_BM 256
 #define P8_BN 256

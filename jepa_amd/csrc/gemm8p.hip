@@ -44,6 +44,7 @@
 #include <type_traits>
 #include <atomic>
 #include "gemm_common.hpp"
+#include "internal.hpp"
 #include "options.hpp"
 
 #define PP_RING (8 * LDS_PART_BYTES)

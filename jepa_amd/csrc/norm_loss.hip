@@ -8,11 +8,7 @@
 //   reg_fn : sqrt(var_tokens(z)+1e-4)                    app/vjepa/train.py:448-449,458
 #include "common.hpp"
 #include "options.hpp"
-
-int vj_reduce_partials_multi(const float* part, float* const* outs, int nseg, int64_t P, int64_t D, float alpha, float beta,
-                             hipStream_t stream);   // rows.hip
-int vj_reduce_partials_strided(const float* part, float* out, int64_t P, int64_t N, int64_t stride, float alpha,
-                               float beta, hipStream_t stream);
+#include "internal.hpp"
 
 #define LN_MAX_CHUNKS 4  // D <= 2048, D % 8 == 0: each lane owns up to 4 chunks of 8 columns
 

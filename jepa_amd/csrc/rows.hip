@@ -8,6 +8,7 @@
 //   x += pos_embed                   src/models/vision_transformer.py:172-174
 //   predictor token assembly         src/models/predictor.py:194-221
 #include "common.hpp"
+#include "internal.hpp"
 #include "../../include/vjepa_hip.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -715,9 +716,6 @@ extern "C" int vj_transpose_bf16(const void* in, void* out, int64_t M, int64_t N
   VJ_LAUNCH_CHECK("vj_transpose_bf16");
   return 0;
 }
-
-extern "C" int vj_reduce_partials(const float* part, float* out, int64_t P, int64_t N, float alpha, float beta,
-                                  hipStream_t stream);
 
 // transpose + bias gradient in one pass over dY: out = in^T (zero padded), colsum[n] = alpha*sum_m in[m][n] + beta*colsum[n]
 extern "C" int64_t vj_transpose_colsum_ws_bytes(int64_t M, int64_t N) { return cdiv64(((M + 63) / 64) * 64, 64) * N * 4; }

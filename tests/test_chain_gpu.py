@@ -144,9 +144,16 @@ GUARD_CASES = [
 
 
 # ------------------------------------------------------------------------------------------------ launch chains
-def test_c_chain_is_bit_identical_to_python_chain():
+@pytest.mark.parametrize("wgrad_tn,wgrad_group", [(1, 1), (1, 0), (0, 1), (0, 0)])
+def test_c_chain_is_bit_identical_to_python_chain(wgrad_tn, wgrad_group):
     """vj_blocks_fwd / vj_blocks_bwd enqueue the same kernels in the same order as the per-kernel Python chain:
-    losses, every gradient and every updated weight must be BIT-identical (split-K is deterministic)."""
+    losses, every gradient and every updated weight must be BIT-identical (split-K is deterministic) -- on every
+    weight-gradient route: transpose-free or transposes + NT split-K (wgrad_tn), grouped or one launch each (wgrad_group)."""
+    with _opt("wgrad_tn", wgrad_tn), _opt("wgrad_group", wgrad_group):
+        _c_chain_against_python_chain()
+
+
+def _c_chain_against_python_chain():
     from jepa_amd.engine import layers
     from jepa_amd.hip.lib import set_option
     res = {}
