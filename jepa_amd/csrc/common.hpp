@@ -174,3 +174,43 @@ void vj_set_error(const char* fmt, ...);
   } while (0)
 
 __host__ __device__ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// ---- launch shapes of the HBM-bound kernels ----
+// one wave per row, four waves per 256-thread workgroup, at most 256 * 16 workgroups
+static inline int rows_grid(int64_t rows) {
+  int64_t g = cdiv64(rows, 4);
+  if (g > 256 * 16) g = 256 * 16;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+// one thread per item in 256-thread workgroups, at most cap_blocks of them (the kernels stride by the grid)
+static inline int flat_grid(int64_t total, int64_t cap_blocks) {
+  int64_t g = cdiv64(total, 256);
+  if (g > cap_blocks) g = cap_blocks;
+  return (int)g;
+}
+// the kernel's side of rows_grid: this lane's index in its wave, the first row of its wave, and the step to the wave's next row
+__device__ __forceinline__ int wave_lane() { return threadIdx.x & 63; }
+__device__ __forceinline__ int64_t wave_row() { return (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); }
+__device__ __forceinline__ int64_t wave_row_step() { return (int64_t)gridDim.x * 4; }
+
+// ---- 16-byte bf16 chunks ----
+// 8 fp32 -> 8 bf16 (RNE): the pixel packing of tubelet_pack / image_pack
+__device__ __forceinline__ u32x4_t pack8_bf16(float4 lo, float4 hi) {
+  u32x4_t o;
+  o[0] = pack_bf2(lo.x, lo.y);
+  o[1] = pack_bf2(lo.z, lo.w);
+  o[2] = pack_bf2(hi.x, hi.y);
+  o[3] = pack_bf2(hi.z, hi.w);
+  return o;
+}
+// 8 bf16 + 8 fp32 position values -> 8 bf16: fp32 add, one rounding.  THE position add of add_pos / add_pos_bcast / add_pos_frames
+__device__ __forceinline__ u32x4_t add_pos8(u32x4_t v, const float* pos) {
+  const float4 p0 = *(const float4*)pos;
+  const float4 p1 = *(const float4*)(pos + 4);
+  v[0] = pack_bf2(bf_lo(v[0]) + p0.x, bf_hi(v[0]) + p0.y);
+  v[1] = pack_bf2(bf_lo(v[1]) + p0.z, bf_hi(v[1]) + p0.w);
+  v[2] = pack_bf2(bf_lo(v[2]) + p1.x, bf_hi(v[2]) + p1.y);
+  v[3] = pack_bf2(bf_lo(v[3]) + p1.z, bf_hi(v[3]) + p1.w);
+  return v;
+}

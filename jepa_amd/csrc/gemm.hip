@@ -187,10 +187,8 @@ void vj_splitk_finish_plan(int nk, int& splitk, int& ktiles_per) {
 }
 int vj_splitk_reduce(const GemmArgs& b, hipStream_t stream) {
   if (b.splitk <= 1) return 0;
-  int64_t g = cdiv64(b.M * b.N / 4, 256);
-  if (g > 256 * 8) g = 256 * 8;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, stream, (const float4*)b.ws, (float*)b.C, b.M, b.N,
-                     b.ldc, b.splitk, b.alpha, b.beta);
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(flat_grid(b.M * b.N / 4, 256 * 8)), dim3(256), 0, stream, (const float4*)b.ws,
+                     (float*)b.C, b.M, b.N, b.ldc, b.splitk, b.alpha, b.beta);
   VJ_LAUNCH_CHECK("vj_gemm_bf16(split-K reduce)");
   return 0;
 }

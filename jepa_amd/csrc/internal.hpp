@@ -10,7 +10,7 @@ int vj_layernorm_bwd_partials(const void* dy_bf16, const void* x_bf16, const flo
                               const void* dres_bf16, void* dx_bf16, bool cs, int64_t rows, int64_t D, void* ws,
                               int64_t ws_bytes, int64_t* nb_out, hipStream_t stream);
 
-// ---- rows.hip
+// ---- reduce.hip
 // out[n] = alpha * sum_p part[p * stride + n] + beta * out[n]
 int vj_reduce_partials_strided(const float* part, float* out, int64_t P, int64_t N, int64_t stride, float alpha,
                                float beta, hipStream_t stream);

@@ -1,6 +1,7 @@
-"""Row kernels (csrc/rows.hip): mask gather / scatter (reference src/masks/utils.py:11-23) bit-exact, tubelet packing = Conv3d unfold
-(src/models/utils/patch_embed.py:56), position add, transposes / column sums, predictor token assembly (src/models/predictor.py:194-221),
-segment reductions, and the ds_read_b64_tr_b16 lane mapping the attention / TN-GEMM kernels rely on."""
+"""Row-granular kernels: mask gather / scatter (reference src/masks/utils.py:11-23) bit-exact, row-window copy / zero fill, position add,
+predictor token assembly (src/models/predictor.py:194-221) (csrc/rows.hip); tubelet packing = Conv3d unfold
+(src/models/utils/patch_embed.py:56) (csrc/input_pack.hip); transposes (single, multi-matrix, with fused column sum), column sums and
+segment reductions (csrc/reduce.hip); and the ds_read_b64_tr_b16 lane mapping the attention / TN-GEMM kernels rely on."""
 import math
 import pytest
 import torch
@@ -186,3 +187,84 @@ def test_reduce_segments_matches_single_reductions(ops):
             ref = alpha * part.double().sum(0) + (o0.double() if acc else 0.0)
             assert rel_l2(out.double().cpu(), ref.cpu()) < 1e-6
 
+
+# ------------------------------------------------------------------------------------------ copy / multi transpose / fused column sum
+def _nonzero_bf16(*shape):
+    """A bf16 pattern without a single zero (values 1 .. 251, all exact in bf16)."""
+    n = math.prod(shape)
+    return (torch.arange(n, dtype=torch.float32) % 251 + 1).reshape(shape).to(torch.bfloat16).to(DEV)
+
+
+@pytest.mark.parametrize("D", [24, 1032])     # 3 and 129 16-byte chunks per row: one trip of the 64-lane chunk loop, and three (the last ragged)
+def test_copy_rows_window_and_zero_fill(ops, D):
+    B, src_rows, src_off, dst_rows, dst_off, n = 3, 7, 2, 9, 4, 3
+    g = torch.Generator().manual_seed(61)
+    src = bf(torch.randn(B, src_rows, D, generator=g)).to(DEV)
+    fill = _nonzero_bf16(B, dst_rows, D)
+    inside = torch.zeros(dst_rows, dtype=torch.bool, device=DEV)
+    inside[dst_off:dst_off + n] = True
+    dst = fill.clone()
+    ops.copy_rows(src, dst, B, src_rows, src_off, dst_rows, dst_off, n, D)
+    assert torch.equal(dst[:, inside], src[:, src_off:src_off + n])
+    assert torch.equal(dst[:, ~inside], fill[:, ~inside])
+    dst = fill.clone()
+    ops.copy_rows(None, dst, B, src_rows, src_off, dst_rows, dst_off, n, D)      # src == NULL: the window is zeroed
+    assert torch.count_nonzero(dst[:, inside]) == 0
+    assert torch.equal(dst[:, ~inside], fill[:, ~inside])
+
+
+def test_transpose_multi_matches_single_transposes(ops):
+    """One launch over four matrices, tables built as ParamArena._build_transpose_plan builds them: every output is ops.transpose's."""
+    g = torch.Generator().manual_seed(62)
+    mats = [bf(torch.randn(100, 64, generator=g)).to(DEV), bf(torch.randn(64, 200, generator=g)).to(DEV),
+            bf(torch.randn(130, 80, generator=g)).to(DEV)[:, :72], bf(torch.randn(1, 8, generator=g)).to(DEV)]
+    assert [(x.shape[0], x.shape[1], x.stride(0)) for x in mats] == [(100, 64, 64), (64, 200, 200), (130, 72, 80), (1, 8, 8)]
+    outs = [_nonzero_bf16(x.shape[1], ops.pad64(x.shape[0])) for x in mats]
+    desc, blocks = [], []
+    for ti, (x, t) in enumerate(zip(mats, outs)):
+        M, N = x.shape
+        Mp = t.shape[1]
+        desc += [x.data_ptr(), t.data_ptr(), M, N, x.stride(0), Mp]
+        for tm in range((Mp + 63) // 64):
+            for tn in range((N + 63) // 64):
+                blocks += [ti, tm, tn, 0]
+    ops.transpose_multi(torch.tensor(desc, dtype=torch.int64, device=DEV), torch.tensor(blocks, dtype=torch.int32, device=DEV),
+                        len(blocks) // 4)
+    for x, t in zip(mats, outs):
+        M = x.shape[0]
+        assert torch.equal(t, ops.transpose(x.contiguous()))      # (ops.transpose takes contiguous matrices only)
+        assert torch.equal(t[:, :M], x.t())
+        assert torch.count_nonzero(t[:, M:]) == 0
+
+
+def _colsum_in_kernel_order(x):
+    """float32 emulation of transpose_bf16_kernel's fused partial + reduce_partials_kernel: per 64-row tile a sequential sum in row
+    order; 8 lanes, lane p summing tiles p, p + 8, ... in order from zero; the lanes added in order 0..7.  Plain IEEE adds."""
+    x = x.float().cpu()
+    M, N = x.shape
+    part = []
+    for m0 in range(0, M, 64):
+        s = torch.zeros(N)
+        for r in range(m0, min(m0 + 64, M)):
+            s = s + x[r]
+        part.append(s)
+    lanes = []
+    for p in range(8):
+        s = torch.zeros(N)
+        for q in range(p, len(part), 8):
+            s = s + part[q]
+        lanes.append(s)
+    t = lanes[0]
+    for p in range(1, 8):
+        t = t + lanes[p]
+    return t
+
+
+@pytest.mark.parametrize("M,N", [(473, 1024), (1100, 72)])     # 8 and 18 row tiles (lanes take one, or two / three partials); N % 64 != 0
+def test_transpose_colsum_is_transpose_plus_ordered_sum(ops, M, N):
+    g = torch.Generator().manual_seed(63)
+    x = bf(torch.randn(M, N, generator=g)).to(DEV)
+    cs = torch.full((N,), 7.0, device=DEV)
+    t = ops.transpose_colsum(x, cs, alpha=1.0, accumulate=False)
+    assert torch.equal(t, ops.transpose(x))
+    assert torch.equal(cs.cpu(), _colsum_in_kernel_order(x))
