@@ -5,7 +5,7 @@
 // ~1800 kernel launches of a step one ctypes call at a time (~39 us each: 70 ms of host time against an 85 ms GPU step);
 // here the per-block sequence lives behind the C ABI, so the host cost of a block is 7 (forward) / ~25 (backward)
 // hipLaunchKernel calls and nothing else.  No arithmetic happens in this file: it only sequences the kernels of
-// gemm*.hip / attention.hip / norm_loss.hip / rows.hip / reduce.hip, lays the saved activations out in a caller-provided workspace
+// gemm*.hip / attention.hip / layernorm.hip / rows.hip / reduce.hip, lays the saved activations out in a caller-provided workspace
 // and orders the two HIP streams (dgrad chain on `stream`, weight gradients on `side`) with events.
 //
 // Saved-activation layout per block (workspace `save_ws`, everything 256-byte aligned, bf16 unless noted):

@@ -53,6 +53,20 @@ __device__ __forceinline__ float row16_sum(float v) {
   v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xf, 0xf, false));   // row_ror:1
   return v;
 }
+// sum over the four waves of a 256-thread workgroup, N values at once for one barrier: block4_stage leaves every wave's totals in
+// red[k][wave] and synchronises; block4_total(red[k]) then adds them in the fixed order wave 0 + 1 + 2 + 3, in whichever threads want it
+template <int N>
+__device__ __forceinline__ void block4_stage(float (*red)[4], const float (&v)[N]) {
+  float w[N];
+#pragma unroll
+  for (int k = 0; k < N; k++) w[k] = wave_sum(v[k]);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < N; k++) red[k][threadIdx.x >> 6] = w[k];
+  }
+  __syncthreads();
+}
+__device__ __forceinline__ float block4_total(const float* red) { return red[0] + red[1] + red[2] + red[3]; }
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -176,10 +190,10 @@ void vj_set_error(const char* fmt, ...);
 __host__ __device__ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---- launch shapes of the HBM-bound kernels ----
-// one wave per row, four waves per 256-thread workgroup, at most 256 * 16 workgroups
-static inline int rows_grid(int64_t rows) {
+// one wave per row, four waves per 256-thread workgroup, at most cap_blocks workgroups (256 * 8 for the LayerNorm family)
+static inline int rows_grid(int64_t rows, int64_t cap_blocks = 256 * 16) {
   int64_t g = cdiv64(rows, 4);
-  if (g > 256 * 16) g = 256 * 16;
+  if (g > cap_blocks) g = cap_blocks;
   if (g < 1) g = 1;
   return (int)g;
 }
@@ -195,6 +209,28 @@ __device__ __forceinline__ int64_t wave_row() { return (int64_t)blockIdx.x * 4 +
 __device__ __forceinline__ int64_t wave_row_step() { return (int64_t)gridDim.x * 4; }
 
 // ---- 16-byte bf16 chunks ----
+// 8 bf16 in registers -> 8 fp32; the same from memory; 8 fp32 -> 8 bf16 (RNE) to memory
+__device__ __forceinline__ void unpack8(const u32x4_t& w, float* v) {
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    v[2 * i] = bf_lo(w[i]);
+    v[2 * i + 1] = bf_hi(w[i]);
+  }
+}
+__device__ __forceinline__ void load8(const bf16_t* p, float* v) { unpack8(*(const u32x4_t*)p, v); }
+__device__ __forceinline__ void store8(bf16_t* p, const float* v) {
+  u32x4_t w;
+#pragma unroll
+  for (int i = 0; i < 4; i++) w[i] = pack_bf2(v[2 * i], v[2 * i + 1]);
+  *(u32x4_t*)p = w;
+}
+// 4 fp32 -> 4 bf16 (RNE): the shadow weights of optim.hip
+__device__ __forceinline__ u32x2_t pack4_bf16(float a, float b, float c, float d) {
+  u32x2_t w;
+  w[0] = pack_bf2(a, b);
+  w[1] = pack_bf2(c, d);
+  return w;
+}
 // 8 fp32 -> 8 bf16 (RNE): the pixel packing of tubelet_pack / image_pack
 __device__ __forceinline__ u32x4_t pack8_bf16(float4 lo, float4 hi) {
   u32x4_t o;

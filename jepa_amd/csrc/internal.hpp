@@ -3,7 +3,7 @@
 #pragma once
 #include "common.hpp"
 
-// ---- norm_loss.hip
+// ---- layernorm.hip
 // The LayerNorm backward kernel alone: dx is complete, the column partials part[*nb_out][nseg * D] (nseg = 3 with `cs`:
 // dgamma | dbeta | column sums of dx; else 2) stay in `ws` for the caller to reduce.
 int vj_layernorm_bwd_partials(const void* dy_bf16, const void* x_bf16, const float* gamma, const float* mean, const float* rstd,

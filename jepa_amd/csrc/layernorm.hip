@@ -1,30 +1,54 @@
-// LayerNorm forward/backward (row per wave, fp32 statistics), the fused target path
-// h = F.layer_norm(norm(x))[masks_pred] and the latent L_p loss of the V-JEPA step.
+// LayerNorm forward/backward (row per wave, fp32 statistics), what is left of it when it is folded into the consuming Linear, and
+// the fused target path h = F.layer_norm(norm(x))[masks_pred] of the V-JEPA step.
 //
 // Reference behaviour restated (never copied):
 //   nn.LayerNorm(eps=1e-6) in every Block / final norm   src/models/vision_transformer.py:252-281, modules.py:97,106
 //   h = F.layer_norm(target_encoder(c)) ; apply_masks    app/vjepa/train.py:424-428
-//   loss_fn: mean(|z-h|^p)/p averaged over masks         app/vjepa/train.py:440-446
-//   reg_fn : sqrt(var_tokens(z)+1e-4)                    app/vjepa/train.py:448-449,458
 #include "common.hpp"
 #include "options.hpp"
 #include "internal.hpp"
 
 #define LN_MAX_CHUNKS 4  // D <= 2048, D % 8 == 0: each lane owns up to 4 chunks of 8 columns
 
-__device__ __forceinline__ void load8(const bf16_t* p, float* v) {
-  const u32x4_t w = *(const u32x4_t*)p;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    v[2 * i] = bf_lo(w[i]);
-    v[2 * i + 1] = bf_hi(w[i]);
-  }
+// the D every kernel here takes; -1 with the error set otherwise (`rule`: the entry points whose message has always stated the rule)
+static int ln_check_D(const char* who, int64_t D, bool rule = false) {
+  VJ_CHECK_ARG(D % 8 == 0 && D <= 512 * LN_MAX_CHUNKS, rule ? "%s: D=%ld unsupported (need D%%8==0, D<=%d)" : "%s: D=%ld unsupported", who,
+               (long)D, 512 * LN_MAX_CHUNKS);
+  return 0;
 }
-__device__ __forceinline__ void store8(bf16_t* p, const float* v) {
-  u32x4_t w;
+static inline int ln_grid(int64_t rows) { return rows_grid(rows, 256 * 8); }
+
+// THE two-pass fp32 row statistics of every kernel here that normalises.  Lane l holds columns l*8 + i*512 .. +7 of the row in v[i];
+// chunks at or past D are never touched.  ln_row_mean<true> also loads the row from xp into v, inside the same `c < D` as the sum (a load
+// loop of its own costs the dead chunks a zero-fill); <false> takes v as it is.  ln_row_rstd: from the variance of the centred values, no
+// E[x^2] - mean^2 cancellation.
+template <bool LOAD>
+__device__ __forceinline__ float ln_row_mean(const bf16_t* xp, float (&v)[LN_MAX_CHUNKS][8], int lane, int D, float invD) {
+  float s = 0.f;
 #pragma unroll
-  for (int i = 0; i < 4; i++) w[i] = pack_bf2(v[2 * i], v[2 * i + 1]);
-  *(u32x4_t*)p = w;
+  for (int i = 0; i < LN_MAX_CHUNKS; i++) {
+    const int c = lane * 8 + i * 512;
+    if (c < D) {
+      if constexpr (LOAD) load8(xp + c, v[i]);
+#pragma unroll
+      for (int j = 0; j < 8; j++) s += v[i][j];
+    }
+  }
+  return wave_sum(s) * invD;
+}
+__device__ __forceinline__ float ln_row_rstd(const float (&v)[LN_MAX_CHUNKS][8], float mean, int lane, int D, float invD, float eps) {
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < LN_MAX_CHUNKS; i++) {
+    if (lane * 8 + i * 512 < D) {
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        const float d = v[i][j] - mean;
+        q += d * d;
+      }
+    }
+  }
+  return rsqrtf(wave_sum(q) * invD + eps);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -57,30 +81,8 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const bf16_t* __rest
   for (int64_t r = wave; r < rows; r += nw) {
     const bf16_t* xp = x + r * D;
     float v[LN_MAX_CHUNKS][8];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < LN_MAX_CHUNKS; i++) {
-      const int c = lane * 8 + i * 512;
-      if (c < D) {
-        load8(xp + c, v[i]);
-#pragma unroll
-        for (int j = 0; j < 8; j++) s += v[i][j];
-      }
-    }
-    const float mean = wave_sum(s) * invD;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < LN_MAX_CHUNKS; i++) {
-      const int c = lane * 8 + i * 512;
-      if (c < D) {
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-          const float d = v[i][j] - mean;
-          q += d * d;
-        }
-      }
-    }
-    const float rstd = rsqrtf(wave_sum(q) * invD + eps);
+    const float mean = ln_row_mean<true>(xp, v, lane, D, invD);
+    const float rstd = ln_row_rstd(v, mean, lane, D, invD, eps);
     bf16_t* yp = y + r * D;
 #pragma unroll
     for (int i = 0; i < LN_MAX_CHUNKS; i++) {
@@ -102,17 +104,9 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const bf16_t* __rest
   }
 }
 
-static inline int ln_grid(int64_t rows) {
-  int64_t g = cdiv64(rows, 4);
-  if (g > 256 * 8) g = 256 * 8;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 extern "C" int vj_layernorm_fwd(const void* x_bf16, const float* gamma, const float* beta, void* y_bf16, float* mean,
                                 float* rstd, int64_t rows, int64_t D, float eps, hipStream_t stream) {
-  VJ_CHECK_ARG(D % 8 == 0 && D <= 512 * LN_MAX_CHUNKS, "vj_layernorm_fwd: D=%ld unsupported (need D%%8==0, D<=%d)",
-               (long)D, 512 * LN_MAX_CHUNKS);
+  if (ln_check_D("vj_layernorm_fwd", D, true)) return -1;
   VJ_CHECK_ARG((mean == nullptr) == (rstd == nullptr), "vj_layernorm_fwd: mean and rstd must both be given or both null");
   if (rows == 0) return 0;
   hipLaunchKernelGGL(layernorm_fwd_kernel, dim3(ln_grid(rows)), dim3(256), 0, stream, (const bf16_t*)x_bf16, gamma,
@@ -123,8 +117,8 @@ extern "C" int vj_layernorm_fwd(const void* x_bf16, const float* gamma, const fl
 
 // ---------------------------------------------------------------------------------------------
 // LayerNorm folded into the consuming Linear (round 5; vj_gemm_bf16_nt_lnfold, gemm.hip): what is left of the LayerNorm pass.
-//   rowstats: rs[m] = {rstd_m, -mean_m * rstd_m} of the bf16 rows x -- the same two-pass fp32 statistics as layernorm_fwd_kernel
-//             (mean, then the variance of the centred values: no E[x^2] - mean^2 cancellation), but x is only READ: half the bytes
+//   rowstats: rs[m] = {rstd_m, -mean_m * rstd_m} of the bf16 rows x -- the statistics of layernorm_fwd_kernel bit for bit (both run
+//             ln_row_mean / ln_row_rstd; tests/test_norm_loss_optim_gpu.py compares them), but x is only READ: half the bytes
 //             of the LayerNorm pass, and the GEMM that consumed its output now reads x directly.
 //   fold_weights: Wf[n,:] = bf16(W[n,:] * gamma), c[n] = sum_k Wf[n,k] (of the ROUNDED values: the epilogue's acc - mean * c then
 //             cancels exactly what the matrix pipe accumulated), bf[n] = b[n] + sum_k W[n,k] beta[k].  One wave per output row;
@@ -139,36 +133,14 @@ __global__ __launch_bounds__(256) void ln_rowstats_kernel(const bf16_t* __restri
   for (int64_t r = wave; r < rows; r += nw) {
     const bf16_t* xp = x + r * D;
     float v[LN_MAX_CHUNKS][8];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < LN_MAX_CHUNKS; i++) {
-      const int c = lane * 8 + i * 512;
-      if (c < D) {
-        load8(xp + c, v[i]);
-#pragma unroll
-        for (int j = 0; j < 8; j++) s += v[i][j];
-      }
-    }
-    const float mean = wave_sum(s) * invD;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < LN_MAX_CHUNKS; i++) {
-      const int c = lane * 8 + i * 512;
-      if (c < D) {
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-          const float d = v[i][j] - mean;
-          q += d * d;
-        }
-      }
-    }
-    const float rstd = rsqrtf(wave_sum(q) * invD + eps);
+    const float mean = ln_row_mean<true>(xp, v, lane, D, invD);
+    const float rstd = ln_row_rstd(v, mean, lane, D, invD, eps);
     if (lane == 0) *(float2*)(rs + 2 * r) = make_float2(rstd, -mean * rstd);
   }
 }
 
 extern "C" int vj_ln_rowstats(const void* x_bf16, float* rowstats, int64_t rows, int64_t D, float eps, hipStream_t stream) {
-  VJ_CHECK_ARG(D % 8 == 0 && D <= 512 * LN_MAX_CHUNKS, "vj_ln_rowstats: D=%ld unsupported (need D%%8==0, D<=%d)", (long)D, 512 * LN_MAX_CHUNKS);
+  if (ln_check_D("vj_ln_rowstats", D, true)) return -1;
   VJ_CHECK_ARG(rowstats != nullptr && ((uintptr_t)rowstats % 8 == 0), "vj_ln_rowstats: rowstats null or misaligned");
   if (rows == 0) return 0;
   hipLaunchKernelGGL(ln_rowstats_kernel, dim3(ln_grid(rows)), dim3(256), 0, stream, (const bf16_t*)x_bf16, rowstats, rows, (int)D, eps);
@@ -273,13 +245,6 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __rest
     nmean = mean_in[r];
     nrstd = rstd_in[r];
   };
-  auto unpack8 = [](const u32x4_t& w, float* v) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      v[2 * i] = bf_lo(w[i]);
-      v[2 * i + 1] = bf_hi(w[i]);
-    }
-  };
 #pragma unroll
   for (int i = 0; i < NCH; i++) nx[i] = nd[i] = nr[i] = (u32x4_t){0u, 0u, 0u, 0u};
   if (rbeg + wv < rend) request(rbeg + wv);
@@ -375,7 +340,7 @@ extern "C" int64_t vj_layernorm_bwd_ws_bytes(int64_t D) { return (int64_t)LN_BWD
 int vj_layernorm_bwd_partials(const void* dy_bf16, const void* x_bf16, const float* gamma, const float* mean, const float* rstd,
                               const void* dres_bf16, void* dx_bf16, bool cs, int64_t rows, int64_t D, void* ws,
                               int64_t ws_bytes, int64_t* nb_out, hipStream_t stream) {
-  VJ_CHECK_ARG(D % 8 == 0 && D <= 512 * LN_MAX_CHUNKS, "vj_layernorm_bwd: D=%ld unsupported", (long)D);
+  if (ln_check_D("vj_layernorm_bwd", D)) return -1;
   VJ_CHECK_ARG(ws_bytes >= vj_layernorm_bwd_ws_bytes(D), "vj_layernorm_bwd: workspace too small");
   *nb_out = 0;
   if (rows == 0) return 0;
@@ -442,56 +407,18 @@ __global__ __launch_bounds__(256) void target_rows_kernel(const bf16_t* __restri
     const int64_t b = r / K;
     const bf16_t* xp = x + (b * N + idx[r]) * D;
     float v[LN_MAX_CHUNKS][8];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < LN_MAX_CHUNKS; i++) {
-      const int c = lane * 8 + i * 512;
-      if (c < D) {
-        load8(xp + c, v[i]);
-#pragma unroll
-        for (int j = 0; j < 8; j++) s += v[i][j];
-      }
-    }
-    float mean = wave_sum(s) * invD;
-    float q = 0.f;
+    float mean = ln_row_mean<true>(xp, v, lane, D, invD);
+    float rstd = ln_row_rstd(v, mean, lane, D, invD, eps1);
 #pragma unroll
     for (int i = 0; i < LN_MAX_CHUNKS; i++) {
       const int c = lane * 8 + i * 512;
       if (c < D) {
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-          const float d = v[i][j] - mean;
-          q += d * d;
-        }
+        for (int j = 0; j < 8; j++) v[i][j] = (v[i][j] - mean) * rstd * gamma[c + j] + beta[c + j];
       }
     }
-    float rstd = rsqrtf(wave_sum(q) * invD + eps1);
-    s = 0.f;
-#pragma unroll
-    for (int i = 0; i < LN_MAX_CHUNKS; i++) {
-      const int c = lane * 8 + i * 512;
-      if (c < D) {
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-          v[i][j] = (v[i][j] - mean) * rstd * gamma[c + j] + beta[c + j];
-          s += v[i][j];
-        }
-      }
-    }
-    mean = wave_sum(s) * invD;
-    q = 0.f;
-#pragma unroll
-    for (int i = 0; i < LN_MAX_CHUNKS; i++) {
-      const int c = lane * 8 + i * 512;
-      if (c < D) {
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-          const float d = v[i][j] - mean;
-          q += d * d;
-        }
-      }
-    }
-    rstd = rsqrtf(wave_sum(q) * invD + eps2);
+    mean = ln_row_mean<false>(nullptr, v, lane, D, invD);
+    rstd = ln_row_rstd(v, mean, lane, D, invD, eps2);
     float* hp = h + r * D;
 #pragma unroll
     for (int i = 0; i < LN_MAX_CHUNKS; i++) {
@@ -516,205 +443,10 @@ __global__ __launch_bounds__(256) void target_rows_kernel(const bf16_t* __restri
 extern "C" int vj_target_rows(const void* x_bf16, const float* gamma, const float* beta, const int64_t* idx,
                               float* h, int64_t B, int64_t N, int64_t K, int64_t D, float eps_norm, float eps_ln,
                               hipStream_t stream) {
-  VJ_CHECK_ARG(D % 8 == 0 && D <= 512 * LN_MAX_CHUNKS, "vj_target_rows: D=%ld unsupported", (long)D);
+  if (ln_check_D("vj_target_rows", D)) return -1;
   if (B * K == 0) return 0;
   hipLaunchKernelGGL(target_rows_kernel, dim3(ln_grid(B * K)), dim3(256), 0, stream, (const bf16_t*)x_bf16, gamma,
                      beta, idx, h, B, N, K, (int)D, eps_norm, eps_ln);
   VJ_LAUNCH_CHECK("vj_target_rows");
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// latent_loss: sum |z-h|^p / p over all elements (z bf16, h fp32), deterministic two-stage reduction,
-// optionally writing dz = sign(z-h)*|z-h|^(p-1) * gscale (bf16) in the same pass.
-// part[blk] holds the block sums; finish kernel folds them:  out[slot] = scale * sum.
-// ---------------------------------------------------------------------------------------------
-#define LOSS_BLOCKS 512
-__global__ __launch_bounds__(256) void latent_loss_kernel(const bf16_t* __restrict__ z, const float* __restrict__ h,
-                                                          bf16_t* __restrict__ dz, float* __restrict__ part,
-                                                          int64_t n8, float p, float gscale) {
-  __shared__ float red[4];
-  float acc = 0.f;
-  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n8; q += (int64_t)gridDim.x * 256) {
-    float zv[8];
-    load8(z + q * 8, zv);
-    const float4 h0 = *(const float4*)(h + q * 8);
-    const float4 h1 = *(const float4*)(h + q * 8 + 4);
-    const float hv[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-    float g[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      const float d = zv[j] - hv[j];
-      const float a = fabsf(d);
-      if (p == 1.0f) {
-        acc += a;
-        g[j] = (d > 0.f) ? gscale : ((d < 0.f) ? -gscale : 0.f);
-      } else {
-        acc += __powf(a, p) / p;
-        const float m = (a > 0.f) ? __powf(a, p - 1.0f) : 0.f;
-        g[j] = (d > 0.f) ? m * gscale : -m * gscale;
-      }
-    }
-    if (dz) store8(dz + q * 8, g);
-  }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-__global__ void scalar_finish_kernel(const float* __restrict__ part, int n, float scale, float* __restrict__ out,
-                                     int accumulate) {
-  __shared__ float red[4];
-  float s = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) s += part[i];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const float v = (red[0] + red[1] + red[2] + red[3]) * scale;
-    *out = accumulate ? (*out + v) : v;
-  }
-}
-
-extern "C" int64_t vj_latent_loss_ws_bytes(void) { return LOSS_BLOCKS * 4; }
-
-// loss_out (device scalar) = [accumulate ? loss_out : 0] + out_scale * sum(|z-h|^p / p)
-extern "C" int vj_latent_loss(const void* z_bf16, const float* h, void* dz_bf16, int64_t numel, float p,
-                              float gscale, float out_scale, int accumulate, float* loss_out, void* ws,
-                              int64_t ws_bytes, hipStream_t stream) {
-  VJ_CHECK_ARG(numel % 8 == 0, "vj_latent_loss: numel=%ld must be a multiple of 8", (long)numel);
-  VJ_CHECK_ARG(ws_bytes >= vj_latent_loss_ws_bytes(), "vj_latent_loss: workspace too small");
-  VJ_CHECK_ARG(p > 0.f, "vj_latent_loss: loss_exp must be > 0");
-  if (numel == 0) return 0;
-  hipLaunchKernelGGL(latent_loss_kernel, dim3(LOSS_BLOCKS), dim3(256), 0, stream, (const bf16_t*)z_bf16, h,
-                     (bf16_t*)dz_bf16, (float*)ws, numel / 8, p, gscale);
-  VJ_LAUNCH_CHECK("vj_latent_loss");
-  hipLaunchKernelGGL(scalar_finish_kernel, dim3(1), dim3(256), 0, stream, (const float*)ws, LOSS_BLOCKS, out_scale,
-                     loss_out, accumulate);
-  VJ_LAUNCH_CHECK("vj_latent_loss(finish)");
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// token_pstd: pstd[b,d] (+)= sqrt(unbiased_var_k z[b,k,d] + 1e-4)   (reg_fn, train.py:448-449)
-// one block per (b, 256-column slab); two-pass over the K rows for accuracy.
-// ---------------------------------------------------------------------------------------------
-// one workgroup per (b, 64-column slab): 4 waves split the K rows, each lane owns one column pair... 8 columns per
-// thread (16-byte loads), shifted single-pass sums (shift = first row) combined across the 8 row-lanes in LDS.
-__global__ __launch_bounds__(256) void token_pstd_kernel(const bf16_t* __restrict__ z, float* __restrict__ pstd,
-                                                         float* __restrict__ stats, int64_t K, int D,
-                                                         int accumulate) {
-  __shared__ float red[2][32][65];
-  const int64_t b = blockIdx.y;
-  const int cg = threadIdx.x & 7, rl = threadIdx.x >> 3;       // 8 column groups of 8, 32 row lanes
-  const int d0 = blockIdx.x * 64 + cg * 8;
-  const bf16_t* zp = z + b * K * D;
-  float s[8], q[8], sh[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) s[j] = q[j] = sh[j] = 0.f;
-  if (d0 < D) {
-    load8(zp + d0, sh);                                         // shift by row 0: well-conditioned single pass
-    for (int64_t k = rl; k < K; k += 32) {
-      float v[8];
-      load8(zp + k * D + d0, v);
-#pragma unroll
-      for (int j = 0; j < 8; j++) {
-        const float t = v[j] - sh[j];
-        s[j] += t;
-        q[j] += t * t;
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 8; j++) {
-    red[0][rl][cg * 8 + j] = s[j];
-    red[1][rl][cg * 8 + j] = q[j];
-  }
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    const int c = threadIdx.x, d = blockIdx.x * 64 + c;
-    if (d < D) {
-      float ss = 0.f, qq = 0.f;
-      for (int r = 0; r < 32; r++) {
-        ss += red[0][r][c];
-        qq += red[1][r][c];
-      }
-      const float var = (qq - ss * ss / (float)K) / (float)(K - 1);   // unbiased, shift-invariant
-      const float v = sqrtf(fmaxf(var, 0.f) + 1e-4f);
-      float* o = pstd + b * D + d;
-      *o = accumulate ? (*o + v) : v;
-      if (stats) {   // per-(b,d) token mean and sqrt(var + eps) of THIS mask, for reg_grad
-        stats[(b * D + d) * 2] = bf2f(zp[d]) + ss / (float)K;
-        stats[(b * D + d) * 2 + 1] = v;
-      }
-    }
-  }
-}
-
-// reg = mean(relu(1 - pstd_sum / n_masks))
-__global__ __launch_bounds__(256) void reg_finish_kernel(const float* __restrict__ pstd, int64_t n, float inv_masks,
-                                                         float* __restrict__ out) {
-  __shared__ float red[4];
-  float s = 0.f;
-  for (int64_t i = threadIdx.x; i < n; i += 256) s += fmaxf(0.f, 1.0f - pstd[i] * inv_masks);
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = (red[0] + red[1] + red[2] + red[3]) / (float)n;
-}
-
-extern "C" int vj_token_pstd(const void* z_bf16, float* pstd, float* stats, int64_t B, int64_t K, int64_t D,
-                             int accumulate, hipStream_t stream) {
-  VJ_CHECK_ARG(K >= 2, "vj_token_pstd: need at least 2 tokens for an unbiased variance (K=%ld)", (long)K);
-  if (B * D == 0) return 0;
-  VJ_CHECK_ARG(D % 8 == 0, "vj_token_pstd: D must be a multiple of 8");
-  hipLaunchKernelGGL(token_pstd_kernel, dim3((unsigned)cdiv64(D, 64), (unsigned)B), dim3(256), 0, stream,
-                     (const bf16_t*)z_bf16, pstd, stats, K, (int)D, accumulate);
-  VJ_LAUNCH_CHECK("vj_token_pstd");
-  return 0;
-}
-
-extern "C" int vj_reg_finish(const float* pstd_sum, int64_t n, int64_t n_masks, float* out, hipStream_t stream) {
-  hipLaunchKernelGGL(reg_finish_kernel, dim3(1), dim3(256), 0, stream, pstd_sum, n, 1.0f / (float)n_masks, out);
-  VJ_LAUNCH_CHECK("vj_reg_finish");
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// reg_grad: dz[b,k,d] += coef * d/dz mean_{b,d} relu(1 - pstd_avg[b,d]),  pstd_avg = pstd_sum / n_masks
-//   = -coef / (B*D*n_masks) * 1[pstd_avg < 1] * (z - mean) / ((K-1) * sqrt(var + eps))       (train.py:448-459)
-// dz holds the latent-loss gradient in units of 1/gscale (see vj_latent_loss); `coef` is pre-divided accordingly.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void reg_grad_kernel(const bf16_t* __restrict__ z, const float* __restrict__ pstd_sum,
-                                                       const float* __restrict__ stats, bf16_t* __restrict__ dz,
-                                                       int64_t B, int64_t K, int D, float inv_masks, float coef) {
-  const int64_t n8 = B * K * D / 8;
-  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n8; q += (int64_t)gridDim.x * 256) {
-    const int64_t e = q * 8;
-    const int d0 = (int)(e % D);
-    const int64_t b = e / ((int64_t)K * D);
-    float zv[8], gv[8];
-    load8(z + e, zv);
-    load8(dz + e, gv);
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      const int64_t bd = b * D + d0 + j;
-      const float active = (pstd_sum[bd] * inv_masks < 1.0f) ? 1.0f : 0.f;
-      gv[j] -= coef * active * (zv[j] - stats[bd * 2]) / ((float)(K - 1) * stats[bd * 2 + 1]);
-    }
-    store8(dz + e, gv);
-  }
-}
-
-extern "C" int vj_reg_grad(const void* z_bf16, const float* pstd_sum, const float* stats, void* dz_bf16, int64_t B,
-                           int64_t K, int64_t D, int64_t n_masks, float coef, hipStream_t stream) {
-  VJ_CHECK_ARG(D % 8 == 0 && K >= 2, "vj_reg_grad: need D %% 8 == 0 and K >= 2");
-  if (B * K * D == 0) return 0;
-  int64_t g = cdiv64(B * K * D / 8, 256);
-  if (g > 256 * 8) g = 256 * 8;
-  hipLaunchKernelGGL(reg_grad_kernel, dim3((unsigned)g), dim3(256), 0, stream, (const bf16_t*)z_bf16, pstd_sum, stats,
-                     (bf16_t*)dz_bf16, B, K, (int)D, 1.0f / (float)n_masks, coef);
-  VJ_LAUNCH_CHECK("vj_reg_grad");
   return 0;
 }

@@ -27,6 +27,21 @@ struct AdamArgs {
   const float* step_dev;  // device step counter t (already advanced by vj_step_advance); bias corrections from it
 };
 
+// THE EMA of four weights with its bf16 re-cast: tgt[q] = m * tgt[q] + (1 - m) * s, shadow (nullable) = bf16 of it.  One product is
+// rounded and the other fused into the sum, and which one is part of the bits of every target weight: left to the compiler's contraction,
+// the update pass of adamw_ema_kernel had always rounded (1 - m) * s (SRC_ROUNDED) while its skip branch and ema_kernel rounded
+// m * tgt.  Both are written out here so that they stay as they were whatever the compiler prefers.
+template <bool SRC_ROUNDED>
+__device__ __forceinline__ void ema4(float* tgt, bf16_t* tgt_bf16, int64_t q, float4 s, float m) {
+  const float4 t4 = ((float4*)tgt)[q];
+  const float ss[4] = {s.x, s.y, s.z, s.w};
+  float t[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+  for (int i = 0; i < 4; i++) t[i] = SRC_ROUNDED ? fmaf(m, t[i], (1.0f - m) * ss[i]) : fmaf(1.0f - m, ss[i], m * t[i]);
+  ((float4*)tgt)[q] = make_float4(t[0], t[1], t[2], t[3]);
+  if (tgt_bf16) ((u32x2_t*)tgt_bf16)[q] = pack4_bf16(t[0], t[1], t[2], t[3]);
+}
+
 __global__ __launch_bounds__(256) void adamw_ema_kernel(AdamArgs a) {
   const int64_t n4 = a.n >> 2;
   bool skip = false;
@@ -47,19 +62,7 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(AdamArgs a) {
   if (skip) {
     if (!a.tgt) return;
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n4; q += (int64_t)gridDim.x * 256) {
-      const float4 p = ((const float4*)a.p)[q];
-      float4 t = ((float4*)a.tgt)[q];
-      t.x = t.x * a.ema + (1.0f - a.ema) * p.x;
-      t.y = t.y * a.ema + (1.0f - a.ema) * p.y;
-      t.z = t.z * a.ema + (1.0f - a.ema) * p.z;
-      t.w = t.w * a.ema + (1.0f - a.ema) * p.w;
-      ((float4*)a.tgt)[q] = t;
-      if (a.tgt_bf16) {
-        u32x2_t w;
-        w[0] = pack_bf2(t.x, t.y);
-        w[1] = pack_bf2(t.z, t.w);
-        ((u32x2_t*)a.tgt_bf16)[q] = w;
-      }
+      ema4<false>(a.tgt, a.tgt_bf16, q, ((const float4*)a.p)[q], a.ema);
     }
     return;
   }
@@ -85,33 +88,23 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(AdamArgs a) {
     ((float4*)a.p)[q] = make_float4(pp[0], pp[1], pp[2], pp[3]);
     ((float4*)a.m)[q] = make_float4(mm[0], mm[1], mm[2], mm[3]);
     ((float4*)a.v)[q] = make_float4(vv[0], vv[1], vv[2], vv[3]);
-    if (a.p_bf16) {
-      u32x2_t w;
-      w[0] = pack_bf2(pp[0], pp[1]);
-      w[1] = pack_bf2(pp[2], pp[3]);
-      ((u32x2_t*)a.p_bf16)[q] = w;
-    }
-    if (a.tgt) {
-      const float4 t4 = ((float4*)a.tgt)[q];
-      float tt[4] = {t4.x, t4.y, t4.z, t4.w};
-#pragma unroll
-      for (int i = 0; i < 4; i++) tt[i] = tt[i] * a.ema + (1.0f - a.ema) * pp[i];
-      ((float4*)a.tgt)[q] = make_float4(tt[0], tt[1], tt[2], tt[3]);
-      if (a.tgt_bf16) {
-        u32x2_t w;
-        w[0] = pack_bf2(tt[0], tt[1]);
-        w[1] = pack_bf2(tt[2], tt[3]);
-        ((u32x2_t*)a.tgt_bf16)[q] = w;
-      }
-    }
+    if (a.p_bf16) ((u32x2_t*)a.p_bf16)[q] = pack4_bf16(pp[0], pp[1], pp[2], pp[3]);
+    if (a.tgt) ema4<true>(a.tgt, a.tgt_bf16, q, make_float4(pp[0], pp[1], pp[2], pp[3]), a.ema);
   }
 }
 
-static inline int flat_grid(int64_t n_items) {
-  int64_t g = cdiv64(n_items, 256);
-  if (g > 256 * 8) g = 256 * 8;
-  if (g < 1) g = 1;
-  return (int)g;
+// one thread per four parameters, at most 256 * 8 workgroups; every caller has returned on n == 0 and checked n % 4 == 0, so n / 4 >= 1
+static inline int optim_grid(int64_t n) { return flat_grid(n / 4, 256 * 8); }
+
+// the arguments both entry points share; the plain one then sets the host's bias corrections, the guarded one the guard
+static AdamArgs adam_args(float* p, const float* g, float* exp_avg, float* exp_avg_sq, void* p_bf16, float* tgt, void* tgt_bf16, int64_t n,
+                          float lr, float wd, float beta1, float beta2, float eps, float gscale, float ema) {
+  AdamArgs a;
+  a.p = p; a.g = g; a.m = exp_avg; a.v = exp_avg_sq; a.p_bf16 = (bf16_t*)p_bf16; a.tgt = tgt;
+  a.tgt_bf16 = (bf16_t*)tgt_bf16; a.n = n; a.lr = lr; a.wd = wd; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
+  a.bc1 = 1.f; a.bc2_sqrt = 1.f; a.gscale = gscale; a.ema = ema;
+  a.gstat = nullptr; a.sel = 0; a.clip = 0.f; a.norm_scale = 1.f; a.step_dev = nullptr;
+  return a;
 }
 
 extern "C" int vj_adamw_ema(float* p, const float* g, float* exp_avg, float* exp_avg_sq, void* p_bf16, float* tgt,
@@ -120,14 +113,10 @@ extern "C" int vj_adamw_ema(float* p, const float* g, float* exp_avg, float* exp
   VJ_CHECK_ARG(n % 4 == 0, "vj_adamw_ema: segment length %ld must be a multiple of 4 (pad the arena)", (long)n);
   VJ_CHECK_ARG(step >= 1, "vj_adamw_ema: step must be >= 1");
   if (n == 0) return 0;
-  AdamArgs a;
-  a.p = p; a.g = g; a.m = exp_avg; a.v = exp_avg_sq; a.p_bf16 = (bf16_t*)p_bf16; a.tgt = tgt;
-  a.tgt_bf16 = (bf16_t*)tgt_bf16; a.n = n; a.lr = lr; a.wd = wd; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
+  AdamArgs a = adam_args(p, g, exp_avg, exp_avg_sq, p_bf16, tgt, tgt_bf16, n, lr, wd, beta1, beta2, eps, gscale, ema);
   a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
   a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-  a.gscale = gscale; a.ema = ema;
-  a.gstat = nullptr; a.sel = 0; a.clip = 0.f; a.norm_scale = 1.f; a.step_dev = nullptr;
-  hipLaunchKernelGGL(adamw_ema_kernel, dim3(flat_grid(n / 4)), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(adamw_ema_kernel, dim3(optim_grid(n)), dim3(256), 0, stream, a);
   VJ_LAUNCH_CHECK("vj_adamw_ema");
   return 0;
 }
@@ -151,14 +140,10 @@ extern "C" int vj_adamw_ema_guarded(float* p, const float* g, float* exp_avg, fl
   VJ_CHECK_ARG(n % 4 == 0, "vj_adamw_ema_guarded: segment length %ld must be a multiple of 4 (pad the arena)", (long)n);
   VJ_CHECK_ARG(gstat != nullptr && step_dev != nullptr && (sel == 0 || sel == 1), "vj_adamw_ema_guarded: bad guard arguments");
   if (n == 0) return 0;
-  AdamArgs a;
-  a.p = p; a.g = g; a.m = exp_avg; a.v = exp_avg_sq; a.p_bf16 = (bf16_t*)p_bf16; a.tgt = tgt;
-  a.tgt_bf16 = (bf16_t*)tgt_bf16; a.n = n; a.lr = lr; a.wd = wd; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-  a.bc1 = 1.f; a.bc2_sqrt = 1.f; a.gscale = gscale; a.ema = ema;
+  AdamArgs a = adam_args(p, g, exp_avg, exp_avg_sq, p_bf16, tgt, tgt_bf16, n, lr, wd, beta1, beta2, eps, gscale, ema);
   a.gstat = gstat; a.sel = sel; a.clip = clip; a.norm_scale = norm_scale; a.step_dev = step_dev;
   // (a cap on the workgroup count -- fewer CUs for the update while it runs beside the next step's forward -- was an option in round 5: level)
-  const int grid = flat_grid(n / 4);
-  hipLaunchKernelGGL(adamw_ema_kernel, dim3(grid), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(adamw_ema_kernel, dim3(optim_grid(n)), dim3(256), 0, stream, a);
   VJ_LAUNCH_CHECK("vj_adamw_ema_guarded");
   return 0;
 }
@@ -167,26 +152,14 @@ extern "C" int vj_adamw_ema_guarded(float* p, const float* g, float* exp_avg, fl
 __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ tgt, const float* __restrict__ src,
                                                   bf16_t* __restrict__ tgt_bf16, int64_t n4, float m) {
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n4; q += (int64_t)gridDim.x * 256) {
-    const float4 s = ((const float4*)src)[q];
-    float4 t = ((float4*)tgt)[q];
-    t.x = t.x * m + (1.0f - m) * s.x;
-    t.y = t.y * m + (1.0f - m) * s.y;
-    t.z = t.z * m + (1.0f - m) * s.z;
-    t.w = t.w * m + (1.0f - m) * s.w;
-    ((float4*)tgt)[q] = t;
-    if (tgt_bf16) {
-      u32x2_t w;
-      w[0] = pack_bf2(t.x, t.y);
-      w[1] = pack_bf2(t.z, t.w);
-      ((u32x2_t*)tgt_bf16)[q] = w;
-    }
+    ema4<false>(tgt, tgt_bf16, q, ((const float4*)src)[q], m);
   }
 }
 
 extern "C" int vj_ema_update(float* tgt, const float* src, void* tgt_bf16, int64_t n, float m, hipStream_t stream) {
   VJ_CHECK_ARG(n % 4 == 0, "vj_ema_update: n must be a multiple of 4");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(ema_kernel, dim3(flat_grid(n / 4)), dim3(256), 0, stream, tgt, src, (bf16_t*)tgt_bf16, n / 4, m);
+  hipLaunchKernelGGL(ema_kernel, dim3(optim_grid(n)), dim3(256), 0, stream, tgt, src, (bf16_t*)tgt_bf16, n / 4, m);
   VJ_LAUNCH_CHECK("vj_ema_update");
   return 0;
 }
@@ -196,17 +169,14 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict_
                                                         int64_t n4) {
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n4; q += (int64_t)gridDim.x * 256) {
     const float4 s = ((const float4*)src)[q];
-    u32x2_t w;
-    w[0] = pack_bf2(s.x, s.y);
-    w[1] = pack_bf2(s.z, s.w);
-    ((u32x2_t*)dst)[q] = w;
+    ((u32x2_t*)dst)[q] = pack4_bf16(s.x, s.y, s.z, s.w);
   }
 }
 
 extern "C" int vj_cast_f32_to_bf16(const float* src, void* dst_bf16, int64_t n, hipStream_t stream) {
   VJ_CHECK_ARG(n % 4 == 0, "vj_cast_f32_to_bf16: n must be a multiple of 4");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(cast_bf16_kernel, dim3(flat_grid(n / 4)), dim3(256), 0, stream, src, (bf16_t*)dst_bf16, n / 4);
+  hipLaunchKernelGGL(cast_bf16_kernel, dim3(optim_grid(n)), dim3(256), 0, stream, src, (bf16_t*)dst_bf16, n / 4);
   VJ_LAUNCH_CHECK("vj_cast_f32_to_bf16");
   return 0;
 }
@@ -221,16 +191,10 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ g
     s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
     bad += (float)(!isfinite(v.x)) + (float)(!isfinite(v.y)) + (float)(!isfinite(v.z)) + (float)(!isfinite(v.w));
   }
-  s = wave_sum(s);
-  bad = wave_sum(bad);
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = s;
-    red[1][threadIdx.x >> 6] = bad;
-  }
-  __syncthreads();
+  block4_stage(red, {s, bad});
   if (threadIdx.x == 0) {
-    part[blockIdx.x] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    part[SQ_BLOCKS + blockIdx.x] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    part[blockIdx.x] = block4_total(red[0]);
+    part[SQ_BLOCKS + blockIdx.x] = block4_total(red[1]);
   }
 }
 __global__ __launch_bounds__(256) void sqnorm_finish_kernel(const float* __restrict__ part, float* __restrict__ out,
@@ -241,16 +205,9 @@ __global__ __launch_bounds__(256) void sqnorm_finish_kernel(const float* __restr
     s += part[i];
     bad += part[SQ_BLOCKS + i];
   }
-  s = wave_sum(s);
-  bad = wave_sum(bad);
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = s;
-    red[1][threadIdx.x >> 6] = bad;
-  }
-  __syncthreads();
+  block4_stage(red, {s, bad});
   if (threadIdx.x == 0) {
-    const float a = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    const float b = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    const float a = block4_total(red[0]), b = block4_total(red[1]);
     out[0] = accumulate ? out[0] + a : a;
     out[1] = accumulate ? out[1] + b : b;
   }
@@ -301,18 +258,8 @@ __global__ __launch_bounds__(256) void grad_stats_multi_kernel(const float* __re
       s2 += fabsf(M2[off + e]);
     }
   }
-  s0 = wave_sum(s0);
-  s1 = wave_sum(s1);
-  s2 = wave_sum(s2);
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = s0;
-    red[1][threadIdx.x >> 6] = s1;
-    red[2][threadIdx.x >> 6] = s2;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3)
-    out[((int64_t)t * GS_CHUNKS + c) * 3 + threadIdx.x] =
-        red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+  block4_stage(red, {s0, s1, s2});
+  if (threadIdx.x < 3) out[((int64_t)t * GS_CHUNKS + c) * 3 + threadIdx.x] = block4_total(red[threadIdx.x]);
 }
 extern "C" int64_t vj_grad_stats_chunks(void) { return GS_CHUNKS; }
 extern "C" int vj_grad_stats_multi(const float* G, const float* M1, const float* M2, const int64_t* desc, int64_t n_tensors,
