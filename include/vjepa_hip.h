@@ -470,6 +470,26 @@ int vj_get_option(const char* name, int* value);
  * counterpart. */
 int vj_ws_guard_check(int64_t* n_checked, int64_t* n_bad);
 
+/* ---- bank of attentive probes on one frozen forward pass (AttentiveClassifierBank) -----------------------------
+ * P probes with ONE query token each, shared by the batch: the scores of every (probe, head) are one column of
+ * S = x_hat U^T (fp32 [B, N, C], C = P * heads padded to a multiple of 4 with zero rows of U), so neither K nor V of
+ * CrossAttention.forward (src/models/utils/modules.py:145-148) is materialised.
+ * vj_pool_softmax_fwd replaces `F.scaled_dot_product_attention`'s soft-max over the keys (modules.py:150-153) for all columns
+ * at once: A = bf16(softmax over n of S[b, n, c]), lse[b, c] = log sum_n exp S (fp32).  The column maximum is subtracted
+ * before the exponential (finite S never gives a NaN; an all-zero padded column gives the uniform distribution).  Keys are
+ * split into vj_pool_softmax_chunk_keys() chunks whose partial (max, sum) pairs go through ws and are merged in ascending chunk
+ * order: no atomics, run-to-run bitwise equal.  ws_bytes >= vj_pool_softmax_fwd_ws_bytes(B, N, C) (< 0 for bad dimensions).
+ * vj_pool_softmax_bwd replaces the soft-max backward autograd runs there: dS = bf16(A * (dA - delta[b, c])), dA fp32
+ * [B, N, C], delta fp32 [B, C] = sum_n A dA (the caller has it as dZ . Z).
+ * C % 4 == 0, B <= 65535, N <= 65535 chunks; fp32 buffers 16-byte aligned, bf16 buffers 8-byte aligned; every argument is
+ * checked on the host before any launch. */
+int64_t vj_pool_softmax_chunk_keys(void);
+int64_t vj_pool_softmax_fwd_ws_bytes(int64_t B, int64_t N, int64_t C);
+int vj_pool_softmax_fwd(const float* S, void* A_bf16, float* lse, int64_t B, int64_t N, int64_t C, void* ws, int64_t ws_bytes,
+                        vj_stream_t stream);
+int vj_pool_softmax_bwd(const void* A_bf16, const float* dA, const float* delta, void* dS_bf16, int64_t B, int64_t N, int64_t C,
+                        vj_stream_t stream);
+
 /* ---- hardware probes (tests / profiles only) ---------------------------------------------------------------- */
 int vj_probe_tr16(uint32_t* out256, int addr_scale, vj_stream_t stream);
 int vj_probe_copy(const void* src, void* dst, int64_t bytes, vj_stream_t stream);

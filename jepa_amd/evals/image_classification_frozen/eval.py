@@ -35,6 +35,8 @@ from ...src.datasets.data_manager import SyntheticImageClassification
 from ...src.models.attentive_pooler import AttentiveClassifier
 from ...src.utils.distributed import AllReduce, init_distributed
 from ...src.utils.logging import AverageMeter, CSVLogger, get_logger
+from ..multihead import parse_multihead_kwargs
+from ..multihead import run as run_multihead
 from ..video_classification_frozen.eval import (_distributed, classifier_state_dict, init_model, init_opt,  # noqa: F401
                                                 load_checkpoint, load_pretrained)
 from ..video_classification_frozen.utils import _widest, max_clips_per_call
@@ -85,6 +87,7 @@ def main(args_eval, resume_preempt=False):
     final_lr = args_opt.get('final_lr')
     warmup = args_opt.get('warmup')
     use_bfloat16 = args_opt.get('use_bfloat16')
+    multihead = parse_multihead_kwargs(args_opt)   # None: the single probe below; a list: one bank of probes (..multihead)
 
     # -- EXPERIMENT-ID/TAG (optional)
     resume_checkpoint = args_eval.get('resume_checkpoint', False) or resume_preempt
@@ -106,7 +109,7 @@ def main(args_eval, resume_preempt=False):
     log_file = os.path.join(folder, f'{tag}_r{rank}.csv')
     latest_path = os.path.join(folder, f'{tag}-latest.pth.tar')
 
-    if rank == 0:
+    if rank == 0 and multihead is None:
         csv_logger = CSVLogger(log_file, ('%d', 'epoch'), ('%.5f', 'loss'), ('%.5f', 'acc'))
 
     # -- pretrained encoder (frozen): the video ViT, or the image ViT with frames_per_clip == 1; both are fed [B,C,H,W] directly
@@ -119,8 +122,9 @@ def main(args_eval, resume_preempt=False):
         p.requires_grad = False
 
     # -- init classifier
-    classifier = AttentiveClassifier(embed_dim=encoder.embed_dim, num_heads=encoder.num_heads, depth=1,
-                                     num_classes=num_classes).to(device)
+    if multihead is None:
+        classifier = AttentiveClassifier(embed_dim=encoder.embed_dim, num_heads=encoder.num_heads, depth=1,
+                                         num_classes=num_classes).to(device)
 
     common = dict(dataset_name=dataset_name, root_path=root_path, resolution=resolution, image_folder=image_folder,
                   batch_size=batch_size, world_size=world_size, rank=rank, num_classes=num_classes,
@@ -129,6 +133,12 @@ def main(args_eval, resume_preempt=False):
     val_loader = make_dataloader(training=False, **common)
     ipe = len(train_loader)
     logger.info(f'Dataloader created... iterations per epoch: {ipe}')
+
+    if multihead is not None:
+        return run_multihead(hps=multihead, init_opt=init_opt, features=_image_features, encoder=encoder,
+                             train_loader=train_loader, val_loader=val_loader, num_classes=num_classes, num_epochs=num_epochs,
+                             use_bfloat16=use_bfloat16, folder=folder, tag=tag, rank=rank, world_size=world_size,
+                             batch_size=batch_size, resume_checkpoint=resume_checkpoint, distributed=_distributed(), device=device)
 
     # -- optimizer and scheduler
     optimizer, scaler, scheduler, wd_scheduler = init_opt(classifier=classifier, wd=wd, start_lr=start_lr, ref_lr=lr,
@@ -198,6 +208,11 @@ def frozen_features(encoder, imgs):
         N, D = f.shape[1], f.shape[2]
         ops.copy_rows(f, out, 1, f.shape[0] * N, 0, B * N, c0 * N, f.shape[0] * N, D)
     return out
+
+
+def _image_features(encoder, data, device):
+    """One batch for the probe bank: the frozen features as a one-view list of [B, N, D], and the labels."""
+    return [frozen_features(encoder, data[0].to(device, non_blocking=True))], data[1].to(device)
 
 
 def run_one_epoch(device, training, encoder, classifier, scaler, optimizer, scheduler, wd_scheduler, data_loader, use_bfloat16,

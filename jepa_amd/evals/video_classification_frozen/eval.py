@@ -17,9 +17,12 @@ arithmetic, CSV columns, checkpoint dictionary and folder / file names.  Differe
   - with `pretrain.frames_per_clip` == 1 the encoder is the 2-D image ViT under FrameAggregation, which (as in the reference) only
     has the concatenated form: `optimization.attend_across_segments` must be true.
   - `main` returns a small record of the run (per-epoch accuracies, per-iteration training loss and learning rate).
+  - `optimization.multihead_kwargs` (optional list of dictionaries overriding lr / start_lr / final_lr / weight_decay / warmup)
+    trains one probe per entry on the same frozen forward pass (..multihead); without the key nothing changes.
 """
 import os
 import pprint
+from functools import partial
 
 import numpy as np
 import torch
@@ -32,6 +35,8 @@ from ...src.models.attentive_pooler import AttentiveClassifier
 from ...src.utils.distributed import AllReduce, init_distributed
 from ...src.utils.logging import AverageMeter, CSVLogger, get_logger
 from ...src.utils.schedulers import CosineWDSchedule, WarmupCosineSchedule
+from ..multihead import parse_multihead_kwargs
+from ..multihead import run as run_multihead
 from .utils import ClipAggregation, FrameAggregation
 
 logger = get_logger(__name__)
@@ -91,6 +96,7 @@ def main(args_eval, resume_preempt=False):
     final_lr = args_opt.get('final_lr')
     warmup = args_opt.get('warmup')
     use_bfloat16 = args_opt.get('use_bfloat16')
+    multihead = parse_multihead_kwargs(args_opt)   # None: the single probe below; a list: one bank of probes (..multihead)
 
     # -- EXPERIMENT-ID/TAG (optional)
     resume_checkpoint = args_eval.get('resume_checkpoint', False) or resume_preempt
@@ -117,7 +123,7 @@ def main(args_eval, resume_preempt=False):
     log_file = os.path.join(folder, f'{tag}_r{rank}.csv')
     latest_path = os.path.join(folder, f'{tag}-latest.pth.tar')
 
-    if rank == 0:
+    if rank == 0 and multihead is None:
         csv_logger = CSVLogger(log_file, ('%d', 'epoch'), ('%.5f', 'loss'), ('%.5f', 'acc'))
 
     # -- pretrained encoder (frozen)
@@ -134,8 +140,9 @@ def main(args_eval, resume_preempt=False):
         p.requires_grad = False
 
     # -- init classifier
-    classifier = AttentiveClassifier(embed_dim=encoder.embed_dim, num_heads=encoder.num_heads, depth=1,
-                                     num_classes=num_classes).to(device)
+    if multihead is None:
+        classifier = AttentiveClassifier(embed_dim=encoder.embed_dim, num_heads=encoder.num_heads, depth=1,
+                                         num_classes=num_classes).to(device)
 
     common = dict(dataset_type=dataset_type, resolution=resolution, frames_per_clip=eval_frames_per_clip,
                   frame_step=eval_frame_step, eval_duration=eval_duration, allow_segment_overlap=True, batch_size=batch_size,
@@ -147,6 +154,13 @@ def main(args_eval, resume_preempt=False):
                                  num_views_per_segment=eval_num_views_per_segment, training=False, **common)
     ipe = len(train_loader)
     logger.info(f'Dataloader created... iterations per epoch: {ipe}')
+
+    if multihead is not None:
+        return run_multihead(hps=multihead, init_opt=init_opt, features=partial(_view_features, attend_across_segments),
+                             encoder=encoder, train_loader=train_loader, val_loader=val_loader, num_classes=num_classes,
+                             num_epochs=num_epochs, use_bfloat16=use_bfloat16, folder=folder, tag=tag, rank=rank,
+                             world_size=world_size, batch_size=batch_size, resume_checkpoint=resume_checkpoint,
+                             distributed=_distributed(), device=device)
 
     # -- optimizer and scheduler
     optimizer, scaler, scheduler, wd_scheduler = init_opt(classifier=classifier, wd=wd, start_lr=start_lr, ref_lr=lr,
@@ -197,6 +211,14 @@ def main(args_eval, resume_preempt=False):
         record['train_acc'].append(train_acc)
         record['val_acc'].append(val_acc)
     return record
+
+
+def _view_features(attend_across_segments, encoder, data, device):
+    """One batch for the probe bank: the frozen features of every view as a flat list of [B, N, D] tensors, and the labels."""
+    clips = [[dij.to(device, non_blocking=True) for dij in di] for di in data[0]]
+    clip_indices = [d.to(device, non_blocking=True) for d in data[2]]
+    outputs = encoder(clips, clip_indices)
+    return (outputs if attend_across_segments else [ost for os_ in outputs for ost in os_]), data[1].to(device)
 
 
 def run_one_epoch(device, training, encoder, classifier, scaler, optimizer, scheduler, wd_scheduler, data_loader, use_bfloat16,

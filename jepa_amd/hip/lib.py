@@ -134,6 +134,10 @@ SIGNATURES = {
     "vj_comm_destroy": (I32, [P]),
     "vj_set_option": (I32, [ctypes.c_char_p, I32]),
     "vj_get_option": (I32, [ctypes.c_char_p, ctypes.POINTER(I32)]),
+    "vj_pool_softmax_chunk_keys": (I64, []),
+    "vj_pool_softmax_fwd_ws_bytes": (I64, [I64, I64, I64]),
+    "vj_pool_softmax_fwd": (I32, [P, P, P, I64, I64, I64, P, I64, P]),
+    "vj_pool_softmax_bwd": (I32, [P, P, P, P, I64, I64, I64, P]),
     "vj_probe_tr16": (I32, [P, I32, P]),
     "vj_probe_copy": (I32, [P, P, I64, P]),
     "vj_probe_lds_bw": (I32, [P, I32, I32, I32, P]),

@@ -615,6 +615,35 @@ def xattn_bwd(q, kv, dy, lse, B, N, H, hd, scale, shared_q=True, stream=None):
     return dq, dkv
 
 
+def pool_softmax_fwd(S, stream=None):
+    """Soft-max down the key axis of S fp32 [B, N, C] (vj_pool_softmax_fwd) -> A bf16 [B, N, C], lse fp32 [B, C]."""
+    lib = load_library()
+    _req(S, F32, "S")
+    if S.dim() != 3:
+        raise ValueError(f"pool_softmax_fwd: expected [B, N, C], got {tuple(S.shape)}")
+    B, N, C = S.shape
+    nws = lib.vj_pool_softmax_fwd_ws_bytes(B, N, C)
+    if nws < 0:
+        check(-1, "vj_pool_softmax_fwd_ws_bytes")
+    A = torch.empty((B, N, C), dtype=BF16, device=S.device)
+    lse = torch.empty((B, C), dtype=F32, device=S.device)
+    ws = Scratch.get(nws, S.device, "pool_softmax", stream=stream)
+    check(lib.vj_pool_softmax_fwd(_ptr(S), _ptr(A), _ptr(lse), B, N, C, _ptr(ws), nws, _stream(stream)), "vj_pool_softmax_fwd")
+    return A, lse
+
+
+def pool_softmax_bwd(A, dA, delta, stream=None):
+    """dS bf16 [B, N, C] = A * (dA - delta[b, c]) (vj_pool_softmax_bwd); A bf16, dA fp32 [B, N, C], delta fp32 [B, C]."""
+    lib = load_library()
+    _req(A, BF16, "A"); _req(dA, F32, "dA"); _req(delta, F32, "delta")
+    if A.dim() != 3 or dA.shape != A.shape or tuple(delta.shape) != (A.shape[0], A.shape[2]):
+        raise ValueError(f"pool_softmax_bwd: A {tuple(A.shape)} / dA {tuple(dA.shape)} / delta {tuple(delta.shape)} do not match")
+    B, N, C = A.shape
+    dS = torch.empty_like(A)
+    check(lib.vj_pool_softmax_bwd(_ptr(A), _ptr(dA), _ptr(delta), _ptr(dS), B, N, C, _stream(stream)), "vj_pool_softmax_bwd")
+    return dS
+
+
 def pred_assemble(e, mask_token, pos, idx_e, idx_p, out=None, stream=None):
     lib = load_library()
     _req(e, BF16, "e")

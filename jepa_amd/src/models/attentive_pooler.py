@@ -211,6 +211,196 @@ class AttentivePooler(nn.Module):
                                blk.mlp.fc1.weight, blk.mlp.fc1.bias, blk.mlp.fc2.weight, blk.mlp.fc2.bias)
 
 
+def _spread_heads(v, H):
+    """v [R, H*hd] -> [R*H, H*hd]: row (r, h) keeps head h's slice of v[r] and zeros elsewhere, so that one GEMM against a [D, D]
+    weight applies each head's own block of it."""
+    R, D = v.shape
+    out = torch.zeros((R, H, H, D // H), dtype=v.dtype, device=v.device)
+    i = torch.arange(H, device=v.device)
+    out[:, i, i] = v.view(R, H, D // H)
+    return out.view(R * H, D)
+
+
+def _pick_heads(m, H):
+    """m [R*H, H*hd] -> [R, H*hd]: head h's slice of row (r, h) -- the block diagonal of what _spread_heads spreads."""
+    R, D = m.shape[0] // H, m.shape[1]
+    return m.view(R, H, H, D // H).diagonal(dim1=1, dim2=2).permute(0, 2, 1).reshape(R, D)
+
+
+class _BankFn(torch.autograd.Function):
+    """P attentive classifiers on ONE pass over the frozen features.  Each probe has one query token shared by the batch, so with
+    x_hat = LayerNorm(x) without affine, q = Wq q0 + bq, t_h = Wk_h^T q_h and u_h = scale * gamma * t_h:
+        scores  S[b,n,(p,h)] = x_hat[b,n] . u_h       (norm1.bias and the key bias shift every key alike: the soft-max drops them)
+        A = softmax over n,   Z[b,(p,h)] = sum_n A x_hat[b,n],   y[b,h] = Wv_h (gamma * Z + beta) + bv_h
+    which is CrossAttention.forward (modules.py:140-157) on norm1(x) without K or V: two GEMM-shaped passes over x_hat forward
+    (scores, pooling) and two backward (dA, dU), all probes' heads as columns.  The tail (q0 + y, norm2, MLP, linear) runs per probe
+    on the lone probe's kernels.  The key half of kv.bias cannot influence the output: its gradient is exactly zero."""
+
+    PER = 15   # tensors per probe: _PoolerFn.NAMES + linear.weight, linear.bias
+
+    @staticmethod
+    def forward(ctx, x, heads, eps, P, *params):
+        B, N, D = x.shape
+        H, hd = heads, D // heads
+        s = hd ** -0.5
+        dev = x.device
+        C = ops.pad64(P * H)                                        # zero rows of U: uniform columns nothing reads
+        x2 = x.detach().reshape(B * N, D).to(torch.bfloat16).contiguous()
+        xh, _, _ = ops.layernorm_fwd(x2, torch.ones(D, dtype=torch.float32, device=dev),
+                                     torch.zeros(D, dtype=torch.float32, device=dev), eps, save_stats=False)
+        del x2
+        U = torch.zeros((C, D), dtype=torch.bfloat16, device=dev)
+        pre = []
+        for p in range(P):
+            qt, n1w, n1b, qw, qb, kvw, kvb = params[p * _BankFn.PER:p * _BankFn.PER + 7]
+            q0 = _bf(qt).reshape(1, D)
+            wq, wkv = _bf(qw), _bf(kvw)
+            qh = ops.gemm_nt(q0, wq, bias=_f32(qb))                                             # [1, D]
+            qblk = _spread_heads(qh, H)                                                         # [H, D]
+            t = ops.gemm_nt(qblk, _wT(wkv[:D]), epilogue=ops.EPI_F32)                           # t_h = Wk_h^T q_h, fp32 [H, D]
+            U[p * H:(p + 1) * H] = (s * n1w.detach().float() * t).to(torch.bfloat16)
+            pre.append((q0, wq, wkv, qblk, t))
+        S = ops.gemm_nt(xh, U, epilogue=ops.EPI_F32).view(B, N, C)
+        A, _ = ops.pool_softmax_fwd(S)
+        del S
+        Z = torch.empty((B, C, D), dtype=torch.float32, device=dev)
+        for b in range(B):
+            ops.gemm_wgrad_tn(A[b], xh[b * N:(b + 1) * N], Z[b])                                # Z[b] = A[b]^T x_hat[b]
+        logits, saved = [], []
+        for p in range(P):
+            qt, n1w, n1b, qw, qb, kvw, kvb, n2w, n2b, f1w, f1b, f2w, f2b, lw, lb = params[p * _BankFn.PER:(p + 1) * _BankFn.PER]
+            q0, wq, wkv, qblk, t = pre[p]
+            R = (n1w.detach().float() * Z[:, p * H:(p + 1) * H] + n1b.detach().float()).to(torch.bfloat16).reshape(B * H, D)
+            y = _pick_heads(ops.gemm_nt(R, wkv[D:], epilogue=ops.EPI_F32), H)                   # y[b,h] = Wv_h R[b,h]
+            if kvb is not None:
+                y = y + kvb.detach().float()[D:]
+            q1 = (y + q0.float()).to(torch.bfloat16)                                            # q0 + xattn(q0, norm1(x))
+            w1, w2 = _bf(f1w), _bf(f2w)
+            q1n, mean2, rstd2 = ops.layernorm_fwd(q1, _f32(n2w), _f32(n2b), eps)
+            dgelu = torch.empty((B, w1.shape[0]), dtype=torch.bfloat16, device=dev)
+            g = ops.gemm_nt(q1n, w1, bias=_f32(f1b), aux_out=dgelu, epilogue=ops.EPI_GELU)
+            q2 = ops.gemm_nt(g, w2, bias=_f32(f2b), residual=q1)
+            ncls = lw.shape[0]
+            lwp = torch.zeros((ops.pad64(ncls), D), dtype=torch.bfloat16, device=dev)           # the head, padded as in _LinearFn
+            lwp[:ncls] = lw.detach().to(torch.bfloat16)
+            lbp = torch.zeros(lwp.shape[0], dtype=torch.float32, device=dev)
+            lbp[:ncls] = lb.detach().float()
+            logits.append(ops.gemm_nt(q2, lwp, bias=lbp)[:, :ncls].float())
+            saved.append((q0, wq, wkv, qblk, t, R, q1, q1n, mean2, rstd2, dgelu, g, w1, w2, q2, lwp))
+        ctx.saved = (xh, A, Z, saved)
+        ctx.meta = (B, N, D, H, hd, eps, P, C)
+        ctx.params = params
+        return torch.stack(logits)
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        xh, A, Z, saved = ctx.saved
+        B, N, D, H, hd, eps, P, C = ctx.meta
+        params = ctx.params
+        s = hd ** -0.5
+        dev = xh.device
+        grads = [None] * (P * _BankFn.PER)
+        zf = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)   # noqa: E731
+        with torch.no_grad():
+            dZ = zf(B, C, D)
+            for p in range(P):
+                qt, n1w, n1b, qw, qb, kvw, kvb, n2w, n2b, f1w, f1b, f2w, f2b, lw, lb = params[p * _BankFn.PER:(p + 1) * _BankFn.PER]
+                q0, wq, wkv, qblk, t, R, q1, q1n, mean2, rstd2, dgelu, g, w1, w2, q2, lwp = saved[p]
+                ncls, Cp = lw.shape[0], lwp.shape[0]
+                # linear
+                dl = torch.zeros((B, Cp), dtype=torch.bfloat16, device=dev)
+                dl[:, :ncls] = dlogits[p].to(torch.bfloat16)
+                g_lw = ops.gemm_wgrad_tn(dl, q2, zf(Cp, D))[:ncls].contiguous()
+                g_lb = ops.colsum(dl, zf(Cp))[:ncls].contiguous()
+                dq2 = ops.gemm_nt(dl, _wT(lwp))
+                # mlp.fc2 (+ residual), mlp.fc1 (fused GELU backward), norm2 -- the lone probe's sequence
+                g_f2w = ops.gemm_wgrad_tn(dq2, g, _zeros_like_param(f2w))
+                g_f2b = ops.colsum(dq2, _zeros_like_param(f2b))
+                du = ops.gemm_nt(dq2, _wT(w2), aux_in=dgelu, epilogue=ops.EPI_DGELU)
+                g_f1w = ops.gemm_wgrad_tn(du, q1n, _zeros_like_param(f1w))
+                g_f1b = ops.colsum(du, _zeros_like_param(f1b))
+                dq1n = ops.gemm_nt(du, _wT(w1))
+                g_n2w, g_n2b = _zeros_like_param(n2w), _zeros_like_param(n2b)
+                dq1 = ops.layernorm_bwd(dq1n, q1, _f32(n2w), mean2, rstd2, g_n2w, g_n2b, dres=dq2)
+                g_qt = ops.colsum(dq1, zf(D))
+                # value path: y[b,h] = Wv_h R[b,h] + bv_h, R = gamma * Z + beta
+                g_kvw = _zeros_like_param(kvw)
+                g_kvb = None if kvb is None else _zeros_like_param(kvb)                          # the key half stays exactly zero
+                if kvb is not None:
+                    ops.colsum(dq1, g_kvb[D:])
+                dyblk = _spread_heads(dq1, H)                                                    # [B*H, D]
+                ops.gemm_wgrad_tn(dyblk, R, g_kvw[D:])                                           # dWv_h = sum_b dy_h R_h^T
+                G = ops.gemm_nt(dyblk, _wT(wkv[D:]), epilogue=ops.EPI_F32).view(B, H, D)         # G = Wv_h^T dy_h
+                g_n1b = G.sum(dim=(0, 1))
+                g_n1w = (G * Z[:, p * H:(p + 1) * H]).sum(dim=(0, 1))
+                dZ[:, p * H:(p + 1) * H] = n1w.detach().float() * G
+                grads[p * _BankFn.PER:(p + 1) * _BankFn.PER] = [g_qt, g_n1w, g_n1b, None, None, g_kvw, g_kvb, g_n2w, g_n2b, g_f1w,
+                                                                g_f1b, g_f2w, g_f2b, g_lw, g_lb]
+            # score path, every probe's heads at once: dA = x_hat . dZ, dS = A (dA - delta), dU = dS^T x_hat
+            dZb = dZ.to(torch.bfloat16)
+            dA = torch.empty((B, N, C), dtype=torch.float32, device=dev)
+            for b in range(B):
+                ops.gemm_nt(xh[b * N:(b + 1) * N], dZb[b], out=dA[b], epilogue=ops.EPI_F32)
+            delta = (dZ * Z).sum(dim=-1)
+            dS = ops.pool_softmax_bwd(A, dA, delta)
+            del dA
+            dU = ops.gemm_wgrad_tn(dS.view(B * N, C), xh, zf(C, D))
+            for p in range(P):
+                qt, n1w, n1b, qw, qb, kvw, kvb = params[p * _BankFn.PER:p * _BankFn.PER + 7]
+                q0, wq, wkv, qblk, t = saved[p][:5]
+                o = p * _BankFn.PER
+                dUp = dU[p * H:(p + 1) * H]
+                grads[o + 1] += (dUp * t).sum(dim=0) * s                                         # u_h = scale * gamma * t_h
+                e = (s * n1w.detach().float() * dUp).to(torch.bfloat16)                          # d t_h, [H, D]
+                ops.gemm_wgrad_tn(qblk, e, grads[o + 5][:D])                                     # dWk_h = q_h e_h^T
+                dq = _pick_heads(ops.gemm_nt(e, wkv[:D], epilogue=ops.EPI_F32), H)               # dq_h = Wk_h e_h, [1, D]
+                if qb is not None:
+                    grads[o + 4] = dq.reshape(D).clone()
+                dqh1 = dq.to(torch.bfloat16)
+                grads[o + 3] = ops.gemm_wgrad_tn(dqh1, q0, _zeros_like_param(qw))                # outer product dq q0^T
+                ops.colsum(ops.gemm_nt(dqh1, _wT(wq)), grads[o], accumulate=True)                # ... and through q = Linear(q0)
+                grads[o] = grads[o].view_as(qt)
+        return (None, None, None, None, *grads)
+
+
+class AttentiveClassifierBank(nn.Module):
+    """A bank of `num_probes` AttentiveClassifier heads trained at once on one frozen forward pass: the grid of probe learning
+    rates / weight decays of a frozen evaluation costs one encoder pass per iteration instead of one per grid point.  The
+    parameters live in `.probes` (an nn.ModuleList of the lone classifier, the reference's names under `probes.{p}.`), built in
+    index order from the global generator: probe 0 equals a lone AttentiveClassifier built under the same seed.
+
+    forward(x [B, N, D]) -> logits fp32 [P, B, num_classes] through ONE autograd node over all probes' parameters (_BankFn); the
+    probes share no parameter, so the backward of the summed per-probe losses gives each probe its own gradient.  The key half
+    of every `xattn.kv.bias` receives an exactly-zero gradient (it cannot influence the output) and stays where it was initialised."""
+
+    def __init__(self, embed_dim=768, num_heads=12, num_classes=1000, num_probes=1, mlp_ratio=4.0, init_std=0.02, qkv_bias=True):
+        super().__init__()
+        if num_probes < 1:
+            raise ValueError("AttentiveClassifierBank: num_probes must be at least 1")
+        self.num_heads = num_heads
+        self.probes = nn.ModuleList([
+            AttentiveClassifier(embed_dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, depth=1, init_std=init_std,
+                                qkv_bias=qkv_bias, num_classes=num_classes) for _ in range(num_probes)])
+
+    def probe_state_dict(self, p):
+        """The reference-format state dict of probe p: loads strictly into a lone AttentiveClassifier (here or the reference's)."""
+        return self.probes[p].state_dict()
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise ValueError("AttentiveClassifierBank: jepa_amd computes only on the GPU through libvjepa_hip.so (no CPU fallback)")
+        if x.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("AttentiveClassifierBank: the features come from a FROZEN encoder (eval.py:330-337 runs it "
+                                      "under torch.no_grad()); no gradient is propagated into them")
+        flat = []
+        for m in self.probes:
+            blk = m.pooler.cross_attention_block
+            flat += [m.pooler.query_tokens, blk.norm1.weight, blk.norm1.bias, blk.xattn.q.weight, blk.xattn.q.bias, blk.xattn.kv.weight,
+                     blk.xattn.kv.bias, blk.norm2.weight, blk.norm2.bias, blk.mlp.fc1.weight, blk.mlp.fc1.bias, blk.mlp.fc2.weight,
+                     blk.mlp.fc2.bias, m.linear.weight, m.linear.bias]
+        return _BankFn.apply(x, self.num_heads, self.probes[0].pooler.cross_attention_block.norm1.eps, len(self.probes), *flat)
+
+
 class AttentiveClassifier(nn.Module):
     """ Attentive Classifier (attentive_pooler.py:105-136) """
 

@@ -4,6 +4,8 @@ shipped eval config with random weights, B = 4 as in the configs.  Reports the f
 training step -- forward, backward, clip_grad_norm_, AdamW -- and for the validation forward over every view), the whole
 run_one_epoch iteration and the peak memory.  One JSON line per config.
 python tools/eval_bench.py [--configs vitl16_k400_16x8x3 vith16_384_k400_16x8x3] [--reps 3]
+--bank P adds the same training iteration with `optimization.multihead_kwargs` of P entries (one AttentiveClassifierBank, P
+optimizers; jepa_amd/evals/multihead.py): bank_train_iteration_ms beside train_iteration_ms of the single probe.
 
 --image: the frozen image-classification eval (jepa_amd/evals/image_classification_frozen) in the in1k setup (batch 16, 1000 classes)
 for ViT-L/16-224 and ViT-H/16-384: frozen images/s, probe ms, one training and one validation iteration, peak memory; the still-image
@@ -49,7 +51,7 @@ def timed(fn, reps):
     return s.elapsed_time(e) / reps
 
 
-def bench(name, reps, B=4):
+def bench(name, reps, B=4, bank=0):
     model_name, res, S, V, C = CONFIGS[name]
     dev = "cuda"
     torch.manual_seed(0)
@@ -94,12 +96,30 @@ def bench(name, reps, B=4):
     del ftrain, fval
     it_train = timed(lambda: run_one_epoch(dev, True, enc, clf, scaler, opt, sched, wd_sched, [train], False, 1, S, True), reps)
     it_val = timed(lambda: run_one_epoch(dev, False, enc, clf, scaler, opt, sched, wd_sched, [val], False, V, S, True), reps)
-    return dict(config=name, batch=B, probe_keys=S * enc.model.num_patches, clips_train=S * B, clips_val=S * V * B,
+    peak = torch.cuda.max_memory_allocated() - base
+    extra = {}
+    if bank:
+        from functools import partial
+        from jepa_amd.evals import multihead as M
+        from jepa_amd.evals.video_classification_frozen.eval import _view_features
+        from jepa_amd.src.models.attentive_pooler import AttentiveClassifierBank
+        del clf, opt
+        probes = AttentiveClassifierBank(enc.embed_dim, enc.num_heads, C, bank).to(dev)
+        opts, scalers, scheds, wd_scheds = (list(t) for t in zip(*[
+            init_opt(m, iterations_per_epoch=1, start_lr=1e-4, ref_lr=1e-4 * (1 + p), warmup=0, num_epochs=10 ** 6, wd=0.01)
+            for p, m in enumerate(probes.probes)]))
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        it_bank = timed(lambda: M.run_one_epoch(dev, True, partial(_view_features, True), enc, probes, scalers, opts, scheds,
+                                                wd_scheds, [train], False), reps)
+        extra = dict(bank_probes=bank, bank_train_iteration_ms=round(it_bank, 2),
+                     bank_peak_mem_gib=round((torch.cuda.max_memory_allocated() - base) / 2 ** 30, 2))
+    return dict(config=name, batch=B, probe_keys=S * enc.model.num_patches, clips_train=S * B, clips_val=S * V * B, **extra,
                 frozen_fwd_clips_per_s_train=round(S * B / t_enc_train * 1e3, 1),
                 frozen_fwd_clips_per_s_val=round(S * V * B / t_enc_val * 1e3, 1),
                 probe_train_step_ms=round(t_probe_train, 3), probe_val_ms=round(t_probe_val, 3),
                 train_iteration_ms=round(it_train, 2), val_iteration_ms=round(it_val, 2),
-                peak_mem_gib=round((torch.cuda.max_memory_allocated() - base) / 2 ** 30, 2),
+                peak_mem_gib=round(peak / 2 ** 30, 2),
                 max_clips_per_call=enc.max_clips_per_call)
 
 
@@ -299,6 +319,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--configs", nargs="*", default=["vitl16_k400_16x8x3", "vith16_384_k400_16x8x3"], choices=sorted(CONFIGS))
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--bank", type=int, default=0, help="also time the training iteration with a bank of this many probes")
     a = ap.parse_args()
     if a.frames:
         print(json.dumps(bench_frames(a.reps, a.rounds)), flush=True)
@@ -310,7 +331,7 @@ def main():
         print(json.dumps(bench_interp()), flush=True)
         return
     for name in a.configs:
-        print(json.dumps(bench(name, a.reps)), flush=True)
+        print(json.dumps(bench(name, a.reps, bank=a.bank)), flush=True)
         torch.cuda.empty_cache()
 
 

@@ -4,7 +4,12 @@ optimizer) and of the cross-attention kernels alone, at the reference's eval sha
 --tokens N [N ...] times ViT-L (head_dim 64) and ViT-H (head_dim 80) widths at those key counts instead, e.g. the probes of the K400
 16x8x3 evals (8 segments attended across: 12 544 keys at 224, 36 864 at 384) or both sides of the single-workgroup limits
 (forward 38 264, backward 19 132 keys), where the _ws entry points switch to the split-key kernels.
-python tools/probe_bench.py [--batch 16] [--reps 20] [--tokens 12544 36864]"""
+python tools/probe_bench.py [--batch 16] [--reps 20] [--tokens 12544 36864]
+--bank P [P ...] compares instead, at each of those shapes, one step of an AttentiveClassifierBank of P probes (arm A) with P
+sequential lone-probe steps on the same features (arm B); the arms take turns for --rounds rounds in this one process.  Also
+printed: the bank step at 64 keys (the per-probe algebra and the norm2 / MLP / linear tail, which do not depend on N) and the peak
+memory of each arm.
+python tools/probe_bench.py --batch 4 --tokens 12544 --bank 1 5 20"""
 import argparse
 import os
 import sys
@@ -14,7 +19,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from jepa_amd.hip import ops  # noqa: E402
 from jepa_amd.hip.lib import load_library  # noqa: E402
-from jepa_amd.src.models.attentive_pooler import AttentiveClassifier  # noqa: E402
+from jepa_amd.src.models.attentive_pooler import AttentiveClassifier, AttentiveClassifierBank  # noqa: E402
 
 
 def timeit(fn, reps):
@@ -29,16 +34,61 @@ def timeit(fn, reps):
     return s.elapsed_time(e) / reps * 1e3
 
 
+def bank_bench(a, shapes):
+    dev = "cuda"
+    for tag, N, D, H in shapes:
+        B = a.batch
+        x = torch.randn(B, N, D, device=dev).to(torch.bfloat16)
+        x_small = x[:, :64].contiguous()
+        y = torch.randint(0, 400, (B,), device=dev)
+        for P in a.bank:
+            torch.manual_seed(0)
+            bank = AttentiveClassifierBank(D, H, 400, P).to(dev)
+
+            def bank_step(feat=x):
+                for p in bank.parameters():
+                    p.grad = None
+                logits = bank(feat)
+                sum(torch.nn.functional.cross_entropy(logits[p], y) for p in range(P)).backward()
+
+            def lone_steps():
+                for m in bank.probes:
+                    for p in m.parameters():
+                        p.grad = None
+                    torch.nn.functional.cross_entropy(m(x), y).backward()
+
+            peak = {}
+            for name, fn in (("bank", bank_step), ("lone", lone_steps)):
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                fn()
+                torch.cuda.synchronize()
+                peak[name] = torch.cuda.max_memory_allocated() / 2 ** 20
+            wins = 0
+            for r in range(a.rounds):
+                ua, ub = timeit(bank_step, a.reps), timeit(lone_steps, a.reps)
+                wins += ua < ub
+                print(f"{tag} B={B} P={P} round {r}: bank {ua / 1e3:8.3f} ms | {P} lone steps {ub / 1e3:8.3f} ms | x{ub / ua:5.2f}")
+            tail = timeit(lambda: bank_step(x_small), a.reps)
+            print(f"{tag} B={B} P={P}: bank faster in {wins}/{a.rounds} rounds; step at 64 keys (per-probe algebra + tail) "
+                  f"{tail / 1e3:.3f} ms; peak memory bank {peak['bank']:.0f} MiB, lone {peak['lone']:.0f} MiB")
+            del bank
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--tokens", type=int, nargs="*", default=None, help="probe key counts N (default: one clip of ViT-L 224 / ViT-H 384)")
+    ap.add_argument("--bank", type=int, nargs="*", default=None, help="probe counts P: bank of P against P lone steps")
+    ap.add_argument("--rounds", type=int, default=5)
     a = ap.parse_args()
     dev = "cuda"
     lib = load_library()
     shapes = (("ViT-L 16x224", 1568, 1024, 16), ("ViT-H 16x384", 4608, 1280, 16)) if not a.tokens else \
         [(f"{w} N={N}", N, D, 16) for N in a.tokens for w, D in (("ViT-L", 1024), ("ViT-H", 1280))]
+    if a.bank:
+        return bank_bench(a, shapes)
     for tag, N, D, H in shapes:
         B, hd = a.batch, D // H
         torch.manual_seed(0)
