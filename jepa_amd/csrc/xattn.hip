@@ -26,6 +26,41 @@
 
 namespace {
 
+// dynamic LDS layout of the single-workgroup kernels: [qv: 128][red: 8][part: (256 / nch) * hd <= 256 * 8 = 2048][sc: N][ds: N (backward only)]
+// (the split-key kernels keep the same arrays, XA_CHUNK scores long, in static LDS)
+#define XA_LDS_FIXED (128 + 8 + 2048)
+// ... and they keep every score of a (b, h, query) there: 1 (forward) or 2 (backward) fp32 arrays of N
+#define XA_LDS_MAX (160 * 1024 - 2048)
+
+// what a workgroup works on: blockIdx.x = (b, h, query) -- (b, h) where NQ = 1 -- and the keys from j0 on
+struct XaSlice {
+  int b, h, iq;
+  int64_t D, rs, koff, col;           // rs: stride of the packed [K | V] rows; koff: key j0 of this (b, h) in kv and dkv; col: this
+                                      // head in a [B, D] tensor (dy, dq)
+  const bf16_t *kbase, *vbase, *qp;
+};
+__device__ __forceinline__ XaSlice xa_slice(const bf16_t* q, int64_t q_bstride, const bf16_t* kv, int NQ, int N, int H, int hd,
+                                            int j0 = 0) {
+  XaSlice s;
+  s.iq = blockIdx.x % NQ;
+  const int bh = blockIdx.x / NQ;
+  s.h = bh % H;
+  s.b = bh / H;
+  s.D = (int64_t)H * hd;
+  s.rs = 2 * s.D;
+  s.koff = ((int64_t)s.b * N + j0) * s.rs + (int64_t)s.h * hd;
+  s.col = (int64_t)s.b * s.D + (int64_t)s.h * hd;
+  s.kbase = kv + s.koff;
+  s.vbase = s.kbase + s.D;
+  s.qp = q + (int64_t)s.b * q_bstride + (int64_t)s.iq * s.D + (int64_t)s.h * hd;
+  return s;
+}
+
+// this head's hd elements of a bf16 row into LDS as fp32, times `mul`.  No barrier here.
+__device__ __forceinline__ void xa_stage(const bf16_t* p, int hd, float* dst, float mul = 1.f) {
+  if ((int)threadIdx.x < hd) dst[threadIdx.x] = bf2f(p[threadIdx.x]) * mul;
+}
+
 __device__ __forceinline__ float xa_block_reduce(float v, float* red, bool is_max) {
   // wave reduction, then the four waves through LDS in a fixed order
   v = is_max ? wave_max(v) : wave_sum(v);
@@ -39,6 +74,13 @@ __device__ __forceinline__ float xa_block_reduce(float v, float* red, bool is_ma
   return r;
 }
 
+// a + the dot product of one 16-byte chunk of a bf16 row with the eight fp32 at v, in element order
+__device__ __forceinline__ float xa_dot8(float a, const u32x4_t& w, const float* v) {
+#pragma unroll
+  for (int i = 0; i < 4; i++) a += bf_lo(w[i]) * v[2 * i] + bf_hi(w[i]) * v[2 * i + 1];
+  return a;
+}
+
 // s_j for every key of this (b, h) into LDS; qv = this head's query row (fp32, LDS), pre-multiplied by scale * log2e
 __device__ __forceinline__ void xa_scores(const bf16_t* __restrict__ kbase, int64_t rs, int N, int hd, const float* qv,
                                           float* sc) {
@@ -46,11 +88,7 @@ __device__ __forceinline__ void xa_scores(const bf16_t* __restrict__ kbase, int6
   for (int j = threadIdx.x; j < N; j += XA_THREADS) {
     const bf16_t* kp = kbase + (int64_t)j * rs;
     float a = 0.f;
-    for (int c = 0; c < nch; c++) {
-      const u32x4_t w = *(const u32x4_t*)(kp + c * 8);
-#pragma unroll
-      for (int i = 0; i < 4; i++) a += bf_lo(w[i]) * qv[c * 8 + 2 * i] + bf_hi(w[i]) * qv[c * 8 + 2 * i + 1];
-    }
+    for (int c = 0; c < nch; c++) a = xa_dot8(a, *(const u32x4_t*)(kp + c * 8), qv + c * 8);
     sc[j] = a;
   }
 }
@@ -84,9 +122,56 @@ __device__ __forceinline__ float xa_weighted_rows(const bf16_t* __restrict__ bas
     for (int g = 0; g < ngrp; g++) tot += part[g * hd + threadIdx.x];
   return tot;
 }
+// the soft-max of the n keys from kbase on: s_j into sc, the block max, p_j = 2^(s_j - max) left in sc, their block sum, and this
+// thread's column of sum_j p_j v_j (valid for threadIdx.x < hd)
+struct XaSoft {
+  float mx, sum, y;
+};
+__device__ __forceinline__ XaSoft xa_softmax_rows(const XaSlice& s, int n, int hd, const float* qv, float* red, float* part,
+                                                  float* sc) {
+  XaSoft r;
+  xa_scores(s.kbase, s.rs, n, hd, qv, sc);
+  r.mx = -INFINITY;
+  for (int j = threadIdx.x; j < n; j += XA_THREADS) r.mx = fmaxf(r.mx, sc[j]);   // own entries: no barrier needed yet
+  r.mx = xa_block_reduce(r.mx, red, true);
+  r.sum = 0.f;
+  for (int j = threadIdx.x; j < n; j += XA_THREADS) {
+    const float p = __builtin_amdgcn_exp2f(sc[j] - r.mx);
+    sc[j] = p;
+    r.sum += p;
+  }
+  r.sum = xa_block_reduce(r.sum, red, false);   // its barriers also publish every thread's p_j
+  r.y = xa_weighted_rows(s.vbase, s.rs, n, hd, sc, part);
+  return r;
+}
 
-// dynamic LDS layout: [qv: 128][red: 8][part: (256 / nch) * hd <= 256 * 8 = 2048][sc: N][ds: N (backward only)]
-#define XA_LDS_FIXED (128 + 8 + 2048)
+// dk_j = scale dS_j q ; dv_j = p_j dy for the n keys from dkb on (dkb: this head's columns of the first key's dK row; dV lies D
+// further): thread = (row group, 8-column chunk), 16-byte stores
+__device__ __forceinline__ void xa_store_dkdv(bf16_t* __restrict__ dkb, int64_t rs, int64_t D, int n, int hd, const float* qraw,
+                                              const float* dyv, float scale, const float* ds, const float* sc) {
+  const int nch = hd >> 3, ngrp = XA_THREADS / nch;
+  const int c = threadIdx.x % nch, rg = threadIdx.x / nch;
+  if (rg < ngrp) {
+    float q8[8], d8[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      q8[i] = qraw[c * 8 + i] * scale;
+      d8[i] = dyv[c * 8 + i];
+    }
+    dkb += c * 8;
+    for (int j = rg; j < n; j += ngrp) {
+      const float s = ds[j], p = sc[j];
+      u32x4_t wk, wv;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        wk[i] = pack_bf2(s * q8[2 * i], s * q8[2 * i + 1]);
+        wv[i] = pack_bf2(p * d8[2 * i], p * d8[2 * i + 1]);
+      }
+      *(u32x4_t*)(dkb + (int64_t)j * rs) = wk;
+      *(u32x4_t*)(dkb + (int64_t)j * rs + D) = wv;
+    }
+  }
+}
 
 __global__ __launch_bounds__(XA_THREADS) void xattn_fwd_kernel(const bf16_t* __restrict__ q, int64_t q_bstride,
                                                                const bf16_t* __restrict__ kv,
@@ -98,35 +183,19 @@ __global__ __launch_bounds__(XA_THREADS) void xattn_fwd_kernel(const bf16_t* __r
   float* red = xs + 128;
   float* part = xs + 136;
   float* sc = xs + XA_LDS_FIXED;
-  const int iq = blockIdx.x % NQ, bh = blockIdx.x / NQ;
-  const int h = bh % H, b = bh / H;
-  const int64_t D = (int64_t)H * hd, rs = 2 * D;
-  const bf16_t* kbase = kv + (int64_t)b * N * rs + (int64_t)h * hd;
-  const bf16_t* vbase = kbase + D;
-  const bf16_t* qp = q + (int64_t)b * q_bstride + (int64_t)iq * D + (int64_t)h * hd;
-  if ((int)threadIdx.x < hd) qv[threadIdx.x] = bf2f(qp[threadIdx.x]) * (scale * XA_LOG2E);
+  const XaSlice s = xa_slice(q, q_bstride, kv, NQ, N, H, hd);
+  xa_stage(s.qp, hd, qv, scale * XA_LOG2E);
   __syncthreads();
-  xa_scores(kbase, rs, N, hd, qv, sc);
-  float mx = -INFINITY;
-  for (int j = threadIdx.x; j < N; j += XA_THREADS) mx = fmaxf(mx, sc[j]);   // own entries: no barrier needed yet
-  mx = xa_block_reduce(mx, red, true);
-  float sum = 0.f;
-  for (int j = threadIdx.x; j < N; j += XA_THREADS) {
-    const float p = __builtin_amdgcn_exp2f(sc[j] - mx);
-    sc[j] = p;
-    sum += p;
-  }
-  sum = xa_block_reduce(sum, red, false);   // its barriers also publish every thread's p_j
-  const float y = xa_weighted_rows(vbase, rs, N, hd, sc, part);
+  const XaSoft m = xa_softmax_rows(s, N, hd, qv, red, part, sc);
   if ((int)threadIdx.x < hd) {
-    const int64_t o = ((int64_t)b * NQ + iq) * D + (int64_t)h * hd + threadIdx.x;
-    float v = y / sum;
+    const int64_t o = ((int64_t)s.b * NQ + s.iq) * s.D + (int64_t)s.h * hd + threadIdx.x;
+    float v = m.y / m.sum;
     // the block's residual (the un-projected query tokens, attentive_pooler.py:97-98 + modules.py:178-179) is
     // the same row for every sample
-    if (resid) v += bf2f(resid[(int64_t)iq * D + (int64_t)h * hd + threadIdx.x]);
+    if (resid) v += bf2f(resid[(int64_t)s.iq * s.D + (int64_t)s.h * hd + threadIdx.x]);
     out[o] = f2bf(v);
   }
-  if (threadIdx.x == 0 && lse2) lse2[((int64_t)b * H + h) * NQ + iq] = mx + log2f(sum);
+  if (threadIdx.x == 0 && lse2) lse2[((int64_t)s.b * H + s.h) * NQ + s.iq] = m.mx + log2f(m.sum);
 }
 
 __global__ __launch_bounds__(XA_THREADS) void xattn_bwd_kernel(const bf16_t* __restrict__ q, int64_t q_bstride,
@@ -142,21 +211,14 @@ __global__ __launch_bounds__(XA_THREADS) void xattn_bwd_kernel(const bf16_t* __r
   float* sc = xs + XA_LDS_FIXED;   // p_j
   float* ds = sc + N;              // dP_j, then dS_j
   __shared__ float dyv[128], qraw[128];
-  const int h = blockIdx.x % H, b = blockIdx.x / H;
-  const int64_t D = (int64_t)H * hd, rs = 2 * D;
-  const bf16_t* kbase = kv + (int64_t)b * N * rs + (int64_t)h * hd;
-  const bf16_t* vbase = kbase + D;
-  const bf16_t* qp = q + (int64_t)b * q_bstride + (int64_t)h * hd;
-  if ((int)threadIdx.x < hd) {
-    const float qf = bf2f(qp[threadIdx.x]);
-    qraw[threadIdx.x] = qf;
-    qv[threadIdx.x] = qf * (scale * XA_LOG2E);
-    dyv[threadIdx.x] = bf2f(dy[(int64_t)b * D + (int64_t)h * hd + threadIdx.x]);
-  }
+  const XaSlice s = xa_slice(q, q_bstride, kv, 1, N, H, hd);
+  xa_stage(s.qp, hd, qraw);
+  xa_stage(s.qp, hd, qv, scale * XA_LOG2E);
+  xa_stage(dy + s.col, hd, dyv);
   __syncthreads();
-  xa_scores(kbase, rs, N, hd, qv, sc);    // s_j
-  xa_scores(vbase, rs, N, hd, dyv, ds);   // dP_j = dy . v_j (same row-dot routine, dy as the vector)
-  const float l2 = lse2[(int64_t)b * H + h];
+  xa_scores(s.kbase, s.rs, N, hd, qv, sc);    // s_j
+  xa_scores(s.vbase, s.rs, N, hd, dyv, ds);   // dP_j = dy . v_j (same row-dot routine, dy as the vector)
+  const float l2 = lse2[(int64_t)s.b * H + s.h];
   float dl = 0.f;
   for (int j = threadIdx.x; j < N; j += XA_THREADS) {
     const float p = __builtin_amdgcn_exp2f(sc[j] - l2);
@@ -167,36 +229,14 @@ __global__ __launch_bounds__(XA_THREADS) void xattn_bwd_kernel(const bf16_t* __r
   for (int j = threadIdx.x; j < N; j += XA_THREADS) ds[j] = sc[j] * (ds[j] - dl);
   __syncthreads();
   // dq = scale * sum_j dS_j k_j   (per sample; the caller sums it over the batch when the projected query is shared)
-  const float dqv = xa_weighted_rows(kbase, rs, N, hd, ds, part);
-  if ((int)threadIdx.x < hd) dq[(int64_t)b * D + (int64_t)h * hd + threadIdx.x] = f2bf(dqv * scale);
-  // dk_j = scale dS_j q ; dv_j = p_j dy : thread = (row group, 8-column chunk), 16-byte stores
-  const int nch = hd >> 3, ngrp = XA_THREADS / nch;
-  const int c = threadIdx.x % nch, rg = threadIdx.x / nch;
-  if (rg < ngrp) {
-    float q8[8], d8[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      q8[i] = qraw[c * 8 + i] * scale;
-      d8[i] = dyv[c * 8 + i];
-    }
-    bf16_t* dkb = dkv + (int64_t)b * N * rs + (int64_t)h * hd + c * 8;
-    for (int j = rg; j < N; j += ngrp) {
-      const float s = ds[j], p = sc[j];
-      u32x4_t wk, wv;
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        wk[i] = pack_bf2(s * q8[2 * i], s * q8[2 * i + 1]);
-        wv[i] = pack_bf2(p * d8[2 * i], p * d8[2 * i + 1]);
-      }
-      *(u32x4_t*)(dkb + (int64_t)j * rs) = wk;
-      *(u32x4_t*)(dkb + (int64_t)j * rs + D) = wv;
-    }
-  }
+  const float dqv = xa_weighted_rows(s.kbase, s.rs, N, hd, ds, part);
+  if ((int)threadIdx.x < hd) dq[s.col + threadIdx.x] = f2bf(dqv * scale);
+  xa_store_dkdv(dkv + s.koff, s.rs, s.D, N, hd, qraw, dyv, scale, ds, sc);
 }
 
 // ---- split-key forms (vj_xattn_fwd_ws / vj_xattn_bwd_ws above the single-workgroup limits) ------------------------------
-// A chunk of XA_CHUNK consecutive keys per workgroup.  The chunk is a compile-time constant, so the chunk count -- and with it
-// every summation order -- depends on N alone, never on the device.  Partials go to the caller's workspace (fp32) and are
+// A chunk of XA_CHUNK consecutive keys per workgroup (blockIdx.y).  The chunk is a compile-time constant, so the chunk count -- and
+// with it every summation order -- depends on N alone, never on the device.  Partials go to the caller's workspace (fp32) and are
 // merged in ascending chunk order; no atomics.
 #define XA_CHUNK 2048
 
@@ -210,33 +250,16 @@ __global__ __launch_bounds__(XA_THREADS) void xattn_fwd_split_kernel(const bf16_
   float* red = xs + 128;
   float* part = xs + 136;
   float* sc = xs + XA_LDS_FIXED;
-  const int bhq = blockIdx.x, ch = blockIdx.y;
-  const int iq = bhq % NQ, bh = bhq / NQ;
-  const int h = bh % H, b = bh / H;
-  const int j0 = ch * XA_CHUNK, n = min(XA_CHUNK, N - j0);
-  const int64_t D = (int64_t)H * hd, rs = 2 * D;
-  const bf16_t* kbase = kv + ((int64_t)b * N + j0) * rs + (int64_t)h * hd;
-  const bf16_t* vbase = kbase + D;
-  const bf16_t* qp = q + (int64_t)b * q_bstride + (int64_t)iq * D + (int64_t)h * hd;
-  if ((int)threadIdx.x < hd) qv[threadIdx.x] = bf2f(qp[threadIdx.x]) * (scale * XA_LOG2E);
+  const int ch = blockIdx.y, j0 = ch * XA_CHUNK, n = min(XA_CHUNK, N - j0);
+  const XaSlice s = xa_slice(q, q_bstride, kv, NQ, N, H, hd, j0);
+  xa_stage(s.qp, hd, qv, scale * XA_LOG2E);
   __syncthreads();
-  xa_scores(kbase, rs, n, hd, qv, sc);
-  float mx = -INFINITY;
-  for (int j = threadIdx.x; j < n; j += XA_THREADS) mx = fmaxf(mx, sc[j]);
-  mx = xa_block_reduce(mx, red, true);
-  float sum = 0.f;
-  for (int j = threadIdx.x; j < n; j += XA_THREADS) {
-    const float p = __builtin_amdgcn_exp2f(sc[j] - mx);
-    sc[j] = p;
-    sum += p;
-  }
-  sum = xa_block_reduce(sum, red, false);
-  const float y = xa_weighted_rows(vbase, rs, n, hd, sc, part);
-  const int64_t slot = (int64_t)bhq * nch + ch;
-  if ((int)threadIdx.x < hd) ws_y[slot * hd + threadIdx.x] = y;
+  const XaSoft m = xa_softmax_rows(s, n, hd, qv, red, part, sc);
+  const int64_t slot = (int64_t)blockIdx.x * nch + ch;
+  if ((int)threadIdx.x < hd) ws_y[slot * hd + threadIdx.x] = m.y;
   if (threadIdx.x == 0) {
-    ws_ml[2 * slot] = mx;
-    ws_ml[2 * slot + 1] = sum;
+    ws_ml[2 * slot] = m.mx;
+    ws_ml[2 * slot + 1] = m.sum;
   }
 }
 
@@ -275,16 +298,10 @@ __global__ __launch_bounds__(XA_THREADS) void xattn_bwd_split_p_kernel(const bf1
                                                                        float* __restrict__ ws_dp, float* __restrict__ ws_delta,
                                                                        int N, int H, int hd, float scale, int nch) {
   __shared__ __attribute__((aligned(16))) float qv[128], dyv[128], red[8];
-  const int bh = blockIdx.x, ch = blockIdx.y;
-  const int h = bh % H, b = bh / H;
-  const int j0 = ch * XA_CHUNK, n = min(XA_CHUNK, N - j0);
-  const int64_t D = (int64_t)H * hd, rs = 2 * D;
-  const bf16_t* kbase = kv + ((int64_t)b * N + j0) * rs + (int64_t)h * hd;
-  const bf16_t* qp = q + (int64_t)b * q_bstride + (int64_t)h * hd;
-  if ((int)threadIdx.x < hd) {
-    qv[threadIdx.x] = bf2f(qp[threadIdx.x]) * (scale * XA_LOG2E);
-    dyv[threadIdx.x] = bf2f(dy[(int64_t)b * D + (int64_t)h * hd + threadIdx.x]);
-  }
+  const int bh = blockIdx.x, ch = blockIdx.y, j0 = ch * XA_CHUNK, n = min(XA_CHUNK, N - j0);
+  const XaSlice s = xa_slice(q, q_bstride, kv, 1, N, H, hd, j0);
+  xa_stage(s.qp, hd, qv, scale * XA_LOG2E);
+  xa_stage(dy + s.col, hd, dyv);
   __syncthreads();
   const float l2 = lse2[bh];
   float* pp = ws_p + (int64_t)bh * N + j0;
@@ -292,18 +309,13 @@ __global__ __launch_bounds__(XA_THREADS) void xattn_bwd_split_p_kernel(const bf1
   const int nc8 = hd >> 3;
   float dl = 0.f;
   for (int j = threadIdx.x; j < n; j += XA_THREADS) {
-    const bf16_t* kp = kbase + (int64_t)j * rs;
-    float s = 0.f, e = 0.f;
+    const bf16_t* kp = s.kbase + (int64_t)j * s.rs;   // K and V of a key lie in one row: both dots in one pass over it
+    float a = 0.f, e = 0.f;
     for (int c = 0; c < nc8; c++) {
-      const u32x4_t wk = *(const u32x4_t*)(kp + c * 8);
-      const u32x4_t wv = *(const u32x4_t*)(kp + D + c * 8);
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        s += bf_lo(wk[i]) * qv[c * 8 + 2 * i] + bf_hi(wk[i]) * qv[c * 8 + 2 * i + 1];
-        e += bf_lo(wv[i]) * dyv[c * 8 + 2 * i] + bf_hi(wv[i]) * dyv[c * 8 + 2 * i + 1];
-      }
+      a = xa_dot8(a, *(const u32x4_t*)(kp + c * 8), qv + c * 8);
+      e = xa_dot8(e, *(const u32x4_t*)(kp + s.D + c * 8), dyv + c * 8);
     }
-    const float p = __builtin_amdgcn_exp2f(s - l2);
+    const float p = __builtin_amdgcn_exp2f(a - l2);
     pp[j] = p;
     dpp[j] = e;
     dl += p * e;
@@ -324,16 +336,10 @@ __global__ __launch_bounds__(XA_THREADS) void xattn_bwd_split_d_kernel(const bf1
                                                                        float* __restrict__ ws_dq, bf16_t* __restrict__ dkv,
                                                                        int N, int H, int hd, float scale, int nch) {
   __shared__ __attribute__((aligned(16))) float part[2048], sc[XA_CHUNK], ds[XA_CHUNK], dyv[128], qraw[128];
-  const int bh = blockIdx.x, ch = blockIdx.y;
-  const int h = bh % H, b = bh / H;
-  const int j0 = ch * XA_CHUNK, n = min(XA_CHUNK, N - j0);
-  const int64_t D = (int64_t)H * hd, rs = 2 * D;
-  const bf16_t* kbase = kv + ((int64_t)b * N + j0) * rs + (int64_t)h * hd;
-  const bf16_t* qp = q + (int64_t)b * q_bstride + (int64_t)h * hd;
-  if ((int)threadIdx.x < hd) {
-    qraw[threadIdx.x] = bf2f(qp[threadIdx.x]);
-    dyv[threadIdx.x] = bf2f(dy[(int64_t)b * D + (int64_t)h * hd + threadIdx.x]);
-  }
+  const int bh = blockIdx.x, ch = blockIdx.y, j0 = ch * XA_CHUNK, n = min(XA_CHUNK, N - j0);
+  const XaSlice s = xa_slice(q, q_bstride, kv, 1, N, H, hd, j0);
+  xa_stage(s.qp, hd, qraw);
+  xa_stage(dy + s.col, hd, dyv);
   float delta = 0.f;
   for (int c = 0; c < nch; c++) delta += ws_delta[(int64_t)bh * nch + c];
   const float* pp = ws_p + (int64_t)bh * N + j0;
@@ -344,30 +350,9 @@ __global__ __launch_bounds__(XA_THREADS) void xattn_bwd_split_d_kernel(const bf1
     ds[j] = p * (dpp[j] - delta);
   }
   __syncthreads();
-  const float dqv = xa_weighted_rows(kbase, rs, n, hd, ds, part);
+  const float dqv = xa_weighted_rows(s.kbase, s.rs, n, hd, ds, part);
   if ((int)threadIdx.x < hd) ws_dq[((int64_t)bh * nch + ch) * hd + threadIdx.x] = dqv;
-  const int nc8 = hd >> 3, ngrp = XA_THREADS / nc8;
-  const int c = threadIdx.x % nc8, rg = threadIdx.x / nc8;
-  if (rg < ngrp) {
-    float q8[8], d8[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      q8[i] = qraw[c * 8 + i] * scale;
-      d8[i] = dyv[c * 8 + i];
-    }
-    bf16_t* dkb = dkv + ((int64_t)b * N + j0) * rs + (int64_t)h * hd + c * 8;
-    for (int j = rg; j < n; j += ngrp) {
-      const float s = ds[j], p = sc[j];
-      u32x4_t wk, wv;
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        wk[i] = pack_bf2(s * q8[2 * i], s * q8[2 * i + 1]);
-        wv[i] = pack_bf2(p * d8[2 * i], p * d8[2 * i + 1]);
-      }
-      *(u32x4_t*)(dkb + (int64_t)j * rs) = wk;
-      *(u32x4_t*)(dkb + (int64_t)j * rs + D) = wv;
-    }
-  }
+  xa_store_dkdv(dkv + s.koff, s.rs, s.D, n, hd, qraw, dyv, scale, ds, sc);
 }
 
 // dq = scale * sum_c dq_c (ascending chunk order), grid B*H
@@ -381,9 +366,12 @@ __global__ __launch_bounds__(128) void xattn_bwd_dq_kernel(const float* __restri
   dq[(int64_t)bh * hd + d] = f2bf(t * scale);   // dq [B, H*hd]: (b*H + h)*hd + d
 }
 
-// the single-workgroup kernels keep every score of a (b, h, query) in dynamic LDS: 1 (forward) or 2 (backward) fp32 arrays of N
-#define XA_LDS_MAX (160 * 1024 - 2048)
 inline int64_t xa_max_keys(int arrays) { return ((int64_t)XA_LDS_MAX / 4 - XA_LDS_FIXED) / arrays; }
+
+// the single-workgroup kernels may use XA_LDS_MAX bytes of dynamic LDS: said once per device and kernel
+inline void xa_allow_lds(VjPerDeviceOnce& once, const void* kernel) {
+  once([kernel] { (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS_MAX); });
+}
 
 // workspace of the split forms: every sub-array 256-byte aligned
 struct XaSplit {
@@ -413,13 +401,31 @@ XaSplit xa_split_layout(int64_t B, int64_t NQ, int64_t N, int64_t H, int64_t hd,
   return s;
 }
 
+// the dimension check of every entry point; vj_xattn_ws_bytes passes no name and gets the answer without a message
+int xa_check_dims(const char* who, int64_t B, int64_t NQ, int64_t N, int64_t H, int64_t hd) {
+  const bool dims = B >= 0 && NQ >= 1 && N >= 1 && H >= 1, head = hd % 8 == 0 && hd >= 8 && hd <= 128;
+  if (!who) return dims && head ? 0 : -1;
+  VJ_CHECK_ARG(dims, "%s: bad dims", who);
+  VJ_CHECK_ARG(head, "%s: head_dim=%ld unsupported (need %%8==0, <=128)", who, (long)hd);
+  return 0;
+}
+
 int xa_check(const char* who, int64_t B, int64_t NQ, int64_t N, int64_t H, int64_t hd, int64_t* lds_bytes, int arrays) {
-  VJ_CHECK_ARG(B >= 0 && NQ >= 1 && N >= 1 && H >= 1, "%s: bad dims", who);
-  VJ_CHECK_ARG(hd % 8 == 0 && hd >= 8 && hd <= 128, "%s: head_dim=%ld unsupported (need %%8==0, <=128)", who, (long)hd);
+  if (int rc = xa_check_dims(who, B, NQ, N, H, hd)) return rc;
   VJ_CHECK_ARG(B * H * NQ < (1ll << 31), "%s: grid too large", who);
   *lds_bytes = (XA_LDS_FIXED + arrays * N) * 4;
-  VJ_CHECK_ARG(*lds_bytes <= 160 * 1024 - 2048, "%s: N=%ld keys do not fit the LDS score buffer (max %ld)", who, (long)N,
-               (long)((160 * 1024 - 2048) / 4 - XA_LDS_FIXED) / arrays);
+  VJ_CHECK_ARG(*lds_bytes <= XA_LDS_MAX, "%s: N=%ld keys do not fit the LDS score buffer (max %ld)", who, (long)N,
+               (long)xa_max_keys(arrays));
+  return 0;
+}
+
+int xa_check_split(const char* who, int64_t B, int64_t NQ, int64_t N, int64_t H, int64_t hd, const XaSplit& s, void* ws,
+                   int64_t ws_bytes) {
+  if (int rc = xa_check_dims(who, B, NQ, N, H, hd)) return rc;
+  VJ_CHECK_ARG(N < (1ll << 31) && B * H * NQ * XA_THREADS <= 0xffffffffll && s.nch <= 65535, "%s: grid too large", who);
+  if (B == 0) return 0;   // nothing to launch: vj_xattn_ws_bytes is 0, so no workspace is required
+  VJ_CHECK_ARG(ws != nullptr && ws_bytes >= s.bytes, "%s: workspace of %ld bytes, need %ld (vj_xattn_ws_bytes)", who,
+               (long)ws_bytes, (long)s.bytes);
   return 0;
 }
 
@@ -431,7 +437,7 @@ extern "C" int vj_xattn_fwd(const void* q, int64_t q_bstride, const void* kv, co
   if (int rc = xa_check("vj_xattn_fwd", B, NQ, N, H, hd, &lds, 1)) return rc;
   if (B == 0) return 0;
   static VjPerDeviceOnce once;
-  once([] { (void)hipFuncSetAttribute((const void*)xattn_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048); });
+  xa_allow_lds(once, (const void*)xattn_fwd_kernel);
   hipLaunchKernelGGL(xattn_fwd_kernel, dim3((unsigned)(B * H * NQ)), dim3(XA_THREADS), (size_t)lds, stream, (const bf16_t*)q,
                      q_bstride, (const bf16_t*)kv, (const bf16_t*)resid, (bf16_t*)out, lse2, (int)B, (int)NQ, (int)N, (int)H,
                      (int)hd, scale);
@@ -447,7 +453,7 @@ extern "C" int vj_xattn_bwd(const void* q, int64_t q_bstride, const void* kv, co
   if (int rc = xa_check("vj_xattn_bwd", B, NQ, N, H, hd, &lds, 2)) return rc;
   if (B == 0) return 0;
   static VjPerDeviceOnce once;
-  once([] { (void)hipFuncSetAttribute((const void*)xattn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048); });
+  xa_allow_lds(once, (const void*)xattn_bwd_kernel);
   hipLaunchKernelGGL(xattn_bwd_kernel, dim3((unsigned)(B * H)), dim3(XA_THREADS), (size_t)lds, stream, (const bf16_t*)q, q_bstride,
                      (const bf16_t*)kv, (const bf16_t*)dy, lse2, (bf16_t*)dq, (bf16_t*)dkv, (int)B, (int)N, (int)H, (int)hd, scale);
   VJ_LAUNCH_CHECK("vj_xattn_bwd");
@@ -455,23 +461,10 @@ extern "C" int vj_xattn_bwd(const void* q, int64_t q_bstride, const void* kv, co
 }
 
 extern "C" int64_t vj_xattn_ws_bytes(int64_t B, int64_t NQ, int64_t N, int64_t H, int64_t hd, int backward) {
-  if (B < 0 || NQ < 1 || N < 1 || H < 1 || hd < 8 || hd > 128 || hd % 8 != 0) return -1;
+  if (xa_check_dims(nullptr, B, NQ, N, H, hd)) return -1;
   if (N <= xa_max_keys(backward ? 2 : 1)) return 0;   // the single-workgroup kernel runs: no workspace
   return xa_split_layout(B, NQ, N, H, hd, backward).bytes;
 }
-
-namespace {
-int xa_check_split(const char* who, int64_t B, int64_t NQ, int64_t N, int64_t H, int64_t hd, const XaSplit& s, void* ws,
-                   int64_t ws_bytes) {
-  VJ_CHECK_ARG(B >= 0 && NQ >= 1 && N >= 1 && H >= 1, "%s: bad dims", who);
-  VJ_CHECK_ARG(hd % 8 == 0 && hd >= 8 && hd <= 128, "%s: head_dim=%ld unsupported (need %%8==0, <=128)", who, (long)hd);
-  VJ_CHECK_ARG(N < (1ll << 31) && B * H * NQ * XA_THREADS <= 0xffffffffll && s.nch <= 65535, "%s: grid too large", who);
-  if (B == 0) return 0;   // nothing to launch: vj_xattn_ws_bytes is 0, so no workspace is required
-  VJ_CHECK_ARG(ws != nullptr && ws_bytes >= s.bytes, "%s: workspace of %ld bytes, need %ld (vj_xattn_ws_bytes)", who,
-               (long)ws_bytes, (long)s.bytes);
-  return 0;
-}
-}  // namespace
 
 extern "C" int vj_xattn_fwd_ws(const void* q, int64_t q_bstride, const void* kv, const void* resid, void* out, float* lse2,
                                int64_t B, int64_t NQ, int64_t N, int64_t H, int64_t hd, float scale, void* ws, int64_t ws_bytes,

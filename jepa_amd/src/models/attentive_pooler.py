@@ -14,6 +14,7 @@ Reference behaviours kept on purpose: CrossAttention owns a `proj` Linear that i
 `xattn.proj.*` exist in the state dict, receive no gradient and do not influence the output; nn.LayerNorm default eps 1e-5.
 """
 import math
+import operator
 
 import torch
 import torch.nn as nn
@@ -64,6 +65,67 @@ def _zeros_like_param(p):
     return torch.zeros(p.shape, dtype=torch.float32, device=p.device)
 
 
+# The lone probe's sequence around the cross-attention, shared by its two autograd nodes (_PoolerFn, _LinearFn) and the bank's one
+def _tail_fwd(q1, tail, eps):
+    """q1 bf16 [B, D] -> q2 = q1 + mlp(norm2(q1)) and what _tail_bwd needs; tail = (n2w, n2b, f1w, f1b, f2w, f2b)."""
+    n2w, n2b, f1w, f1b, f2w, f2b = tail
+    w1, w2 = _bf(f1w), _bf(f2w)
+    q1n, mean2, rstd2 = ops.layernorm_fwd(q1, _f32(n2w), _f32(n2b), eps)
+    dgelu = torch.empty((q1.shape[0], w1.shape[0]), dtype=torch.bfloat16, device=q1.device)
+    g = ops.gemm_nt(q1n, w1, bias=_f32(f1b), aux_out=dgelu, epilogue=ops.EPI_GELU)
+    q2 = ops.gemm_nt(g, w2, bias=_f32(f2b), residual=q1)
+    return q2, (q1, q1n, mean2, rstd2, dgelu, g, w1, w2)
+
+
+def _tail_bwd(dq2, saved, tail):
+    """mlp.fc2 (+ residual), mlp.fc1 (fused GELU backward), norm2: dq1 and the gradients of `tail` in its order."""
+    (q1, q1n, mean2, rstd2, dgelu, g, w1, w2), (n2w, n2b, f1w, f1b, f2w, f2b) = saved, tail
+    g_f2w = ops.gemm_wgrad_tn(dq2, g, _zeros_like_param(f2w))
+    g_f2b = ops.colsum(dq2, _zeros_like_param(f2b))
+    du = ops.gemm_nt(dq2, _wT(w2), aux_in=dgelu, epilogue=ops.EPI_DGELU)
+    g_f1w = ops.gemm_wgrad_tn(du, q1n, _zeros_like_param(f1w))
+    g_f1b = ops.colsum(du, _zeros_like_param(f1b))
+    dq1n = ops.gemm_nt(du, _wT(w1))
+    g_n2w, g_n2b = _zeros_like_param(n2w), _zeros_like_param(n2b)
+    dq1 = ops.layernorm_bwd(dq1n, q1, _f32(n2w), mean2, rstd2, g_n2w, g_n2b, dres=dq2)   # + the residual path of q1
+    return dq1, (g_n2w, g_n2b, g_f1w, g_f1b, g_f2w, g_f2b)
+
+
+def _head_fwd(xb, w, b):
+    """nn.Linear on bf16 [R, D] rows (the classifier head, attentive_pooler.py:130-135) -> fp32 [R, C] and the padded weight: the
+    classes are padded to a multiple of 64 (zero rows / zero bias), so any num_classes meets the GEMM's N % 4 and the dgrad's K % 32."""
+    (C, D), Cp = w.shape, ops.pad64(w.shape[0])
+    wp = torch.zeros((Cp, D), dtype=torch.bfloat16, device=xb.device)
+    wp[:C] = w.detach().to(torch.bfloat16)
+    bp = torch.zeros(Cp, dtype=torch.float32, device=xb.device)
+    if b is not None:
+        bp[:C] = b.detach().float()
+    return ops.gemm_nt(xb, wp, bias=bp)[:, :C].float(), wp
+
+
+def _head_bwd(dy, xb, wp, has_b=True):
+    """dy [R, C] -> dx bf16 [R, D], the weight gradient [C, D] and the bias gradient [C] (None without a bias)."""
+    C, (Cp, D) = dy.shape[1], wp.shape
+    dl = torch.zeros((xb.shape[0], Cp), dtype=torch.bfloat16, device=xb.device)
+    dl[:, :C] = dy.to(torch.bfloat16)
+    gw = ops.gemm_wgrad_tn(dl, xb, torch.zeros((Cp, D), dtype=torch.float32, device=xb.device))[:C].contiguous()
+    gb = ops.colsum(dl, torch.zeros(Cp, dtype=torch.float32, device=xb.device))[:C].contiguous() if has_b else None
+    return ops.gemm_nt(dl, _wT(wp)), gw, gb
+
+
+def _qproj_bwd(dqh1, q0, wq, qw, g_qt):
+    """q = Linear(q0), dqh1 bf16 [1, D]: returns g_qw (the outer product dqh^T q0) and adds the path through Wq^T into g_qt."""
+    g_qw = ops.gemm_wgrad_tn(dqh1, q0, _zeros_like_param(qw))
+    ops.colsum(ops.gemm_nt(dqh1, _wT(wq)), g_qt, accumulate=True)
+    return g_qw
+
+
+def _probe_params(pooler, head=()):
+    """A probe's parameter tensors in _PoolerFn.NAMES order, then those of its linear head where the caller has one."""
+    blk = pooler.cross_attention_block
+    return [pooler.query_tokens, *(operator.attrgetter(n)(blk) for n in _PoolerFn.NAMES[1:]), *head]
+
+
 class _PoolerFn(torch.autograd.Function):
     """AttentivePooler.forward (attentive_pooler.py:96-102) for one query token:  q0 -> q0 + xattn(q0, norm1(x)) -> + mlp(norm2(.))."""
 
@@ -71,94 +133,65 @@ class _PoolerFn(torch.autograd.Function):
              "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
 
     @staticmethod
-    def forward(ctx, x, heads, eps, qt, n1w, n1b, qw, qb, kvw, kvb, n2w, n2b, f1w, f1b, f2w, f2b):
+    def forward(ctx, x, heads, eps, *params):
+        qt, n1w, n1b, qw, qb, kvw, kvb = params[:7]
         B, N, D = x.shape
         hd = D // heads
         x2 = x.detach().reshape(B * N, D).to(torch.bfloat16).contiguous()
         q0 = _bf(qt).reshape(1, D)
-        wq, wkv, w1, w2 = _bf(qw), _bf(kvw), _bf(f1w), _bf(f2w)
+        wq, wkv = _bf(qw), _bf(kvw)
         qh = ops.gemm_nt(q0, wq, bias=_f32(qb))                                                 # [1, D]: the same row for every sample
         xn, mean1, rstd1 = ops.layernorm_fwd(x2, _f32(n1w), _f32(n1b), eps)
         kv = ops.gemm_nt(xn, wkv, bias=_f32(kvb))                                              # packed [B, N, 2, H, hd]
         q1, lse = ops.xattn_fwd(qh, kv, B, 1, N, heads, hd, hd ** -0.5, resid=q0, shared_q=True)   # q0 + softmax(q k^T) v
-        q1n, mean2, rstd2 = ops.layernorm_fwd(q1, _f32(n2w), _f32(n2b), eps)
-        dgelu = torch.empty((B, w1.shape[0]), dtype=torch.bfloat16, device=x.device)
-        g = ops.gemm_nt(q1n, w1, bias=_f32(f1b), aux_out=dgelu, epilogue=ops.EPI_GELU)
-        q2 = ops.gemm_nt(g, w2, bias=_f32(f2b), residual=q1)
-        ctx.saved = (x2, xn, mean1, rstd1, kv, qh, q0, lse, q1, q1n, mean2, rstd2, dgelu, g, wq, wkv, w1, w2)
+        q2, tail = _tail_fwd(q1, params[7:], eps)
+        ctx.saved = (x2, xn, mean1, rstd1, kv, qh, q0, lse, wq, wkv, tail)
         ctx.meta = (B, N, D, heads, hd, eps)
-        ctx.params = (qt, n1w, n1b, qw, qb, kvw, kvb, n2w, n2b, f1w, f1b, f2w, f2b)
+        ctx.params = params
         return q2.float().view(B, 1, D)
 
     @staticmethod
     def backward(ctx, dout):
-        x2, xn, mean1, rstd1, kv, qh, q0, lse, q1, q1n, mean2, rstd2, dgelu, g, wq, wkv, w1, w2 = ctx.saved
+        x2, xn, mean1, rstd1, kv, qh, q0, lse, wq, wkv, tail = ctx.saved
         B, N, D, heads, hd, eps = ctx.meta
-        qt, n1w, n1b, qw, qb, kvw, kvb, n2w, n2b, f1w, f1b, f2w, f2b = ctx.params
+        qt, n1w, n1b, qw, qb, kvw, kvb = ctx.params[:7]
         dev = x2.device
         with torch.no_grad():
             dq2 = dout.reshape(B, D).to(torch.bfloat16).contiguous()
-            # mlp.fc2 (+ residual), mlp.fc1 (fused GELU backward), norm2
-            g_f2w = ops.gemm_wgrad_tn(dq2, g, _zeros_like_param(f2w))
-            g_f2b = ops.colsum(dq2, _zeros_like_param(f2b))
-            du = ops.gemm_nt(dq2, _wT(w2), aux_in=dgelu, epilogue=ops.EPI_DGELU)
-            g_f1w = ops.gemm_wgrad_tn(du, q1n, _zeros_like_param(f1w))
-            g_f1b = ops.colsum(du, _zeros_like_param(f1b))
-            dq1n = ops.gemm_nt(du, _wT(w1))
-            g_n2w, g_n2b = _zeros_like_param(n2w), _zeros_like_param(n2b)
-            dq1 = ops.layernorm_bwd(dq1n, q1, _f32(n2w), mean2, rstd2, g_n2w, g_n2b, dres=dq2)   # + the residual path of q1
+            dq1, g_tail = _tail_bwd(dq2, tail, ctx.params[7:])
             # q1 = q0 + y: the query token collects the batch sum; y goes back through the cross-attention
             g_qt = ops.colsum(dq1, torch.zeros(D, dtype=torch.float32, device=dev))
             dqh, dkv = ops.xattn_bwd(qh, kv, dq1, lse, B, N, heads, hd, hd ** -0.5, shared_q=True)
             g_qb = ops.colsum(dqh, torch.zeros(D, dtype=torch.float32, device=dev))              # the projected query is shared: batch sum
             dqh1 = torch.empty((1, D), dtype=torch.bfloat16, device=dev)
             ops.cast_bf16(g_qb, dqh1.view(-1))
-            g_qw = ops.gemm_wgrad_tn(dqh1, q0, _zeros_like_param(qw))                              # outer product dqh^T q0
-            ops.colsum(ops.gemm_nt(dqh1, _wT(wq)), g_qt, accumulate=True)                          # ... and through q = Linear(q0)
+            g_qw = _qproj_bwd(dqh1, q0, wq, qw, g_qt)
             # kv = Linear(norm1(x)): weight / bias gradients, then norm1's affine parameters (x itself is frozen)
             g_kvw = ops.gemm_wgrad_tn(dkv, xn, _zeros_like_param(kvw))
             g_kvb = ops.colsum(dkv, _zeros_like_param(kvb))
             dxn = ops.gemm_nt(dkv, _wT(wkv))
             g_n1w, g_n1b = _zeros_like_param(n1w), _zeros_like_param(n1b)
             ops.layernorm_bwd(dxn, x2, _f32(n1w), mean1, rstd1, g_n1w, g_n1b)
-        if qb is None:
-            g_qb = None
-        if kvb is None:
-            g_kvb = None
-        return (None, None, None, g_qt.view_as(qt), g_n1w, g_n1b, g_qw, g_qb, g_kvw, g_kvb, g_n2w, g_n2b, g_f1w, g_f1b, g_f2w,
-                g_f2b)
+        return (None, None, None, g_qt.view_as(qt), g_n1w, g_n1b, g_qw, None if qb is None else g_qb, g_kvw,
+                None if kvb is None else g_kvb, *g_tail)
 
 
 class _LinearFn(torch.autograd.Function):
-    """nn.Linear on [B, D] rows (the classifier head, attentive_pooler.py:130-135); the class dimension is padded to a multiple of
-    64 inside (zero rows / zero bias) so that any num_classes meets the GEMM's N % 4 and the dgrad's K % 32."""
+    """nn.Linear on [B, D] rows: _head_fwd / _head_bwd as an autograd node of its own."""
 
     @staticmethod
     def forward(ctx, x, w, b):
-        C, D = w.shape
-        Cp = ops.pad64(C)
-        xb = x.detach().reshape(-1, D).to(torch.bfloat16).contiguous()
-        wp = torch.zeros((Cp, D), dtype=torch.bfloat16, device=x.device)
-        wp[:C] = w.detach().to(torch.bfloat16)
-        bp = torch.zeros(Cp, dtype=torch.float32, device=x.device)
-        if b is not None:
-            bp[:C] = b.detach().float()
-        y = ops.gemm_nt(xb, wp, bias=bp)
-        ctx.saved = (xb, wp)
-        ctx.meta = (C, D, Cp, x.shape, b is not None)
-        return y[:, :C].float().reshape(*x.shape[:-1], C)
+        xb = x.detach().reshape(-1, w.shape[1]).to(torch.bfloat16).contiguous()
+        y, wp = _head_fwd(xb, w, b)
+        ctx.saved = (xb, wp, x.shape, b is not None)
+        return y.reshape(*x.shape[:-1], w.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
-        xb, wp = ctx.saved
-        C, D, Cp, xshape, has_b = ctx.meta
+        xb, wp, xshape, has_b = ctx.saved
         with torch.no_grad():
-            dl = torch.zeros((xb.shape[0], Cp), dtype=torch.bfloat16, device=xb.device)
-            dl[:, :C] = dy.reshape(-1, C).to(torch.bfloat16)
-            gw = ops.gemm_wgrad_tn(dl, xb, torch.zeros((Cp, D), dtype=torch.float32, device=xb.device))[:C]
-            gb = ops.colsum(dl, torch.zeros(Cp, dtype=torch.float32, device=xb.device))[:C] if has_b else None
-            dx = ops.gemm_nt(dl, _wT(wp)).float().reshape(xshape)
-        return dx, gw.contiguous(), None if gb is None else gb.contiguous()
+            dx, gw, gb = _head_bwd(dy.reshape(xb.shape[0], -1), xb, wp, has_b)
+        return dx.float().reshape(xshape), gw, gb
 
 
 class AttentivePooler(nn.Module):
@@ -205,10 +238,7 @@ class AttentivePooler(nn.Module):
             raise NotImplementedError("AttentivePooler: the features come from a FROZEN encoder (eval.py:330-337 runs it under "
                                       "torch.no_grad()); no gradient is propagated into them")
         blk = self.cross_attention_block
-        eps = blk.norm1.eps
-        return _PoolerFn.apply(x, blk.xattn.num_heads, eps, self.query_tokens, blk.norm1.weight, blk.norm1.bias, blk.xattn.q.weight,
-                               blk.xattn.q.bias, blk.xattn.kv.weight, blk.xattn.kv.bias, blk.norm2.weight, blk.norm2.bias,
-                               blk.mlp.fc1.weight, blk.mlp.fc1.bias, blk.mlp.fc2.weight, blk.mlp.fc2.bias)
+        return _PoolerFn.apply(x, blk.xattn.num_heads, blk.norm1.eps, *_probe_params(self))
 
 
 def _spread_heads(v, H):
@@ -241,9 +271,8 @@ class _BankFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, heads, eps, P, *params):
         B, N, D = x.shape
-        H, hd = heads, D // heads
+        H, hd, dev = heads, D // heads, x.device
         s = hd ** -0.5
-        dev = x.device
         C = ops.pad64(P * H)                                        # zero rows of U: uniform columns nothing reads
         x2 = x.detach().reshape(B * N, D).to(torch.bfloat16).contiguous()
         xh, _, _ = ops.layernorm_fwd(x2, torch.ones(D, dtype=torch.float32, device=dev),
@@ -268,25 +297,17 @@ class _BankFn(torch.autograd.Function):
             ops.gemm_wgrad_tn(A[b], xh[b * N:(b + 1) * N], Z[b])                                # Z[b] = A[b]^T x_hat[b]
         logits, saved = [], []
         for p in range(P):
-            qt, n1w, n1b, qw, qb, kvw, kvb, n2w, n2b, f1w, f1b, f2w, f2b, lw, lb = params[p * _BankFn.PER:(p + 1) * _BankFn.PER]
-            q0, wq, wkv, qblk, t = pre[p]
+            pp = params[p * _BankFn.PER:(p + 1) * _BankFn.PER]
+            (qt, n1w, n1b, qw, qb, kvw, kvb), (q0, wq, wkv, qblk, t) = pp[:7], pre[p]
             R = (n1w.detach().float() * Z[:, p * H:(p + 1) * H] + n1b.detach().float()).to(torch.bfloat16).reshape(B * H, D)
             y = _pick_heads(ops.gemm_nt(R, wkv[D:], epilogue=ops.EPI_F32), H)                   # y[b,h] = Wv_h R[b,h]
             if kvb is not None:
                 y = y + kvb.detach().float()[D:]
             q1 = (y + q0.float()).to(torch.bfloat16)                                            # q0 + xattn(q0, norm1(x))
-            w1, w2 = _bf(f1w), _bf(f2w)
-            q1n, mean2, rstd2 = ops.layernorm_fwd(q1, _f32(n2w), _f32(n2b), eps)
-            dgelu = torch.empty((B, w1.shape[0]), dtype=torch.bfloat16, device=dev)
-            g = ops.gemm_nt(q1n, w1, bias=_f32(f1b), aux_out=dgelu, epilogue=ops.EPI_GELU)
-            q2 = ops.gemm_nt(g, w2, bias=_f32(f2b), residual=q1)
-            ncls = lw.shape[0]
-            lwp = torch.zeros((ops.pad64(ncls), D), dtype=torch.bfloat16, device=dev)           # the head, padded as in _LinearFn
-            lwp[:ncls] = lw.detach().to(torch.bfloat16)
-            lbp = torch.zeros(lwp.shape[0], dtype=torch.float32, device=dev)
-            lbp[:ncls] = lb.detach().float()
-            logits.append(ops.gemm_nt(q2, lwp, bias=lbp)[:, :ncls].float())
-            saved.append((q0, wq, wkv, qblk, t, R, q1, q1n, mean2, rstd2, dgelu, g, w1, w2, q2, lwp))
+            q2, tail = _tail_fwd(q1, pp[7:13], eps)
+            lg, lwp = _head_fwd(q2, pp[13], pp[14])
+            logits.append(lg)
+            saved.append((q0, wq, wkv, qblk, t, R, tail, q2, lwp))
         ctx.saved = (xh, A, Z, saved)
         ctx.meta = (B, N, D, H, hd, eps, P, C)
         ctx.params = params
@@ -294,34 +315,18 @@ class _BankFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogits):
-        xh, A, Z, saved = ctx.saved
+        (xh, A, Z, saved), params = ctx.saved, ctx.params
         B, N, D, H, hd, eps, P, C = ctx.meta
-        params = ctx.params
-        s = hd ** -0.5
-        dev = xh.device
+        s, dev = hd ** -0.5, xh.device
         grads = [None] * (P * _BankFn.PER)
         zf = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)   # noqa: E731
         with torch.no_grad():
             dZ = zf(B, C, D)
             for p in range(P):
-                qt, n1w, n1b, qw, qb, kvw, kvb, n2w, n2b, f1w, f1b, f2w, f2b, lw, lb = params[p * _BankFn.PER:(p + 1) * _BankFn.PER]
-                q0, wq, wkv, qblk, t, R, q1, q1n, mean2, rstd2, dgelu, g, w1, w2, q2, lwp = saved[p]
-                ncls, Cp = lw.shape[0], lwp.shape[0]
-                # linear
-                dl = torch.zeros((B, Cp), dtype=torch.bfloat16, device=dev)
-                dl[:, :ncls] = dlogits[p].to(torch.bfloat16)
-                g_lw = ops.gemm_wgrad_tn(dl, q2, zf(Cp, D))[:ncls].contiguous()
-                g_lb = ops.colsum(dl, zf(Cp))[:ncls].contiguous()
-                dq2 = ops.gemm_nt(dl, _wT(lwp))
-                # mlp.fc2 (+ residual), mlp.fc1 (fused GELU backward), norm2 -- the lone probe's sequence
-                g_f2w = ops.gemm_wgrad_tn(dq2, g, _zeros_like_param(f2w))
-                g_f2b = ops.colsum(dq2, _zeros_like_param(f2b))
-                du = ops.gemm_nt(dq2, _wT(w2), aux_in=dgelu, epilogue=ops.EPI_DGELU)
-                g_f1w = ops.gemm_wgrad_tn(du, q1n, _zeros_like_param(f1w))
-                g_f1b = ops.colsum(du, _zeros_like_param(f1b))
-                dq1n = ops.gemm_nt(du, _wT(w1))
-                g_n2w, g_n2b = _zeros_like_param(n2w), _zeros_like_param(n2b)
-                dq1 = ops.layernorm_bwd(dq1n, q1, _f32(n2w), mean2, rstd2, g_n2w, g_n2b, dres=dq2)
+                pp = params[p * _BankFn.PER:(p + 1) * _BankFn.PER]
+                (qt, n1w, n1b, qw, qb, kvw, kvb), (q0, wq, wkv, qblk, t, R, tail, q2, lwp) = pp[:7], saved[p]
+                dq2, g_lw, g_lb = _head_bwd(dlogits[p], q2, lwp)
+                dq1, g_tail = _tail_bwd(dq2, tail, pp[7:13])
                 g_qt = ops.colsum(dq1, zf(D))
                 # value path: y[b,h] = Wv_h R[b,h] + bv_h, R = gamma * Z + beta
                 g_kvw = _zeros_like_param(kvw)
@@ -334,8 +339,7 @@ class _BankFn(torch.autograd.Function):
                 g_n1b = G.sum(dim=(0, 1))
                 g_n1w = (G * Z[:, p * H:(p + 1) * H]).sum(dim=(0, 1))
                 dZ[:, p * H:(p + 1) * H] = n1w.detach().float() * G
-                grads[p * _BankFn.PER:(p + 1) * _BankFn.PER] = [g_qt, g_n1w, g_n1b, None, None, g_kvw, g_kvb, g_n2w, g_n2b, g_f1w,
-                                                                g_f1b, g_f2w, g_f2b, g_lw, g_lb]
+                grads[p * _BankFn.PER:(p + 1) * _BankFn.PER] = [g_qt, g_n1w, g_n1b, None, None, g_kvw, g_kvb, *g_tail, g_lw, g_lb]
             # score path, every probe's heads at once: dA = x_hat . dZ, dS = A (dA - delta), dU = dS^T x_hat
             dZb = dZ.to(torch.bfloat16)
             dA = torch.empty((B, N, C), dtype=torch.float32, device=dev)
@@ -356,9 +360,7 @@ class _BankFn(torch.autograd.Function):
                 dq = _pick_heads(ops.gemm_nt(e, wkv[:D], epilogue=ops.EPI_F32), H)               # dq_h = Wk_h e_h, [1, D]
                 if qb is not None:
                     grads[o + 4] = dq.reshape(D).clone()
-                dqh1 = dq.to(torch.bfloat16)
-                grads[o + 3] = ops.gemm_wgrad_tn(dqh1, q0, _zeros_like_param(qw))                # outer product dq q0^T
-                ops.colsum(ops.gemm_nt(dqh1, _wT(wq)), grads[o], accumulate=True)                # ... and through q = Linear(q0)
+                grads[o + 3] = _qproj_bwd(dq.to(torch.bfloat16), q0, wq, qw, grads[o])
                 grads[o] = grads[o].view_as(qt)
         return (None, None, None, None, *grads)
 
@@ -392,12 +394,7 @@ class AttentiveClassifierBank(nn.Module):
         if x.requires_grad and torch.is_grad_enabled():
             raise NotImplementedError("AttentiveClassifierBank: the features come from a FROZEN encoder (eval.py:330-337 runs it "
                                       "under torch.no_grad()); no gradient is propagated into them")
-        flat = []
-        for m in self.probes:
-            blk = m.pooler.cross_attention_block
-            flat += [m.pooler.query_tokens, blk.norm1.weight, blk.norm1.bias, blk.xattn.q.weight, blk.xattn.q.bias, blk.xattn.kv.weight,
-                     blk.xattn.kv.bias, blk.norm2.weight, blk.norm2.bias, blk.mlp.fc1.weight, blk.mlp.fc1.bias, blk.mlp.fc2.weight,
-                     blk.mlp.fc2.bias, m.linear.weight, m.linear.bias]
+        flat = [t for m in self.probes for t in _probe_params(m.pooler, (m.linear.weight, m.linear.bias))]
         return _BankFn.apply(x, self.num_heads, self.probes[0].pooler.cross_attention_block.norm1.eps, len(self.probes), *flat)
 
 

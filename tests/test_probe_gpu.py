@@ -110,6 +110,48 @@ def test_xattn_kernel_against_sdpa():
             assert rel_l2(dkvv[0], kf.grad) < 1.5e-2 and rel_l2(dkvv[1], vf.grad) < 1.5e-2
 
 
+@pytest.mark.parametrize("N", [1, 255, 256, 257])
+@pytest.mark.parametrize("hd", [8, 24, 80, 128])
+def test_xattn_thread_mapping_edges(hd, N):
+    """The edges of the single-workgroup kernels' thread mapping, at the bounds of test_xattn_kernel_against_sdpa.  Threads are
+    (row group, 8-column chunk): hd = 8 is one chunk per row and 256 row groups, hd = 80 is 25 row groups with 6 idle threads,
+    hd = 128 is 16 chunks; N = 1 / 255 / 256 / 257 is one partial pass of the 256-thread stride over the keys, one full pass, then
+    two.  Three queries forward, one query forward and backward."""
+    from jepa_amd.hip import ops
+    B, H = 2, 2
+    D = H * hd
+    g = torch.Generator().manual_seed(1000 * hd + N)
+    for NQ in (3, 1):
+        q = torch.randn(B, NQ, D, generator=g).to(torch.bfloat16).to(DEV)
+        kv = torch.randn(B * N, 2 * D, generator=g).to(torch.bfloat16).to(DEV)
+        out, lse = ops.xattn_fwd(q.reshape(B * NQ, D), kv, B, NQ, N, H, hd, hd ** -0.5, shared_q=False)
+        qf = q.float().reshape(B, NQ, H, hd).permute(0, 2, 1, 3).requires_grad_(True)
+        kvf = kv.float().reshape(B, N, 2, H, hd).permute(2, 0, 3, 1, 4)
+        kf, vf = kvf[0].detach().requires_grad_(True), kvf[1].detach().requires_grad_(True)
+        ref = torch.nn.functional.scaled_dot_product_attention(qf, kf, vf)
+        e = rel_l2(out.reshape(B, NQ, H, hd).permute(0, 2, 1, 3), ref)
+        print("out", NQ, e)
+        assert e < 8e-3, ("out", NQ, e)
+        if NQ != 1:
+            continue
+        dy = torch.randn(B, D, generator=g).to(torch.bfloat16).to(DEV)
+        dq, dkv = ops.xattn_bwd(q.reshape(B, D), kv, dy, lse, B, N, H, hd, hd ** -0.5, shared_q=False)
+        ref.backward(dy.float().reshape(B, 1, H, hd).permute(0, 2, 1, 3))
+        dkvv = dkv.float().reshape(B, N, 2, H, hd).permute(2, 0, 3, 1, 4)
+        errs = {"dq": rel_l2(dq.reshape(B, 1, H, hd).permute(0, 2, 1, 3), qf.grad), "dk": rel_l2(dkvv[0], kf.grad),
+                "dv": rel_l2(dkvv[1], vf.grad)}
+        print(errs)
+        # One key: p = 1 whatever q, so dq and dk are exactly zero.  fp32 SDPA leaves a rounding residue there at hd = 80 and 128
+        # (|dq| 5.5e-7 and 9.8e-7; exactly 0 at hd = 8 and 24), against which an exact 0 has relative error 0.999998: the bound says
+        # nothing.  Zero to the bit instead, which is what the kernels gave before their bodies were shared; dv as everywhere.
+        if N == 1:
+            print("reference |dq|, |dk|", float(qf.grad.norm()), float(kf.grad.norm()))
+            assert not dq.any() and not dkvv[0].any()
+            errs = {"dv": errs["dv"]}
+        for name, e in errs.items():
+            assert e < 1.5e-2, (name, e)
+
+
 def test_frozen_eval_loop_encoder_to_probe():
     """The reference's frozen evaluation end to end on the HIP path (evals/video_classification_frozen/eval.py:330-352): clips ->
     frozen encoder under no_grad (every parameter requires_grad=False) -> AttentiveClassifier -> CrossEntropy -> backward ->

@@ -32,7 +32,11 @@ def _inputs(B, NQ, N, H, hd, shared, seed):
 # (B, N, H, hd, shared q): the split backward runs at every N here; the split forward only at 38 265 and 73 728, so 24 000 and
 # 36 864 pair the single-workgroup forward with the split backward (the ViT-H/16-384 K400 probe: 8 x 4608 keys)
 CASES = [(1, 19133, 2, 32, False), (4, 24000, 2, 80, True), (4, 36864, 2, 64, False), (1, 36864, 1, 128, True),
-         (1, 38265, 2, 128, True), (4, 38265, 1, 32, False), (4, 73728, 1, 64, True), (1, 73728, 2, 80, False)]
+         (1, 38265, 2, 128, True), (4, 38265, 1, 32, False), (4, 73728, 1, 64, True), (1, 73728, 2, 80, False),
+         # the split forms at their smallest N with one 8-column chunk per row (hd = 8) and three (hd = 24); then 20 chunks of exactly
+         # XA_CHUNK = 2048 keys: the last chunk is full, where every case above has a ragged one
+         (2, 19133, 1, 8, True), (2, 19133, 1, 24, False), (1, 38265, 1, 8, False), (1, 38265, 1, 24, True),
+         (2, 40960, 2, 64, False)]
 
 
 @pytest.mark.parametrize("B,N,H,hd,shared", CASES)
@@ -94,3 +98,46 @@ def test_ws_entry_points_keep_the_bits_within_the_limits(N):
                            scale, s), "vj_xattn_bwd")
     assert torch.equal(out, out_ws) and torch.equal(lse, lse_ws)
     assert torch.equal(dq, dq_ws) and torch.equal(dkv, dkv_ws)
+
+
+@pytest.mark.parametrize("shared", [True, False])
+@pytest.mark.parametrize("hd", [16, 64])
+@pytest.mark.parametrize("N", [256, 1024, 32768, 65536])
+def test_xattn_exact_on_zero_query(N, hd, shared):
+    """An exact pin that holds in any summation order: with q = 0 every score is exactly 0, every p exactly 1 and their sum exactly N
+    (a power of two); with integer V in [-4, 4] the sum of the v_j is an integer below 2^24.  So out is V.sum / N + resid to the bit,
+    whichever chunk, key or head a workgroup starts from -- and a wrong start shows.  N = 256, 1024: the single-workgroup kernels;
+    32 768: the single-workgroup forward with the split backward; 65 536: both split.
+    Backward: dk = scale dS q is 0 everywhere; dv_j = p dy with p = 2^(-lse2): one bf16 rounding (2^-8) of dy / N, plus 1e-5 for p
+    (lse2 within 2 fp32 ulps of 16: 16 * 2 * 2^-24 * ln 2 = 2.8e-6)."""
+    from jepa_amd.hip import ops
+    B, H = 2, 2
+    D, scale = H * hd, hd ** -0.5
+    g = torch.Generator().manual_seed(N + hd)
+    q = torch.zeros(1 if shared else B, D, dtype=torch.bfloat16, device=DEV)
+    k = torch.randn(B, N, H, hd, generator=g)
+    v = torch.randint(-4, 5, (B, N, H, hd), generator=g).float()
+    kv = torch.stack([k, v], dim=2).reshape(B * N, 2 * D).to(torch.bfloat16).to(DEV)
+    resid = torch.randn(1, D, generator=g).to(torch.bfloat16).to(DEV)
+    dy = torch.randn(B, D, generator=g).to(torch.bfloat16).to(DEV)
+    out, lse = ops.xattn_fwd(q, kv, B, 1, N, H, hd, scale, resid=resid, shared_q=shared)
+    kvf = kv.float().reshape(B, N, 2, D)
+    expect = (kvf[:, :, 1].sum(dim=1) / N + resid.float()).to(torch.bfloat16)
+    print("out elements that differ", int((out != expect).sum()), "lse2", lse.min().item(), lse.max().item())
+    assert torch.equal(out, expect)
+    assert torch.allclose(lse, torch.full_like(lse, math.log2(N)), atol=2e-3, rtol=1e-4)
+    dq, dkv = ops.xattn_bwd(q, kv, dy, lse, B, N, H, hd, scale, shared_q=shared)
+    dkv = dkv.reshape(B, N, 2, D)
+    assert bool((dkv[:, :, 0] == 0).all())                                    # signed zeros compare equal
+    want = (dy.double() / N).reshape(B, 1, D)
+    excess = ((dkv[:, :, 1].double() - want).abs() - want.abs() * (2.0 ** -8 + 1e-5)).max().item()
+    print("dv worst excess over the bound", excess)
+    assert excess <= 0
+    # dq against float64 attention on the same inputs, differentiated by autograd
+    qd = q.double().expand(B, D).reshape(B, H, 1, hd).clone().requires_grad_(True)
+    kd, vd = kvf.double().reshape(B, N, 2, H, hd).permute(2, 0, 3, 1, 4)
+    ref = torch.softmax(qd @ kd.transpose(-1, -2) * scale, dim=-1) @ vd
+    ref.backward(dy.double().reshape(B, H, 1, hd))
+    e = rel_l2(dq.reshape(B, H, 1, hd).double(), qd.grad)
+    print("dq", e)
+    assert e < 1.5e-2, ("dq", e)
