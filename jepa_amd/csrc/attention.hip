@@ -38,24 +38,17 @@ __global__ __launch_bounds__(256) void attn_fwd_sm_kernel(const bf16_t* __restri
   constexpr int DIST = NBUF - 1;
   static_assert(RT::CAN_FULL, "tile items must be a multiple of the workgroup size");
   constexpr bool PSUM = RS == 1;
-  static_assert(!PSUM || (HDP == 32 && RT::CAN_FULL && RT::NIT == 1), "row sums on the pad column: 32-wide class, one DMA item per thread");
-  constexpr int NDMA = RT::NIT;
-  __shared__ __attribute__((aligned(16))) char smem[NBUF * 2 * RT::BYTES];
+  constexpr int NDMA = RT::NIT, BUFB = 2 * RT::BYTES;
+  __shared__ __attribute__((aligned(16))) char smem[NBUF * BUFB];
   const TrFrag<HDP> trf(threadIdx.x & 63);
   constexpr int KS = HDP / 32, DT = HeadTiles<HDP>::DT;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int li = lane & 15, g = lane >> 4;
-  int logical = xcd_logical(blockIdx.x, gridDim.x);
-  const int si = attn_seg_of(sg, logical);
-  const int S = sg.S[si], nqb = sg.nb[si];
-  const int64_t rs = (int64_t)3 * H * hd;
-  const bf16_t* qkv = qkv_all + sg.row0[si] * rs;
-  bf16_t* o = o_all + sg.row0[si] * ((int64_t)H * hd);
-  float* lse2 = lse2_all ? lse2_all + (int64_t)H * sg.row0[si] : nullptr;
-  const int qb = logical % nqb, bh = logical / nqb;
-  const int h = bh % H, b = bh / H;
-  const bf16_t* qbase = qkv + (int64_t)b * S * rs + (int64_t)h * hd;
-  const bf16_t* kbase = qbase + (int64_t)H * hd;
+  const AttnWg wg = attn_wg(sg, H);
+  const int S = wg.S, qb = wg.blk;
+  const int64_t rs = (int64_t)3 * H * hd, os = (int64_t)H * hd;
+  const bf16_t* qbase = wg.rows(qkv_all, rs, hd);
+  const bf16_t* kbase = qbase + os;
   const int q0 = qb * 128 + w * (16 * QT);
 
   // Q fragments carry the soft-max scale: bf16(q * scale * log2 e), once per workgroup
@@ -86,76 +79,32 @@ __global__ __launch_bounds__(256) void attn_fwd_sm_kernel(const bf16_t* __restri
   }
 
   const int nt = (S + 63) / 64;
-  int dma_row[NDMA];
-  unsigned dma_voff[NDMA], dma_col2[NDMA];
-  bool vpad = false;           // PSUM: this thread's DMA item is the pad chunk (columns >= hd) of its V row
-#pragma unroll
-  for (int it = 0; it < NDMA; it++) {
-    const int item = tid + it * NT;
-    const int row = item / RT::CHP, c = (item % RT::CHP) ^ rm_swz<HDP>(row);
-    const int col = c * 8 < hd ? c * 8 : 0;
-    if constexpr (PSUM) vpad = c * 8 >= hd;
-    dma_row[it] = row;
-    dma_col2[it] = (unsigned)col * 2u;
-    dma_voff[it] = ((unsigned)row * (unsigned)rs + (unsigned)col) * 2u;
-  }
-  if constexpr (PSUM) {
-    // the pad chunk of every V row: column hd = 1.0, the rest 0, written ONCE into every ring buffer; the V DMA skips these
-    // lanes (exec-masked), so the chunk survives every tile.  P.V then accumulates sum_k P[q][k] in output column hd.
-    if (vpad) {
-      const u32x4_t one = {0x00003F80u, 0u, 0u, 0u};
-#pragma unroll
-      for (int d = 0; d < NBUF; d++) *(u32x4_t*)(smem + d * 2 * RT::BYTES + RT::BYTES + tid * 16) = one;
-    }
-  }
-  const int64_t v_off = (int64_t)H * hd;
-  const int wu = __builtin_amdgcn_readfirstlane(w);
-  const unsigned rs2 = (unsigned)rs * 2u;
+  const TileDma<HDP, NT, PSUM> dma(tid, hd);
+  if constexpr (PSUM) dma.template fill_ypad<NBUF>(smem, tid);
+  // V tile = K tile + os: ONE running tile pointer in the key loop
   auto issue = [&](const int tile, const int buf_off, auto full_tag) {
-    constexpr bool FULL = decltype(full_tag)::value;
-    char* kb = smem + buf_off;
     const bf16_t* kt = kbase + (int64_t)tile * 64 * rs;   // uniform
-    const bf16_t* vt = kt + v_off;
-#pragma unroll
-    for (int it = 0; it < NDMA; it++) {
-      unsigned vo;
-      if constexpr (FULL) {
-        vo = dma_voff[it];
-      } else {
-        const int last = S - 1 - tile * 64;
-        const int r = dma_row[it] < last ? dma_row[it] : last;
-        vo = (unsigned)r * rs2 + dma_col2[it];
-      }
-      char* dst = kb + (it * NT + wu * 64) * 16;
-      dma16_sv(kt, vo, lds_addr(dst));
-      if constexpr (PSUM) {
-        if (!vpad) dma16_sv(vt, vo, lds_addr(dst + RT::BYTES));   // never all lanes of a wave: one pad chunk per 4 lanes
-      } else {
-        dma16_sv(vt, vo, lds_addr(dst + RT::BYTES));
-      }
-    }
+    dma.template issue<decltype(full_tag)::value>(kt, rs, kt + os, rs, 0, S - tile * 64, smem + buf_off);
   };
-  constexpr int BUFB = 2 * RT::BYTES, RINGB = NBUF * BUFB;
   __builtin_amdgcn_s_waitcnt(0x0f70);
 #pragma unroll
   for (int d = 0; d < DIST; d++)
     if (d < nt) issue(d, d * BUFB, std::false_type{});
-  int cur_off = 0, nxt_off = DIST * BUFB;
-  const bool wave_live = qb * 128 + wu * (16 * QT) < S;   // wave-uniform
+  RingCursor<NBUF, BUFB> ring;
+  const bool wave_live = qb * 128 + dma.wu * (16 * QT) < S;   // wave-uniform
 
   // FIRST: tile 0 -- the base is unknown (seed 0), the exact-maximum path runs unconditionally and nothing is rescaled.
   auto iter = [&](const int t, auto fast_tag, auto first_tag) {
     constexpr bool FAST = decltype(fast_tag)::value, FIRST = decltype(first_tag)::value;
     const int k0 = t * 64;
-    char* k_lds = smem + cur_off;
+    char* k_lds = smem + ring.cur;
     char* v_lds = k_lds + RT::BYTES;
     if (DIST >= 2 && (FAST || t + 1 < nt)) wait_vmcnt<2 * NDMA>();
     else wait_vmcnt<0>();
     lgkm_barrier();
-    if constexpr (FAST) issue(t + DIST, nxt_off, std::true_type{});
-    else if (t + DIST < nt) issue(t + DIST, nxt_off, std::false_type{});
-    cur_off = cur_off + BUFB == RINGB ? 0 : cur_off + BUFB;
-    nxt_off = nxt_off + BUFB == RINGB ? 0 : nxt_off + BUFB;
+    if constexpr (FAST) issue(t + DIST, ring.nxt, std::true_type{});
+    else if (t + DIST < nt) issue(t + DIST, ring.nxt, std::false_type{});
+    ring.advance();
     // round 5: a wave all of whose queries lie beyond S (the last query block of a sequence that is not a multiple of 128: S = 264 ->
     // three of the third block's four waves, a quarter of the segment's waves) takes part in the DMA and the barrier and leaves the pipes
     // to the waves that have rows -- it stores nothing, so the results are untouched
@@ -287,19 +236,8 @@ __global__ __launch_bounds__(256) void attn_fwd_sm_kernel(const bf16_t* __restri
     }
     const int q = q0 + qt * 16 + li;
     if (q < S) {
-      const float inv = 1.0f / l;
-      bf16_t* op = o + ((int64_t)b * S + q) * ((int64_t)H * hd) + (int64_t)h * hd;
-#pragma unroll
-      for (int dt = 0; dt < DT; dt++) {
-        const int d = dt * 16 + 4 * g;
-        if (d < hd) {
-          u32x2_t ov;
-          ov[0] = cvt_pk_bf16(oacc[qt][dt][0] * inv, oacc[qt][dt][1] * inv);
-          ov[1] = cvt_pk_bf16(oacc[qt][dt][2] * inv, oacc[qt][dt][3] * inv);
-          *(u32x2_t*)(op + d) = ov;
-        }
-      }
-      if (g == 0 && lse2) lse2[((int64_t)b * H + h) * S + q] = mrun[qt] + log2f(l);
+      store_acc_row<DT>(wg.rows(o_all, os, hd) + q * os, oacc[qt], g, hd, 1.0f / l);
+      if (g == 0 && lse2_all) wg.stats(lse2_all, H)[q] = mrun[qt] + log2f(l);
     }
   }
 }
@@ -330,25 +268,15 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(const bf16_t* __rest
   constexpr int KS = HDP / 32, DT = HeadTiles<HDP>::DT;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int li = lane & 15, g = lane >> 4;
-  int logical = xcd_logical(blockIdx.x, gridDim.x);
-  const int si = attn_seg_of(sg, logical);
-  const int S = sg.S[si], nkb = sg.nb[si];
-  const int64_t rs = (int64_t)3 * H * hd;
-  const int64_t os = (int64_t)H * hd;
-  const bf16_t* qkv = qkv_all + sg.row0[si] * rs;
-  const bf16_t* dout = dout_all + sg.row0[si] * os;
-  const float* lse2 = lse2_all + (int64_t)H * sg.row0[si];
-  const float* delta = delta_all + (int64_t)H * sg.row0[si];
-  bf16_t* dqkv = dqkv_all + sg.row0[si] * rs;
-  if (colkv != nullptr) colkv += sg.col0[si] * (2 * os);
-  const int kb = logical % nkb, bh = logical / nkb;
-  const int h = bh % H, b = bh / H;
-  const bf16_t* qbase = qkv + (int64_t)b * S * rs + (int64_t)h * hd;
-  const bf16_t* kbase = qbase + (int64_t)H * hd;
-  const bf16_t* vbase = qbase + (int64_t)2 * H * hd;
-  const bf16_t* dobase = dout + (int64_t)b * S * os + (int64_t)h * hd;
-  const float* lse_b = lse2 + ((int64_t)b * H + h) * S;
-  const float* dl_b = delta + ((int64_t)b * H + h) * S;
+  const AttnWg wg = attn_wg(sg, H);
+  const int S = wg.S, kb = wg.blk;
+  const int64_t rs = (int64_t)3 * H * hd, os = (int64_t)H * hd;
+  const bf16_t* qbase = wg.rows(qkv_all, rs, hd);
+  const bf16_t* kbase = qbase + os;
+  const bf16_t* vbase = kbase + os;
+  const bf16_t* dobase = wg.rows(dout_all, os, hd);
+  const float* lse_b = wg.stats(lse2_all, H);
+  const float* dl_b = wg.stats(delta_all, H);
   int key[KT];
   bool key_ok[KT];
 #pragma unroll
@@ -467,17 +395,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(const bf16_t* __rest
       bf16x8_t pfr[KT], dfr[KT];
 #pragma unroll
       for (int kt = 0; kt < KT; kt++) {
-        u32x4_t pw, dw;
-        pw[0] = cvt_pk_bf16(pv[kt][0][0], pv[kt][0][1]);
-        pw[1] = cvt_pk_bf16(pv[kt][0][2], pv[kt][0][3]);
-        pw[2] = cvt_pk_bf16(pv[kt][1][0], pv[kt][1][1]);
-        pw[3] = cvt_pk_bf16(pv[kt][1][2], pv[kt][1][3]);
-        dw[0] = cvt_pk_bf16(dsv[kt][0][0], dsv[kt][0][1]);
-        dw[1] = cvt_pk_bf16(dsv[kt][0][2], dsv[kt][0][3]);
-        dw[2] = cvt_pk_bf16(dsv[kt][1][0], dsv[kt][1][1]);
-        dw[3] = cvt_pk_bf16(dsv[kt][1][2], dsv[kt][1][3]);
-        pfr[kt] = __builtin_bit_cast(bf16x8_t, pw);
-        dfr[kt] = __builtin_bit_cast(bf16x8_t, dw);
+        pfr[kt] = pack_frag(pv[kt][0], pv[kt][1]);
+        dfr[kt] = pack_frag(dsv[kt][0], dsv[kt][1]);
       }
 #pragma unroll
       for (int dt = 0; dt < DT; dt++) {
@@ -493,7 +412,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(const bf16_t* __rest
   }
 
   // column partials for the qkv bias gradient (colkv != nullptr): this workgroup's sum over its keys of dK | dV (fp32, before the
-  // bf16 rounding) -> colkv[b * nkb + kb][h*hd + d | H*hd + h*hd + d]; padded keys (garbage accumulators, never stored) are masked
+  // bf16 rounding) -> colkv[b * nb + kb][h*hd + d | H*hd + h*hd + d]; padded keys (garbage accumulators, never stored) are masked
   if (colkv != nullptr) {
     float ck[DT][4], cv[DT][4];
 #pragma unroll
@@ -527,15 +446,15 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(const bf16_t* __rest
         float t = red[(0 * 2 + which) * HDP + d] + red[(1 * 2 + which) * HDP + d] + red[(2 * 2 + which) * HDP + d] +
                   red[(3 * 2 + which) * HDP + d];
         if (which == 0) t *= scale;
-        colkv[((int64_t)b * nkb + kb) * (2 * os) + (int64_t)which * os + (int64_t)h * hd + d] = t;
+        wg.colrow(colkv, 2 * os, hd)[(int64_t)which * os + d] = t;
       }
     }
   }
 #pragma unroll
   for (int kt = 0; kt < KT; kt++) {
     if (key_ok[kt]) {
-      bf16_t* dkp = dqkv + ((int64_t)b * S + key[kt]) * rs + (int64_t)H * hd + (int64_t)h * hd;
-      bf16_t* dvp = dkp + (int64_t)H * hd;
+      bf16_t* dkp = wg.rows(dqkv_all, rs, hd) + key[kt] * rs + os;
+      bf16_t* dvp = dkp + os;
 #pragma unroll
       for (int dt = 0; dt < DT; dt++) {
         const int d = dt * 16 + 4 * g;
@@ -570,32 +489,23 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
                                                           bf16_t* __restrict__ dqkv_all, AttnSegs sg, int H, int hd,
                                                           float sc, float scale, float* __restrict__ colq) {
   // {K,V} x NBUF ring filled by LDS-DMA (see the forward kernel): one barrier per tile, tile t+DIST in flight
-  constexpr int NBUF = HDP <= 64 ? 3 : 2, DIST = NBUF - 1, BUFB = 2 * RowTile<HDP>::BYTES, RINGB = NBUF * BUFB;
-  __shared__ __attribute__((aligned(16))) char smem[RINGB];
+  constexpr int NBUF = HDP <= 64 ? 3 : 2, DIST = NBUF - 1, BUFB = 2 * RowTile<HDP>::BYTES;
+  __shared__ __attribute__((aligned(16))) char smem[NBUF * BUFB];
   const TrFrag<HDP> trf(threadIdx.x & 63);
   constexpr int KS = HDP / 32, DT = HeadTiles<HDP>::DT;
   constexpr int QW = 2;   // 16-query tiles per wave
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int li = lane & 15, g = lane >> 4;
-  int logical = xcd_logical(blockIdx.x, gridDim.x);
-  const int si = attn_seg_of(sg, logical);
-  const int S = sg.S[si], nqb = sg.nb[si];
-  const int64_t rs = (int64_t)3 * H * hd;
-  const int64_t os = (int64_t)H * hd;
-  const bf16_t* qkv = qkv_all + sg.row0[si] * rs;
-  const bf16_t* o = o_all + sg.row0[si] * os;
-  const bf16_t* dout = dout_all + sg.row0[si] * os;
-  const float* lse2 = lse2_all + (int64_t)H * sg.row0[si];
-  float* delta = delta_all + (int64_t)H * sg.row0[si];
-  bf16_t* dqkv = dqkv_all + sg.row0[si] * rs;
-  if (colq != nullptr) colq += sg.col0[si] * os;
-  const int qb = logical % nqb, bh = logical / nqb;
-  const int h = bh % H, b = bh / H;
-  const bf16_t* qbase = qkv + (int64_t)b * S * rs + (int64_t)h * hd;
-  const bf16_t* kbase = qbase + (int64_t)H * hd;
-  const bf16_t* vbase = qbase + (int64_t)2 * H * hd;
-  const bf16_t* dobase = dout + (int64_t)b * S * os + (int64_t)h * hd;
-  const bf16_t* obase = o + (int64_t)b * S * os + (int64_t)h * hd;
+  const AttnWg wg = attn_wg(sg, H);
+  const int S = wg.S, qb = wg.blk;
+  const int64_t rs = (int64_t)3 * H * hd, os = (int64_t)H * hd;
+  const bf16_t* qbase = wg.rows(qkv_all, rs, hd);
+  const bf16_t* kbase = qbase + os;
+  const bf16_t* vbase = kbase + os;
+  const bf16_t* dobase = wg.rows(dout_all, os, hd);
+  const bf16_t* obase = wg.rows(o_all, os, hd);
+  const float* lse_b = wg.stats(lse2_all, H);
+  float* dl_b = wg.stats(delta_all, H);
   const int q0 = qb * (64 * QW) + w * (16 * QW);
 
   bf16x8_t qf[QW][KS], dof[QW][KS];
@@ -617,9 +527,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
     }
     dsum += __shfl_xor(dsum, 16, 64);   // the four lane groups g hold the four 8-element chunks of a step
     dsum += __shfl_xor(dsum, 32, 64);
-    lse_q[qt] = q < S ? lse2[((int64_t)b * H + h) * S + q] : INFINITY;
+    lse_q[qt] = q < S ? lse_b[q] : INFINITY;
     dl_q[qt] = q < S ? dsum : 0.f;
-    if (g == 0 && q < S) delta[((int64_t)b * H + h) * S + q] = dsum;
+    if (g == 0 && q < S) dl_b[q] = dsum;
     // Q is the stationary operand of the score product and is used for nothing else here: it carries scale * log2 e
 #pragma unroll
     for (int ks = 0; ks < KS; ks++) qf[qt][ks] = scale_frag(qf[qt][ks], sc);
@@ -645,21 +555,20 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
 #pragma unroll
   for (int d = 0; d < DIST; d++)
     if (d < nt) dma.template issue<false>(kbase, rs, vbase, rs, d * 64, S, smem + d * BUFB);
-  int cur_off = 0, nxt_off = DIST * BUFB;
+  RingCursor<NBUF, BUFB> ring;
 
   for (int t = 0; t < nt; t++) {
     const int k0 = t * 64;
-    char* k_lds = smem + cur_off;
+    char* k_lds = smem + ring.cur;
     char* v_lds = k_lds + RowTile<HDP>::BYTES;
     if (DIST >= 2 && t + 1 < nt) wait_vmcnt<NDMA2>();
     else wait_vmcnt<0>();
     lgkm_barrier();
     if (t + DIST < nt) {
-      if ((t + DIST) * 64 + 64 <= S) dma.template issue<true>(kbase, rs, vbase, rs, (t + DIST) * 64, S, smem + nxt_off);
-      else dma.template issue<false>(kbase, rs, vbase, rs, (t + DIST) * 64, S, smem + nxt_off);
+      if ((t + DIST) * 64 + 64 <= S) dma.template issue<true>(kbase, rs, vbase, rs, (t + DIST) * 64, S, smem + ring.nxt);
+      else dma.template issue<false>(kbase, rs, vbase, rs, (t + DIST) * 64, S, smem + ring.nxt);
     }
-    cur_off = cur_off + BUFB == RINGB ? 0 : cur_off + BUFB;
-    nxt_off = nxt_off + BUFB == RINGB ? 0 : nxt_off + BUFB;
+    ring.advance();
     // Two halves of the 64-key tile (c = 0, 1: keys 32c .. 32c+31 = the contraction chunk of one dQ MFMA): S^T / dP^T / dS^T of a half
     // for all QW query tiles, then its dQ MFMAs.  Per accumulator the same operations in the same order as the round-4 form (all
     // four key blocks first, then both halves): bit-identical; only one half's scores are live.
@@ -717,14 +626,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
       }
       bf16x8_t dsf[QW];
 #pragma unroll
-      for (int qt = 0; qt < QW; qt++) {
-        u32x4_t dw;
-        dw[0] = cvt_pk_bf16(sacc[qt][0][0], sacc[qt][0][1]);
-        dw[1] = cvt_pk_bf16(sacc[qt][0][2], sacc[qt][0][3]);
-        dw[2] = cvt_pk_bf16(sacc[qt][1][0], sacc[qt][1][1]);
-        dw[3] = cvt_pk_bf16(sacc[qt][1][2], sacc[qt][1][3]);
-        dsf[qt] = __builtin_bit_cast(bf16x8_t, dw);
-      }
+      for (int qt = 0; qt < QW; qt++) dsf[qt] = pack_frag(sacc[qt][0], sacc[qt][1]);
 #pragma unroll
       for (int dt = 0; dt < DT; dt++) {
         const bf16x8_t ktf = trf.load(k_lds, c * 32, dt * 16);
@@ -736,7 +638,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
   }
 
   // column partials for the qkv bias gradient (colq != nullptr): this workgroup's sum over its 128 queries of dQ (fp32, before the
-  // bf16 rounding) -> colq[b * nqb + qb][h*hd + d]; padded queries have P = 0, hence dQ = 0, and need no mask
+  // bf16 rounding) -> colq[b * nb + qb][h*hd + d]; padded queries have P = 0, hence dQ = 0, and need no mask
   if (colq != nullptr) {
     float cq[DT][4];
 #pragma unroll
@@ -754,25 +656,13 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
         for (int r = 0; r < 4; r++) red[w * HDP + dt * 16 + 4 * g + r] = cq[dt][r];
     }
     lgkm_barrier();
-    if (tid < hd) colq[((int64_t)b * nqb + qb) * os + (int64_t)h * hd + tid] =
+    if (tid < hd) wg.colrow(colq, os, hd)[tid] =
         (red[tid] + red[HDP + tid] + red[2 * HDP + tid] + red[3 * HDP + tid]) * scale;
   }
 #pragma unroll
   for (int qt = 0; qt < QW; qt++) {
     const int q = q0 + qt * 16 + li;
-    if (q < S) {
-      bf16_t* dqp = dqkv + ((int64_t)b * S + q) * rs + (int64_t)h * hd;
-#pragma unroll
-      for (int dt = 0; dt < DT; dt++) {
-        const int d = dt * 16 + 4 * g;
-        if (d < hd) {
-          u32x2_t a;
-          a[0] = cvt_pk_bf16(dqacc[qt][dt][0] * scale, dqacc[qt][dt][1] * scale);
-          a[1] = cvt_pk_bf16(dqacc[qt][dt][2] * scale, dqacc[qt][dt][3] * scale);
-          *(u32x2_t*)(dqp + d) = a;
-        }
-      }
-    }
+    if (q < S) store_acc_row<DT>(wg.rows(dqkv_all, rs, hd) + q * rs, dqacc[qt], g, hd, scale);
   }
 }
 
@@ -780,7 +670,36 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
 // host entry points
 // =============================================================================================================
 static int pick_hdp(int64_t hd) { return hd <= 32 ? 32 : (hd <= 64 ? 64 : (hd <= 80 ? 96 : (hd <= 128 ? 128 : 0))); }
-#define LOG2E 1.4426950408889634f
+constexpr float LOG2E = 1.4426950408889634f;
+static int attn_check_hd(const char* who, int64_t hd) {
+  VJ_CHECK_ARG(hd % 8 == 0 && pick_hdp(hd) != 0, "%s: head_dim=%ld unsupported (need %%8==0, <=128)", who, (long)hd);
+  return 0;
+}
+
+// run-time head_dim -> the tiling of its class as a type: f(AttnClass<...>{}).  HDP = the padded head dimension of all three kernels.
+// Forward: NBUF ring buffers; row sums from the matrix pipe, head_dim 24 on the V image's pad column (RS = 1), the other head sizes
+// from an all-ones operand (RS = 2).  dK/dV: KT 16-key tiles per wave (32 keys at head_dim <= 32: every Q / dO fragment and transposed
+// read serves two key tiles; 64 keys per wave, and 64 queries per wave in the dQ kernel, were tried in round 5: -0.09 / +0.23 ms per
+// step, profiles/r05_attn_tiles.md)
+template <int HDP_, int NBUF_, int RS_, int KT_>
+struct AttnClass { static constexpr int HDP = HDP_, NBUF = NBUF_, RS = RS_, KT = KT_; };
+template <class F>
+static inline int with_head_dim(int64_t hd, F&& f) {
+  switch (pick_hdp(hd)) {
+    case 32: return hd == 24 ? f(AttnClass<32, 3, 1, 2>{}) : f(AttnClass<32, 3, 2, 2>{});
+    case 64: return f(AttnClass<64, 2, 2, 1>{});
+    case 96: return f(AttnClass<96, 2, 2, 1>{});
+    default: return f(AttnClass<128, 2, 2, 1>{});
+  }
+}
+static int dkdv_kt(int64_t hd) { return with_head_dim(hd, [](auto c) { return decltype(c)::KT; }); }
+// one past the last token row of a segment list: lse2 and the delta workspace hold H floats per token row up to there
+static int64_t attn_rows_end(const vj_seg_t* segs, int64_t n_segs) {
+  int64_t rows_end = 0;
+  for (int64_t i = 0; i < n_segs; i++)
+    if (segs[i].B * segs[i].S > 0 && segs[i].row0 + segs[i].B * segs[i].S > rows_end) rows_end = segs[i].row0 + segs[i].B * segs[i].S;
+  return rows_end;
+}
 
 // segment list -> kernel argument (workgroups per segment = B * H * blocks(S)); empty segments are dropped
 static int make_segs(const vj_seg_t* segs, int64_t n_segs, int64_t H, int64_t rows_per_block, AttnSegs* out, int64_t* nblk,
@@ -818,9 +737,8 @@ static int make_segs(const vj_seg_t* segs, int64_t n_segs, int64_t H, int64_t ro
 // row0_i .. row0_i + B_i*S_i, its lse2 block at H*row0_i laid out [B_i, H, S_i]).
 extern "C" int vj_attn_fwd_segs(const void* qkv, void* o, float* lse2, const vj_seg_t* segs, int64_t n_segs, int64_t H,
                                 int64_t hd, float scale, hipStream_t stream) {
-  VJ_CHECK_ARG(hd % 8 == 0 && pick_hdp(hd) != 0, "vj_attn_fwd: head_dim=%ld unsupported (need %%8==0, <=128)", (long)hd);
+  if (int rc = attn_check_hd("vj_attn_fwd", hd)) return rc;
   VJ_CHECK_ARG(H > 0, "vj_attn_fwd: bad dims");
-  const int64_t rs = 3 * H * hd, os = H * hd;
   AttnSegs sg;
   int64_t nblk = 0;
   if (int rc = make_segs(segs, n_segs, H, 128, &sg, &nblk, "vj_attn_fwd")) return rc;
@@ -828,20 +746,12 @@ extern "C" int vj_attn_fwd_segs(const void* qkv, void* o, float* lse2, const vj_
   // scale < 0: the q part of qkv ALREADY carries |scale| * log2(e) (the qkv GEMM applied it before its bf16 rounding, epilogue 4
   // of vj_gemm_bf16_nt): the kernels' own factor becomes 1 (scale_frag(x, 1) is the identity)
   const float sc = scale < 0.f ? 1.0f : scale * LOG2E;
-  // row sums from the matrix pipe: head_dim 24 on the V image's pad column (RS = 1), the other head sizes from an all-ones operand (RS = 2)
-#define VJ_FWD_SM(HDPV, NB, RSV)                                                                                       \
-  hipLaunchKernelGGL((attn_fwd_sm_kernel<HDPV, NB, RSV>), dim3((unsigned)nblk), dim3(256), 0, stream,                  \
-                     (const bf16_t*)qkv, (bf16_t*)o, lse2, sg, (int)H, (int)hd, sc)
-  switch (pick_hdp(hd)) {
-    case 32:
-      if (hd == 24) VJ_FWD_SM(32, 3, 1);
-      else VJ_FWD_SM(32, 3, 2);
-      break;
-    case 64: VJ_FWD_SM(64, 2, 2); break;
-    case 96: VJ_FWD_SM(96, 2, 2); break;
-    default: VJ_FWD_SM(128, 2, 2);
-  }
-#undef VJ_FWD_SM
+  with_head_dim(hd, [&](auto c) {
+    using C = decltype(c);
+    hipLaunchKernelGGL((attn_fwd_sm_kernel<C::HDP, C::NBUF, C::RS>), dim3((unsigned)nblk), dim3(256), 0, stream, (const bf16_t*)qkv,
+                       (bf16_t*)o, lse2, sg, (int)H, (int)hd, sc);
+    return 0;
+  });
   VJ_LAUNCH_CHECK("vj_attn_fwd");
   return 0;
 }
@@ -853,25 +763,22 @@ extern "C" int vj_attn_fwd(const void* qkv, void* o, float* lse2, int64_t B, int
   return vj_attn_fwd_segs(qkv, o, lse2, &one, 1, H, hd, scale, stream);
 }
 
-extern "C" int64_t vj_attn_bwd_ws_bytes(int64_t B, int64_t S, int64_t H) { return B * S * H * 4; }
-
 // Workspace of vj_attn_bwd / vj_attn_bwd_segs / vj_attn_bwd_colsum for a segment list: delta = rowsum(dO . O), 4 * H bytes per token row
 // up to the last row of the list (laid out like lse2).
 extern "C" int64_t vj_attn_bwd_segs_ws_bytes(const vj_seg_t* segs, int64_t n_segs, int64_t H, int64_t hd) {
   (void)hd;
   if (segs == nullptr || n_segs <= 0) return 0;
-  int64_t rows_end = 0;
-  for (int64_t i = 0; i < n_segs; i++)
-    if (segs[i].B * segs[i].S > 0 && segs[i].row0 + segs[i].B * segs[i].S > rows_end) rows_end = segs[i].row0 + segs[i].B * segs[i].S;
-  return rows_end * H * 4;
+  return attn_rows_end(segs, n_segs) * H * 4;
+}
+extern "C" int64_t vj_attn_bwd_ws_bytes(int64_t B, int64_t S, int64_t H) {
+  const vj_seg_t one = {0, B, S};
+  return vj_attn_bwd_segs_ws_bytes(&one, 1, H, 0);
 }
 
-// dK/dV tiling: 16-key tiles per wave (32 keys at head_dim <= 32: every Q / dO fragment and transposed read serves two key tiles; 64 keys per
-// wave, and 64 queries per wave in the dQ kernel, were tried in round 5: -0.09 / +0.23 ms per step, profiles/r05_attn_tiles.md)
-static int dkdv_kt(int64_t hd) { return pick_hdp(hd) == 32 ? 2 : 1; }
 // rows of the column-partial matrices vj_attn_bwd_colsum writes for one [B, S] segment: colq [rows_q][H*hd], colkv [rows_kv][2*H*hd]
 extern "C" int vj_attn_bwd_colsum_rows(int64_t B, int64_t S, int64_t hd, int64_t* rows_q, int64_t* rows_kv) {
-  VJ_CHECK_ARG(rows_q != nullptr && rows_kv != nullptr && hd % 8 == 0 && pick_hdp(hd) != 0, "vj_attn_bwd_colsum_rows: bad arguments");
+  VJ_CHECK_ARG(rows_q != nullptr && rows_kv != nullptr, "vj_attn_bwd_colsum_rows: bad arguments");
+  if (int rc = attn_check_hd("vj_attn_bwd_colsum_rows", hd)) return rc;
   *rows_q = B * cdiv64(S, 128);   // the dQ kernel: 128 queries per workgroup
   *rows_kv = B * cdiv64(S, 64 * dkdv_kt(hd));
   return 0;
@@ -883,7 +790,7 @@ extern "C" int vj_attn_bwd_colsum_rows(int64_t B, int64_t S, int64_t hd, int64_t
 extern "C" int vj_attn_bwd_segs(const void* qkv, const void* o, const void* dout, const float* lse2, void* dqkv,
                                 const vj_seg_t* segs, int64_t n_segs, int64_t H, int64_t hd, float scale, void* ws,
                                 int64_t ws_bytes, float* colq, float* colkv, hipStream_t stream) {
-  VJ_CHECK_ARG(hd % 8 == 0 && pick_hdp(hd) != 0, "vj_attn_bwd: head_dim=%ld unsupported", (long)hd);
+  if (int rc = attn_check_hd("vj_attn_bwd", hd)) return rc;
   VJ_CHECK_ARG(H > 0 && (colq == nullptr) == (colkv == nullptr), "vj_attn_bwd: bad arguments");
   const int kt = dkdv_kt(hd);
   AttnSegs sq, sk;
@@ -891,10 +798,7 @@ extern "C" int vj_attn_bwd_segs(const void* qkv, const void* o, const void* dout
   if (int rc = make_segs(segs, n_segs, H, 128, &sq, &gq, "vj_attn_bwd")) return rc;
   if (int rc = make_segs(segs, n_segs, H, 64 * kt, &sk, &gk, "vj_attn_bwd")) return rc;
   if (gq == 0) return 0;
-  int64_t rows_end = 0;   // the delta workspace mirrors lse2: H floats per token row up to the last row of the list
-  for (int64_t i = 0; i < n_segs; i++)
-    if (segs[i].B * segs[i].S > 0 && segs[i].row0 + segs[i].B * segs[i].S > rows_end) rows_end = segs[i].row0 + segs[i].B * segs[i].S;
-  VJ_CHECK_ARG(ws != nullptr && ws_bytes >= rows_end * H * 4, "vj_attn_bwd: workspace too small");
+  VJ_CHECK_ARG(ws != nullptr && ws_bytes >= attn_rows_end(segs, n_segs) * H * 4, "vj_attn_bwd: workspace too small");
   float* delta = (float*)ws;
   // scale < 0: q is stored pre-scaled by c = |scale| * log2(e) (vj_attn_fwd_segs).  The kernels' own score factor is then 1;
   // dQ = |scale| * dS K is unchanged (the gradient of the UNscaled q: what the qkv dgrad / wgrad expect, since the GEMM's
@@ -904,23 +808,14 @@ extern "C" int vj_attn_bwd_segs(const void* qkv, const void* o, const void* dout
   const float sc = pre ? 1.0f : sabs * LOG2E;
   const float kscale = pre ? 1.0f / LOG2E : sabs;
   // dQ first: it also produces delta[b,h,s] = dO . O for the dK/dV kernel behind it on the same stream.
-  // dK/dV: KTV = dkdv_kt(hd) 16-key tiles per wave
-#define VJ_BWD_LAUNCH(HDPV, KTV)                                                                                    \
-  do {                                                                                                              \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<HDPV>), dim3((unsigned)gq), dim3(256), 0, stream,                        \
-                       (const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)dout, lse2, delta, (bf16_t*)dqkv, sq,   \
-                       (int)H, (int)hd, sc, sabs, colq);                                                            \
-    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<HDPV, KTV>), dim3((unsigned)gk), dim3(256), 0, stream,                 \
-                       (const bf16_t*)qkv, (const bf16_t*)dout, lse2, delta, (bf16_t*)dqkv, sk, (int)H, (int)hd,    \
-                       sc, kscale, colkv);                                                                          \
-  } while (0)
-  switch (pick_hdp(hd)) {
-    case 32: VJ_BWD_LAUNCH(32, 2); break;
-    case 64: VJ_BWD_LAUNCH(64, 1); break;
-    case 96: VJ_BWD_LAUNCH(96, 1); break;
-    default: VJ_BWD_LAUNCH(128, 1);
-  }
-#undef VJ_BWD_LAUNCH
+  with_head_dim(hd, [&](auto c) {
+    using C = decltype(c);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<C::HDP>), dim3((unsigned)gq), dim3(256), 0, stream, (const bf16_t*)qkv, (const bf16_t*)o,
+                       (const bf16_t*)dout, lse2, delta, (bf16_t*)dqkv, sq, (int)H, (int)hd, sc, sabs, colq);
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<C::HDP, C::KT>), dim3((unsigned)gk), dim3(256), 0, stream, (const bf16_t*)qkv,
+                       (const bf16_t*)dout, lse2, delta, (bf16_t*)dqkv, sk, (int)H, (int)hd, sc, kscale, colkv);
+    return 0;
+  });
   VJ_LAUNCH_CHECK("vj_attn_bwd");
   return 0;
 }

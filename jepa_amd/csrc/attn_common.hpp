@@ -1,5 +1,6 @@
 // Shared pieces of the attention kernels (attention.hip: forward + the two-kernel backward): the swizzled row-major tile image,
-// transposed fragment reads, segment tables.
+// transposed fragment reads, tile staging and ring cursor, fragment packing, accumulator stores, segment tables and the workgroup
+// decode.
 #pragma once
 #include "common.hpp"
 #include "lds_pipe.hpp"
@@ -132,17 +133,22 @@ struct TrFrag {
 };
 
 // ---- LDS-DMA staging of one 64-row tile of TWO row-major operands (X at +0, Y at +RowTile::BYTES of a ring buffer) ----
-// Used by the backward kernels (the forward kernel carries its own copy of the same scheme).  Rows beyond `nrows`
-// re-read row nrows-1 and chunks beyond the real head dimension re-read chunk 0: the callers mask such rows / never
-// use such columns, so the DMA needs no zero fill.
-template <int HDP, int NT>
+// Used by all three kernels.  Rows beyond `nrows` re-read row nrows-1 and chunks beyond the real head dimension re-read chunk 0: the
+// callers mask such rows / never use such columns, so the DMA needs no zero fill.
+// YPAD (the forward with its row sums on the pad column, head_dim 24): the pad chunk (columns >= hd) of every Y row holds 1.0 in
+// column hd and 0 after it, written ONCE into every ring buffer by fill_ypad; the Y DMA skips the lanes of that chunk (exec-masked;
+// never all lanes of a wave: one pad chunk per 4 lanes), so the chunk survives every tile and P.V accumulates sum_k P[q][k] in
+// output column hd.
+template <int HDP, int NT, bool YPAD = false>
 struct TileDma {
   using RT = RowTile<HDP, NT>;
   static_assert(RT::CAN_FULL, "tile items must be a multiple of the workgroup size");
   static constexpr int NDMA = RT::NIT;
+  static_assert(!YPAD || (HDP == 32 && NDMA == 1), "row sums on the pad column: 32-wide class, one DMA item per thread");
   int row[NDMA];
   unsigned col2[NDMA];   // byte offset of the (swizzled, clamped) source chunk inside a row
   int wu;
+  bool ypad = false;     // YPAD: this thread's DMA item is the pad chunk of its Y row
   __device__ __forceinline__ TileDma(int tid, int hd) {
     wu = __builtin_amdgcn_readfirstlane(tid >> 6);
 #pragma unroll
@@ -151,6 +157,15 @@ struct TileDma {
       const int r = item / RT::CHP, c = (item % RT::CHP) ^ rm_swz<HDP>(r);
       row[it] = r;
       col2[it] = (unsigned)(c * 8 < hd ? c * 8 : 0) * 2u;
+      if constexpr (YPAD) ypad = c * 8 >= hd;
+    }
+  }
+  template <int NBUF>
+  __device__ __forceinline__ void fill_ypad(char* ring, int tid) const {
+    if (ypad) {
+      const u32x4_t one = {0x00003F80u, 0u, 0u, 0u};
+#pragma unroll
+      for (int d = 0; d < NBUF; d++) *(u32x4_t*)(ring + d * 2 * RT::BYTES + RT::BYTES + tid * 16) = one;
     }
   }
   // wave-uniform tile bases in SGPRs + 32-bit per-lane byte offsets (row * row stride + chunk): no 64-bit vector address
@@ -168,10 +183,38 @@ struct TileDma {
       if constexpr (!FULL) r = r < last ? r : last;
       char* dst = buf + (it * NT + wu * 64) * 16;   // wave-uniform; the hardware adds lane * 16
       dma16_sv(xt, (unsigned)r * rsx2 + col2[it], lds_addr(dst));
-      dma16_sv(yt, (unsigned)r * rsy2 + col2[it], lds_addr(dst + RT::BYTES));
+      if (!YPAD || !ypad) dma16_sv(yt, (unsigned)r * rsy2 + col2[it], lds_addr(dst + RT::BYTES));
     }
   }
 };
+
+// {cur, nxt} byte offsets into an NBUF-deep ring of BUFB-byte buffers: tile t is read at `cur` while tile t + NBUF - 1 lands at `nxt`
+template <int NBUF, int BUFB>
+struct RingCursor {
+  int cur = 0, nxt = (NBUF - 1) * BUFB;
+  __device__ __forceinline__ void advance() {
+    cur = cur + BUFB == NBUF * BUFB ? 0 : cur + BUFB;
+    nxt = nxt + BUFB == NBUF * BUFB ? 0 : nxt + BUFB;
+  }
+};
+
+// MFMA operand from two accumulator-shaped 4-vectors (k-slots 0..3 and 4..7), rounded to bf16
+template <class V>
+__device__ __forceinline__ bf16x8_t pack_frag(const V& lo, const V& hi) {
+  const u32x4_t w = {cvt_pk_bf16(lo[0], lo[1]), cvt_pk_bf16(lo[2], lo[3]), cvt_pk_bf16(hi[0], hi[1]), cvt_pk_bf16(hi[2], hi[3])};
+  return __builtin_bit_cast(bf16x8_t, w);
+}
+
+// One row of a transposed accumulator (lane group g owns columns dt*16 + 4g .. + 3 of tile dt) times `mul`, to bf16, 8-byte stores
+template <int DT>
+__device__ __forceinline__ void store_acc_row(bf16_t* row, const f32x4_t (&acc)[DT], int g, int hd, float mul) {
+#pragma unroll
+  for (int dt = 0; dt < DT; dt++) {
+    const int d = dt * 16 + 4 * g;
+    const u32x2_t v = {cvt_pk_bf16(acc[dt][0] * mul, acc[dt][1] * mul), cvt_pk_bf16(acc[dt][2] * mul, acc[dt][3] * mul)};
+    if (d < hd) *(u32x2_t*)(row + d) = v;
+  }
+}
 
 __device__ __forceinline__ bf16x8_t load_frag_global(const bf16_t* p, bool valid) {
   u32x4_t v = {0, 0, 0, 0};
@@ -198,4 +241,28 @@ __device__ __forceinline__ int attn_seg_of(const AttnSegs& sg, int& logical) {
     if (i + 1 < sg.n && logical >= sg.blk_end[i]) si = i + 1;
   logical -= si > 0 ? sg.blk_end[si - 1] : 0;
   return si;
+}
+// What a workgroup works on, from blockIdx.x: its segment's S / nb / row0 / col0, its block `blk` of the nb of its (sample b, head h)
+struct AttnWg {
+  int S, nb, blk, h, b;
+  int64_t row0, col0;
+  // token 0 of (b, h) in a token-major tensor of `stride` elements per token; the [S] statistics row of (b, h) (lse2, delta);
+  // this workgroup's row, at head h, of a column-partial matrix `width` floats wide
+  template <class T>
+  __device__ __forceinline__ T* rows(T* p, int64_t stride, int hd) const { return p + (row0 + (int64_t)b * S) * stride + (int64_t)h * hd; }
+  template <class T>
+  __device__ __forceinline__ T* stats(T* p, int H) const { return p + (int64_t)H * row0 + ((int64_t)b * H + h) * S; }
+  __device__ __forceinline__ float* colrow(float* p, int64_t width, int hd) const {
+    return p + (col0 + (int64_t)b * nb + blk) * width + (int64_t)h * hd;
+  }
+};
+__device__ __forceinline__ AttnWg attn_wg(const AttnSegs& sg, int H) {
+  int logical = xcd_logical(blockIdx.x, gridDim.x);
+  const int si = attn_seg_of(sg, logical);
+  AttnWg g;
+  g.S = sg.S[si], g.nb = sg.nb[si], g.row0 = sg.row0[si], g.col0 = sg.col0[si];
+  g.blk = logical % g.nb;
+  const int bh = logical / g.nb;
+  g.h = bh % H, g.b = bh / H;
+  return g;
 }
