@@ -69,6 +69,27 @@ int vj_add_pos(void* x_bf16, const float* pos, const int64_t* idx, int64_t B, in
 int vj_clip_transform(const uint8_t* frames, int64_t frames_bytes, const int64_t* desc, const int32_t* boxes, float* out,
                       int64_t B, int64_t T, int64_t S, float mean_r, float mean_g, float mean_b, float std_r, float std_g,
                       float std_b, vj_stream_t stream);
+/* The normalise-first form the frozen video eval needs:        evals/video_classification_frozen/utils.py:256-274,298-301,326-343
+ * (ToTensor / 255 -> tensor_normalize -> random_resized_crop; EvalVideoTransform and eval_transform: ClipToTensor / 255 -> Normalize).
+ * Same arguments, tables and limits as vj_clip_transform, but mean_*, std_* are in 0..1 units and every source byte u of channel c
+ * becomes n = (float(u) / 255 - mean_c) / std_c (three separately rounded fp32 operations) BEFORE the taps are blended; nothing is
+ * done after the blend.  A box with h == w == S is a crop without a resize: its output is n of the addressed pixel, bit for bit.
+ * Several rows of desc may name the same byte offset (the spatial views of one segment share one copy of their frames). */
+int vj_clip_transform_pre(const uint8_t* frames, int64_t frames_bytes, const int64_t* desc, const int32_t* boxes, float* out,
+                          int64_t B, int64_t T, int64_t S, float mean_r, float mean_g, float mean_b, float std_r, float std_g,
+                          float std_b, vj_stream_t stream);
+/* RandomErasing(mode='pixel', max_count=1, cube=True)._erase_cube         src/datasets/utils/video/randerase.py:116-156
+ * as the reference applies it after flip and normalisation (app/vjepa/transforms.py:110-113, eval utils.py:278-281).  The box and
+ * the N(0,1) values are draws and stay on the host; this is the copy:
+ *   clips[b,c,t,top+y,left+x] = noise[noise_off[b] + ((t*3+c)*h+y)*w+x],   y < h, x < w
+ *   clips      fp32 [B,3,T,S,S], written in place (the output of vj_clip_transform[_pre])
+ *   ebox       int32 [B,4] = (top, left, h, w); h == 0: clip b is not erased; 16-byte aligned
+ *   noise      fp32 [noise_elems]: per erased clip one [T,3,h,w] block starting at noise_off[b] (int64 [B])
+ * Bit-exact.  Callers validate the tables on the host (RawClipBatch.validate); the kernel skips a clip whose box leaves S x S or
+ * whose block leaves [0, noise_elems), so nothing outside either buffer is touched.  B == 0 or noise_elems == 0 (no clip of the
+ * batch is erased) launches nothing.  B < 65536, 3*T*S*S < 2^31. */
+int vj_clip_erase(float* clips, const int32_t* ebox, const float* noise, int64_t noise_elems, const int64_t* noise_off, int64_t B,
+                  int64_t T, int64_t S, vj_stream_t stream);
 
 /* ---- still-image front end of the video encoder and position-table interpolation ------------------------------
  * input.unsqueeze(2).repeat(1, 1, frames_per_clip, 1, 1) + patch_embed    evals/image_classification_frozen/eval.py:452-455

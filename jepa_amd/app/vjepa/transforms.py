@@ -10,7 +10,9 @@ frames as they came, an int32 [T,4] box table, the flip flag).  `default_collate
 
 Supported: the transform of the three pretrain configs -- auto_augment false, reprob 0, random horizontal flip, random resize
 scale / aspect ratio, crop size, motion_shift false and true.  `auto_augment=True` (PIL RandAugment) and `reprob > 0`
-(RandomErasing) raise NotImplementedError.
+(RandomErasing) raise NotImplementedError here.  The RandomErasing draw itself (`draw_erase`) and the tables that carry it to
+`vj_clip_erase` live in this module; the frozen eval's transforms (evals/video_classification_frozen/utils.py), which set
+reprob 0.25, use them, together with the normalise-first flag and per-clip view boxes of `RawClip` / `RawClipBatch`.
 """
 import math
 import random
@@ -67,26 +69,65 @@ def _draw_box(scale, ratio, height, width, num_repeat=10):
     return (height - h) // 2, (width - w) // 2, h, w
 
 
-class RawClip:
-    """One undecorated clip on its way to the device: uint8 frames [T,H,W,3], int32 boxes [T,4] = (i, j, h, w), the flip flag,
-    and the constants of the transform that drew them (output side, mean and std in 0..255 units)."""
-    __slots__ = ("frames", "boxes", "flip", "crop_size", "mean", "std")
+def draw_erase(probability, num_frames, img_h, img_w, min_area=0.02, max_area=1 / 3, min_aspect=0.3):
+    """RandomErasing(probability, mode='pixel', max_count=1, num_splits=1, cube=True) as DRAWS only, with the reference's calls in
+    the reference's order on the global generators (src/datasets/utils/video/randerase.py:116-156): `random.random()`; up to 100
+    tries of two `random.uniform`; the strict `w < img_w and h < img_h` test; two `random.randint`; then one
+    `torch.empty((3, h, w)).normal_()` per frame.  Returns ((top, left, h, w), noise fp32 [T,3,h,w]) or ((0, 0, 0, 0), None) when
+    the clip is not erased (the first draw, or 100 boxes that do not fit)."""
+    if random.random() > probability:
+        return (0, 0, 0, 0), None
+    area = img_h * img_w
+    log_aspect = (math.log(min_aspect), math.log(1 / min_aspect))
+    for _ in range(100):
+        target_area = random.uniform(min_area, max_area) * area / 1
+        aspect_ratio = math.exp(random.uniform(*log_aspect))
+        h = int(round(math.sqrt(target_area * aspect_ratio)))
+        w = int(round(math.sqrt(target_area / aspect_ratio)))
+        if w < img_w and h < img_h:
+            top = random.randint(0, img_h - h)
+            left = random.randint(0, img_w - w)
+            noise = torch.stack([torch.empty((3, h, w), dtype=torch.float32).normal_() for _ in range(num_frames)])
+            return (top, left, h, w), noise
+    return (0, 0, 0, 0), None
 
-    def __init__(self, frames, boxes, flip, crop_size, mean, std):
+
+class RawClip:
+    """One undecorated clip on its way to the device: uint8 frames [T,H,W,3], int32 boxes [T,4] = (i, j, h, w) -- or [V,T,4], one
+    table per spatial view of the same frames --, the flip flag, and the constants of the transform that drew them (output side,
+    mean and std).  `pre` selects the frozen eval's normalise-first arithmetic (mean / std in 0..1 units; otherwise 0..255).
+    `ebox` = (top, left, h, w) and `noise` fp32 [T,3,h,w] are the RandomErasing draw of the clip (h == 0 / None: not erased)."""
+    __slots__ = ("frames", "boxes", "flip", "crop_size", "mean", "std", "pre", "ebox", "noise")
+
+    def __init__(self, frames, boxes, flip, crop_size, mean, std, pre=False, ebox=(0, 0, 0, 0), noise=None):
         self.frames, self.boxes, self.flip = frames, boxes, bool(flip)
         self.crop_size, self.mean, self.std = int(crop_size), tuple(mean), tuple(std)
+        self.pre, self.ebox, self.noise = bool(pre), tuple(int(v) for v in ebox), noise
+
+    @property
+    def num_views(self):
+        return self.boxes.shape[0] if self.boxes.dim() == 3 else 1
 
 
 class RawClipBatch:
     """A collated list of RawClips, all CPU tensors:
-        frames  uint8 [nbytes]   clip after clip, each [T,Hs,Ws,3], each starting on a 16-byte boundary
-        desc    int64 [B,4]      (byte offset, Hs, Ws, flip)
-        boxes   int32 [B,T,4]    (i, j, h, w) per frame
-    """
+        frames     uint8 [nbytes]   clip after clip, each [T,Hs,Ws,3], each starting on a 16-byte boundary, each ONCE
+        desc       int64 [R,4]      (byte offset, Hs, Ws, flip)
+        boxes      int32 [R,T,4]    (i, j, h, w) per frame
+        ebox       int32 [R,4]      (top, left, h, w) of the erased box; h == 0: none
+        noise      fp32 [n]         per erased row one [T,3,h,w] block
+        noise_off  int64 [R]        where the row's block starts in `noise`
+    R = num_views * B rows, view-major: rows [v*B, (v+1)*B) are view v of the B clips, and the rows of one clip share its byte
+    offset.  `pre`: the normalise-first form (mean / std in 0..1 units)."""
 
-    def __init__(self, frames, desc, boxes, crop_size, mean, std):
+    def __init__(self, frames, desc, boxes, crop_size, mean, std, pre=False, num_views=1, ebox=None, noise=None, noise_off=None):
         self.frames, self.desc, self.boxes = frames, desc, boxes
         self.crop_size, self.mean, self.std = int(crop_size), tuple(mean), tuple(std)
+        self.pre, self.num_views = bool(pre), int(num_views)
+        R = desc.shape[0]
+        self.ebox = torch.zeros((R, 4), dtype=torch.int32) if ebox is None else ebox
+        self.noise = torch.zeros(0, dtype=torch.float32) if noise is None else noise
+        self.noise_off = torch.zeros(R, dtype=torch.int64) if noise_off is None else noise_off
 
     def __len__(self):
         return self.desc.shape[0]
@@ -95,17 +136,29 @@ class RawClipBatch:
     def num_frames(self):
         return self.boxes.shape[1]
 
+    @property
+    def erased(self):
+        """Whether any row of the batch carries an erase box (decided on the host: no launch otherwise)."""
+        return self.noise.numel() > 0 and bool((self.ebox[:, 2] > 0).any())
+
     def validate(self):
-        """Refuse, on the host, anything that would send the kernel outside a frame or the buffer."""
+        """Refuse, on the host, anything that would send the kernels outside a frame, a clip or a buffer."""
         f, d, bx = self.frames, self.desc, self.boxes
         if f.dtype != torch.uint8 or f.dim() != 1 or d.dtype != torch.int64 or d.dim() != 2 or d.shape[1] != 4 \
                 or bx.dtype != torch.int32 or bx.dim() != 3 or bx.shape[2] != 4 or bx.shape[0] != d.shape[0]:
             raise ValueError(f"RawClipBatch: malformed tables frames {tuple(f.shape)} {f.dtype}, desc {tuple(d.shape)} "
                              f"{d.dtype}, boxes {tuple(bx.shape)} {bx.dtype}")
+        eb, nz, no = self.ebox, self.noise, self.noise_off
+        if eb.dtype != torch.int32 or tuple(eb.shape) != (d.shape[0], 4) or nz.dtype != torch.float32 or nz.dim() != 1 \
+                or no.dtype != torch.int64 or tuple(no.shape) != (d.shape[0],):
+            raise ValueError(f"RawClipBatch: malformed erase tables ebox {tuple(eb.shape)} {eb.dtype}, noise {tuple(nz.shape)} "
+                             f"{nz.dtype}, noise_off {tuple(no.shape)} {no.dtype}")
         if self.crop_size <= 0 or self.crop_size % 4 != 0:
             raise ValueError(f"RawClipBatch: crop_size={self.crop_size} must be a positive multiple of 4")
         if len(self.mean) != 3 or len(self.std) != 3 or any(s == 0 for s in self.std):
             raise ValueError("RawClipBatch: mean / std need three values each and a non-zero std")
+        if self.num_views <= 0 or d.shape[0] % self.num_views != 0:
+            raise ValueError(f"RawClipBatch: {d.shape[0]} rows are not {self.num_views} views of a whole number of clips")
         if d.shape[0] == 0:
             return self
         T = bx.shape[1]
@@ -120,16 +173,30 @@ class RawClipBatch:
         if bool(bad.any()):
             b, t = (int(v) for v in bad.nonzero()[0])
             raise ValueError(f"RawClipBatch: box {bx[b, t].tolist()} of clip {b} frame {t} leaves its {int(Hs[b])}x{int(Ws[b])} frame")
+        e64, S = eb.to(torch.int64), self.crop_size
+        top, left, eh, ew = e64[:, 0], e64[:, 1], e64[:, 2], e64[:, 3]
+        on = eh != 0
+        bad = on & ((top < 0) | (left < 0) | (eh < 0) | (ew <= 0) | (top + eh > S) | (left + ew > S))
+        if bool(bad.any()):
+            b = int(bad.nonzero()[0])
+            raise ValueError(f"RawClipBatch: erase box {eb[b].tolist()} of clip {b} leaves its {S}x{S} clip")
+        bad = on & ((no < 0) | (no + T * 3 * eh * ew > nz.numel()))
+        if bool(bad.any()):
+            b = int(bad.nonzero()[0])
+            raise ValueError(f"RawClipBatch: the noise block of clip {b} ({T}x3x{int(eh[b])}x{int(ew[b])} values at {int(no[b])}) "
+                             f"leaves the noise buffer of {nz.numel()} values")
         return self
 
     def clip_frames(self, b):
-        """The uint8 [T,Hs,Ws,3] frames of clip b (a view of the flat buffer)."""
+        """The uint8 [T,Hs,Ws,3] frames of row b (a view of the flat buffer)."""
         off, Hs, Ws = (int(v) for v in self.desc[b, :3])
         T = self.num_frames
         return self.frames[off:off + T * Hs * Ws * 3].view(T, Hs, Ws, 3)
 
     def pin_memory(self):
         self.frames, self.desc, self.boxes = self.frames.pin_memory(), self.desc.pin_memory(), self.boxes.pin_memory()
+        self.ebox, self.noise_off = self.ebox.pin_memory(), self.noise_off.pin_memory()
+        self.noise = self.noise.pin_memory() if self.noise.numel() else self.noise
         return self
 
     def to(self, device):
@@ -138,25 +205,36 @@ class RawClipBatch:
 
 
 def collate_raw_clips(batch, *, collate_fn_map=None):
-    """default_collate of a list of RawClip -> one validated RawClipBatch."""
+    """default_collate of a list of RawClip -> one validated RawClipBatch.  Clips that carry V views each give V * B rows,
+    view-major, over ONE copy of every clip's frames."""
     first = batch[0]
-    T = first.boxes.shape[0]
+    T, V = first.frames.shape[0], first.num_views
     offs, total = [], 0
     for c in batch:
-        if c.frames.shape[0] != T or c.boxes.shape != (T, 4):
-            raise ValueError("collate: clips of one batch must have the same number of frames")
-        if (c.crop_size, c.mean, c.std) != (first.crop_size, first.mean, first.std):
-            raise ValueError("collate: clips of one batch must come from one transform")
+        if c.frames.shape[0] != T or tuple(c.boxes.shape[-2:]) != (T, 4) or c.num_views != V:
+            raise ValueError("collate: clips of one batch must have the same number of frames and views")
+        if (c.crop_size, c.mean, c.std, c.pre) != (first.crop_size, first.mean, first.std, first.pre):
+            raise ValueError("collate: clips of one batch must come from one transform (crop size, mean / std, normalise-first flag)")
         offs.append(total)
         total += -(-c.frames.numel() // ALIGN) * ALIGN
     flat = torch.zeros(total, dtype=torch.uint8)
     for c, off in zip(batch, offs):
         n = c.frames.numel()
         flat[off:off + n] = c.frames.reshape(-1)
-    desc = torch.tensor([[off, c.frames.shape[1], c.frames.shape[2], int(c.flip)] for c, off in zip(batch, offs)],
-                        dtype=torch.int64).reshape(len(batch), 4)
-    boxes = torch.stack([c.boxes for c in batch])
-    return RawClipBatch(flat, desc, boxes, first.crop_size, first.mean, first.std).validate()
+    rows = [(c, off, v) for v in range(V) for c, off in zip(batch, offs)]
+    desc = torch.tensor([[off, c.frames.shape[1], c.frames.shape[2], int(c.flip)] for c, off, _ in rows],
+                        dtype=torch.int64).reshape(len(rows), 4)
+    boxes = torch.stack([c.boxes.reshape(V, T, 4)[v] for c, _, v in rows])
+    ebox = torch.tensor([c.ebox if c.noise is not None else (0, 0, 0, 0) for c, _, _ in rows], dtype=torch.int32).reshape(len(rows), 4)
+    noise_off, blocks, n = [], [], 0
+    for c, _, _ in rows:
+        noise_off.append(n if c.noise is not None else 0)
+        if c.noise is not None:
+            blocks.append(c.noise.to(torch.float32).reshape(-1))
+            n += blocks[-1].numel()
+    noise = torch.cat(blocks) if blocks else torch.zeros(0, dtype=torch.float32)
+    return RawClipBatch(flat, desc, boxes, first.crop_size, first.mean, first.std, pre=first.pre, num_views=V, ebox=ebox,
+                        noise=noise, noise_off=torch.tensor(noise_off, dtype=torch.int64)).validate()
 
 
 default_collate_fn_map[RawClip] = collate_raw_clips

@@ -5,6 +5,8 @@
 //   PatchEmbed3D token/K ordering    src/models/utils/patch_embed.py:31-57
 //   still image -> repeated clip     evals/image_classification_frozen/eval.py:452-455
 //   VideoTransform.__call__          app/vjepa/transforms.py:86-115,138-153
+//   eval VideoTransform / EvalVideoTransform   evals/video_classification_frozen/utils.py:251-283,303-323,326-343
+//   RandomErasing._erase_cube        src/datasets/utils/video/randerase.py:116-156
 #include "common.hpp"
 #include "../../include/vjepa_hip.h"
 
@@ -108,6 +110,13 @@ extern "C" int vj_image_pack(const float* images, void* out_bf16, const int64_t*
 // bytes come through the cache (neighbouring outputs share them).  Every source row / column is clamped into the frame and a
 // clip whose extent does not lie inside the buffer is written as zeros, whatever the descriptor says: nothing outside
 // [frames, frames + frames_bytes) is ever read.
+//
+// PRE is the normalise-first form of the frozen eval (evals/video_classification_frozen/utils.py:256-274: ToTensor / 255, then
+// tensor_normalize, then random_resized_crop; EvalVideoTransform: ClipToTensor / 255, then Normalize): every source byte u of
+// channel c becomes n = (float(u) / 255 - mean_c) / std_c -- three separately rounded fp32 operations, mean / std in 0..1 units --
+// and the taps are blended with the same arithmetic; nothing follows the blend.  n depends on (u, c) alone, so a block computes the
+// 768 values once into LDS and a tap is a table read.  A box with h == w == S has scale 1: the fused coordinate is the integer dst,
+// the weights are exactly 1 and 0, and the output is the tap itself, bit for bit (the validation views: crops without a resize).
 // ---------------------------------------------------------------------------------------------
 // ClipAxis (here), InterpAxis and CubicAxis (pos_interp.hip) look alike and stay three: each encodes the rounding of the code it
 // reproduces -- a FUSED coordinate for the CPU reference of the clip transform, unfused products for F.interpolate's linear modes,
@@ -135,10 +144,19 @@ struct ClipNorm {
   float mean[3], std[3];
 };
 
+template <bool PRE>
 __global__ __launch_bounds__(256) void clip_transform_kernel(const uint8_t* __restrict__ frames, int64_t frames_bytes,
                                                              const int64_t* __restrict__ desc,
                                                              const int4* __restrict__ boxes, float* __restrict__ out,
                                                              int64_t B, int T, int S, ClipNorm nm) {
+  [[maybe_unused]] const float* lut = nullptr;
+  if constexpr (PRE) {
+    __shared__ float norm_lut[3][256];
+#pragma unroll
+    for (int c = 0; c < 3; c++) norm_lut[c][threadIdx.x] = ((float)threadIdx.x / 255.f - nm.mean[c]) / nm.std[c];
+    __syncthreads();
+    lut = &norm_lut[0][0];
+  }
   const uint32_t qpr = (uint32_t)S / 4;  // 16-byte output chunks per row
   const uint32_t total = (uint32_t)B * T * S * qpr;   // < 2^31 (checked by the launcher): 32-bit index arithmetic
   const int64_t plane = (int64_t)T * S * S;
@@ -169,10 +187,17 @@ __global__ __launch_bounds__(256) void clip_transform_kernel(const uint8_t* __re
         const ClipAxis ax = clip_axis(x, sx, box.y, box.w, (int)Ws);
 #pragma unroll
         for (int c = 0; c < 3; c++) {
-          const float p00 = (float)r0[ax.i0 * 3 + c], p01 = (float)r0[ax.i1 * 3 + c];
-          const float p10 = (float)r1[ax.i0 * 3 + c], p11 = (float)r1[ax.i1 * 3 + c];
+          float p00, p01, p10, p11;
+          if constexpr (PRE) {
+            p00 = lut[c * 256 + r0[ax.i0 * 3 + c]], p01 = lut[c * 256 + r0[ax.i1 * 3 + c]];
+            p10 = lut[c * 256 + r1[ax.i0 * 3 + c]], p11 = lut[c * 256 + r1[ax.i1 * 3 + c]];
+          } else {
+            p00 = (float)r0[ax.i0 * 3 + c], p01 = (float)r0[ax.i1 * 3 + c];
+            p10 = (float)r1[ax.i0 * 3 + c], p11 = (float)r1[ax.i1 * 3 + c];
+          }
           const float top = ax.w0 * p00 + ax.w1 * p01, bot = ax.w0 * p10 + ax.w1 * p11;
-          v[c][k] = (ay.w0 * top + ay.w1 * bot - nm.mean[c]) / nm.std[c];
+          if constexpr (PRE) v[c][k] = ay.w0 * top + ay.w1 * bot;
+          else v[c][k] = (ay.w0 * top + ay.w1 * bot - nm.mean[c]) / nm.std[c];
         }
       }
 #pragma unroll
@@ -186,21 +211,76 @@ __global__ __launch_bounds__(256) void clip_transform_kernel(const uint8_t* __re
   }
 }
 
+template <bool PRE>
+static int clip_transform_launch(const char* what, const uint8_t* frames, int64_t frames_bytes, const int64_t* desc,
+                                 const int32_t* boxes, float* out, int64_t B, int64_t T, int64_t S, const ClipNorm& nm,
+                                 hipStream_t stream) {
+  VJ_CHECK_ARG(B >= 0 && T > 0 && S > 0 && frames_bytes >= 0 && T < (1 << 20) && S < (1 << 20),
+               "%s: bad dims B=%ld T=%ld S=%ld frames_bytes=%ld", what, (long)B, (long)T, (long)S, (long)frames_bytes);
+  VJ_CHECK_ARG(S % 4 == 0, "%s: S=%ld must be a multiple of 4", what, (long)S);
+  VJ_CHECK_ARG(nm.std[0] != 0.f && nm.std[1] != 0.f && nm.std[2] != 0.f, "%s: std must be non-zero", what);
+  if (B == 0) return 0;
+  VJ_CHECK_ARG(frames != nullptr && desc != nullptr && boxes != nullptr && out != nullptr, "%s: null pointer", what);
+  VJ_CHECK_ARG(((uintptr_t)out % 16 == 0) && ((uintptr_t)boxes % 16 == 0), "%s: out and boxes must be 16-byte aligned", what);
+  const int64_t total = B * T * S * (S / 4);
+  VJ_CHECK_ARG(B < (1ll << 31) && total < (1ll << 31), "%s: batch too large (B=%ld)", what, (long)B);
+  hipLaunchKernelGGL(clip_transform_kernel<PRE>, dim3(flat_grid(total, 256 * 32)), dim3(256), 0, stream, frames, frames_bytes, desc,
+                     (const int4*)boxes, out, B, (int)T, (int)S, nm);
+  VJ_LAUNCH_CHECK(what);
+  return 0;
+}
+
 extern "C" int vj_clip_transform(const uint8_t* frames, int64_t frames_bytes, const int64_t* desc, const int32_t* boxes,
                                  float* out, int64_t B, int64_t T, int64_t S, float mean_r, float mean_g, float mean_b,
                                  float std_r, float std_g, float std_b, hipStream_t stream) {
-  VJ_CHECK_ARG(B >= 0 && T > 0 && S > 0 && frames_bytes >= 0 && T < (1 << 20) && S < (1 << 20),
-               "vj_clip_transform: bad dims B=%ld T=%ld S=%ld frames_bytes=%ld", (long)B, (long)T, (long)S, (long)frames_bytes);
-  VJ_CHECK_ARG(S % 4 == 0, "vj_clip_transform: S=%ld must be a multiple of 4", (long)S);
-  VJ_CHECK_ARG(std_r != 0.f && std_g != 0.f && std_b != 0.f, "vj_clip_transform: std must be non-zero");
-  if (B == 0) return 0;
-  VJ_CHECK_ARG(frames != nullptr && desc != nullptr && boxes != nullptr && out != nullptr, "vj_clip_transform: null pointer");
-  VJ_CHECK_ARG(((uintptr_t)out % 16 == 0) && ((uintptr_t)boxes % 16 == 0), "vj_clip_transform: out and boxes must be 16-byte aligned");
-  const int64_t total = B * T * S * (S / 4);
-  VJ_CHECK_ARG(B < (1ll << 31) && total < (1ll << 31), "vj_clip_transform: batch too large (B=%ld)", (long)B);
-  ClipNorm nm = {{mean_r, mean_g, mean_b}, {std_r, std_g, std_b}};
-  hipLaunchKernelGGL(clip_transform_kernel, dim3(flat_grid(total, 256 * 32)), dim3(256), 0, stream, frames, frames_bytes, desc, (const int4*)boxes,
-                     out, B, (int)T, (int)S, nm);
-  VJ_LAUNCH_CHECK("vj_clip_transform");
+  const ClipNorm nm = {{mean_r, mean_g, mean_b}, {std_r, std_g, std_b}};
+  return clip_transform_launch<false>("vj_clip_transform", frames, frames_bytes, desc, boxes, out, B, T, S, nm, stream);
+}
+
+extern "C" int vj_clip_transform_pre(const uint8_t* frames, int64_t frames_bytes, const int64_t* desc, const int32_t* boxes,
+                                     float* out, int64_t B, int64_t T, int64_t S, float mean_r, float mean_g, float mean_b,
+                                     float std_r, float std_g, float std_b, hipStream_t stream) {
+  const ClipNorm nm = {{mean_r, mean_g, mean_b}, {std_r, std_g, std_b}};
+  return clip_transform_launch<true>("vj_clip_transform_pre", frames, frames_bytes, desc, boxes, out, B, T, S, nm, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// clip_erase: RandomErasing in cube mode (randerase.py:116-156: one box per clip, fresh N(0,1) values for every frame, written
+// after flip and normalisation) as a copy: clips[b,c,t,top+y,left+x] = noise[noise_off[b] + ((t*3+c)*h+y)*w+x] for the box
+// ebox[b] = (top, left, h, w); h == 0: the clip is not erased.  The values are a DRAW, made on the host in the reference's order
+// and shipped as [T,3,h,w] per erased clip.  Block row b walks the 3*T*h*w values of clip b, consecutive threads on consecutive
+// noise elements and (within a box row) consecutive pixels.  A clip whose box leaves S x S or whose block leaves
+// [0, noise_elems) is skipped whole: nothing outside either buffer is read or written.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void clip_erase_kernel(float* __restrict__ clips, const int4* __restrict__ ebox,
+                                                         const float* __restrict__ noise, int64_t noise_elems,
+                                                         const int64_t* __restrict__ noise_off, int T, int S) {
+  const int64_t b = blockIdx.y;
+  const int4 e = ebox[b];  // (top, left, h, w)
+  if (e.z <= 0 || e.w <= 0 || e.x < 0 || e.y < 0 || e.z > S - e.x || e.w > S - e.y) return;
+  const int64_t off = noise_off[b];
+  const uint32_t n = (uint32_t)T * 3u * (uint32_t)e.z * (uint32_t)e.w;   // <= 3*T*S*S < 2^31 (checked by the launcher)
+  if (off < 0 || off > noise_elems || (int64_t)n > noise_elems - off) return;
+  const uint32_t h = (uint32_t)e.z, w = (uint32_t)e.w;
+  float* base = clips + b * 3 * T * (int64_t)S * S + (int64_t)e.x * S + e.y;
+  for (uint32_t q = blockIdx.x * 256u + threadIdx.x; q < n; q += gridDim.x * 256u) {
+    const uint32_t r = q / w, x = q - r * w;
+    const uint32_t tc = r / h, y = r - tc * h;
+    const uint32_t t = tc / 3u, c = tc - t * 3u;
+    base[((int64_t)c * T + t) * S * S + (int64_t)y * S + x] = noise[off + q];
+  }
+}
+
+extern "C" int vj_clip_erase(float* clips, const int32_t* ebox, const float* noise, int64_t noise_elems, const int64_t* noise_off,
+                             int64_t B, int64_t T, int64_t S, hipStream_t stream) {
+  VJ_CHECK_ARG(B >= 0 && T > 0 && S > 0 && noise_elems >= 0 && B < 65536 && 3 * T * S * S < (1ll << 31) && T < (1 << 20) && S < (1 << 20),
+               "vj_clip_erase: bad dims B=%ld T=%ld S=%ld noise_elems=%ld", (long)B, (long)T, (long)S, (long)noise_elems);
+  if (B == 0 || noise_elems == 0) return 0;   // no clip of the batch is erased: nothing is launched
+  VJ_CHECK_ARG(clips != nullptr && ebox != nullptr && noise != nullptr && noise_off != nullptr, "vj_clip_erase: null pointer");
+  VJ_CHECK_ARG((uintptr_t)ebox % 16 == 0, "vj_clip_erase: ebox must be 16-byte aligned");
+  const int64_t widest = 3 * T * S * S;
+  hipLaunchKernelGGL(clip_erase_kernel, dim3(flat_grid(widest, 256), (unsigned)B), dim3(256), 0, stream, clips, (const int4*)ebox,
+                     noise, noise_elems, noise_off, (int)T, (int)S);
+  VJ_LAUNCH_CHECK("vj_clip_erase");
   return 0;
 }

@@ -20,7 +20,12 @@ A clip entry may also be a `RawClipBatch` (app/vjepa/transforms.py: decoded uint
 buffer + descriptor and box tables).  Then the uint8 bytes and the two small tables are what crosses PCIe (3 bytes per SOURCE
 pixel instead of 12 per output pixel: 0.38 x the fp32 clip for 240x320 sources at 224x224), and `vj_clip_transform` runs on the
 copy stream, after the copies, into the slot's fp32 [B,3,T,S,S] buffer; `ready` is recorded after it, so `next()` hands out the same tensors as for fp32 batches.
-The flat buffer changes size from batch to batch: its pinned and device staging buffers only ever grow.
+The flat buffer changes size from batch to batch: its pinned and device staging buffers only ever grow.  A batch in the frozen
+eval's normalise-first form goes through `vj_clip_transform_pre`, and a batch that carries RandomErasing boxes also ships its
+noise and has `vj_clip_erase` write it, on the copy stream after the transform (no copy and no launch when no clip is erased).
+
+`EvalPrefetcher` is the same machinery for the batch structure of the frozen video eval (a list over segments of `RawClipBatch`,
+labels, clip indices): it iterates like the loader it wraps and hands out what `run_one_epoch` takes.
 """
 import torch
 
@@ -94,8 +99,14 @@ class DevicePrefetcher:
         if out is None or tuple(out.shape) != shape or out.dtype != torch.float32:
             out = torch.empty(shape, dtype=torch.float32, device=self.device)
             self._dev[slot][("clip", i)] = out
-        return ops.clip_transform(frames, desc, boxes, raw.crop_size, raw.mean, raw.std, out=out,
-                                  stream=self.copy_stream.cuda_stream)
+        ops.clip_transform(frames, desc, boxes, raw.crop_size, raw.mean, raw.std, out=out, stream=self.copy_stream.cuda_stream,
+                           pre=raw.pre)
+        if raw.erased:
+            noise = self._stage_flat(slot, ("noise", i), raw.noise)
+            ebox = self._stage(slot, ("ebox", i), raw.ebox)
+            noise_off = self._stage(slot, ("noise_off", i), raw.noise_off)
+            ops.clip_erase(out, ebox, noise, noise_off, stream=self.copy_stream.cuda_stream)
+        return out
 
     def _launch(self):
         clip_list, masks_enc, masks_pred = self.fetch()
@@ -142,3 +153,84 @@ class DevicePrefetcher:
             me = [repeat_interleave_batch(m, self.batch_size, repeat=self.num_clips) for m in me]
             mp = [repeat_interleave_batch(m, self.batch_size, repeat=self.num_clips) for m in mp]
         return clips_d, me, mp
+
+
+class EvalPrefetcher(DevicePrefetcher):
+    """The input edge of the frozen video eval.  `loader` yields `(segments, labels, clip_indices)` with `segments` a list over
+    temporal segments of `RawClipBatch` (uint8 frames once per clip, V view-major box rows per clip:
+    evals/video_classification_frozen/utils.py); iterating the prefetcher yields, per batch,
+
+        ([[view 0, ..., view V-1] per segment] of fp32 [B,3,T,S,S] device tensors, labels, [clip indices per segment])
+
+    all on the device -- what `run_one_epoch` and the probe bank's `_view_features` build themselves from fp32 loader batches with
+    `.to(device)` (which is the identity on these).  The reference does those copies in front of the forward (eval.py:313-317);
+    here batch k+1 is fetched, copied and transformed on the copy stream while batch k's frozen forward runs.  Slot reuse and the
+    pinned-buffer wait are DevicePrefetcher's.  The tensors of a batch stay valid until the second `next` after it."""
+
+    def __init__(self, loader, device, depth=2, timing=False):
+        """timing=True keeps, per batch, a pair of timing events in `edge_events`: the compute stream arriving at the input edge
+        and the copy stream having finished the batch (tools/eval_bench.py reads the wait from them)."""
+        super().__init__(None, device, depth=depth)
+        self.loader = loader
+        self._it = None
+        self.timing, self.edge_events = timing, []
+
+    def __len__(self):
+        return len(self.loader)
+
+    @property
+    def dataset(self):
+        return self.loader.dataset
+
+    def _launch(self):
+        segments, labels, clip_indices = next(self._it)
+        slot = self._slot
+        self._slot = (slot + 1) % self.depth
+        if self._h2d_done[slot] is not None:
+            self._h2d_done[slot].synchronize()         # the DMA engine is done with this slot's pinned staging buffers
+        with torch.cuda.stream(self.copy_stream):
+            if self._free_ev[slot] is not None:
+                self.copy_stream.wait_event(self._free_ev[slot])
+            clips = []
+            for i, raw in enumerate(segments):
+                if not isinstance(raw, RawClipBatch):
+                    raise TypeError(f"EvalPrefetcher: segment {i} is {type(raw).__name__}, expected the RawClipBatch that the eval's "
+                                    "transforms collate to (fp32 batches go to run_one_epoch as they are)")
+                out, B = self._stage_raw(slot, i, raw), len(raw) // raw.num_views
+                clips.append([out[v * B:(v + 1) * B] for v in range(raw.num_views)])
+            lab = self._stage(slot, "labels", torch.as_tensor(labels))
+            idx = [self._stage(slot, ("idx", i), torch.as_tensor(ci)) for i, ci in enumerate(clip_indices)]
+            ready = torch.cuda.Event(enable_timing=self.timing)
+            ready.record(self.copy_stream)
+        self._h2d_done[slot] = ready
+        self._inflight = (slot, ready, clips, lab, idx)
+
+    def __iter__(self):
+        self._it = iter(self.loader)
+        self._inflight = None
+        return self
+
+    def __next__(self):
+        cur = torch.cuda.current_stream()
+        if self._last_slot is not None:   # everything that read the previous batch has been enqueued by now
+            ev = torch.cuda.Event()
+            ev.record(cur)
+            self._free_ev[self._last_slot] = ev
+        if self._inflight is None:
+            self._launch()               # StopIteration of the loader ends the epoch
+        slot, ready, clips, lab, idx = self._inflight
+        self._inflight = None
+        if self.timing:
+            arrive = torch.cuda.Event(enable_timing=True)
+            arrive.record(cur)
+            self.edge_events.append((arrive, ready))
+        cur.wait_event(ready)
+        self._last_slot = slot
+        try:
+            self._launch()               # batch k+1 overlaps the forward of batch k
+        except StopIteration:
+            self._inflight = None
+        return clips, lab, idx
+
+    def next(self, lookahead=True):
+        raise TypeError("EvalPrefetcher is iterated like the loader it wraps")

@@ -9,9 +9,15 @@ arithmetic, CSV columns, checkpoint dictionary and folder / file names.  Differe
   - the frozen encoder and the probe compute in bf16 with fp32 accumulation and statistics on the HIP kernels of this package;
     the reference's fp16 autocast (eval.py:323) would do nothing to these modules and is not entered.  `use_bfloat16` still
     selects the GradScaler path of the update, as in the reference.
-  - there are no real video datasets: `data.dataset_type` must be `synthetic` (seeded labelled clips,
-    src/datasets/data_manager.py: SyntheticVideoClassification); extension keys `data.synthetic_length` (items per split,
-    default 8 batches) and `data.num_workers` (default 0).
+  - there are no real video datasets: `data.dataset_type` must be `synthetic` (seeded labelled fp32 views,
+    src/datasets/data_manager.py: SyntheticVideoClassification) or `synthetic_frames` (seeded labelled uint8 frames of mixed source
+    sizes, SyntheticFramesClassification, through the eval's own transforms: .utils make_transforms with the reference's
+    reprob 0.25 for training and its centre-crop / multi-view forms for validation); extension keys `data.synthetic_length` (items
+    per split, default 8 batches) and `data.num_workers` (default 0).
+  - uint8 frames are what crosses to the device: the transforms only draw, the views are made by vj_clip_transform_pre and
+    vj_clip_erase on a copy stream, and batch k+1 uploads while batch k's frozen forward runs (engine.input.EvalPrefetcher).
+    `auto_augment` is false where the reference's probe training sets it true (PIL RandAugment is not implemented; logged once),
+    and the short-side resize of the validation transforms is the loader's job (the synthetic frames have that short side).
   - the classifier is wrapped in DistributedDataParallel only when a process group with more than one rank is active; its
     checkpoint keys carry the `module.` prefix either way, so checkpoints move between this package and the reference.
   - with `pretrain.frames_per_clip` == 1 the encoder is the 2-D image ViT under FrameAggregation, which (as in the reference) only
@@ -29,7 +35,8 @@ import torch
 import torch.nn.functional as F
 from torch.nn.parallel import DistributedDataParallel
 
-from ...src.datasets.data_manager import SyntheticVideoClassification
+from ...engine.input import EvalPrefetcher
+from ...src.datasets.data_manager import SyntheticFramesClassification, SyntheticVideoClassification
 from ...src.models import vision_transformer as vit
 from ...src.models.attentive_pooler import AttentiveClassifier
 from ...src.utils.distributed import AllReduce, init_distributed
@@ -37,7 +44,7 @@ from ...src.utils.logging import AverageMeter, CSVLogger, get_logger
 from ...src.utils.schedulers import CosineWDSchedule, WarmupCosineSchedule
 from ..multihead import parse_multihead_kwargs
 from ..multihead import run as run_multihead
-from .utils import ClipAggregation, FrameAggregation
+from .utils import ClipAggregation, FrameAggregation, make_transforms
 
 logger = get_logger(__name__)
 
@@ -46,6 +53,8 @@ np.random.seed(_GLOBAL_SEED)
 torch.manual_seed(_GLOBAL_SEED)
 
 pp = pprint.PrettyPrinter(indent=4)
+
+_randaugment_logged = False
 
 
 def _distributed():
@@ -152,6 +161,9 @@ def main(args_eval, resume_preempt=False):
                                    num_views_per_segment=1, training=True, **common)
     val_loader = make_dataloader(root_path=val_data_path, num_segments=eval_num_segments,
                                  num_views_per_segment=eval_num_views_per_segment, training=False, **common)
+    if str(dataset_type).lower() == 'synthetic_frames':
+        # uint8 frames: the views are made on the device, and the upload of batch k+1 runs under batch k's frozen forward
+        train_loader, val_loader = EvalPrefetcher(train_loader, device), EvalPrefetcher(val_loader, device)
     ipe = len(train_loader)
     logger.info(f'Dataloader created... iterations per epoch: {ipe}')
 
@@ -351,18 +363,34 @@ def load_pretrained(encoder, pretrained, checkpoint_key='target_encoder'):
 def make_dataloader(root_path, batch_size, world_size, rank, dataset_type='VideoDataset', resolution=224, frames_per_clip=16,
                     frame_step=4, num_segments=8, eval_duration=None, num_views_per_segment=1, allow_segment_overlap=True,
                     training=False, num_workers=12, subset_file=None, num_classes=None, synthetic_length=None, seed=None):
-    """The reference's loader factory (eval.py:442-488) for `dataset_type: synthetic`; every real dataset type raises, as
-    data_manager.init_data does."""
-    if str(dataset_type).lower() != 'synthetic':
+    """The reference's loader factory (eval.py:442-488) for `dataset_type: synthetic` (finished fp32 views) and
+    `synthetic_frames` (uint8 frames through the eval's transforms, with the reference's arguments: eval.py:460-469 -- batches of
+    RawClipBatch, one per segment, for engine.input.EvalPrefetcher); every real dataset type raises, as data_manager.init_data
+    does."""
+    kind = str(dataset_type).lower()
+    if kind not in ('synthetic', 'synthetic_frames'):
         raise NotImplementedError(
             f"dataset_type={dataset_type!r}: the reference's decord/torchvision video pipeline is not part of this package; "
-            "use data.dataset_type: synthetic, or pass your own loader to run_one_epoch")
+            "use data.dataset_type: synthetic or synthetic_frames, or pass your own loader to run_one_epoch")
     if num_classes is None:
-        raise ValueError("make_dataloader(dataset_type='synthetic') needs num_classes")
+        raise ValueError(f"make_dataloader(dataset_type={kind!r}) needs num_classes")
     length = synthetic_length if synthetic_length is not None else 8 * batch_size * world_size
-    dataset = SyntheticVideoClassification(length, num_classes, frames_per_clip, resolution, num_segments=num_segments,
-                                           num_views_per_segment=num_views_per_segment, frame_step=frame_step,
-                                           seed=(0 if training else 1) if seed is None else seed)
+    seed = (0 if training else 1) if seed is None else seed
+    if kind == 'synthetic_frames':
+        global _randaugment_logged
+        if training and not _randaugment_logged:
+            _randaugment_logged = True
+            logger.info("probe training: the reference's RandAugment (auto_augment=True, eval.py:465) is NOT applied -- it runs "
+                        "through PIL on the CPU; the random resized crop and RandomErasing (reprob 0.25) are")
+        transform = make_transforms(training=training, num_views_per_clip=num_views_per_segment, random_horizontal_flip=False,
+                                    random_resize_aspect_ratio=(0.75, 4/3), random_resize_scale=(0.08, 1.0), reprob=0.25,
+                                    auto_augment=False, motion_shift=False, crop_size=resolution)
+        short = None if training else (resolution if num_views_per_segment > 1 else int(resolution * 256 / 224))
+        dataset = SyntheticFramesClassification(length, num_classes, frames_per_clip, resolution, transform,
+                                                num_segments=num_segments, short_side=short, frame_step=frame_step, seed=seed)
+    else:
+        dataset = SyntheticVideoClassification(length, num_classes, frames_per_clip, resolution, num_segments=num_segments,
+                                               num_views_per_segment=num_views_per_segment, frame_step=frame_step, seed=seed)
     sampler = torch.utils.data.distributed.DistributedSampler(dataset, num_replicas=world_size, rank=rank, shuffle=training)
     return torch.utils.data.DataLoader(dataset, sampler=sampler, batch_size=batch_size, drop_last=False,
                                        num_workers=num_workers, pin_memory=True, persistent_workers=False)

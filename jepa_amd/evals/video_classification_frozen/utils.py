@@ -4,11 +4,21 @@ ClipAggregation keeps the reference's constructor, attributes and forward contra
 over views of [B,C,T,H,W] clips; the output is a list over views of [B, S*N, D] (attend_across_segments) or a list over views of
 lists over segments of [B, N, D].  The frozen encoder runs on every clip in the reference's order (segment-major, then view, then
 sample) and the per-view concatenation is written by the bit-exact row copy (vj_copy_rows) straight into one bf16 buffer per
-view.  The reference's video transforms (make_transforms and the decord loader behind them) are not part of this package.
+view.
+
+`make_transforms`, `VideoTransform` and `EvalVideoTransform` (utils.py:162-323) keep the reference's names, signatures and DRAWS and
+do no pixel work: they take decoded uint8 [T,H,W,3] frames and return a `RawClip` (app/vjepa/transforms.py) in the eval's
+normalise-first form -- the frames as they came, the crop boxes of every view, the flip, the RandomErasing box and noise -- and
+`engine.input.EvalPrefetcher` makes the fp32 views on the device (vj_clip_transform_pre, vj_clip_erase).  Out of scope, raising:
+`auto_augment=True` (PIL RandAugment) and the short-side resize of the two validation forms (cv2.resize in the reference), which is
+the loader's job here.  The decord loader behind the transforms is not part of this package.
 """
+import numpy as np
 import torch
 import torch.nn as nn
 
+from ...app.vjepa.transforms import RawClip, draw_erase
+from ...app.vjepa.transforms import VideoTransform as _PretrainVideoTransform
 from ...hip import ops
 from ...src.models.utils.pos_embs import get_1d_sincos_pos_embed
 
@@ -172,3 +182,132 @@ class ClipAggregation(nn.Module):
                 ops.copy_rows(f[k:k + n], outs[j][b:b + n], n, N, 0, num_clips * N, i * N, N, D)
                 k += n
         return outs
+
+
+def make_transforms(
+    training=True,
+    random_horizontal_flip=True,
+    random_resize_aspect_ratio=(3/4, 4/3),
+    random_resize_scale=(0.3, 1.0),
+    reprob=0.0,
+    auto_augment=False,
+    motion_shift=False,
+    crop_size=224,
+    num_views_per_clip=1,
+    normalize=((0.485, 0.456, 0.406),
+               (0.229, 0.224, 0.225))
+):
+    if not training and num_views_per_clip > 1:
+        return EvalVideoTransform(num_views_per_clip=num_views_per_clip, short_side_size=crop_size, normalize=normalize)
+    return VideoTransform(
+        training=training, random_horizontal_flip=random_horizontal_flip, random_resize_aspect_ratio=random_resize_aspect_ratio,
+        random_resize_scale=random_resize_scale, reprob=reprob, auto_augment=auto_augment, motion_shift=motion_shift,
+        crop_size=crop_size, normalize=normalize)
+
+
+def _uint8_frames(buffer, who):
+    frames = torch.as_tensor(np.asarray(buffer) if isinstance(buffer, (list, tuple)) else buffer)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError(f"{who}: expected a uint8 [T,H,W,3] buffer, got {frames.dtype} {tuple(frames.shape)}")
+    return frames.contiguous()
+
+
+def _normalize_constants(normalize):
+    """mean and std as the fp32 values the reference holds (torch.tensor(normalize), 0..1 units), as Python floats."""
+    t = torch.tensor(normalize, dtype=torch.float32)
+    return tuple(t[0].tolist()), tuple(t[1].tolist())
+
+
+def _require_short_side(H, W, want, who):
+    if min(H, W) != want:
+        raise ValueError(f"{who}: frames of {H}x{W} do not have the short side {want} that the reference's Resize would leave; the "
+                         "bilinear short-side resize is the loader's job (it is not done on the device), so hand in frames whose "
+                         f"short side is {want}")
+
+
+class VideoTransform(object):
+    """The reference's eval VideoTransform (utils.py:199-283) as draws.  training=True: the random-resized-crop box (or two, with
+    motion shift), the flip and the RandomErasing box and noise, in the reference's order on the global generators; the device
+    normalises every source pixel first and resizes after.  training=False: the centre crop of frames whose short side already is
+    int(crop_size * 256 / 224).  Either way the call returns one `RawClip` (one view) that holds the frames untouched, where the
+    reference returns a list with one finished fp32 view."""
+
+    def __init__(
+        self,
+        training=True,
+        random_horizontal_flip=True,
+        random_resize_aspect_ratio=(3/4, 4/3),
+        random_resize_scale=(0.3, 1.0),
+        reprob=0.0,
+        auto_augment=False,
+        motion_shift=False,
+        crop_size=224,
+        normalize=((0.485, 0.456, 0.406),
+                   (0.229, 0.224, 0.225))
+    ):
+        if auto_augment:
+            raise NotImplementedError("auto_augment=True: RandAugment runs through PIL on the CPU and is not the crop / flip / "
+                                      "normalise / erase arithmetic the device kernels implement")
+        self.training = training
+        self.short_side_size = int(crop_size * 256 / 224)
+        self.random_horizontal_flip = random_horizontal_flip
+        self.random_resize_aspect_ratio = random_resize_aspect_ratio
+        self.random_resize_scale = random_resize_scale
+        self.auto_augment = auto_augment
+        self.motion_shift = motion_shift
+        self.crop_size = crop_size
+        self.reprob = reprob
+        self.mean, self.std = _normalize_constants(normalize)
+        # box(es) and flip are drawn exactly as in pretraining (the same functions of src/datasets/utils/video/transforms.py)
+        self._spatial = _PretrainVideoTransform(
+            random_horizontal_flip=random_horizontal_flip, random_resize_aspect_ratio=random_resize_aspect_ratio,
+            random_resize_scale=random_resize_scale, motion_shift=motion_shift, crop_size=crop_size, normalize=normalize)
+
+    def __call__(self, buffer):
+        frames = _uint8_frames(buffer, "VideoTransform")
+        T, H, W, _ = frames.shape
+        S = self.crop_size
+        if not self.training:
+            _require_short_side(H, W, self.short_side_size, "VideoTransform(training=False)")
+            x1 = int(round((W - S) / 2.))
+            y1 = int(round((H - S) / 2.))
+            boxes = torch.tensor([y1, x1, S, S], dtype=torch.int32).repeat(1, T, 1)
+            return RawClip(frames, boxes, False, S, self.mean, self.std, pre=True)
+        boxes, flip = self._spatial.draw(T, H, W)
+        ebox, noise = ((0, 0, 0, 0), None)
+        if self.reprob > 0:
+            ebox, noise = draw_erase(self.reprob, T, S, S)
+        return RawClip(frames, boxes, flip, S, self.mean, self.std, pre=True, ebox=ebox, noise=noise)
+
+
+class EvalVideoTransform(object):
+    """The reference's multi-view validation transform (utils.py:286-323) as boxes: `num_views_per_clip` crops of side
+    `short_side_size` along the long side of frames whose short side already is `short_side_size`, starting at multiples of
+    spatial_step = (max(H, W) - side) // (views - 1).  Returns ONE `RawClip` whose box table is [V,T,4], where the reference returns
+    a list of V finished views: the views share the frames, which cross to the device once."""
+
+    def __init__(
+        self,
+        num_views_per_clip=1,
+        short_side_size=224,
+        normalize=((0.485, 0.456, 0.406),
+                   (0.229, 0.224, 0.225))
+    ):
+        if num_views_per_clip < 2:
+            raise ValueError("EvalVideoTransform: the reference divides by num_views_per_clip - 1; one view is VideoTransform(training=False)")
+        self.views_per_clip = num_views_per_clip
+        self.short_side_size = short_side_size
+        self.mean, self.std = _normalize_constants(normalize)
+
+    def view_starts(self, H, W):
+        spatial_step = (max(H, W) - self.short_side_size) // (self.views_per_clip - 1)
+        return [i * spatial_step for i in range(self.views_per_clip)]
+
+    def __call__(self, buffer):
+        frames = _uint8_frames(buffer, "EvalVideoTransform")
+        T, H, W, _ = frames.shape
+        S = self.short_side_size
+        _require_short_side(H, W, S, "EvalVideoTransform")
+        rows = [[start, 0, S, S] if H > W else [0, start, S, S] for start in self.view_starts(H, W)]
+        boxes = torch.tensor(rows, dtype=torch.int32)[:, None, :].repeat(1, T, 1)
+        return RawClip(frames, boxes, False, S, self.mean, self.std, pre=True)

@@ -148,11 +148,13 @@ def image_pack(images, tubelet, patch, idx=None, out=None, stream=None):
     return out
 
 
-def clip_transform(frames, desc, boxes, S, mean, std, out=None, stream=None):
+def clip_transform(frames, desc, boxes, S, mean, std, out=None, stream=None, pre=False):
     """Decoded uint8 frames -> fp32 clips [B,3,T,S,S]: per-frame crop + bilinear resize to S x S, clip flip, (x - mean) / std.
     frames: flat uint8 buffer of [T,Hs,Ws,3] clips; desc int64 [B,4] = (byte offset, Hs, Ws, flip); boxes int32 [B,T,4] =
     (i, j, h, w); mean / std: three floats each in 0..255 units.  The tables must have been validated on the host
-    (jepa_amd.app.vjepa.transforms.RawClipBatch.validate) before they were copied to the device."""
+    (jepa_amd.app.vjepa.transforms.RawClipBatch.validate) before they were copied to the device.
+    pre=True is the frozen eval's normalise-first form (vj_clip_transform_pre): every source pixel becomes (u / 255 - mean) / std
+    with mean / std in 0..1 units before the blend, and a box of side S is a bit-exact crop."""
     lib = load_library()
     _req(frames, torch.uint8, "frames")
     _req(desc, I64, "desc")
@@ -171,9 +173,28 @@ def clip_transform(frames, desc, boxes, S, mean, std, out=None, stream=None):
         _req(out, F32, "out")
         if tuple(out.shape) != (B, 3, T, S, S):
             raise ValueError(f"clip_transform: out {tuple(out.shape)} is not {(B, 3, T, S, S)}")
-    check(lib.vj_clip_transform(_ptr(frames), frames.numel(), _ptr(desc), _ptr(boxes), _ptr(out), B, T, S, *mean, *std,
-                                _stream(stream)), "vj_clip_transform")
+    fn, what = (lib.vj_clip_transform_pre, "vj_clip_transform_pre") if pre else (lib.vj_clip_transform, "vj_clip_transform")
+    check(fn(_ptr(frames), frames.numel(), _ptr(desc), _ptr(boxes), _ptr(out), B, T, S, *mean, *std, _stream(stream)), what)
     return out
+
+
+def clip_erase(clips, ebox, noise, noise_off, stream=None):
+    """RandomErasing in cube mode, in place: clips[b,c,t,top+y,left+x] = noise[noise_off[b] + ((t*3+c)*h+y)*w+x] for
+    ebox[b] = (top, left, h, w) (h == 0: clip b stays as it is).  clips fp32 [B,3,T,S,S]; ebox int32 [B,4]; noise fp32 [n];
+    noise_off int64 [B].  Bit-exact; an empty noise buffer (no clip of the batch is erased) launches nothing."""
+    lib = load_library()
+    _req(clips, F32, "clips")
+    _req(ebox, torch.int32, "ebox")
+    _req(noise, F32, "noise")
+    _req(noise_off, I64, "noise_off")
+    if clips.dim() != 5 or clips.shape[1] != 3 or clips.shape[3] != clips.shape[4] or tuple(ebox.shape) != (clips.shape[0], 4) \
+            or noise.dim() != 1 or tuple(noise_off.shape) != (clips.shape[0],):
+        raise ValueError(f"clip_erase: clips {tuple(clips.shape)} / ebox {tuple(ebox.shape)} / noise {tuple(noise.shape)} / noise_off "
+                         f"{tuple(noise_off.shape)}: expected [B,3,T,S,S], [B,4], [n], [B]")
+    B, _, T, S, _ = clips.shape
+    check(lib.vj_clip_erase(_ptr(clips), _ptr(ebox), _ptr(noise), noise.numel(), _ptr(noise_off), B, T, S, _stream(stream)),
+          "vj_clip_erase")
+    return clips
 
 
 def add_pos_bcast(y, pos, B, S, Gt, out=None, stream=None):

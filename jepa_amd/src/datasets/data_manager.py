@@ -104,6 +104,68 @@ class SyntheticVideoClassification(torch.utils.data.Dataset):
         return clips, label, indices
 
 
+class SyntheticFramesClassification(torch.utils.data.Dataset):
+    """Seeded labelled uint8 frame buffers for the frozen video-classification eval: the decoded-video counterpart of
+    SyntheticVideoClassification.  Item layout: ([S segments] of transform(uint8 [T,Hs,Ws,3]), label, [S] of int64 frame indices);
+    `transform` is one of the eval's transforms (evals/video_classification_frozen/utils.py make_transforms), which return one
+    `RawClip` per segment that carries every spatial view.
+
+    Item i depends on (seed, i) alone.  Its label is uniform in [0, num_classes); its frames are the class pattern of
+    SyntheticVideoClassification (the same plane wave per channel, drawn from (pattern_seed, label), laid over the source frame in
+    relative coordinates) plus N(0,1) noise, mapped to bytes as 127.5 + 48 * value and clamped.  Source sizes are mixed and follow
+    `short_side`: None (training: the transform crops and resizes anything) cycles through sizes around `crop_size` -- landscape,
+    portrait, square, wide; a number (validation: the short side the reference's Resize would leave, which the transforms require)
+    cycles through landscape and portrait sources of that short side with odd and even long sides."""
+
+    def __init__(self, length, num_classes, frames_per_clip, crop_size, transform, num_segments=1, short_side=None, frame_step=4,
+                 seed=0, signal=1.0, pattern_seed=0):
+        if transform is None:
+            raise ValueError("SyntheticFramesClassification needs the eval's clip transform (make_transforms)")
+        self.length, self.num_classes, self.frames, self.crop = length, num_classes, frames_per_clip, crop_size
+        self.S, self.frame_step, self.seed, self.signal, self.pattern_seed = num_segments, frame_step, seed, signal, pattern_seed
+        self.transform, self.short_side = transform, short_side
+        c = crop_size
+        if short_side is None:
+            self.sizes = ((c * 8 // 7, c * 3 // 2), (c * 3 // 2, c * 9 // 8), (c, c), (c * 5 // 4, c * 2 + 1))
+        else:
+            s = short_side
+            self.sizes = ((s, s * 4 // 3 + 1), (s * 16 // 9, s), (s, s * 16 // 9), (s * 3 // 2 + 1, s))
+
+    def __len__(self):
+        return self.length
+
+    def source_size(self, i):
+        return self.sizes[(self.seed + i) % len(self.sizes)]
+
+    def _pattern(self, label, H, W):
+        g = torch.Generator().manual_seed((1 << 62) + self.pattern_seed * 1_000_003 + label)   # items use seeds < 2^62
+        f = 1.0 + 3.0 * torch.rand(3, 3, generator=g)                  # cycles per clip along (t, h, w), per channel
+        phase = 6.283185307179586 * torch.rand(3, generator=g)
+        amp = self.signal * (0.5 + torch.rand(3, generator=g))
+        t = torch.arange(self.frames, dtype=torch.float32) / self.frames
+        y = torch.arange(H, dtype=torch.float32) / H
+        x = torch.arange(W, dtype=torch.float32) / W
+        arg = (f[:, 0, None, None, None] * t[None, :, None, None] + f[:, 1, None, None, None] * y[None, None, :, None]
+               + f[:, 2, None, None, None] * x[None, None, None, :])
+        return (amp[:, None, None, None] * torch.cos(6.283185307179586 * arg + phase[:, None, None, None])).permute(1, 2, 3, 0)
+
+    def frames_of(self, i):
+        """(list over segments of uint8 [T,Hs,Ws,3] arrays, label) of item i, before the transform."""
+        g = torch.Generator().manual_seed((self.seed * 1_000_003 + i) % (1 << 62))
+        label = int(torch.randint(0, self.num_classes, (1,), generator=g))
+        H, W = self.source_size(i)
+        pat = self._pattern(label, H, W)
+        segs = [(127.5 + 48.0 * (torch.randn(self.frames, H, W, 3, generator=g) + pat)).clamp_(0, 255).to(torch.uint8).numpy()
+                for _ in range(self.S)]
+        return segs, label
+
+    def __getitem__(self, i):
+        segs, label = self.frames_of(i)
+        span = self.frames * self.frame_step
+        indices = [torch.arange(s * span, (s + 1) * span, self.frame_step, dtype=torch.int64) for s in range(self.S)]
+        return [self.transform(f) for f in segs], label, indices
+
+
 class SyntheticImageClassification(torch.utils.data.Dataset):
     """Seeded labelled images for the frozen image-classification eval, in the item layout of the reference's image datasets
     under its eval transform (evals/image_classification_frozen/eval.py:286, 404-409): (fp32 [3,H,W], label).

@@ -18,7 +18,16 @@ of 196 tokens.  The direct route (patch rows packed straight from the [B,C,T,H,W
 concatenated along the batch, segments along time, the permuted [B*T,C,H,W] fp32 copy through ATen, then the model) and against the
 direct route with one (segment, view) tensor per trunk call, the arms taking turns inside this process in both orders; frames/s and peak memory of each; the temporal position pass (vj_add_pos_frames);
 and vj_pos_interp2d_bicubic once per new size.
-python tools/eval_bench.py --frames [--rounds 4] [--reps 3]"""
+python tools/eval_bench.py --frames [--rounds 4] [--reps 3]
+
+--uint8: the input edge of the video eval on the K400 16x8x3 protocol (ViT-L/16-224, batch 4): one training and one validation
+iteration of run_one_epoch fed pinned fp32 views that it moves with `.to(device)` in front of the forward (the path of
+`dataset_type: synthetic`, and of the parent commit) against uint8 frames through EvalPrefetcher (the views made on the device, batch
+k+1 uploading under batch k's frozen forward), the two arms taking turns inside this process in both orders.  Per arm and round:
+host-to-device bytes per iteration, wall time per iteration, the wait at the input edge (fp32: the copies themselves, timed alone;
+uint8: how long the compute stream stood at the prefetcher's event), and the two kernels timed alone.  The host batches are built
+once, before the clock starts: what a loader costs to decode and draw is not part of these figures.
+python tools/eval_bench.py --uint8 [--rounds 3] [--reps 3]"""
 import argparse
 import json
 import os
@@ -311,8 +320,105 @@ def bench_frames(reps, rounds, B=2, S=8, V=3, T=16, res=224, max_frames=1024):
                                                  repeat_call_us=round(timed(lambda: ops.pos_interp2d_bicubic(table, scale), 20) * 1e3, 1)))
 
 
+def bench_uint8(reps, rounds, B=4, name="vitl16_k400_16x8x3"):
+    import random
+    import statistics
+    import time
+
+    import numpy as np
+    from jepa_amd.engine.input import EvalPrefetcher
+    from jepa_amd.evals.video_classification_frozen.utils import make_transforms
+    from jepa_amd.hip import ops
+    model_name, res, S, V, C = CONFIGS[name]
+    dev, T = "cuda", 16
+    random.seed(0)
+    np.random.seed(0)
+    torch.manual_seed(0)
+    enc = ClipAggregation(vit.__dict__[model_name](img_size=res, patch_size=16, num_frames=T, tubelet_size=2, uniform_power=True),
+                          tubelet_size=2, attend_across_segments=True).to(dev).eval()
+    for p in enc.parameters():
+        p.requires_grad = False
+    clf = AttentiveClassifier(embed_dim=enc.embed_dim, num_heads=enc.num_heads, depth=1, num_classes=C).to(dev)
+    opt, scaler, sched, wd_sched = init_opt(clf, iterations_per_epoch=1, start_lr=1e-4, ref_lr=1e-4, warmup=0,
+                                            num_epochs=10 ** 6, wd=0.01)
+    g = torch.Generator().manual_seed(0)
+    labels = torch.randint(0, C, (B,), generator=g)
+
+    def host_batch(training):
+        """(uint8 batch, the same batch as pinned fp32 views) in the loader's layout."""
+        tf = make_transforms(training=training, num_views_per_clip=1 if training else V, random_horizontal_flip=False,
+                             random_resize_aspect_ratio=(0.75, 4 / 3), random_resize_scale=(0.08, 1.0), reprob=0.25, crop_size=res)
+        hw = (240, 320) if training else (res, res * 4 // 3)       # a 4:3 source as decoded / after the reference's Resize(224)
+        items = [([tf(torch.randint(0, 256, (T,) + hw + (3,), generator=g, dtype=torch.uint8)) for _ in range(S)], int(labels[b]),
+                  [torch.arange(T) * 4 + s * 64 for s in range(S)]) for b in range(B)]
+        segs, lab, idx = torch.utils.data.default_collate(items)
+        segs = [s.pin_memory() for s in segs]
+        views = []
+        for raw in segs:
+            frames, desc, boxes = raw.to(dev)
+            out = ops.clip_transform(frames, desc, boxes, raw.crop_size, raw.mean, raw.std, pre=True)
+            if raw.erased:
+                ops.clip_erase(out, raw.ebox.to(dev), raw.noise.to(dev), raw.noise_off.to(dev))
+            n = len(raw) // raw.num_views
+            views.append([out[v * n:(v + 1) * n].cpu().pin_memory() for v in range(raw.num_views)])
+        return (segs, lab, idx), (views, lab, idx)
+
+    def kernels_alone(segs):
+        raw = segs[0]
+        frames, desc, boxes = raw.to(dev)
+        out = torch.empty((len(raw), 3, T, res, res), device=dev)
+        t_tf = timed(lambda: ops.clip_transform(frames, desc, boxes, raw.crop_size, raw.mean, raw.std, out=out, pre=True), 10)
+        er = next((s for s in segs if s.erased), None)
+        t_er = None
+        if er is not None:
+            eb, nz, no = er.ebox.to(dev), er.noise.to(dev), er.noise_off.to(dev)
+            t_er = timed(lambda: ops.clip_erase(out, eb, nz, no), 10)
+        return t_tf, t_er
+
+    def copies_alone(views):
+        return timed(lambda: [[v.to(dev, non_blocking=True) for v in seg] for seg in views], 3)
+
+    out = {}
+    for training in (True, False):
+        raw, fp32 = host_batch(training)
+        args = (1, S, True) if training else (V, S, True)
+        n_it = reps + 1
+        rows = []
+        for r in range(rounds):
+            order = ("fp32", "uint8") if r % 2 == 0 else ("uint8", "fp32")
+            row = {}
+            for arm in order:
+                pf = EvalPrefetcher([raw] * n_it, torch.device(dev), timing=True) if arm == "uint8" else None
+                loader = pf if pf is not None else [fp32] * n_it
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                run_one_epoch(dev, training, enc, clf, scaler, opt, sched, wd_sched, loader, False, *args)
+                torch.cuda.synchronize()
+                wall = (time.perf_counter() - t0) * 1e3 / n_it
+                if pf is not None:
+                    waits = [max(0.0, a.elapsed_time(b)) for a, b in pf.edge_events]
+                    row[arm] = dict(h2d_mb=round(pf.bytes_copied / n_it / 1e6, 1), iteration_ms=round(wall, 2),
+                                    edge_wait_ms_first=round(waits[0], 2), edge_wait_ms_rest=round(statistics.mean(waits[1:]), 3))
+                else:
+                    nbytes = sum(v.numel() * 4 for seg in fp32[0] for v in seg)
+                    row[arm] = dict(h2d_mb=round(nbytes / 1e6, 1), iteration_ms=round(wall, 2),
+                                    edge_wait_ms=round(copies_alone(fp32[0]), 2))
+            row["uint8_faster"] = row["uint8"]["iteration_ms"] < row["fp32"]["iteration_ms"]
+            rows.append(row)
+        t_tf, t_er = kernels_alone(raw[0])
+        out["train" if training else "val"] = dict(
+            rounds=rows, uint8_faster_in_every_round=all(r["uint8_faster"] for r in rows),
+            clip_transform_pre_ms_per_segment=round(t_tf, 3), clip_erase_ms_per_segment=None if t_er is None else round(t_er, 4),
+            rows_per_segment=len(raw[0][0]), erased_clips=int(sum(int((s.ebox[:, 2] > 0).sum()) for s in raw[0])),
+            noise_mb=round(sum(s.noise.numel() for s in raw[0]) * 4 / 1e6, 3))
+        del raw, fp32
+        torch.cuda.empty_cache()
+    return dict(config=name, batch=B, reps=reps, iterations_per_arm=reps + 1, **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--uint8", action="store_true", help="the video eval's input edge: fp32 views + .to(device) against uint8 frames + prefetch")
     ap.add_argument("--frames", action="store_true", help="FrameAggregation on the ViT-L/16 image model instead of the video eval")
     ap.add_argument("--image", action="store_true", help="the image-classification eval instead of the video one")
     ap.add_argument("--image-configs", nargs="*", default=["vitl16_in1k", "vith16_384_in1k"], choices=sorted(IMAGE_CONFIGS))
@@ -321,6 +427,9 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--bank", type=int, default=0, help="also time the training iteration with a bank of this many probes")
     a = ap.parse_args()
+    if a.uint8:
+        print(json.dumps(bench_uint8(a.reps, a.rounds)), flush=True)
+        return
     if a.frames:
         print(json.dumps(bench_frames(a.reps, a.rounds)), flush=True)
         return
