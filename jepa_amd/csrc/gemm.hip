@@ -11,7 +11,9 @@
 // multiplied.  Staging is LDS-DMA (global_load_lds_dwordx4: no VGPR round trip) with the XOR swizzle applied on the
 // per-lane SOURCE address (the DMA destination is lane-linear).  The MFMA is issued with swapped operands (D = Bfrag x Afrag) so each lane owns four
 // CONSECUTIVE output columns: 8-byte bf16 / 16-byte fp32 epilogue accesses for C, bias, residual and aux.
-// Workgroup ids are remapped so every XCD (private L2) works on a contiguous band of tiles.
+// Workgroup ids are remapped so every XCD (private L2) works on a contiguous band of tiles.  Shared with the other GEMM files
+// (gemm_common.hpp): xcd_logical / tile_of / unit_k_range, called one by one as in gemm8.hip (gemm_unit, which wraps them, reorders this
+// kernel's prologue: profiles/gemm_bodies_refactor.md), the launcher preamble and the epilogues.
 #include "gemm_common.hpp"
 #include "internal.hpp"
 #include "options.hpp"
@@ -69,18 +71,10 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4 ? 2 : 1)) void gemm_nt_
 
   // ---- XCD-aware, grouped tile mapping (bijective for any grid size) ----
   const int ntile = p.tiles_m * p.tiles_n;
-  const int nblk = ntile * p.splitk;
-  const int bid = blockIdx.x;
-  const int qx = nblk >> 3, rx = nblk & 7, xcd = bid & 7, pos = bid >> 3;
-  const int logical_all = (xcd < rx ? xcd * (qx + 1) : rx * (qx + 1) + (xcd - rx) * qx) + pos;
+  const int logical_all = xcd_logical(blockIdx.x, ntile * p.splitk);
   const int slice = logical_all / ntile;
-  const int logical = logical_all - slice * ntile;
-  constexpr int GM = 8;
-  const int per_group = GM * p.tiles_n;
-  const int group = logical / per_group, in_g = logical - group * per_group;
-  const int first_m = group * GM;
-  const int gsz = (p.tiles_m - first_m) < GM ? (p.tiles_m - first_m) : GM;
-  const int tm = first_m + in_g % gsz, tn = in_g / gsz;
+  int tm, tn;
+  tile_of(logical_all - slice * ntile, p.tiles_m, p.tiles_n, tm, tn);
   const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
 
   f32x4_t acc[FM][FN];
@@ -89,9 +83,8 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4 ? 2 : 1)) void gemm_nt_
 #pragma unroll
     for (int j = 0; j < FN; j++) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
-  const int nk_all = (int)(p.K / BK);
-  const int kt0 = slice * p.ktiles_per;
-  const int kt1 = (kt0 + p.ktiles_per) < nk_all ? (kt0 + p.ktiles_per) : nk_all;
+  int kt0, nkt;   // this workgroup's K-tile range (split-K for wgrads)
+  unit_k_range<BK>(p, slice, kt0, nkt);
 
   // fragment read offsets (bytes inside a tile), constant across K-tiles
   const int frow = lane & 15, fg = lane >> 4;
@@ -112,7 +105,6 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4 ? 2 : 1)) void gemm_nt_
   }
 
   constexpr int LOADS = NIT_A + NIT_B;  // LDS-DMA instructions per thread per stage
-  const int nkt = kt1 - kt0;
   // prologue: put the first NS-1 stages in flight
 #pragma unroll
   for (int st = 0; st < NS - 1; st++) {
@@ -196,29 +188,13 @@ int vj_splitk_reduce(const GemmArgs& b, hipStream_t stream) {
 template <int BK, int NS, int EPI, int BM, int BN, int WM, int WN>
 static int launch_gemm(const GemmArgs& a, void* ws, int64_t ws_bytes, hipStream_t stream) {
   constexpr int smem = NS * (BM + BN) * BK * 2;
-  // function-local static with an initialiser: set exactly once, thread-safe (the C ABI is re-entrant)
-  static VjPerDeviceOnce attr_once;   // the dynamic-LDS limit is a per-device attribute of the function
-  attr_once([] {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<BK, NS, EPI, BM, BN, WM, WN>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-  });
+  set_max_dynamic_lds<gemm_nt_kernel<BK, NS, EPI, BM, BN, WM, WN>>(smem);
+  // wgrad: fill the chip (>= 2 waves of workgroups); each slice keeps >= 8 K-tiles of work.  Concurrent workgroups per round: 2 per CU for
+  // the 4-wave tiles, 1 per CU for 256x256; K-tile time scales with the tile area and BK
+  const int slots = (BM * BN >= 256 * 256) ? 256 : 512;
+  const double us_kt = 1.45 * ((double)BM * BN * BK) / (256.0 * 256.0 * 64.0) * (slots == 512 ? 2.6 : 1.3);
   GemmArgs b = a;
-  b.tiles_m = (int)cdiv64(a.M, BM);
-  b.tiles_n = (int)cdiv64(a.N, BN);
-  b.splitk = 1;
-  b.ws = nullptr;
-  const int nk = (int)(a.K / BK);
-  if (EPI == EPI_F32 && ws != nullptr) {
-    // wgrad: fill the chip (>= 2 waves of workgroups); each slice keeps >= 8 K-tiles of work
-    const int64_t tiles = (int64_t)b.tiles_m * b.tiles_n;
-    // concurrent workgroups per round: 2 per CU for the 4-wave tiles, 1 per CU for 256x256; K-tile time scales with
-    // the tile area and BK
-    const int slots = (BM * BN >= 256 * 256) ? 256 : 512;
-    const double us_kt = 1.45 * ((double)BM * BN * BK) / (256.0 * 256.0 * 64.0) * (slots == 512 ? 2.6 : 1.3);
-    b.splitk = pick_splitk(tiles, nk, slots, us_kt, 8, a.M, a.N, ws_bytes);
-    b.ws = (float*)ws;
-  }
-  vj_splitk_finish_plan(nk, b.splitk, b.ktiles_per);
+  plan_tiles(b, BM, BN, BK, slots, us_kt, EPI == EPI_F32 ? ws : nullptr, ws_bytes);
   const int nblk = b.tiles_m * b.tiles_n * b.splitk;
   hipLaunchKernelGGL((gemm_nt_kernel<BK, NS, EPI, BM, BN, WM, WN>), dim3(nblk), dim3(WM * WN * 64), smem, stream,
                      b);

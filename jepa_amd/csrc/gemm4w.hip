@@ -19,7 +19,9 @@
 //     phase 3: read ra0(next) from A0, issue part +3, wait for B(next) | 16 MFMA  acc[4..7][0..1] += rb0 x ra1
 // Hazards: a part is read only after a barrier that follows every thread's counted wait for it; a slot is re-filled at
 // least two barriers after the section that read it last (see the slot arithmetic next to issue_part4).
-#include "gemm_common.hpp"
+// Shared with gemm8.hip / gemm8p.hip (gemm_tile.hpp): per-thread part offsets, quadrant MFMAs, tail waits; with every one-tile kernel
+// (gemm_common.hpp): work-unit decode, launcher preamble, epilogues.  Its own: twelve row-group bases, fragments as two bases + immediates.
+#include "gemm_tile.hpp"
 #include "internal.hpp"
 #include <type_traits>
 #include <cstdlib>
@@ -28,13 +30,6 @@
 #define W4_BN 128
 #define W4_BK 64
 #define W4_SLOTS 5
-
-// wait until at most `parts` younger parts (4 DMA instructions each) are still in flight
-__device__ __forceinline__ void wait_parts(int parts) {
-  if (parts >= 2) wait_vmcnt<8>();
-  else if (parts == 1) wait_vmcnt<4>();
-  else wait_vmcnt<0>();
-}
 
 // part index p: -1 = A0(0);  3T = B(T), 3T+1 = A1(T), 3T+2 = A0(T+1).  Slot (p+5) % 5: part p+5 overwrites part p, and
 // part p+5 is issued in the section that reads part p+2 -- part p was read three sections (>= 2 barriers) earlier.
@@ -83,6 +78,16 @@ __device__ __forceinline__ void issue_edge(const GemmArgs& p, int kind, int tile
   }
 }
 
+// fragments first .. first + N - 1 of a part: fragment i sits 16 rows = 2048 bytes behind fragment 0 with the same swizzle key, so the two
+// per-lane bases of fragment 0 (one per k-step) + immediates cover all of them
+template <int N>
+__device__ __forceinline__ void read_frags(bf16x8_t (&r)[N][2], const char* slot, const int (&base)[2], int first) {
+#pragma unroll
+  for (int i = 0; i < N; i++)
+#pragma unroll
+    for (int ks = 0; ks < 2; ks++) r[i][ks] = *(const bf16x8_t*)(slot + base[ks] + (first + i) * 2048);
+}
+
 // K loop of one workgroup.  EDGE: the tile sticks out of the matrix (clamped per-chunk addressing); otherwise one base
 // pointer per operand.  The steady state (all three look-ahead parts exist) is straight-line: unconditional issues and a
 // constant vmcnt(8); the last two K-tiles run the same phases with existence checks and shrinking wait counts.
@@ -97,16 +102,13 @@ __device__ __forceinline__ void k_loop_4w(const GemmArgs& p, char* smem, f32x4_t
 #pragma unroll
   for (int ks = 0; ks < 2; ks++) {
     const int c = ks * 4 + fg;
-    a_base[ks] = (wm * 64 + frow) * 128 + ((c ^ (frow & 7)) * 16);
-    b_base[ks] = (wn * 64 + frow) * 128 + ((c ^ (frow & 7)) * 16);
+    a_base[ks] = part_chunk_off(wm * 64 + frow, c);
+    b_base[ks] = part_chunk_off(wn * 64 + frow, c);
   }
   PartBase src;
   unsigned voff_a = 0, voff_b = 0;
   if constexpr (!EDGE) {
-    const int r0 = tid >> 3, cpos = tid & 7;
-    const int c = cpos ^ (r0 & 7);   // rows r0 + 32 j share r0 & 7
-    voff_a = (unsigned)((r0 * p.lda + c * 8) * 2);
-    voff_b = (unsigned)((r0 * p.ldb + c * 8) * 2);
+    part_voff<false>(tid, p.lda, p.ldb, voff_a, voff_b);   // rows r0 + 32 j share r0 & 7
     const char* a0 = (const char*)(p.A + m0 * p.lda + (int64_t)kt0 * W4_BK);
     const char* b0 = (const char*)(p.B + n0 * p.ldb + (int64_t)kt0 * W4_BK);
 #pragma unroll
@@ -134,7 +136,7 @@ __device__ __forceinline__ void k_loop_4w(const GemmArgs& p, char* smem, f32x4_t
     }
   };
   auto wait_for = [&](int q) {   // this thread's share of part q has landed; younger parts stay in flight
-    if (q <= last_part) wait_parts(issued - q);
+    if (q <= last_part) wait_younger_parts<4>(issued - q);
   };
 
   // ---- prologue: A0(0) -> slot 4, B(0) -> 0, A1(0) -> 1 in flight; A0(0) and B(0) landed for everyone; A0(1) -> slot 2
@@ -144,11 +146,7 @@ __device__ __forceinline__ void k_loop_4w(const GemmArgs& p, char* smem, f32x4_t
   wait_for(0);
   section_barrier();
   {
-    const char* slot = smem + 4 * LDS_PART_BYTES;
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int ks = 0; ks < 2; ks++) ra0[i][ks] = *(const bf16x8_t*)(slot + a_base[ks] + i * 2048);
+    read_frags(ra0, smem + 4 * LDS_PART_BYTES, a_base, 0);
     issue_if(2, K0{}, 1, 2);
   }
 
@@ -157,86 +155,50 @@ __device__ __forceinline__ void k_loop_4w(const GemmArgs& p, char* smem, f32x4_t
     int s = s0 + d;
     return s >= 2 * W4_SLOTS ? s - 2 * W4_SLOTS : (s >= W4_SLOTS ? s - W4_SLOTS : s);
   };
-  auto mma = [&](auto quad_tag, const bf16x8_t (&rb)[2][2], const bf16x8_t (&ra)[4][2]) {
-    constexpr int QI = decltype(quad_tag)::value >> 1, QJ = decltype(quad_tag)::value & 1;   // accumulator quadrant
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ks++)
-#pragma unroll
-      for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-          acc[4 * QI + i][2 * QJ + j] =
-              __builtin_amdgcn_mfma_f32_16x16x32_bf16(rb[j][ks], ra[i][ks], acc[4 * QI + i][2 * QJ + j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  using Q00 = std::integral_constant<int, 0>;
-  using Q01 = std::integral_constant<int, 1>;
-  using Q10 = std::integral_constant<int, 2>;
-  using Q11 = std::integral_constant<int, 3>;
-
   auto k_tile = [&](int t, auto tail_tag) {
     constexpr bool TAIL = decltype(tail_tag)::value;
     const int pb = 3 * t;
     // ---------------- phase 0: rb0 <- B(t); part +3 = B(t+1)
     {
-      const char* slot = smem + s0 * LDS_PART_BYTES;
-#pragma unroll
-      for (int j = 0; j < 2; j++)
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++) rb0[j][ks] = *(const bf16x8_t*)(slot + b_base[ks] + j * 2048);
+      read_frags(rb0, smem + s0 * LDS_PART_BYTES, b_base, 0);
       if constexpr (TAIL) issue_if(pb + 3, K1{}, t + 1, slot_of(3));
       else issue(K1{}, t + 1, slot_of(3));
       section_barrier();
-      mma(Q00{}, rb0, ra0);
+      quad_mma<0, 0>(acc, rb0, ra0);
     }
     // ---------------- phase 1: rb1 <- B(t); A1(t) must land
     {
-      const char* slot = smem + s0 * LDS_PART_BYTES;
-#pragma unroll
-      for (int j = 0; j < 2; j++)
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++) rb1[j][ks] = *(const bf16x8_t*)(slot + b_base[ks] + (2 + j) * 2048);
+      read_frags(rb1, smem + s0 * LDS_PART_BYTES, b_base, 2);
       if constexpr (TAIL) wait_for(pb + 1);
-      else wait_parts(2);
+      else wait_younger_parts<4>(2);
       section_barrier();
-      mma(Q01{}, rb1, ra0);
+      quad_mma<0, 1>(acc, rb1, ra0);
     }
     // ---------------- phase 2: ra1 <- A1(t); part +3 = A1(t+1); A0(t+1) must land
     {
-      const char* slot = smem + slot_of(1) * LDS_PART_BYTES;
-#pragma unroll
-      for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++) ra1[i][ks] = *(const bf16x8_t*)(slot + a_base[ks] + i * 2048);
+      read_frags(ra1, smem + slot_of(1) * LDS_PART_BYTES, a_base, 0);
       if constexpr (TAIL) {
         issue_if(pb + 4, K2{}, t + 1, slot_of(4));
         wait_for(pb + 2);
       } else {
         issue(K2{}, t + 1, slot_of(4));
-        wait_parts(2);
+        wait_younger_parts<4>(2);
       }
       section_barrier();
-      mma(Q11{}, rb1, ra1);
+      quad_mma<1, 1>(acc, rb1, ra1);
     }
     // ---------------- phase 3: ra0 <- A0(t+1); part +3 = A0(t+2); B(t+1) must land
     {
-      if (!TAIL || t + 1 < nk) {
-        const char* slot = smem + slot_of(2) * LDS_PART_BYTES;
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-          for (int ks = 0; ks < 2; ks++) ra0[i][ks] = *(const bf16x8_t*)(slot + a_base[ks] + i * 2048);
-      }
+      if (!TAIL || t + 1 < nk) read_frags(ra0, smem + slot_of(2) * LDS_PART_BYTES, a_base, 0);
       if constexpr (TAIL) {
         issue_if(pb + 5, K0{}, t + 2, slot_of(5));
         wait_for(pb + 3);
       } else {
         issue(K0{}, t + 2, slot_of(5));
-        wait_parts(2);
+        wait_younger_parts<4>(2);
       }
       section_barrier();
-      mma(Q10{}, rb0, ra1);
+      quad_mma<1, 0>(acc, rb0, ra1);
     }
     s0 = slot_of(3);
   };
@@ -256,15 +218,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_4w_kernel(GemmArgs p) {
   const int wm = wave_u >> 1, wn = wave_u & 1;
   const int frow = lane & 15, fg = lane >> 4;
 
-  const int ntile = p.tiles_m * p.tiles_n;
-  const int logical_all = xcd_logical(blockIdx.x, ntile * p.splitk);
-  const int slice = logical_all / ntile;
-  int tm, tn;
-  tile_of(logical_all - slice * ntile, p.tiles_m, p.tiles_n, tm, tn);
-  const int64_t m0 = (int64_t)tm * W4_BM, n0 = (int64_t)tn * W4_BN;
-  const int nk_all = (int)(p.K / W4_BK);
-  const int kt0 = slice * p.ktiles_per;
-  const int nk = (kt0 + p.ktiles_per < nk_all ? kt0 + p.ktiles_per : nk_all) - kt0;
+  const GemmUnit u = gemm_unit<W4_BM, W4_BN, W4_BK>(p);
+  const int64_t m0 = u.m0, n0 = u.n0;
   const bool interior = (m0 + W4_BM <= p.M) && (n0 + W4_BN <= p.N);   // workgroup-uniform
 
   f32x4_t acc[8][4];
@@ -272,18 +227,18 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_4w_kernel(GemmArgs p) {
   for (int i = 0; i < 8; i++)
 #pragma unroll
     for (int j = 0; j < 4; j++) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-  if (interior) k_loop_4w<false>(p, smem, acc, m0, n0, kt0, nk, tid, wave_u, wm, wn, frow, fg);
-  else k_loop_4w<true>(p, smem, acc, m0, n0, kt0, nk, tid, wave_u, wm, wn, frow, fg);
+  if (interior) k_loop_4w<false>(p, smem, acc, m0, n0, u.kt0, u.nk, tid, wave_u, wm, wn, frow, fg);
+  else k_loop_4w<true>(p, smem, acc, m0, n0, u.kt0, u.nk, tid, wave_u, wm, wn, frow, fg);
   if (p.dbg & 1) {
-    if (acc[0][0][0] == 12345.678f && acc[7][3][3] == 0.5f) *(float*)p.C = acc[3][2][1];
+    acc_sink(p, acc);
     return;
   }
-  const int elane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  const int elane = lane_id();
   const int efrow = elane & 15, efg = elane >> 4;
   if (!(p.dbg & 2) && gemm_epilogue_try_staged<EPI, 8, false>(p, acc, m0 + wm * 128, n0 + wn * 64, efrow, efg, elane,
                                                               smem + wave_u * 16384))
     return;
-  gemm_epilogue<EPI, 8, 4, /*INTERIOR_VARIANT=*/(EPI == EPI_F32), false>(p, acc, m0 + wm * 128, n0 + wn * 64, efrow, efg, slice);
+  gemm_epilogue<EPI, 8, 4, /*INTERIOR_VARIANT=*/(EPI == EPI_F32), false>(p, acc, m0 + wm * 128, n0 + wn * 64, efrow, efg, u.slice);
 }
 
 // (A persistent form of this kernel -- two workgroups per CU walking tile lists -- was built in round 5: bit-identical, slower on every
@@ -292,10 +247,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_4w_kernel(GemmArgs p) {
 template <int EPI>
 static int launch4w(const GemmArgs& a, void* ws, int64_t ws_bytes, hipStream_t stream) {
   constexpr int smem = W4_SLOTS * LDS_PART_BYTES;
-  static VjPerDeviceOnce attr_once;   // the dynamic-LDS limit is a per-device attribute of the function
-  attr_once([] {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_4w_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-  });
+  set_max_dynamic_lds<gemm_nt_4w_kernel<EPI>>(smem);
   static const bool occ_dbg = [] {
     if (getenv("VJ_GEMM_DBG_OCC")) {
       int n = -1;
@@ -305,18 +257,8 @@ static int launch4w(const GemmArgs& a, void* ws, int64_t ws_bytes, hipStream_t s
     return true;
   }();
   (void)occ_dbg;
-  GemmArgs b = a;
-  b.tiles_m = (int)cdiv64(a.M, W4_BM);
-  b.tiles_n = (int)cdiv64(a.N, W4_BN);
-  b.splitk = 1;
-  b.ws = nullptr;
-  const int nk = (int)(a.K / W4_BK);
-  if (EPI == EPI_F32 && ws != nullptr) {   // wgrad: 512 workgroup slots per round, K-tile time of a half-size tile
-    const int64_t tiles = (int64_t)b.tiles_m * b.tiles_n;
-    b.splitk = pick_splitk(tiles, nk, 512, 1.45, 8, a.M, a.N, ws_bytes);
-    b.ws = (float*)ws;
-  }
-  vj_splitk_finish_plan(nk, b.splitk, b.ktiles_per);
+  GemmArgs b = a;   // wgrad: 512 workgroup slots per round, K-tile time of a half-size tile
+  plan_tiles(b, W4_BM, W4_BN, W4_BK, 512, 1.45, EPI == EPI_F32 ? ws : nullptr, ws_bytes);
   hipLaunchKernelGGL(gemm_nt_4w_kernel<EPI>, dim3(b.tiles_m * b.tiles_n * b.splitk), dim3(256), smem, stream, b);
   VJ_LAUNCH_CHECK("vj_gemm_bf16_nt(4-wave)");
   return vj_splitk_reduce(b, stream);

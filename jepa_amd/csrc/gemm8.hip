@@ -13,20 +13,19 @@
 //     section of one wave overlaps the MFMA section of the other.
 // Hazards: part q is read only after a barrier that follows every thread's vmcnt for it (end of L(q-1)); its slot is
 // re-filled by part q+8 issued in L(q+4), >= 7 barrier intervals after the last read.
-#include "gemm_common.hpp"
+// Shared with gemm8p.hip / gemm4w.hip (gemm_tile.hpp): part image offsets, fragment reads, quadrant MFMAs, row-group bases, tail waits;
+// with every one-tile kernel (gemm_common.hpp): K range of a work unit, launcher preamble, epilogues.  Its own: the tile decode and the
+// fragment-offset loops (profiles/gemm_bodies_refactor.md: the shared forms cost this kernel 1 - 2 %).
+#include "gemm_tile.hpp"
 #include "internal.hpp"
 
 #define P8_BM 256
 #define P8_BN 256
 #define P8_BK 64
 
-// Interior tiles (all 256 x 256 rows exist): a part's two chunks per thread are rows r0 and r0 + 64 of the part at the
-// same swizzled chunk column, so their addresses are a WAVE-UNIFORM base per (operand, sub-part, j) -- fixed for the
-// whole K loop, held in SGPRs -- plus one 32-bit per-thread byte offset per operand (+ 128 bytes per K-tile).  That
-// removes the 64-bit VALU address arithmetic (v_mad_u64_u32 / v_lshl_add_u64 per chunk) from every load section.
+// Interior tiles (all 256 x 256 rows exist): wave-uniform row-group bases, fixed for the whole K loop, + one per-thread offset per operand
 struct PartBase8 {
-  const char* a[2][2];   // [sub-part mq][j]: A rows m0 + j*128 + mq*64 (+ r0)
-  const char* b[2][2];   // [sub-part nq][j]: B rows n0 + j*128 + nq*32 (+ (r0>>5)*64 + (r0&31))
+  RowGroupBases rg;
   unsigned voff_a, voff_b;
 };
 
@@ -47,8 +46,8 @@ __device__ __forceinline__ void issue_part(const GemmArgs& p, const PartBase8& p
 #pragma unroll
     for (int j = 0; j < 2; j++) {
       const unsigned dst = slot + (j * 512 + wave_u * 64) * 16;
-      if (isA) dma16_sv(pb.a[sub][j], pb.voff_a + koff, dst);
-      else dma16_sv(pb.b[sub][j], pb.voff_b + koff, dst);
+      if (isA) dma16_sv(pb.rg.a(sub, j), pb.voff_a + koff, dst);
+      else dma16_sv(pb.rg.b(sub, j), pb.voff_b + koff, dst);
     }
     return;
   }
@@ -83,26 +82,14 @@ __device__ __forceinline__ void gemm8_body(const GemmArgs& p, char* smem, int tm
   const int frow = lane & 15, fg = lane >> 4;
 
   const int64_t m0 = (int64_t)tm * P8_BM, n0 = (int64_t)tn * P8_BN;
-  const int nk_all = (int)(p.K / P8_BK);
-  const int kt0 = slice * p.ktiles_per;                   // this workgroup's K-tile range (split-K for wgrads)
-  const int nk = (kt0 + p.ktiles_per < nk_all ? kt0 + p.ktiles_per : nk_all) - kt0;
+  int kt0, nk;   // this workgroup's K-tile range (split-K for wgrads)
+  unit_k_range<P8_BK>(p, slice, kt0, nk);
   const int last_part = 4 * nk - 2;   // parts: -1 (A0 of tile 0), then per tile B0, B1, A1 and A0 of the next tile
   PartBase8 pb;
   if constexpr (!EDGE) {
-    const int r0 = tid >> 3, cpos = tid & 7;          // chunk j of a part: part row j*64 + r0, chunk column cpos
-    const int c = cpos ^ (r0 & 7);
-    const int rb = (r0 >> 5) * 64 + (r0 & 31);        // B parts interleave the four wave columns' 32-row halves
-    pb.voff_a = (unsigned)((r0 * p.lda + c * 8) * 2);
-    pb.voff_b = (unsigned)((rb * p.ldb + c * 8) * 2);
-    const char* a0 = (const char*)(p.A + m0 * p.lda + (int64_t)kt0 * P8_BK);
-    const char* b0 = (const char*)(p.B + n0 * p.ldb + (int64_t)kt0 * P8_BK);
-#pragma unroll
-    for (int sub = 0; sub < 2; sub++)
-#pragma unroll
-      for (int j = 0; j < 2; j++) {
-        pb.a[sub][j] = a0 + (int64_t)(j * 128 + sub * 64) * p.lda * 2;
-        pb.b[sub][j] = b0 + (int64_t)(j * 128 + sub * 32) * p.ldb * 2;
-      }
+    part_voff(tid, p.lda, p.ldb, pb.voff_a, pb.voff_b);
+    make_row_group_bases(pb.rg, (const char*)(p.A + m0 * p.lda + (int64_t)kt0 * P8_BK), (const char*)(p.B + n0 * p.ldb + (int64_t)kt0 * P8_BK),
+                         p.lda * 2, p.ldb * 2);
   }
 
   f32x4_t acc[8][4];
@@ -112,21 +99,15 @@ __device__ __forceinline__ void gemm8_body(const GemmArgs& p, char* smem, int tm
     for (int j = 0; j < 4; j++) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
   bf16x8_t ra0[4][2], ra1[4][2], rb0[2][2], rb1[2][2];  // [fragment][k-step]
 
-  // per-lane fragment byte offsets inside a part (rows are 128 B, chunks XOR-swizzled by row & 7)
+  // per-lane fragment byte offsets inside a part (frag_offsets' loops written out: the call moves this kernel's register allocation)
   int a_off[4][2], b_off[2][2];
 #pragma unroll
   for (int ks = 0; ks < 2; ks++) {
     const int c = ks * 4 + fg;
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int pr = wm * 64 + i * 16 + frow;
-      a_off[i][ks] = pr * 128 + ((c ^ (pr & 7)) * 16);
-    }
+    for (int i = 0; i < 4; i++) a_off[i][ks] = part_chunk_off(wm * 64 + i * 16 + frow, c);
 #pragma unroll
-    for (int j = 0; j < 2; j++) {
-      const int pr = wn * 32 + j * 16 + frow;
-      b_off[j][ks] = pr * 128 + ((c ^ (pr & 7)) * 16);
-    }
+    for (int j = 0; j < 2; j++) b_off[j][ks] = part_chunk_off(wn * 32 + j * 16 + frow, c);
   }
 
   // ---- prologue: parts -1 (A0 of tile 0), 0, 1, 2 in flight; part -1 landed for everyone
@@ -139,16 +120,10 @@ __device__ __forceinline__ void gemm8_body(const GemmArgs& p, char* smem, int tm
   section_barrier();
   if (late_group) section_barrier();
   // L(-1): A0 fragments of tile 0; issue part 3; part 0 must have landed before the next barrier
-  {
-    const char* slot = smem + 7 * LDS_PART_BYTES;   // (-1 + 8) % 8
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int ks = 0; ks < 2; ks++) ra0[i][ks] = *(const bf16x8_t*)(slot + a_off[i][ks]);
-    if (3 <= last_part) issue_part<EDGE>(p, pb, 3, m0, n0, kt0, smem, tid, wave_u);
-    if (3 <= last_part) wait_vmcnt<6>();
-    else wait_vmcnt<0>();
-  }
+  frag_read_a(ra0, smem + 7 * LDS_PART_BYTES, a_off);   // slot (-1 + 8) % 8
+  if (3 <= last_part) issue_part<EDGE>(p, pb, 3, m0, n0, kt0, smem, tid, wave_u);
+  if (3 <= last_part) wait_vmcnt<6>();
+  else wait_vmcnt<0>();
   section_barrier();
   section_barrier();
 
@@ -162,85 +137,33 @@ __device__ __forceinline__ void gemm8_body(const GemmArgs& p, char* smem, int tm
       if (t > 0) {          // first K-tile the fragment reads are skipped -- WRONG results, same MFMA operands forever -- which
       } else                // bounds what moving the LDS reads out of the load sections could buy
 #endif
-      if (ph == 0) {
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-          for (int ks = 0; ks < 2; ks++) rb0[j][ks] = *(const bf16x8_t*)(slot + b_off[j][ks]);
-      } else if (ph == 1) {
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-          for (int ks = 0; ks < 2; ks++) rb1[j][ks] = *(const bf16x8_t*)(slot + b_off[j][ks]);
-      } else if (ph == 2) {
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-          for (int ks = 0; ks < 2; ks++) ra1[i][ks] = *(const bf16x8_t*)(slot + a_off[i][ks]);
-      } else if (t + 1 < nk) {
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-          for (int ks = 0; ks < 2; ks++) ra0[i][ks] = *(const bf16x8_t*)(slot + a_off[i][ks]);
-      }
+      if (ph == 0) frag_read_b(rb0, slot, b_off);
+      else if (ph == 1) frag_read_b(rb1, slot, b_off);
+      else if (ph == 2) frag_read_a(ra1, slot, a_off);
+      else if (t + 1 < nk) frag_read_a(ra0, slot, a_off);
       if (q + 4 <= last_part) {
         issue_part<EDGE>(p, pb, q + 4, m0, n0, kt0, smem, tid, wave_u);
         wait_vmcnt<6>();                              // part q+1 landed; q+2..q+4 in flight
-      } else {                                     // tail: fewer younger parts behind part q+1
-        const int younger = last_part - (q + 1);
-        if (younger >= 2) wait_vmcnt<4>();
-        else if (younger == 1) wait_vmcnt<2>();
-        else wait_vmcnt<0>();
+      } else {
+        wait_younger_parts<2>(last_part - (q + 1));   // tail: fewer younger parts behind part q+1
       }
       section_barrier();
       // ---------------- C(q): one quadrant x K = 64
-      __builtin_amdgcn_s_setprio(1);
-      if (ph == 0) {
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++)
-#pragma unroll
-          for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rb0[j][ks], ra0[i][ks], acc[i][j], 0, 0, 0);
-      } else if (ph == 1) {
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++)
-#pragma unroll
-          for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-              acc[i][2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rb1[j][ks], ra0[i][ks], acc[i][2 + j], 0, 0, 0);
-      } else if (ph == 2) {
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++)
-#pragma unroll
-          for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-              acc[4 + i][2 + j] =
-                  __builtin_amdgcn_mfma_f32_16x16x32_bf16(rb1[j][ks], ra1[i][ks], acc[4 + i][2 + j], 0, 0, 0);
-      } else {
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++)
-#pragma unroll
-          for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-              acc[4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rb0[j][ks], ra1[i][ks], acc[4 + i][j], 0, 0, 0);
-      }
-      __builtin_amdgcn_s_setprio(0);
+      if (ph == 0) quad_mma<0, 0>(acc, rb0, ra0);
+      else if (ph == 1) quad_mma<0, 1>(acc, rb1, ra0);
+      else if (ph == 2) quad_mma<1, 1>(acc, rb1, ra1);
+      else quad_mma<1, 0>(acc, rb0, ra1);
       section_barrier();
     }
   }
   if (!late_group) section_barrier();   // the early group matches the late group's extra barrier
   if (p.dbg & 1) {   // diagnostics: no output traffic (keeps the accumulators alive through one predicated store)
-    if (acc[0][0][0] == 12345.678f && acc[7][3][3] == 0.5f) *(float*)p.C = acc[3][2][1];
+    acc_sink(p, acc);
     return;
   }
   // every wave is past its last LDS read and every DMA has landed: the ring is free, 16 KB of it per wave.
   // The lane id is re-derived here (mbcnt) so that nothing epilogue-only stays live across the K loop (256 VGPRs).
-  const int elane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  const int elane = lane_id();
   const int efrow = elane & 15, efg = elane >> 4;
   if (!(p.dbg & 2) && gemm_epilogue_try_staged<EPI, 8, false>(p, acc, m0 + wm * 128, n0 + wn * 64, efrow, efg, elane,
                                                     smem + wave_u * 16384))
@@ -268,23 +191,9 @@ __global__ __launch_bounds__(512) void gemm_nt_8phase_kernel(GemmArgs p) {
 template <int EPI>
 static int launch8(const GemmArgs& a, void* ws, int64_t ws_bytes, hipStream_t stream) {
   constexpr int smem = 8 * LDS_PART_BYTES;
-  // function-local static with an initialiser: set exactly once, thread-safe (the C ABI is re-entrant)
-  static VjPerDeviceOnce attr_once;   // the dynamic-LDS limit is a per-device attribute of the function
-  attr_once([] {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_8phase_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-  });
-  GemmArgs b = a;
-  b.tiles_m = (int)cdiv64(a.M, P8_BM);
-  b.tiles_n = (int)cdiv64(a.N, P8_BN);
-  b.splitk = 1;
-  b.ws = nullptr;
-  const int nk = (int)(a.K / P8_BK);
-  if (EPI == EPI_F32 && ws != nullptr) {   // wgrad: one workgroup per CU needs >= ~256 of them; >= 8 K-tiles per slice
-    const int64_t tiles = (int64_t)b.tiles_m * b.tiles_n;
-    b.splitk = pick_splitk(tiles, nk, 256, 1.45, 8, a.M, a.N, ws_bytes);
-    b.ws = (float*)ws;
-  }
-  vj_splitk_finish_plan(nk, b.splitk, b.ktiles_per);
+  set_max_dynamic_lds<gemm_nt_8phase_kernel<EPI>>(smem);
+  GemmArgs b = a;   // wgrad: one workgroup per CU needs >= ~256 of them; >= 8 K-tiles per slice
+  plan_tiles(b, P8_BM, P8_BN, P8_BK, 256, 1.45, EPI == EPI_F32 ? ws : nullptr, ws_bytes);
   hipLaunchKernelGGL(gemm_nt_8phase_kernel<EPI>, dim3(b.tiles_m * b.tiles_n * b.splitk), dim3(512), smem, stream, b);
   VJ_LAUNCH_CHECK("vj_gemm_bf16_nt(8-phase)");
   return vj_splitk_reduce(b, stream);

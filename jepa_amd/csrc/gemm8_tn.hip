@@ -20,9 +20,10 @@
 //   * the LDS-DMA is issued through inline assembly (lds_pipe.hpp): after the builtin form the compiler puts an
 //     `s_waitcnt vmcnt(0)` in front of the transpose reads.
 //
-// Split-K over the token tiles and the fp32 epilogue are shared with the NT kernels (gemm_common.hpp).
+// Split-K over the token tiles, the work-unit decode and the fp32 epilogue are shared with the NT kernels (gemm_common.hpp), the tail wait
+// ladder with the 256-row NT schedules (gemm_tile.hpp).  Its own: mma_rd, the quadrant MFMAs with the transpose reads pinned underneath.
 #include <type_traits>
-#include "gemm_common.hpp"
+#include "gemm_tile.hpp"
 #include "options.hpp"
 
 namespace {
@@ -152,14 +153,9 @@ __global__ __launch_bounds__(512) void gemm_tn_8phase_kernel(std::conditional_t<
     p = ga.g;
     logical_all = xcd_logical(blockIdx.x, p.tiles_m * p.tiles_n * p.splitk);
   }
-  const int ntile = p.tiles_m * p.tiles_n;
-  const int slice = logical_all / ntile;
-  int tm, tn;
-  tile_of(logical_all - slice * ntile, p.tiles_m, p.tiles_n, tm, tn);
-  const int64_t m0 = (int64_t)tm * 256, n0 = (int64_t)tn * 256;
-  const int nk_all = (int)((p.K + 63) / 64);
-  const int kt0 = slice * p.ktiles_per;
-  const int nk = (kt0 + p.ktiles_per < nk_all ? kt0 + p.ktiles_per : nk_all) - kt0;
+  const GemmUnit u = gemm_unit<256, 256, 64, /*K_ROUND_UP=*/true>(p, logical_all);
+  const int64_t m0 = u.m0, n0 = u.n0;
+  const int slice = u.slice, kt0 = u.kt0, nk = u.nk;
   const int last_part = 4 * nk - 2;
 
   f32x4_t acc[2][2][4][2];   // [row half][column half][16-row block][16-column block]
@@ -203,11 +199,7 @@ __global__ __launch_bounds__(512) void gemm_tn_8phase_kernel(std::conditional_t<
   // that opens the early group's C(q)) has waited for part q+1.  Prefetch distance 5 keeps three parts in flight as before.
   // Slot reuse: part p+8 is issued in L(p+3), at least two barriers after the last read of part p by either group.
   auto wait_landed = [&](int q) {   // tail-safe form of "part q+2 has landed": parts q+3 .. min(q+5, last_part) may be in flight
-    const int younger = last_part - (q + 2);
-    if (younger >= 3) wait_vmcnt<6>();
-    else if (younger == 2) wait_vmcnt<4>();
-    else if (younger == 1) wait_vmcnt<2>();
-    else wait_vmcnt<0>();
+    wait_younger_parts<2, 3>(last_part - (q + 2));
   };
   // 16 MFMAs of one accumulator quadrant with NF fragment loads (two transpose reads each) spread underneath them
   auto mma_rd = [&](f32x4_t (&acc4)[4][2], const bf16x8_t (&rb)[2][2], const bf16x8_t (&ra)[4][2], auto nf_tag, auto&& load_frag)
@@ -269,7 +261,7 @@ __global__ __launch_bounds__(512) void gemm_tn_8phase_kernel(std::conditional_t<
       fs.base[kind] = (const char*)((isA ? p.A + tok0 * p.lda : p.B + tok0 * p.ldb) + cbase);
       fs.lim[kind] = (int)((isA ? p.M : p.N) - cbase - 8);
     }
-    fs.tail_tile = (p.K & 63) ? nk_all - 1 - kt0 : -1;
+    fs.tail_tile = (p.K & 63) ? (int)((p.K + 63) / 64) - 1 - kt0 : -1;
   }
   const unsigned rowoff_a = (unsigned)tl.row0 * (unsigned)p.lda * 2u, rowoff_b = (unsigned)tl.row0 * (unsigned)p.ldb * 2u;
   auto issue_loop = [&](auto kind_tag, int q, int tile) __attribute__((always_inline)) {
@@ -337,7 +329,7 @@ __global__ __launch_bounds__(512) void gemm_tn_8phase_kernel(std::conditional_t<
   }
   if (!late_group) section_barrier();
 
-  const int elane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  const int elane = lane_id();
   const int efrow = elane & 15, efg = elane >> 4;
 #pragma unroll
   for (int ih = 0; ih < 2; ih++)
@@ -373,15 +365,6 @@ static GemmArgs tn_args(const void* dY, int64_t ldy, const void* X, int64_t ldx,
   return b;
 }
 
-template <bool GROUPED>
-static void tn_set_attr() {
-  static VjPerDeviceOnce attr_once;   // the dynamic-LDS limit is a per-device attribute of the function
-  attr_once([] {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_8phase_kernel<GROUPED>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              8 * LDS_PART_BYTES);
-  });
-}
-
 // dW[N1,N2] = alpha * dY[T,N1]^T X[T,N2] + beta * dW.  (backward of every nn.Linear on the path)
 extern "C" int vj_gemm_bf16_tn_splitk(const void* dY, int64_t ldy, const void* X, int64_t ldx, float* dW, int64_t ldw,
                                       int64_t T, int64_t N1, int64_t N2, float alpha, float beta, void* ws,
@@ -390,7 +373,7 @@ extern "C" int vj_gemm_bf16_tn_splitk(const void* dY, int64_t ldy, const void* X
   if (N1 == 0 || N2 == 0) return 0;
   if (int rc = tn_check("vj_gemm_bf16_tn_splitk", dY, ldy, X, ldx, dW, ldw, T, N1, N2)) return rc;
   VJ_CHECK_ARG(ws != nullptr && ws_bytes >= N1 * N2 * 4, "vj_gemm_bf16_tn_splitk: workspace must hold at least N1*N2 fp32");
-  tn_set_attr<false>();
+  set_max_dynamic_lds<gemm_tn_8phase_kernel<false>>(8 * LDS_PART_BYTES);
   TnSingleArgs a;
   GemmArgs& b = a.g;
   b = tn_args(dY, ldy, X, ldx, dW, ldw, T, N1, N2, alpha, beta);
@@ -454,7 +437,7 @@ extern "C" int vj_gemm_bf16_tn_grouped(const void* probs_v, int64_t n, int64_t T
     a.g[i] = a.g[a.n - 1];
   }
   VJ_CHECK_ARG(units < (1ll << 31), "vj_gemm_bf16_tn_grouped: grid too large");
-  tn_set_attr<true>();
+  set_max_dynamic_lds<gemm_tn_8phase_kernel<true>>(8 * LDS_PART_BYTES);
   hipLaunchKernelGGL(gemm_tn_8phase_kernel<true>, dim3((unsigned)units), dim3(512), 8 * LDS_PART_BYTES, stream, a);
   VJ_LAUNCH_CHECK("vj_gemm_bf16_tn_grouped");
   for (int i = 0; i < a.n; i++)

@@ -1,5 +1,6 @@
 // Persistent 8-phase bf16 MFMA GEMM for gfx950: C[M,N] = A[M,K] * B[N,K]^T, 256x256 tiles, 8 waves, BK = 64.
 //
+// Shared with gemm8.hip / gemm4w.hip (gemm_tile.hpp): part image and fragment offsets, fragment reads, quadrant MFMAs, row-group bases.
 // Same K loop as gemm8.hip (four 16 KB parts per K-tile in an 8-slot LDS ring, LDS-DMA four parts ahead, counted vmcnt across
 // raw barriers, two wave groups one barrier interval apart, MFMA 16x16x32 with swapped operands) and the same fused epilogues
 // (gemm_common.hpp), so every output is BIT-IDENTICAL to the one-tile-per-workgroup kernel.  What changes is everything
@@ -43,7 +44,7 @@
 // K % 64 == 0, K >= 256, more tiles than CUs, 16-byte-aligned rows of C (and aux), C not aliasing the residual.
 #include <type_traits>
 #include <atomic>
-#include "gemm_common.hpp"
+#include "gemm_tile.hpp"
 #include "internal.hpp"
 #include "options.hpp"
 
@@ -51,21 +52,6 @@
 #define PP_STAGE_PER_WAVE 4096
 
 namespace {
-
-// the 8 wave-uniform row-group bases of one tile: A rows m0 + j*128 + mq*64, B rows n0 + j*128 + nq*32 (byte pointers at k = 0)
-struct PpBases {
-  const char* a[2][2];   // [mq][j]
-  const char* b[2][2];   // [nq][j]
-};
-__device__ __forceinline__ void pp_make_bases(PpBases& pb, const char* a0, const char* b0, int64_t lda2, int64_t ldb2) {
-#pragma unroll
-  for (int sub = 0; sub < 2; sub++)
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-      pb.a[sub][j] = a0 + (int64_t)(j * 128 + sub * 64) * lda2;
-      pb.b[sub][j] = b0 + (int64_t)(j * 128 + sub * 32) * ldb2;
-    }
-}
 
 // logical tile index -> shifted tile origin (always a full 256 x 256 tile inside the matrix)
 __device__ __forceinline__ void pp_tile_origin(const GemmArgs& p, int logical, int64_t& m0, int64_t& n0, int& tm) {
@@ -120,45 +106,25 @@ __device__ __forceinline__ void pp_body(const GemmArgs& p) {
 
   const int nk = (int)(p.K / 64);
   const int64_t lda2 = p.lda * 2, ldb2 = p.ldb * 2;
-  // per-thread byte offsets of a part's chunks (see gemm8.hip): row r0 (+ 64 j), chunk column swizzled by the row
-  unsigned voff_a, voff_b;
-  {
-    const int r0 = tid >> 3, cpos = tid & 7;
-    const int c = cpos ^ (r0 & 7);
-    const int rb = (r0 >> 5) * 64 + (r0 & 31);        // B parts interleave the four wave columns' 32-row halves
-    voff_a = (unsigned)((r0 * p.lda + c * 8) * 2);
-    voff_b = (unsigned)((rb * p.ldb + c * 8) * 2);
-  }
+  unsigned voff_a, voff_b;   // per-thread byte offsets of a part's chunks
+  part_voff(tid, p.lda, p.ldb, voff_a, voff_b);
   const unsigned ring = lds_addr(smem);
   const unsigned dst_lane = (unsigned)(wave_u * 64) * 16;   // this wave's 1 KB piece inside each 8 KB half-part
 
-  // issue one part (two DMA instructions per thread): kind 0 B0, 1 B1, 2 A1, 3 A0 of K-tile `kt` into ring half `half`
-  auto issue = [&](auto kind_tag, const PpBases& bs, int kt, int half) __attribute__((always_inline)) {
+  // issue one part (two DMA instructions per thread): kind 0 B0, 1 B1, 2 A1, 3 A0 of K-tile `kt` into ring half `half`.  `bs` = the
+  // current tile's RowGroupBases, or the NEXT tile's RowGroupOrigin (tail of the K loop, once per tile): only its two origin pointers
+  // are kept in SGPRs, the row-group bases are derived at the issue site (a handful of SALU instructions per part)
+  auto issue = [&](auto kind_tag, const auto& bs, int kt, int half) __attribute__((always_inline)) {
     constexpr int KIND = decltype(kind_tag)::value;
     const unsigned slot = ring + (unsigned)(half * 4 + KIND) * LDS_PART_BYTES + dst_lane;
     const unsigned koff = (unsigned)kt * 128u;
     if constexpr (KIND == 0 || KIND == 1) {
-      dma16_sv(bs.b[KIND][0], voff_b + koff, slot);
-      dma16_sv(bs.b[KIND][1], voff_b + koff, slot + 512 * 16);
+      dma16_sv(bs.b(KIND, 0), voff_b + koff, slot);
+      dma16_sv(bs.b(KIND, 1), voff_b + koff, slot + 512 * 16);
     } else {
       constexpr int MQ = KIND == 2 ? 1 : 0;
-      dma16_sv(bs.a[MQ][0], voff_a + koff, slot);
-      dma16_sv(bs.a[MQ][1], voff_a + koff, slot + 512 * 16);
-    }
-  };
-  // the same for the NEXT tile (tail of the K loop, once per tile): only its two origin pointers are kept in SGPRs, the
-  // row-group bases are derived at the issue site (a handful of SALU instructions per part)
-  auto issue_next = [&](auto kind_tag, const char* a0n, const char* b0n, int kt, int half) __attribute__((always_inline)) {
-    constexpr int KIND = decltype(kind_tag)::value;
-    const unsigned slot = ring + (unsigned)(half * 4 + KIND) * LDS_PART_BYTES + dst_lane;
-    const unsigned koff = (unsigned)kt * 128u;
-    if constexpr (KIND == 0 || KIND == 1) {
-      dma16_sv(b0n + (int64_t)(KIND * 32) * ldb2, voff_b + koff, slot);
-      dma16_sv(b0n + (int64_t)(128 + KIND * 32) * ldb2, voff_b + koff, slot + 512 * 16);
-    } else {
-      constexpr int MQ = KIND == 2 ? 1 : 0;
-      dma16_sv(a0n + (int64_t)(MQ * 64) * lda2, voff_a + koff, slot);
-      dma16_sv(a0n + (int64_t)(128 + MQ * 64) * lda2, voff_a + koff, slot + 512 * 16);
+      dma16_sv(bs.a(MQ, 0), voff_a + koff, slot);
+      dma16_sv(bs.a(MQ, 1), voff_a + koff, slot + 512 * 16);
     }
   };
   using K_B0 = std::integral_constant<int, 0>;
@@ -179,59 +145,16 @@ __device__ __forceinline__ void pp_body(const GemmArgs& p) {
     wn_t = (half && !late_group) ? (2 + (wave_u & 1)) : wn;
     live = !(half && late_group);
     int tl = lane;
-    if constexpr (HALF) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(tl));
-    const int fr = tl & 15, fgq = tl >> 4;
-#pragma unroll
-    for (int ks = 0; ks < 2; ks++) {
-      const int c = ks * 4 + fgq;
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const int pr = wm_t * 64 + i * 16 + fr;
-        a_off[i][ks] = pr * 128 + ((c ^ (pr & 7)) * 16);
-      }
-#pragma unroll
-      for (int j = 0; j < 2; j++) {
-        const int pr = wn_t * 32 + j * 16 + fr;
-        b_off[j][ks] = pr * 128 + ((c ^ (pr & 7)) * 16);
-      }
-    }
+    if constexpr (HALF) tl = lane_id_volatile();
+    frag_offsets(a_off, b_off, wm_t, wn_t, tl & 15, tl >> 4);
   };
 
   f32x4_t acc[8][4];
   bf16x8_t ra0[4][2], ra1[4][2], rb0[2][2], rb1[2][2];  // [fragment][k-step]
 
-  auto read_a = [&](bf16x8_t (&ra)[4][2], const char* slot) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int ks = 0; ks < 2; ks++) ra[i][ks] = *(const bf16x8_t*)(slot + a_off[i][ks]);
-  };
-  auto read_b = [&](bf16x8_t (&rb)[2][2], const char* slot) __attribute__((always_inline)) {
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-#pragma unroll
-      for (int ks = 0; ks < 2; ks++) rb[j][ks] = *(const bf16x8_t*)(slot + b_off[j][ks]);
-  };
-  auto mma = [&](auto quad_tag, const bf16x8_t (&rb)[2][2], const bf16x8_t (&ra)[4][2]) __attribute__((always_inline)) {
-    constexpr int QI = decltype(quad_tag)::value >> 1, QJ = decltype(quad_tag)::value & 1;   // accumulator quadrant
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ks++)
-#pragma unroll
-      for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-          acc[4 * QI + i][2 * QJ + j] =
-              __builtin_amdgcn_mfma_f32_16x16x32_bf16(rb[j][ks], ra[i][ks], acc[4 * QI + i][2 * QJ + j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  using Q00 = std::integral_constant<int, 0>;
-  using Q01 = std::integral_constant<int, 1>;
-  using Q10 = std::integral_constant<int, 2>;
-  using Q11 = std::integral_constant<int, 3>;
-
-  PpBases cur;                              // wave-uniform (SGPR) row-group base pointers of the current tile
+  RowGroupBases cur;                        // wave-uniform (SGPR) row-group base pointers of the current tile
   const char *a0n = nullptr, *b0n = nullptr;   // origin pointers of the next tile
+  auto nxt = [&]() __attribute__((always_inline)) { return RowGroupOrigin{a0n, b0n, lda2, ldb2}; };   // (read by TAIL0 / TAIL1 only)
 
   using M_STEADY = std::integral_constant<int, PP_STEADY>;
   using M_HEAD0 = std::integral_constant<int, PP_HEAD0>;
@@ -264,15 +187,15 @@ __device__ __forceinline__ void pp_body(const GemmArgs& p) {
     const int ho = h ^ 1;
     // ---------------- LX
     if constexpr (LIVE) {
-      read_b(rb0, half_c + 0 * LDS_PART_BYTES);
-      read_b(rb1, half_c + 1 * LDS_PART_BYTES);
+      frag_read_b(rb0, half_c + 0 * LDS_PART_BYTES, b_off);
+      frag_read_b(rb1, half_c + 1 * LDS_PART_BYTES, b_off);
     }
     if constexpr (TAIL1) {
-      issue_next(K_A1{}, a0n, b0n, 0, ho);
-      issue_next(K_A0{}, a0n, b0n, 1, ho);
+      issue(K_A1{}, nxt(), 0, ho);
+      issue(K_A0{}, nxt(), 1, ho);
     } else if constexpr (TAIL0) {
       issue(K_A1{}, cur, t + 1, ho);
-      issue_next(K_A0{}, a0n, b0n, 0, ho);
+      issue(K_A0{}, nxt(), 0, ho);
     } else {
       issue(K_A1{}, cur, t + 1, ho);
       issue(K_A0{}, cur, t + 2, ho);
@@ -280,21 +203,21 @@ __device__ __forceinline__ void pp_body(const GemmArgs& p) {
     if constexpr (!HEAD0) wait_vmcnt<8>();
     section_barrier();
     if constexpr (LIVE) {
-      mma(Q00{}, rb0, ra0);
-      mma(Q01{}, rb1, ra0);
+      quad_mma<0, 0>(acc, rb0, ra0);
+      quad_mma<0, 1>(acc, rb1, ra0);
     }
     section_barrier();
     // ---------------- LY
     if constexpr (LIVE) {
-      read_a(ra1, half_c + 2 * LDS_PART_BYTES);
-      if constexpr (!TAIL1) read_a(ra0, half_c + 3 * LDS_PART_BYTES);   // (the next tile's A0(0) is read at its start, after the epilogue)
+      frag_read_a(ra1, half_c + 2 * LDS_PART_BYTES, a_off);
+      if constexpr (!TAIL1) frag_read_a(ra0, half_c + 3 * LDS_PART_BYTES, a_off);   // (the next tile's A0(0) is read at its start, after the epilogue)
     }
     if constexpr (TAIL1) {
-      issue_next(K_B0{}, a0n, b0n, 1, h);
-      issue_next(K_B1{}, a0n, b0n, 1, h);
+      issue(K_B0{}, nxt(), 1, h);
+      issue(K_B1{}, nxt(), 1, h);
     } else if constexpr (TAIL0) {
-      issue_next(K_B0{}, a0n, b0n, 0, h);
-      issue_next(K_B1{}, a0n, b0n, 0, h);
+      issue(K_B0{}, nxt(), 0, h);
+      issue(K_B1{}, nxt(), 0, h);
     } else {
       issue(K_B0{}, cur, t + 2, h);
       issue(K_B1{}, cur, t + 2, h);
@@ -302,8 +225,8 @@ __device__ __forceinline__ void pp_body(const GemmArgs& p) {
     if constexpr (!HEAD0 && !TAIL1) wait_vmcnt<8>();
     section_barrier();
     if constexpr (LIVE) {
-      mma(Q11{}, rb1, ra1);
-      mma(Q10{}, rb0, ra1);
+      quad_mma<1, 1>(acc, rb1, ra1);
+      quad_mma<1, 0>(acc, rb0, ra1);
     }
     section_barrier();
   };
@@ -312,7 +235,7 @@ __device__ __forceinline__ void pp_body(const GemmArgs& p) {
   int64_t m0, n0;
   int tm_cur;                                  // un-shifted row-tile index of the current tile (column-sum slot / row ownership)
   pp_tile_origin(p, band0 + pos, m0, n0, tm_cur);
-  pp_make_bases(cur, (const char*)(p.A + m0 * p.lda), (const char*)(p.B + n0 * p.ldb), lda2, ldb2);
+  make_row_group_bases(cur, (const char*)(p.A + m0 * p.lda), (const char*)(p.B + n0 * p.ldb), lda2, ldb2);
   int h = 0;                                   // ring half of the current tile's K-tile 0 (toggles every K-tile, across tiles)
   issue(K_A0{}, cur, 0, 1);                    // part -1: A0(0) -> half h^1, slot 3
   issue(K_B0{}, cur, 0, 0);
@@ -353,7 +276,7 @@ __device__ __forceinline__ void pp_body(const GemmArgs& p) {
       lap(4, st_tiles != 0);       // [epilogue end -> past the next tile's first barrier: the skew between the eight waves]
       next_origin();
       if (late_group) section_barrier();
-      read_a(ra0, smem + ((h ^ 1) * 4 + 3) * LDS_PART_BYTES);   // L(-1): A0(0)
+      frag_read_a(ra0, smem + ((h ^ 1) * 4 + 3) * LDS_PART_BYTES, a_off);   // L(-1): A0(0)
       section_barrier();
       section_barrier();
       lap(0, st_tiles != 0);   // [tile start: first barrier -> K loop] (the first tile starts its clock here)
@@ -370,13 +293,12 @@ __device__ __forceinline__ void pp_body(const GemmArgs& p) {
       //      (bias loads + s_waitcnt vmcnt(0)) also retires every LDS-DMA this wave has issued.
       if (p.dbg & 1) {   // diagnostics: no output traffic (keeps the accumulators alive through one predicated store)
         wait_vmcnt<0>();
-        if (acc[0][0][0] == 12345.678f && acc[7][3][3] == 0.5f) *(float*)p.C = acc[3][2][1];
+        acc_sink(p, acc);
       } else {
         // lane id re-derived through a VOLATILE asm: everything the epilogue computes from it (LDS staging offsets, row /
         // column addresses) is then re-computed per tile instead of being hoisted out of the tile loop, where it would
         // sit in VGPRs across the K loop (the K loop owns all 256)
-        int elane;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(elane));
+        const int elane = lane_id_volatile();
         const int efrow = elane & 15, efg = elane >> 4;
         wait_vmcnt<0>();
         lap(2, true);              // [wait for the next tile's prefetched parts]
@@ -409,7 +331,7 @@ __device__ __forceinline__ void pp_body(const GemmArgs& p) {
     m0 = m0n;
     n0 = n0n;
     tm_cur = tm_next;
-    pp_make_bases(cur, a0n, b0n, lda2, ldb2);
+    make_row_group_bases(cur, a0n, b0n, lda2, ldb2);
   }
   if constexpr (STAMP) {
     if (stamper && lane == 0) {   // 64 bytes per (workgroup, wave group) at the start of C (every tile's real output is older than this)
@@ -467,14 +389,8 @@ static bool persist_ok(const GemmArgs& a, int ncu) {
 template <int EPI>
 static int launch8p(const GemmArgs& a, hipStream_t stream) {
   constexpr int smem = PP_RING + 8 * PP_STAGE_PER_WAVE;   // 160 KB: the whole LDS of a CU
-  static VjPerDeviceOnce attr_once;   // the dynamic-LDS limit is a per-device attribute of the function
-  attr_once([] {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_4phase_persist_pre_kernel<EPI, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_4phase_persist_pre_kernel<EPI, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_4phase_persist_stamp_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if constexpr (EPI == EPI_BF16)
-      (void)hipFuncSetAttribute((const void*)gemm_nt_4phase_persist_half_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-  });
+  set_max_dynamic_lds<gemm_nt_4phase_persist_pre_kernel<EPI, 4>, gemm_nt_4phase_persist_pre_kernel<EPI, 0>, gemm_nt_4phase_persist_stamp_kernel<EPI>>(smem);
+  if constexpr (EPI == EPI_BF16) set_max_dynamic_lds<gemm_nt_4phase_persist_half_kernel>(smem);
   GemmArgs b = a;
   b.tiles_m = (int)cdiv64(a.M, 256);
   b.tiles_n = (int)cdiv64(a.N, 256);

@@ -55,6 +55,16 @@ static inline int with_epilogue(int epilogue, void* ws, int64_t ws_bytes, F&& f)
   }
 }
 
+// This lane's index in its wave, re-derived (mbcnt) at the point of use so that nothing computed from it stays live across a K loop that
+// owns every VGPR.  The VOLATILE form also keeps the compiler from hoisting what is computed from it (out of a tile loop, to the top of an
+// epilogue): each site that uses it says what that would cost there.
+__device__ __forceinline__ int lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+__device__ __forceinline__ int lane_id_volatile() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
+
 // Variant of a fused epilogue: one flag word, the template argument F of gemm_epilogue_impl / gemm_epilogue_staged.  Every flag is
 // workgroup-uniform (wave-uniform for EF_EDGE / EF_QS) and resolved by the caller-side switch, so that each variant is branch-free inside.
 enum : unsigned {
@@ -586,8 +596,7 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs& p, f32x4_t 
     // (lane id re-derived through a volatile asm: the per-lane address below is then computed HERE, not hoisted to the top of the epilogue,
     //  where it would be one 64-bit value too many next to 128 accumulators + 64 operand registers + 16 sums -- hipcc spilled it, and the
     //  reload's wait behind the epilogue's stores drained them)
-    int l2;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l2));
+    const int l2 = lane_id_volatile();
     if ((l2 & 15) == 0) {
       float* cp = p.colpart + (int64_t)slot * p.N + n_base + (l2 >> 4) * 4;
 #pragma unroll
@@ -778,6 +787,29 @@ static inline int pick_splitk(int64_t tiles, int nk, int slots, double us_per_kt
 void vj_splitk_finish_plan(int nk, int& splitk, int& ktiles_per);
 int vj_splitk_reduce(const GemmArgs& b, hipStream_t stream);
 
+// The preamble of every one-tile-per-workgroup NT launcher: tile counts of `b` for a BM x BN tile and its K-slice plan.  ws != nullptr
+// (the fp32 weight-gradient epilogue only): split-K over `slots` concurrent workgroups whose K-tile takes us_per_ktile.
+static inline void plan_tiles(GemmArgs& b, int BM, int BN, int BK, int slots, double us_per_ktile, void* ws, int64_t ws_bytes) {
+  b.tiles_m = (int)cdiv64(b.M, BM);
+  b.tiles_n = (int)cdiv64(b.N, BN);
+  b.splitk = 1;
+  b.ws = nullptr;
+  const int nk = (int)(b.K / BK);
+  if (ws != nullptr) {
+    b.splitk = pick_splitk((int64_t)b.tiles_m * b.tiles_n, nk, slots, us_per_ktile, 8, b.M, b.N, ws_bytes);
+    b.ws = (float*)ws;
+  }
+  vj_splitk_finish_plan(nk, b.splitk, b.ktiles_per);
+}
+
+// The dynamic-LDS limit is a per-device attribute of a kernel function: set once per device for each of KERNELS (a function-local static
+// with an initialiser per instantiation: exactly once, thread-safe -- the C ABI is re-entrant).
+template <auto... KERNELS>
+static inline void set_max_dynamic_lds(int bytes) {
+  static VjPerDeviceOnce attr_once;
+  attr_once([bytes] { ((void)hipFuncSetAttribute((const void*)KERNELS, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), ...); });
+}
+
 // Grouped tile mapping of the logical tile index (xcd_logical, common.hpp):
 // GM row-tiles form a group that sweeps all column tiles (keeps the A panel hot in L2)
 // raster (persistent kernel only, option gemm_raster): bits 0-7 = group size G (0 -> 8); bit 8 clear = G ROW tiles sweep all column tiles,
@@ -810,4 +842,33 @@ __device__ __forceinline__ void tile_of(int logical, int tiles_m, int tiles_n, i
   const int gsz = (tiles_m - first_m) < GM ? (tiles_m - first_m) : GM;
   tm = first_m + in_g % gsz;
   tn = in_g / gsz;
+}
+
+// The work unit of a one-tile-per-workgroup launch: logical unit index (xcd_logical of blockIdx.x over tiles x K slices) -> K slice,
+// tile (tile_of) and its origin, and the slice's K-tile range [kt0, kt0 + nk).  K_ROUND_UP: the last K-tile may be partial (TN kernel).
+struct GemmUnit {
+  int slice, tm, tn;
+  int64_t m0, n0;
+  int kt0, nk;
+};
+template <int BK, bool K_ROUND_UP = false>
+__device__ __forceinline__ void unit_k_range(const GemmArgs& p, int slice, int& kt0, int& nk) {
+  const int nk_all = (int)((p.K + (K_ROUND_UP ? BK - 1 : 0)) / BK);
+  kt0 = slice * p.ktiles_per;
+  nk = (kt0 + p.ktiles_per < nk_all ? kt0 + p.ktiles_per : nk_all) - kt0;
+}
+template <int BM, int BN, int BK, bool K_ROUND_UP = false>
+__device__ __forceinline__ GemmUnit gemm_unit(const GemmArgs& p, int logical_all) {
+  GemmUnit u;
+  const int ntile = p.tiles_m * p.tiles_n;
+  u.slice = logical_all / ntile;
+  tile_of(logical_all - u.slice * ntile, p.tiles_m, p.tiles_n, u.tm, u.tn);
+  u.m0 = (int64_t)u.tm * BM;
+  u.n0 = (int64_t)u.tn * BN;
+  unit_k_range<BK, K_ROUND_UP>(p, u.slice, u.kt0, u.nk);
+  return u;
+}
+template <int BM, int BN, int BK>
+__device__ __forceinline__ GemmUnit gemm_unit(const GemmArgs& p) {
+  return gemm_unit<BM, BN, BK>(p, xcd_logical(blockIdx.x, p.tiles_m * p.tiles_n * p.splitk));
 }
