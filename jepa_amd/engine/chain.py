@@ -9,11 +9,12 @@ Reference loops replaced: `for blk in self.blocks: x = blk(x, mask=masks)` (src/
 `for blk in self.predictor_blocks: x = blk(x, mask=masks)` (src/models/predictor.py:231-232) and their autograd graph.
 """
 import ctypes
-import os
 
 import torch
 
-from ..hip.lib import LAYER_CB, VjBlock, VjLinear, VjLnFold, VjNorm, VjSeg, check, get_option, load_library
+from ..hip.lib import LAYER_CB, VjBlock, VjLinear, VjLnFold, VjNorm, check, get_option, load_library
+from ..hip.ops import grow_only, seg_array
+from .streams import device_index
 
 
 def _p(t):
@@ -46,38 +47,26 @@ def fold_array(folds):
     return arr
 
 
-def seg_array(segs):
-    arr = (VjSeg * len(segs))()
-    for i, s in enumerate(segs):
-        arr[i] = VjSeg(s.row0, s.B, s.S)
-    return arr
-
-
 class Workspace:
-    """Growable device buffers keyed by tag.  A buffer is only ever replaced after a device-wide synchronise (growth is
-    rare: the first steps of a run), so no stream can still be using the old one."""
+    """Growable device buffers keyed by (GPU, tag) -- ops.grow_only: replaced only after a device-wide synchronise; growth is
+    rare (the first steps of a run)."""
 
     _bufs = {}
 
     @classmethod
     def get(cls, tag, nbytes, device):
-        key = (device.index if device.index is not None else torch.cuda.current_device(), tag)
-        buf = cls._bufs.get(key)
-        if buf is None or buf.numel() < nbytes:
-            if buf is not None:
-                torch.cuda.synchronize(device)
-                cls._bufs[key] = buf = None
-            # 30 % headroom: sequence lengths change with every mask draw, and every regrowth costs a device-wide sync
-            buf = torch.empty(int(nbytes * 1.3) + 256, dtype=torch.uint8, device=device)
-            cls._bufs[key] = buf
-        return buf
-
+        return grow_only(cls._bufs, (device_index(device), tag), nbytes, _headroom, device)
 
     @classmethod
     def release(cls, prefix):
         """Drop every buffer whose tag starts with `prefix` (a Trainer's namespace) -- called when the owner dies."""
         for key in [k for k in cls._bufs if str(k[1]).startswith(prefix)]:
             del cls._bufs[key]
+
+
+def _headroom(nbytes):
+    """30 % headroom: sequence lengths change with every mask draw, and every regrowth costs a device-wide sync."""
+    return int(nbytes * 1.3) + 256
 
 
 class TrunkCtx:

@@ -13,7 +13,7 @@ With world_size == 1 every method is a no-op.  On CPU tensors (gloo, used by the
 runs synchronously.
 
 Collectives (VJ_DP_COLL): every bucket's all-reduce is issued ON the engine's own communication stream -- a stream that was tested
-for sharing a hardware queue with none of the compute streams (engine/layers.py independent_stream):
+for sharing a hardware queue with none of the compute streams (engine/streams.py independent_stream):
   "sync"  (default) torch.distributed's process group (backend "nccl" IS RCCL on ROCm; the group the launcher created), called with
           async_op=False inside the stream's context: ProcessGroupNCCL then launches on that stream;
   "capi"  the library's own RCCL binding (`vj_comm_*`, include/vjepa_hip.h: what a host without torch.distributed calls); the 128-byte
@@ -25,6 +25,8 @@ for sharing a hardware queue with none of the compute streams (engine/layers.py 
 """
 import torch
 import torch.distributed as dist
+
+from .streams import independent_stream, side_stream
 
 
 class GradReducer:
@@ -154,8 +156,7 @@ class GradReducer:
         if self.comm_stream is not None:
             return
         # a communication stream that shares a hardware queue with neither compute stream: on a shared queue the collectives
-        # and the backward serialise (engine/layers.py independent_stream)
-        from .layers import independent_stream, side_stream
+        # and the backward serialise (engine/streams.py independent_stream)
         dev = self.arena.G.device
         with torch.cuda.device(dev):
             others = [torch.cuda.current_stream(dev), side_stream(dev).stream] + [x for x in self.extra_streams if x is not None]

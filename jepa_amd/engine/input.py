@@ -35,9 +35,11 @@ from ..src.utils.tensors import repeat_interleave_batch
 
 
 class DevicePrefetcher:
-    def __init__(self, fetch, device, batch_size=None, num_clips=1, depth=2):
+    def __init__(self, fetch, device, batch_size=None, num_clips=1, depth=2, timing=False):
         """fetch(): returns the next host batch `(clip_tensors, masks_enc, masks_pred)` (raises StopIteration when the
-        data is exhausted -- the caller's `fetch` normally re-creates its loader instead)."""
+        data is exhausted -- the caller's `fetch` normally re-creates its loader instead).
+        timing=True keeps, per batch, a pair of timing events in `edge_events`: the compute stream arriving at the input edge
+        and the copy stream having finished the batch (tools/eval_bench.py reads the wait from them)."""
         self.fetch, self.device = fetch, torch.device(device)
         self.batch_size, self.num_clips, self.depth = batch_size, num_clips, depth
         self.copy_stream = torch.cuda.Stream(device=self.device)
@@ -46,52 +48,40 @@ class DevicePrefetcher:
         self._free_ev = [None] * depth                 # compute-stream event: slot's previous contents are consumed
         self._h2d_done = [None] * depth                # copy-stream event: the slot's pinned buffers have been read
         self._slot = 0
-        self._inflight = None                          # (slot, ready_event, structure)
+        self._inflight = None                          # (slot, ready_event, staged batch)
         self._last_slot = None
         self.bytes_copied = 0
+        self.timing, self.edge_events = timing, []
+
+    @staticmethod
+    def _fit(store, key, t, flat, **where):
+        """The staging buffer of `store` that takes t: one of exactly t's shape, or (flat: a 1-D buffer whose length changes from
+        batch to batch) the first t.numel() elements of one that grows (x1.25) and is never shrunk."""
+        buf, n = store.get(key), t.numel()
+        if flat:
+            if buf is None or buf.numel() < n:
+                buf = store[key] = torch.empty(max(n + n // 4, 1), dtype=t.dtype, **where)
+            return buf[:n]
+        if buf is None or buf.shape != t.shape or buf.dtype != t.dtype:
+            buf = store[key] = torch.empty(t.shape, dtype=t.dtype, **where)
+        return buf
 
     # -- one tensor through pinned staging into the slot's device buffer
-    def _stage(self, slot, key, t):
+    def _stage(self, slot, key, t, flat=False):
         t = t.contiguous()
-        host, dev = self._host[slot].get(key), self._dev[slot].get(key)
-        if dev is None or dev.shape != t.shape or dev.dtype != t.dtype:
-            dev = torch.empty(t.shape, dtype=t.dtype, device=self.device)
-            self._dev[slot][key] = dev
-        if t.is_pinned():
-            src = t
-        else:
-            if host is None or host.shape != t.shape or host.dtype != t.dtype:
-                host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-                self._host[slot][key] = host
-            host.copy_(t)       # pageable -> pinned (host memcpy; loaders with pin_memory=True skip this)
-            src = host
+        dev = self._fit(self._dev[slot], key, t, flat, device=self.device)
+        src = t
+        if not t.is_pinned():
+            src = self._fit(self._host[slot], key, t, flat, pin_memory=True)
+            src.copy_(t)        # pageable -> pinned (host memcpy; loaders with pin_memory=True skip this)
         dev.copy_(src, non_blocking=True)
         self.bytes_copied += t.numel() * t.element_size()
         return dev
 
-    # -- a flat byte buffer whose length changes from batch to batch: staging buffers grow (x1.25) and are never shrunk
-    def _stage_flat(self, slot, key, t):
-        n = t.numel()
-        host, dev = self._host[slot].get(key), self._dev[slot].get(key)
-        if dev is None or dev.numel() < n:
-            dev = torch.empty(max(n + n // 4, 1), dtype=t.dtype, device=self.device)
-            self._dev[slot][key] = dev
-        if t.is_pinned():
-            src = t
-        else:
-            if host is None or host.numel() < n:
-                host = torch.empty(max(n + n // 4, 1), dtype=t.dtype, pin_memory=True)
-                self._host[slot][key] = host
-            host[:n].copy_(t)
-            src = host[:n]
-        dev[:n].copy_(src, non_blocking=True)
-        self.bytes_copied += n * t.element_size()
-        return dev[:n]
-
     # -- uint8 frames + tables through staging, then the augmentation kernel into the slot's fp32 clip buffer
     def _stage_raw(self, slot, i, raw):
         raw.validate()                                 # on the host, before anything is copied
-        frames = self._stage_flat(slot, ("raw", i), raw.frames)
+        frames = self._stage(slot, ("raw", i), raw.frames, flat=True)
         desc = self._stage(slot, ("desc", i), raw.desc)
         boxes = self._stage(slot, ("boxes", i), raw.boxes)
         shape = (len(raw), 3, raw.num_frames, raw.crop_size, raw.crop_size)
@@ -102,14 +92,24 @@ class DevicePrefetcher:
         ops.clip_transform(frames, desc, boxes, raw.crop_size, raw.mean, raw.std, out=out, stream=self.copy_stream.cuda_stream,
                            pre=raw.pre)
         if raw.erased:
-            noise = self._stage_flat(slot, ("noise", i), raw.noise)
+            noise = self._stage(slot, ("noise", i), raw.noise, flat=True)
             ebox = self._stage(slot, ("ebox", i), raw.ebox)
             noise_off = self._stage(slot, ("noise_off", i), raw.noise_off)
             ops.clip_erase(out, ebox, noise, noise_off, stream=self.copy_stream.cuda_stream)
         return out
 
+    def _stage_batch(self, slot, batch):
+        """What a host batch becomes on the device (called under the copy stream)."""
+        clip_list, masks_enc, masks_pred = batch
+        clips = [self._stage_raw(slot, i, u) if isinstance(u, RawClipBatch) else self._stage(slot, ("clip", i), u)
+                 for i, u in enumerate(clip_list)]
+        me = [self._stage(slot, ("me", i), m) for i, m in enumerate(masks_enc)]
+        mp = [self._stage(slot, ("mp", i), m) for i, m in enumerate(masks_pred)]
+        return clips, me, mp
+
+    # -- the slot protocol: acquire a slot, stage under the copy stream, publish `ready` ...
     def _launch(self):
-        clip_list, masks_enc, masks_pred = self.fetch()
+        batch = self.fetch()                           # StopIteration: nothing is in flight, no slot is taken
         slot = self._slot
         self._slot = (slot + 1) % self.depth
         if self._h2d_done[slot] is not None:
@@ -117,30 +117,27 @@ class DevicePrefetcher:
         with torch.cuda.stream(self.copy_stream):
             if self._free_ev[slot] is not None:
                 self.copy_stream.wait_event(self._free_ev[slot])
-            clips = [self._stage_raw(slot, i, u) if isinstance(u, RawClipBatch) else self._stage(slot, ("clip", i), u)
-                     for i, u in enumerate(clip_list)]
-            me = [self._stage(slot, ("me", i), m) for i, m in enumerate(masks_enc)]
-            mp = [self._stage(slot, ("mp", i), m) for i, m in enumerate(masks_pred)]
-            ready = torch.cuda.Event()
+            staged = self._stage_batch(slot, batch)
+            ready = torch.cuda.Event(enable_timing=self.timing)
             ready.record(self.copy_stream)
         self._h2d_done[slot] = ready
-        self._inflight = (slot, ready, clips, me, mp)
+        self._inflight = (slot, ready, staged)
 
-    def next(self, lookahead=True):
-        """Device tensors of the next batch (clips concatenated over num_clips, masks batch-repeated like
-        train.py:398-406); starts copying the batch after it unless lookahead=False.  The train loop passes
-        lookahead=False on the last iteration of an epoch: the reference re-creates its loader iterator at the first
-        `next(loader)` of the next epoch, i.e. AFTER `sampler.set_epoch(epoch + 1)` (train.py:366-381) -- fetching across
-        the boundary would permute epoch e+1 with epoch e's seed and draw one batch too many at the end of training."""
+    # -- ... then retire the previous slot, wait for the batch, look ahead
+    def _take(self, lookahead=True):
         cur = torch.cuda.current_stream()
         if self._last_slot is not None:   # everything that read the previous batch has been enqueued by now
             ev = torch.cuda.Event()
             ev.record(cur)
             self._free_ev[self._last_slot] = ev
         if self._inflight is None:
-            self._launch()
-        slot, ready, clips, me, mp = self._inflight
+            self._launch()               # StopIteration of the source ends the data
+        slot, ready, staged = self._inflight
         self._inflight = None
+        if self.timing:
+            arrive = torch.cuda.Event(enable_timing=True)
+            arrive.record(cur)
+            self.edge_events.append((arrive, ready))
         cur.wait_event(ready)
         self._last_slot = slot
         if lookahead:
@@ -148,6 +145,15 @@ class DevicePrefetcher:
                 self._launch()           # batch k+1 overlaps step k
             except StopIteration:
                 self._inflight = None
+        return staged
+
+    def next(self, lookahead=True):
+        """Device tensors of the next batch (clips concatenated over num_clips, masks batch-repeated like
+        train.py:398-406); starts copying the batch after it unless lookahead=False.  The train loop passes
+        lookahead=False on the last iteration of an epoch: the reference re-creates its loader iterator at the first
+        `next(loader)` of the next epoch, i.e. AFTER `sampler.set_epoch(epoch + 1)` (train.py:366-381) -- fetching across
+        the boundary would permute epoch e+1 with epoch e's seed and draw one batch too many at the end of training."""
+        clips, me, mp = self._take(lookahead)
         clips_d = clips[0] if len(clips) == 1 else torch.cat(clips, dim=0)
         if self.batch_size is not None:
             me = [repeat_interleave_batch(m, self.batch_size, repeat=self.num_clips) for m in me]
@@ -165,15 +171,13 @@ class EvalPrefetcher(DevicePrefetcher):
     all on the device -- what `run_one_epoch` and the probe bank's `_view_features` build themselves from fp32 loader batches with
     `.to(device)` (which is the identity on these).  The reference does those copies in front of the forward (eval.py:313-317);
     here batch k+1 is fetched, copied and transformed on the copy stream while batch k's frozen forward runs.  Slot reuse and the
-    pinned-buffer wait are DevicePrefetcher's.  The tensors of a batch stay valid until the second `next` after it."""
+    pinned-buffer wait are DevicePrefetcher's: this class supplies what is staged and what is handed out.  The tensors of a batch
+    stay valid until the second `next` after it."""
 
     def __init__(self, loader, device, depth=2, timing=False):
-        """timing=True keeps, per batch, a pair of timing events in `edge_events`: the compute stream arriving at the input edge
-        and the copy stream having finished the batch (tools/eval_bench.py reads the wait from them)."""
-        super().__init__(None, device, depth=depth)
+        super().__init__(lambda: next(self._it), device, depth=depth, timing=timing)
         self.loader = loader
         self._it = None
-        self.timing, self.edge_events = timing, []
 
     def __len__(self):
         return len(self.loader)
@@ -182,28 +186,18 @@ class EvalPrefetcher(DevicePrefetcher):
     def dataset(self):
         return self.loader.dataset
 
-    def _launch(self):
-        segments, labels, clip_indices = next(self._it)
-        slot = self._slot
-        self._slot = (slot + 1) % self.depth
-        if self._h2d_done[slot] is not None:
-            self._h2d_done[slot].synchronize()         # the DMA engine is done with this slot's pinned staging buffers
-        with torch.cuda.stream(self.copy_stream):
-            if self._free_ev[slot] is not None:
-                self.copy_stream.wait_event(self._free_ev[slot])
-            clips = []
-            for i, raw in enumerate(segments):
-                if not isinstance(raw, RawClipBatch):
-                    raise TypeError(f"EvalPrefetcher: segment {i} is {type(raw).__name__}, expected the RawClipBatch that the eval's "
-                                    "transforms collate to (fp32 batches go to run_one_epoch as they are)")
-                out, B = self._stage_raw(slot, i, raw), len(raw) // raw.num_views
-                clips.append([out[v * B:(v + 1) * B] for v in range(raw.num_views)])
-            lab = self._stage(slot, "labels", torch.as_tensor(labels))
-            idx = [self._stage(slot, ("idx", i), torch.as_tensor(ci)) for i, ci in enumerate(clip_indices)]
-            ready = torch.cuda.Event(enable_timing=self.timing)
-            ready.record(self.copy_stream)
-        self._h2d_done[slot] = ready
-        self._inflight = (slot, ready, clips, lab, idx)
+    def _stage_batch(self, slot, batch):
+        segments, labels, clip_indices = batch
+        clips = []
+        for i, raw in enumerate(segments):
+            if not isinstance(raw, RawClipBatch):
+                raise TypeError(f"EvalPrefetcher: segment {i} is {type(raw).__name__}, expected the RawClipBatch that the eval's "
+                                "transforms collate to (fp32 batches go to run_one_epoch as they are)")
+            out, B = self._stage_raw(slot, i, raw), len(raw) // raw.num_views
+            clips.append([out[v * B:(v + 1) * B] for v in range(raw.num_views)])
+        lab = self._stage(slot, "labels", torch.as_tensor(labels))
+        idx = [self._stage(slot, ("idx", i), torch.as_tensor(ci)) for i, ci in enumerate(clip_indices)]
+        return clips, lab, idx
 
     def __iter__(self):
         self._it = iter(self.loader)
@@ -211,26 +205,7 @@ class EvalPrefetcher(DevicePrefetcher):
         return self
 
     def __next__(self):
-        cur = torch.cuda.current_stream()
-        if self._last_slot is not None:   # everything that read the previous batch has been enqueued by now
-            ev = torch.cuda.Event()
-            ev.record(cur)
-            self._free_ev[self._last_slot] = ev
-        if self._inflight is None:
-            self._launch()               # StopIteration of the loader ends the epoch
-        slot, ready, clips, lab, idx = self._inflight
-        self._inflight = None
-        if self.timing:
-            arrive = torch.cuda.Event(enable_timing=True)
-            arrive.record(cur)
-            self.edge_events.append((arrive, ready))
-        cur.wait_event(ready)
-        self._last_slot = slot
-        try:
-            self._launch()               # batch k+1 overlaps the forward of batch k
-        except StopIteration:
-            self._inflight = None
-        return clips, lab, idx
+        return self._take()
 
     def next(self, lookahead=True):
         raise TypeError("EvalPrefetcher is iterated like the loader it wraps")

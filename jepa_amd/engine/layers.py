@@ -16,119 +16,18 @@ import os
 from dataclasses import dataclass
 from typing import List, Optional
 
+import numpy as np
 import torch
 
 from ..hip import ops
+from ..hip.lib import get_option
 from . import chain
+from .streams import (SideStream, _INDEP_LOG, independent_stream, low_priority_stream, side_stream,  # noqa: F401  (re-exported)
+                      streams_concurrent)
 from .weights import BlockW, EncoderW, LinearW, PredictorW
 
 LN_EPS = 1e-6  # partial(nn.LayerNorm, eps=1e-6), vision_transformer.py:252-281 / predictor.py:242-246
-
-
-class SideStream:
-    """Second HIP stream of the step: the EMA-target forward in the forward phase, the weight-gradient GEMMs (and the
-    reductions feeding the bias gradients) in the backward phase -- work that is off the main chain and fills the CUs its
-    kernels leave idle.  `fork` makes the side stream wait for everything enqueued so far on the main stream; `join` makes
-    the main stream wait for the side stream.  (A separate lowest-priority stream for the weight gradients was measured in
-    round 3: no effect, +0.1 % in 7 of 8 interleaved rounds -- both phases are throughput-bound, not dispatch-order-bound.)"""
-
-    def __init__(self, device):
-        import os
-        with torch.cuda.device(device):
-            self.stream = independent_stream(device, [torch.cuda.current_stream(device)])
-        self.enabled = os.environ.get("VJ_NO_OVERLAP", "0") != "1"   # serial mode for per-kernel profiling
-
-    def fork(self, *tensors):
-        self.stream.wait_stream(torch.cuda.current_stream())
-        for t in tensors:          # allocator plumbing: these buffers are read on the side stream
-            if t is not None:
-                t.record_stream(self.stream)
-
-    def join(self):
-        torch.cuda.current_stream().wait_stream(self.stream)
-
-
-def low_priority_stream(device):
-    """A HIP stream of the LOWEST priority the device offers (torch.cuda.Stream only reaches the default and higher ones), wrapped
-    for torch: the workgroups of the deferred fused update should take CUs only where the two forward streams leave them.
-    Falls back to a plain stream when the runtime call is unavailable."""
-    import ctypes
-    dev = torch.device(device)
-    try:
-        hip = ctypes.CDLL("libamdhip64.so")
-        least, greatest = ctypes.c_int(0), ctypes.c_int(0)
-        with torch.cuda.device(dev):
-            if hip.hipDeviceGetStreamPriorityRange(ctypes.byref(least), ctypes.byref(greatest)) != 0:
-                raise OSError("hipDeviceGetStreamPriorityRange")
-            h = ctypes.c_void_p()
-            if hip.hipStreamCreateWithPriority(ctypes.byref(h), 1, least.value) != 0 or not h.value:   # 1 = hipStreamNonBlocking
-                raise OSError("hipStreamCreateWithPriority")
-        return torch.cuda.ExternalStream(h.value, device=dev)
-    except (OSError, AttributeError):
-        return torch.cuda.Stream(device=dev)
-
-
-_INDEP_LOG = []   # (candidate index, [concurrent with others[i]]) of every independent_stream() call: diagnostics / tests
-
-
-def streams_concurrent(a, b, spin_us=300.0):
-    """True when a kernel on stream `a` and one on stream `b` run at the same time (different hardware queues): two idle one-wave
-    kernels of `spin_us` each (vj_probe_spin_stamped) leave their start / end stamps of the chip-wide 100 MHz timer in device memory;
-    the streams are concurrent when the two intervals overlap by more than half a spin.  Judged on the DEVICE's clock (round 6; it was
-    host wall-clock time around both, which eight ranks and their loader workers can stretch past any threshold).  Synchronises the
-    two streams."""
-    from ..hip.lib import check, load_library
-    lib = load_library()
-    ticks = int(spin_us * 100)
-    dev = a.device if hasattr(a, "device") else torch.device("cuda", torch.cuda.current_device())
-    stamps = torch.zeros(4, dtype=torch.int64, device=dev)
-    torch.cuda.current_stream(dev).synchronize()      # the zero fill is complete before either probe writes
-    best = 0
-    for _ in range(2):                       # the first pass also pays one-time costs (code load, queue creation)
-        check(lib.vj_probe_spin_stamped(ticks, stamps.data_ptr(), a.cuda_stream), "vj_probe_spin_stamped")
-        check(lib.vj_probe_spin_stamped(ticks, stamps.data_ptr() + 16, b.cuda_stream), "vj_probe_spin_stamped")
-        a.synchronize()
-        b.synchronize()
-        a0, a1, b0, b1 = stamps.tolist()
-        best = max(best, min(a1, b1) - max(a0, b0))
-    return best > ticks // 2
-
-
-def independent_stream(device, others, make=None, tries=16):
-    """A stream that shares a hardware queue with none of `others` (torch streams).  ROCclr maps streams onto GPU_MAX_HW_QUEUES
-    hardware queues round-robin, and torch hands out its 32 pooled streams round-robin, so the n-th stream a process creates may
-    land on the queue of the main or the side stream -- kernels of the two then serialise (measured: 72 -> 86 ms per step when the
-    deferred update's stream aliased a forward stream, round 5; the same signature as the unexplained vj_comm_* slowdown of round 4).
-    Candidates come from `make()` (default: torch.cuda.Stream) and are tested with streams_concurrent; the last one is returned
-    with a warning if none is independent (GPU_MAX_HW_QUEUES too small)."""
-    dev = torch.device(device)
-    make = make or (lambda: torch.cuda.Stream(device=dev))
-    cand = None
-    for i in range(tries):
-        cand = make()
-        ok = [streams_concurrent(cand, o) for o in others]
-        _INDEP_LOG.append((i, ok))
-        if all(ok):
-            return cand
-    import warnings
-    warnings.warn("jepa_amd: no stream independent of the existing ones was found (GPU_MAX_HW_QUEUES too small?); "
-                  "streams will serialise on a shared hardware queue")
-    return cand
-
-
-_SIDE = {}
-
-
-def side_stream(device):
-    """One SideStream per GPU, keyed by device INDEX: torch.device('cuda') and torch.device('cuda:0') are different
-    dictionary keys but the same GPU, and the fork/join partners must be the same stream object."""
-    device = torch.device(device)
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    s = _SIDE.get(idx)
-    if s is None:
-        s = _SIDE[idx] = SideStream(torch.device("cuda", idx))
-    return s
-
+LOG2E = 1.4426950408889634
 
 # The C launch chains (vj_blocks_fwd / vj_blocks_bwd) are the default for the Trainer; VJ_PY_CHAIN=1 keeps the
 # per-kernel Python chain below (same kernels, same order: bit-identical results, ~10x the host time).
@@ -146,19 +45,30 @@ class Seg:
     def rows(self):
         return self.B * self.S
 
+    @classmethod
+    def table(cls, B, lengths):
+        """One segment of B sequences per length, each starting at the row where the one before it ends."""
+        segs, r = [], 0
+        for S in lengths:
+            segs.append(cls(r, B, S))
+            r += B * S
+        return segs
+
 
 def _rows(t, seg):
     return t[seg.row0:seg.row0 + seg.rows]
 
 
+def _total_rows(segs):
+    return segs[-1].row0 + segs[-1].rows if segs else 0
+
+
 def _q_prescaled(D: int) -> bool:
-    from ..hip.lib import get_option
     return get_option("attn_softmax") == 2 and D % 4 == 0
 
 
 def _f32_mul(a: float, b: float) -> float:
     """a * b rounded as the C chain rounds it (float * float)."""
-    import numpy as np
     return float(np.float32(np.float32(a) * np.float32(b)))
 
 
@@ -171,22 +81,16 @@ def block_forward(x, bw: BlockW, segs: List[Seg], heads: int, save: bool, fold=N
     scale = hd ** -0.5
     if fold is not None and save:
         raise ValueError("block_forward: folded LayerNorms keep nothing for a backward")
+    epi, q_alpha = ops.EPI_BF16, 1.0
+    if _q_prescaled(D):   # option attn_softmax = 2 (as vj_blocks_fwd): the q third of qkv carries scale * log2(e)
+        epi, q_alpha = ops.EPI_QKV, _f32_mul(scale, LOG2E)
+        scale = -scale    # "q is pre-scaled" for the attention entry points
     y1 = mean1 = rstd1 = None
     if fold is not None:
-        rs = ops.ln_rowstats(x, LN_EPS)
-        if _q_prescaled(D):
-            qkv = ops.gemm_nt_lnfold(x, fold.w_qkv, fold.b_qkv, rs, fold.c_qkv, epilogue=ops.EPI_QKV,
-                                     alpha=_f32_mul(scale, 1.4426950408889634))
-            scale = -scale
-        else:
-            qkv = ops.gemm_nt_lnfold(x, fold.w_qkv, fold.b_qkv, rs, fold.c_qkv)
-    elif _q_prescaled(D):   # option attn_softmax = 2 (as vj_blocks_fwd): the q third of qkv carries scale * log2(e)
-        y1, mean1, rstd1 = ops.layernorm_fwd(x, bw.norm1.g, bw.norm1.b, LN_EPS, save_stats=save)
-        qkv = ops.gemm_nt(y1, bw.qkv.w, bias=bw.qkv.b, epilogue=ops.EPI_QKV, alpha=_f32_mul(scale, 1.4426950408889634))
-        scale = -scale    # "q is pre-scaled" for the attention entry points
+        qkv = ops.gemm_nt_lnfold(x, fold.w_qkv, fold.b_qkv, ops.ln_rowstats(x, LN_EPS), fold.c_qkv, epilogue=epi, alpha=q_alpha)
     else:
         y1, mean1, rstd1 = ops.layernorm_fwd(x, bw.norm1.g, bw.norm1.b, LN_EPS, save_stats=save)
-        qkv = ops.gemm_nt(y1, bw.qkv.w, bias=bw.qkv.b)
+        qkv = ops.gemm_nt(y1, bw.qkv.w, bias=bw.qkv.b, epilogue=epi, alpha=q_alpha)
     o = torch.empty_like(x)
     lses = []
     for sg in segs:
@@ -210,11 +114,8 @@ def block_forward(x, bw: BlockW, segs: List[Seg], heads: int, save: bool, fold=N
 # them; round-3 interleaved A/B at ViT-L B=24: 86.38 vs 86.83 ms/step, faster in 8 of 8 rounds, -25 W, and the 294
 # transpose launches / 35 GB per step of the NT route are gone -- profiles/r03_abab_switches.md).  The run-time option
 # "wgrad_tn" = 0 (VJ_WGRAD_TN=0) selects the transposes + NT split-K route, kept as the cross-check of the TN kernel.
-from ..hip.lib import get_option as _get_option  # noqa: E402
-
-
 def _tn_ok(n_out: int, k_in: int) -> bool:
-    return _get_option("wgrad_tn") != 0 and n_out % 8 == 0 and k_in % 8 == 0   # as chain.hip: any non-zero value is "on"
+    return get_option("wgrad_tn") != 0 and n_out % 8 == 0 and k_in % 8 == 0   # as chain.hip: any non-zero value is "on"
 
 
 def _wgrad(dy, x_in, lw: LinearW, alpha: float, beta: float = 0.0, bias_done: bool = False):
@@ -234,8 +135,20 @@ def _wgrad(dy, x_in, lw: LinearW, alpha: float, beta: float = 0.0, bias_done: bo
 
 def _group_ok(bw) -> bool:
     """Option wgrad_group: the four weight gradients of a block as one vj_gemm_bf16_tn_grouped launch (as vj_blocks_bwd)."""
-    return (_get_option("wgrad_tn") != 0 and _get_option("wgrad_group") != 0 and
+    return (get_option("wgrad_tn") != 0 and get_option("wgrad_group") != 0 and
             all(d % 8 == 0 for lw in (bw.qkv, bw.proj, bw.fc1, bw.fc2) for d in lw.gw.shape))
+
+
+def _on_side(fn, *tensors):
+    """fn() on the side stream, behind everything enqueued so far on this one (tensors: what it reads there); inline when the
+    side stream is disabled.  The caller joins before the results are consumed."""
+    side = side_stream(tensors[0].device)
+    if side.enabled:
+        side.fork(*tensors)
+        with torch.cuda.stream(side.stream):
+            fn()
+    else:
+        fn()
 
 
 def _wgrad_group(items, alpha: float, beta: float):
@@ -245,13 +158,7 @@ def _wgrad_group(items, alpha: float, beta: float):
             if lw.gb is not None and not bias_done:
                 ops.colsum(dy, lw.gb, alpha=alpha, accumulate=beta != 0.0)
         ops.gemm_wgrad_tn_grouped([(dy, x_in, lw.gw) for dy, x_in, lw, _ in items], alpha=alpha, beta=beta)
-    side = side_stream(items[0][0].device)
-    if side.enabled:
-        side.fork(*[t for dy, x_in, _, _ in items for t in (dy, x_in)])
-        with torch.cuda.stream(side.stream):
-            run()
-    else:
-        run()
+    _on_side(run, *[t for dy, x_in, _, _ in items for t in (dy, x_in)])
 
 
 def _linear_backward(dy, x_in, lw: LinearW, alpha: float, need_dx=True, dgelu_aux=None, beta: float = 0.0,
@@ -259,15 +166,10 @@ def _linear_backward(dy, x_in, lw: LinearW, alpha: float, need_dx=True, dgelu_au
     """dW (fp32, into lw.gw) = alpha * dy^T x_in + beta * dW ; db likewise ; returns dx = dy W (bf16).
     The weight-gradient half goes to the side stream; the caller joins before the gradients are consumed.
     defer (list): only record the weight-gradient problem; the caller launches the block's group (_wgrad_group)."""
-    side = side_stream(dy.device)
     if defer is not None:
         defer.append((dy, x_in, lw, bias_done))
-    elif side.enabled:
-        side.fork(dy, x_in)
-        with torch.cuda.stream(side.stream):
-            _wgrad(dy, x_in, lw, alpha, beta, bias_done)
     else:
-        _wgrad(dy, x_in, lw, alpha, beta, bias_done)
+        _on_side(lambda: _wgrad(dy, x_in, lw, alpha, beta, bias_done), dy, x_in)
     if not need_dx:
         return None
     if dgelu_aux is not None:
@@ -322,6 +224,52 @@ def _wait_gates(gates, chained):
             cur.wait_event(ev)
 
 
+def _pack_masked(pack, clips, tubelet, patch, masks, kdim):
+    """The patch rows every mask keeps, mask after mask: (tok bf16 [sum_i B*K_i, kdim], segs)."""
+    segs = Seg.table(clips.shape[0], [m.shape[1] for m in masks])
+    tok = torch.empty((_total_rows(segs), kdim), dtype=torch.bfloat16, device=clips.device)
+    for sg, m in zip(segs, masks):
+        pack(clips, tubelet, patch, idx=m, out=_rows(tok, sg))
+    return tok, segs
+
+
+def _chained(ws_tag) -> bool:
+    """The trunk goes out as C launch chains: the caller owns a workspace (ws_tag, engine/chain.py) and the switch is on.
+    USE_C_CHAIN is read at call time (tests flip it between two trainers)."""
+    return ws_tag is not None and USE_C_CHAIN
+
+
+def _trunk_forward(x, views, segs, save, ws_tag, gemm_flags=0, gates=None):
+    """x through every block of `views` (EncoderW / PredictorW) -> (x, saved blocks): one C call per gated range, else the
+    per-kernel Python chain."""
+    if _chained(ws_tag):
+        return chain.blocks_forward(x, views, segs, save, ws_tag, LN_EPS, gemm_flags=gemm_flags, gates=gates)
+    folds = None if save else getattr(views, "folds", None)
+    saved_blocks = []
+    for bi, bw in enumerate(views.blocks):
+        x, sv = block_forward(x, bw, segs, views.heads, save, fold=None if folds is None else folds[bi])
+        saved_blocks.append(sv)
+    return x, saved_blocks
+
+
+def _trunk_backward(dx, saved_blocks, views, segs, tag, alpha, beta, on_layer_done, ws_tag, last_fc2_bias_done):
+    """The blocks of `views` in reverse, whichever chain the forward took; on_layer_done(tag, layer) after every block."""
+    done = None if on_layer_done is None else (lambda li: on_layer_done(tag, li))
+    if isinstance(saved_blocks, chain.TrunkCtx):
+        side = side_stream(dx.device)
+        return chain.blocks_backward(dx, saved_blocks, views, alpha, side.stream.cuda_stream if side.enabled else None, done,
+                                     beta_acc=beta, tag=ws_tag, last_fc2_bias_done=last_fc2_bias_done)
+    nb = len(views.blocks)
+    for li in range(nb - 1, -1, -1):
+        dx = block_backward(dx, saved_blocks[li], views.blocks[li], segs, views.heads, alpha, beta,
+                            fc2_bias_done=li + 1 < nb or last_fc2_bias_done,
+                            prev_fc2_gb=views.blocks[li - 1].fc2.gb if li > 0 else None)
+        saved_blocks[li] = None
+        if done is not None:
+            done(li)      # bucket launch waits on the side stream's event, not on this stream
+    return dx
+
+
 def _image_model_tokens(ew: EncoderW, clips, masks, N, kdim):
     """Patch rows of the image model's input (tok bf16 [rows, 3*p*p], segs): images [B,3,H,W], or frames given as one clip tensor
     [B,3,T,H,W] or a list of such tensors of one frame size.  vj_tubelet_pack with tubelet 1 emits a clip's rows in (b,t,h,w) order,
@@ -347,15 +295,7 @@ def _image_model_tokens(ew: EncoderW, clips, masks, N, kdim):
         return tok, segs
     if len(parts) != 1 or parts[0].shape[2] != 1:
         raise ValueError("encoder_forward: masks address one image's token grid; frames [B,C,T,H,W] take none")
-    B = parts[0].shape[0]
-    segs, r = [], 0
-    for m in masks:
-        segs.append(Seg(r, B, m.shape[1]))
-        r += B * m.shape[1]
-    tok = torch.empty((r, kdim), dtype=torch.bfloat16, device=parts[0].device)
-    for sg, m in zip(segs, masks):
-        ops.tubelet_pack(parts[0], 1, p, idx=m, out=_rows(tok, sg))
-    return tok, segs
+    return _pack_masked(ops.tubelet_pack, parts[0], 1, p, masks, kdim)
 
 
 def encoder_forward(ew: EncoderW, clips, masks: Optional[List[torch.Tensor]], save: bool, final_norm=True, ws_tag=None,
@@ -398,29 +338,15 @@ def encoder_forward(ew: EncoderW, clips, masks: Optional[List[torch.Tensor]], sa
             segs = [Seg(0, B, N)]
             tok = pack(clips, ew.tubelet, ew.patch_size)
         else:
-            segs, r = [], 0
-            for m in masks:
-                segs.append(Seg(r, B, m.shape[1]))
-                r += B * m.shape[1]
-            tok = torch.empty((r, kdim), dtype=torch.bfloat16, device=clips.device)
-            for sg, m in zip(segs, masks):
-                pack(clips, ew.tubelet, ew.patch_size, idx=m, out=_rows(tok, sg))
-    chained = ws_tag is not None and USE_C_CHAIN
-    _wait_gates(gates, chained)
+            tok, segs = _pack_masked(pack, clips, ew.tubelet, ew.patch_size, masks, kdim)
+    _wait_gates(gates, _chained(ws_tag))
     x = ops.gemm_nt(tok, ew.patch.w, bias=ew.patch.b, flags=(gemm_flags & 0xffff if not gemm_flags >> 16 else 0) or None)
     if still and masks is None:
         x = ops.add_pos_bcast(x, pos, B, cells, N // cells)
     else:
         for i, sg in enumerate(segs):
             ops.add_pos(_rows(x, sg), pos, sg.B, sg.S, idx=None if masks is None else masks[i])
-    if chained:    # ws_tag: the caller owns one workspace per trunk (engine/chain.py)
-        x, saved_blocks = chain.blocks_forward(x, ew, segs, save, ws_tag, LN_EPS, gemm_flags=gemm_flags, gates=gates)
-    else:
-        saved_blocks = []
-        folds = ew.folds if (ew.folds is not None and not save) else None
-        for bi, bw in enumerate(ew.blocks):
-            x, sv = block_forward(x, bw, segs, ew.heads, save, fold=None if folds is None else folds[bi])
-            saved_blocks.append(sv)
+    x, saved_blocks = _trunk_forward(x, ew, segs, save, ws_tag, gemm_flags, gates)
     if not final_norm:
         return x, segs, None
     out, mean, rstd = ops.layernorm_fwd(x, ew.norm.g, ew.norm.b, LN_EPS, save_stats=save)
@@ -438,20 +364,7 @@ def encoder_backward(dout, saved, ew: EncoderW, segs, alpha: float, on_layer_don
     last_gb = ew.blocks[-1].fc2.gb if _tn_ok(8, 8) else None
     dx = ops.layernorm_bwd(dout, xl, ew.norm.g, mean, rstd, ew.norm.gg, ew.norm.gb, alpha=alpha, accumulate=beta != 0.0,
                            dxsum=last_gb)
-    if isinstance(saved_blocks, chain.TrunkCtx):
-        side = side_stream(dout.device)
-        dx = chain.blocks_backward(dx, saved_blocks, ew, alpha, side.stream.cuda_stream if side.enabled else None,
-                                   (lambda li: on_layer_done("enc", li)) if on_layer_done is not None else None,
-                                   beta_acc=beta, tag=ws_tag, last_fc2_bias_done=last_gb is not None)
-    else:
-        nb = len(ew.blocks)
-        for li in range(nb - 1, -1, -1):
-            dx = block_backward(dx, saved_blocks[li], ew.blocks[li], segs, ew.heads, alpha, beta,
-                                fc2_bias_done=li + 1 < nb or last_gb is not None,
-                                prev_fc2_gb=ew.blocks[li - 1].fc2.gb if li > 0 else None)
-            saved_blocks[li] = None
-            if on_layer_done is not None:
-                on_layer_done("enc", li)      # bucket launch waits on the side stream's event, not on this stream
+    dx = _trunk_backward(dx, saved_blocks, ew, segs, "enc", alpha, beta, on_layer_done, ws_tag, last_gb is not None)
     _linear_backward(dx, tok, ew.patch, alpha, need_dx=False, beta=beta)
     side_stream(dout.device).join()
     if on_layer_done is not None:
@@ -468,28 +381,18 @@ def predictor_forward(pw: PredictorW, z, enc_segs: List[Seg], masks_enc, masks_p
     _wait_gates(gates, False)
     e = ops.gemm_nt(z, pw.embed.w, bias=pw.embed.b)
     n_tok = len(pw.mask_tokens)
-    segs, tsegs, r, rt = [], [], 0, 0
-    for sg, mp in zip(enc_segs, masks_pred):
-        Kp = mp.shape[1]
-        segs.append(Seg(r, sg.B, sg.S + Kp))
-        tsegs.append(Seg(rt, sg.B, Kp))
-        r += sg.B * (sg.S + Kp)
-        rt += sg.B * Kp
-    x = torch.empty((r, Dp), dtype=torch.bfloat16, device=dev)
+    B = enc_segs[0].B     # the segments of one batch: the callers build them with one B
+    tsegs = Seg.table(B, [mp.shape[1] for _, mp in zip(enc_segs, masks_pred)])     # target rows
+    segs = Seg.table(B, [sg.S + tsg.S for sg, tsg in zip(enc_segs, tsegs)])        # whole sequences: context + target rows
+    x = torch.empty((_total_rows(segs), Dp), dtype=torch.bfloat16, device=dev)
     for i, (sg, psg) in enumerate(zip(enc_segs, segs)):
         # mask_index = i % num_mask_tokens (predictor.py:206; PredictorMultiMaskWrapper passes mask_index=i)
         ops.pred_assemble(_rows(e, sg), pw.mask_tokens[i % n_tok], pw.pos, masks_enc[i], masks_pred[i],
                           out=_rows(x, psg))
-    if ws_tag is not None and USE_C_CHAIN:
-        x, saved_blocks = chain.blocks_forward(x, pw, segs, save, ws_tag, LN_EPS, gemm_flags=gemm_flags)
-    else:
-        saved_blocks = []
-        for bw in pw.blocks:
-            x, sv = block_forward(x, bw, segs, pw.heads, save)
-            saved_blocks.append(sv)
+    x, saved_blocks = _trunk_forward(x, pw, segs, save, ws_tag, gemm_flags)
     # predictor_norm is row-wise and only target rows are projected (x[:, N_ctxt:], predictor.py:233-237):
     # normalise just those rows.
-    t = torch.empty((rt, Dp), dtype=torch.bfloat16, device=dev)
+    t = torch.empty((_total_rows(tsegs), Dp), dtype=torch.bfloat16, device=dev)
     for sg, psg, tsg in zip(enc_segs, segs, tsegs):
         ops.copy_rows(_rows(x, psg), _rows(t, tsg), psg.B, psg.S, sg.S, tsg.S, 0, tsg.S, Dp)
     tn, mean, rstd = ops.layernorm_fwd(t, pw.norm.g, pw.norm.b, LN_EPS, save_stats=save)
@@ -510,27 +413,13 @@ def predictor_backward(dzhat, saved, pw: PredictorW, enc_segs, alpha: float, on_
     # (column sums over ALL rows of that gradient) is the column sum of dt: it comes out of this LayerNorm backward
     last_gb = pw.blocks[-1].fc2.gb if _tn_ok(8, 8) else None
     dt = ops.layernorm_bwd(dtn, t, pw.norm.g, mean, rstd, pw.norm.gg, pw.norm.gb, alpha=alpha, accumulate=acc, dxsum=last_gb)
-    total = segs[-1].row0 + segs[-1].rows
-    dx = torch.empty((total, Dp), dtype=torch.bfloat16, device=dzhat.device)
+    dx = torch.empty((_total_rows(segs), Dp), dtype=torch.bfloat16, device=dzhat.device)
     for sg, psg, tsg in zip(enc_segs, segs, tsegs):
         ops.copy_rows(None, _rows(dx, psg), psg.B, 0, 0, psg.S, 0, sg.S, Dp)   # context rows start at zero grad (no ATen fill on the step)
         ops.copy_rows(_rows(dt, tsg), _rows(dx, psg), psg.B, tsg.S, 0, psg.S, sg.S, tsg.S, Dp)
     if on_layer_done is not None:
         on_layer_done("pred", len(pw.blocks))
-    if isinstance(saved_blocks, chain.TrunkCtx):
-        side = side_stream(dzhat.device)
-        dx = chain.blocks_backward(dx, saved_blocks, pw, alpha, side.stream.cuda_stream if side.enabled else None,
-                                   (lambda li: on_layer_done("pred", li)) if on_layer_done is not None else None,
-                                   beta_acc=beta, tag=ws_tag, last_fc2_bias_done=last_gb is not None)
-    else:
-        nb = len(pw.blocks)
-        for li in range(nb - 1, -1, -1):
-            dx = block_backward(dx, saved_blocks[li], pw.blocks[li], segs, pw.heads, alpha, beta,
-                                fc2_bias_done=li + 1 < nb or last_gb is not None,
-                                prev_fc2_gb=pw.blocks[li - 1].fc2.gb if li > 0 else None)
-            saved_blocks[li] = None
-            if on_layer_done is not None:
-                on_layer_done("pred", li)
+    dx = _trunk_backward(dx, saved_blocks, pw, segs, "pred", alpha, beta, on_layer_done, ws_tag, last_gb is not None)
     # token assembly backward: mask-token grads = sum of the target rows; context rows flow to predictor_embed
     de = torch.empty(e_shape, dtype=torch.bfloat16, device=dzhat.device)
     used = set()

@@ -14,21 +14,37 @@ pos_embed (m*x + (1-m)*x == x up to one rounding); both masks run through one fu
 batch).
 """
 import math
-from dataclasses import dataclass
+import os
+import weakref
 
 import torch
 
 from ..hip import ops
-import weakref
-
+from ..hip.lib import set_option
 from . import chain, dp, optstate
-from .layers import encoder_backward, encoder_forward, low_priority_stream, predictor_backward, predictor_forward, side_stream
 from . import weights as _weights
-from .weights import ParamArena, bump_generation, encoder_views, is_no_decay, predictor_views
+from .layers import encoder_backward, encoder_forward, predictor_backward, predictor_forward
+from .streams import device_index, independent_stream, low_priority_stream, side_stream
+from .weights import FoldW, ParamArena, bump_generation, encoder_views, is_no_decay, predictor_views
+
+_OVERLAP_FWD = os.environ.get("VJ_OVERLAP_FWD", "1") != "0"   # diagnostics: 0 = target forward on the main stream
+# Fold the target encoder's LayerNorms into its qkv / fc1 GEMMs (vj_blocks_fwd_lnfold).  Built, parity-tested and measured in round 5:
+# it removes the 48 LayerNorm launches of the target forward and their output traffic, but the heavier GEMM epilogue takes the gain
+# back (profiles/r05_ln_fold.md), so it is opt-in (VJ_LN_FOLD=1 or Trainer.set_ln_fold(True)).
+_LN_FOLD = os.environ.get("VJ_LN_FOLD", "0") == "1"
+_UPD_LOW_PRIO = os.environ.get("VJ_UPD_LOW_PRIO", "0") == "1"   # the deferred update's stream at the device's lowest priority (A/B)
+# GEMM kernel selection of the EMA target encoder's forward (vj_blocks_fwd gemm_flags: low 16 bits = flags, bits 16-23 = first
+# block they apply to); 0 = automatic everywhere
+_TGT_GEMM_FLAGS = int(os.environ.get("VJ_TGT_GEMM_FLAGS", "0"), 0)
+# the same for the predictor trunk (A/B measurements: tools/abab.py pred_flags / pred_dgrad_flags; 0 = the automatic selection):
+# forward through vj_blocks_fwd's gemm_flags, backward by setting option gemm_dgrad_flags around the predictor's backward chain only
+_PRED_GEMM_FLAGS = int(os.environ.get("VJ_PRED_GEMM_FLAGS", "0"), 0)
+_PRED_DGRAD_FLAGS = int(os.environ.get("VJ_PRED_DGRAD_FLAGS", "0"), 0)
 
 
-class _TargetArena:
-    """EMA target weights: fp32 + bf16 arenas laid out exactly like the encoder range of the trainer arena."""
+class _TargetArena(ParamArena):
+    """EMA target weights: fp32 + bf16 arenas laid out exactly like the encoder range [lo, hi) of the trainer arena, whose slots
+    they share -- ParamArena's views with `lo` as the base offset; no gradients, no moments."""
 
     def __init__(self, src: ParamArena, lo, hi, prefix, target_named_params, device):
         self.device = device
@@ -38,29 +54,13 @@ class _TargetArena:
         self.Pb = torch.zeros(hi - lo, dtype=torch.bfloat16, device=device)
         self.wT = {}
         self.frozen = {}
-        with torch.no_grad():
-            for name, p in target_named_params:
-                s = self.slots[name]
-                v = self.P[s.off - lo:s.off - lo + s.numel]
-                v.copy_(p.data.reshape(-1).to(device=device, dtype=torch.float32))
-                p.data = v.view(s.shape)
-        ops.cast_bf16(self.P, self.Pb)
-
-    def f32(self, name):
-        s = self.slots[name]
-        return self.P[s.off - self.lo:s.off - self.lo + s.numel].view(s.shape)
-
-    def bf16(self, name):
-        s = self.slots[name]
-        return self.Pb[s.off - self.lo:s.off - self.lo + s.numel].view(s.shape)
-
-    def refresh_bf16(self):
-        ops.cast_bf16(self.P, self.Pb)
+        for name, p in target_named_params:
+            self.adopt(name, p)
+        self.refresh_bf16()
 
     # ---- LayerNorms folded into the qkv / fc1 GEMMs of the target forward (vj_blocks_fwd_lnfold)
     def make_folds(self, depth):
         """One FoldW per block, refreshed in place from the fp32 target weights after every EMA update."""
-        from .weights import FoldW
         self.folds = []
         for i in range(depth):
             wq, w1 = self.f32(f"enc.blocks.{i}.attn.qkv.weight"), self.f32(f"enc.blocks.{i}.mlp.fc1.weight")
@@ -127,22 +127,6 @@ class StepOutput:
         return (h[5] + h[7]) > 0
 
 
-import os as _os
-_OVERLAP_FWD = _os.environ.get("VJ_OVERLAP_FWD", "1") != "0"   # diagnostics: 0 = target forward on the main stream
-# Fold the target encoder's LayerNorms into its qkv / fc1 GEMMs (vj_blocks_fwd_lnfold).  Built, parity-tested and measured in round 5:
-# it removes the 48 LayerNorm launches of the target forward and their output traffic, but the heavier GEMM epilogue takes the gain
-# back (profiles/r05_ln_fold.md), so it is opt-in (VJ_LN_FOLD=1 or Trainer.set_ln_fold(True)).
-_LN_FOLD = _os.environ.get("VJ_LN_FOLD", "0") == "1"
-_UPD_LOW_PRIO = _os.environ.get("VJ_UPD_LOW_PRIO", "0") == "1"   # the deferred update's stream at the device's lowest priority (A/B)
-# GEMM kernel selection of the EMA target encoder's forward (vj_blocks_fwd gemm_flags: low 16 bits = flags, bits 16-23 = first
-# block they apply to); 0 = automatic everywhere
-_TGT_GEMM_FLAGS = int(_os.environ.get("VJ_TGT_GEMM_FLAGS", "0"), 0)
-# the same for the predictor trunk (A/B measurements: tools/abab.py pred_flags / pred_dgrad_flags; 0 = the automatic selection):
-# forward through vj_blocks_fwd's gemm_flags, backward by setting option gemm_dgrad_flags around the predictor's backward chain only
-_PRED_GEMM_FLAGS = int(_os.environ.get("VJ_PRED_GEMM_FLAGS", "0"), 0)
-_PRED_DGRAD_FLAGS = int(_os.environ.get("VJ_PRED_DGRAD_FLAGS", "0"), 0)
-
-
 def _strip(name):
     return name[len("backbone."):] if name.startswith("backbone.") else name
 
@@ -158,8 +142,7 @@ class Trainer:
         self.device = torch.device(device) if device is not None else next(encoder.parameters()).device
         if self.device.type != "cuda":
             raise ValueError("jepa_amd.Trainer needs a GPU device: the step runs in libvjepa_hip.so only")
-        if self.device.index is None:   # 'cuda' and 'cuda:0' must name the same streams / workspaces everywhere
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = torch.device("cuda", device_index(self.device))   # 'cuda' and 'cuda:0' name the same streams / workspaces
         self.micro_batch = micro_batch
         self._ws = f"trainer{id(self)}:"   # workspace namespace: two Trainers in one process never share activations
         weakref.finalize(self, chain.Workspace.release, self._ws)
@@ -326,7 +309,6 @@ class Trainer:
                 self.reducer.begin(side.stream if side.enabled else None)
             lhook = hook if last else None
             if _PRED_DGRAD_FLAGS:
-                from ..hip.lib import set_option
                 old_dg = set_option("gemm_dgrad_flags", _PRED_DGRAD_FLAGS)
             dz = predictor_backward(dzhat, saved_p, self.pw, segs, alpha, on_layer_done=lhook, beta=beta,
                                     ws_tag=self._ws + "bwd_tmp")
@@ -378,8 +360,7 @@ class Trainer:
 
     def _make_update_stream(self):
         """A stream for the deferred update that shares a hardware queue with neither the main nor the side stream (a shared
-        queue serialises the two: engine/layers.py independent_stream)."""
-        from .layers import independent_stream
+        queue serialises the two: engine/streams.py independent_stream)."""
         with torch.cuda.device(self.device):
             others = [torch.cuda.current_stream(self.device), side_stream(self.device).stream]
             comm = getattr(getattr(self, "reducer", None), "comm_stream", None)

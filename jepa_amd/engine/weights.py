@@ -17,6 +17,8 @@ from typing import List, Optional
 import torch
 
 from ..hip import ops
+from .optstate import ALIGN, Slot as _Slot, is_no_decay, layout, pad64 as _pad  # noqa: F401  (pure, CPU-testable)
+from .streams import device_index
 
 # Bumped whenever parameters are rewritten through raw arena pointers (the fused AdamW / EMA kernels, shadow refreshes):
 # torch's per-tensor `_version` counters do not see those writes, so every cache of derived weights (bf16 copies of
@@ -38,13 +40,10 @@ PENDING_UPDATE = {}   # device index -> torch.cuda.Event recorded after the last
 def wait_pending_update(device=None):
     if not PENDING_UPDATE:
         return
-    idx = torch.cuda.current_device() if device is None or torch.device(device).index is None else torch.device(device).index
+    idx = device_index(device)
     ev = PENDING_UPDATE.get(idx)
     if ev is not None:
         torch.cuda.current_stream(idx).wait_event(ev)
-
-
-from .optstate import ALIGN, Slot as _Slot, is_no_decay, layout, pad64 as _pad  # noqa: F401  (pure, CPU-testable)
 
 
 # ----------------------------------------------------------------------------------------------- view structs
@@ -115,6 +114,8 @@ class PredictorW:
 class ParamArena:
     """Flat fp32 master/grad/moment arenas + bf16 shadows for a list of (name, Parameter) groups."""
 
+    lo = 0   # the slot offset at which the buffers start (an arena that mirrors one range of another starts at that range)
+
     def __init__(self, groups, device, with_moments=True, bind_grads=True):
         """groups: list of lists of (name, param); each group becomes one contiguous, 64-padded range."""
         self.device = device
@@ -127,26 +128,32 @@ class ParamArena:
         self.M2 = torch.zeros(off, dtype=torch.float32, device=device) if with_moments else None
         self.wT = {}
         self.frozen = {}  # name -> fp32 device tensor (frozen tables such as pos_embed)
-        with torch.no_grad():
-            for s in self.slots.values():
-                self.P[s.off:s.off + s.numel].copy_(s.param.data.reshape(-1).to(device=device, dtype=torch.float32))
-                s.param.data = self.P[s.off:s.off + s.numel].view(s.shape)
-                if bind_grads:
-                    s.param.grad = self.G[s.off:s.off + s.numel].view(s.shape)
+        for name, s in self.slots.items():
+            self.adopt(name, s.param)
+            if bind_grads:
+                s.param.grad = self.grad(name)
         self.refresh_bf16()
 
+    def adopt(self, name, param):
+        """Copy a parameter into its fp32 slot and make it a view of the slot."""
+        v = self.f32(name)
+        with torch.no_grad():
+            v.copy_(param.data.reshape(v.shape).to(device=self.device, dtype=torch.float32))
+        param.data = v
+
     # -- views
-    def f32(self, name):
+    def _view(self, buf, name):
         s = self.slots[name]
-        return self.P[s.off:s.off + s.numel].view(s.shape)
+        return buf[s.off - self.lo:s.off - self.lo + s.numel].view(s.shape)
+
+    def f32(self, name):
+        return self._view(self.P, name)
 
     def grad(self, name):
-        s = self.slots[name]
-        return self.G[s.off:s.off + s.numel].view(s.shape)
+        return self._view(self.G, name)
 
     def bf16(self, name):
-        s = self.slots[name]
-        return self.Pb[s.off:s.off + s.numel].view(s.shape)
+        return self._view(self.Pb, name)
 
     def refresh_bf16(self):
         ops.cast_bf16(self.P, self.Pb)

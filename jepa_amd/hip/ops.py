@@ -5,10 +5,11 @@ Every function takes CUDA(HIP) torch tensors, validates dtype/contiguity, and en
 provider here; no torch operator computes anything on this path.
 """
 import ctypes
+import math
 
 import torch
 
-from .lib import check, load_library
+from .lib import VjReduceSeg, VjSeg, check, load_library
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -22,13 +23,15 @@ _raw_stream = torch._C._cuda_getCurrentRawStream   # C accessor: ~20x cheaper th
 _dev_index = None
 
 
-def _stream(stream=None):
+def _device():
     global _dev_index
-    if stream is not None:
-        return ctypes.c_void_p(stream)
     if _dev_index is None:
         _dev_index = torch.cuda.current_device()   # one process per GPU: the device never changes afterwards
-    return ctypes.c_void_p(_raw_stream(_dev_index))
+    return _dev_index
+
+
+def _stream(stream=None):
+    return ctypes.c_void_p(_raw_stream(_device()) if stream is None else stream)
 
 
 def _ptr(t):
@@ -45,27 +48,35 @@ def _req(t, dtype, name):
     return t
 
 
+def grow_only(bufs, key, nbytes, grown, device):
+    """bufs[key]: a device buffer (uint8) of at least nbytes, allocated with grown(nbytes) bytes when it is missing or too small --
+    the one body of Scratch and engine.chain.Workspace.  A buffer is only replaced after a device-wide synchronise, so no
+    enqueued kernel can still be using the old allocation, which is dropped before the new one is made."""
+    buf = bufs.get(key)
+    if buf is None or buf.numel() < nbytes:
+        if buf is not None:
+            torch.cuda.synchronize(device)
+            bufs[key] = buf = None
+        buf = bufs[key] = torch.empty(grown(nbytes), dtype=torch.uint8, device=device)
+    return buf
+
+
 class Scratch:
     """Per-(device, tag, STREAM) scratch workspace for kernels that need partial-sum buffers.  The step runs kernels
     on two streams at once (dgrad chain / weight gradients), so two launches of the same kernel family may be in
-    flight together: each stream gets its own buffer.  A buffer is only replaced (regrown) after a device-wide
-    synchronise, so no enqueued kernel can still be using the old allocation."""
+    flight together: each stream gets its own buffer, of exactly the largest size asked for so far (1 MiB at least)."""
 
     _bufs = {}
 
     @classmethod
     def get(cls, nbytes, device, tag="default", stream=None):
-        global _dev_index
-        if _dev_index is None:
-            _dev_index = torch.cuda.current_device()
-        key = (_dev_index, tag, _raw_stream(_dev_index) if stream is None else stream)
-        buf = cls._bufs.get(key)
-        if buf is None or buf.numel() < nbytes:
-            if buf is not None:
-                torch.cuda.synchronize()
-            buf = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
-            cls._bufs[key] = buf
-        return buf
+        dev = _device()
+        key = (dev, tag, _raw_stream(dev) if stream is None else stream)
+        return grow_only(cls._bufs, key, nbytes, _scratch_bytes, device)
+
+
+def _scratch_bytes(nbytes):
+    return max(int(nbytes), 1 << 20)
 
 
 # ---------------------------------------------------------------- rows
@@ -214,7 +225,6 @@ def add_pos_bcast(y, pos, B, S, Gt, out=None, stream=None):
 def pos_interp3d(table, scale_factor, stream=None):
     """Trilinear F.interpolate(scale_factor=..., align_corners=False) of an fp32 position table [Nt,Nh,Nw,D] along its three grid
     axes -> [floor(Nt*st), floor(Nh*sh), floor(Nw*sw), D]."""
-    import math
     lib = load_library()
     _req(table, F32, "table")
     Nt, Nh, Nw, D = table.shape
@@ -228,7 +238,6 @@ def pos_interp3d(table, scale_factor, stream=None):
 def pos_interp2d_bicubic(table, scale_factor, stream=None):
     """Bicubic F.interpolate(scale_factor=s, align_corners=False) of an fp32 position table [Nh,Nw,D] along its two grid axes ->
     [floor(Nh*s), floor(Nw*s), D]."""
-    import math
     lib = load_library()
     _req(table, F32, "table")
     Nh, Nw, D = table.shape
@@ -290,14 +299,16 @@ GEMM_FLAGS = 0  # default kernel-selection flags of vj_gemm_bf16_nt (0 = automat
 KERNEL_TIMERS = None  # bench.py sets this to a dict: name -> list of (start_event, end_event, work) on the launch stream
 
 
-def _timed(name, work):
-    """Context helper: HIP events around one launch on the stream the kernel is enqueued on."""
+def _timed(name, work, what, fn, *args):
+    """check(fn(*args), what); while KERNEL_TIMERS is set, between two HIP events on the current stream, kept under `name` with
+    the launch's `work` (FLOP)."""
     if KERNEL_TIMERS is None:
-        return None
+        return check(fn(*args), what)
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     KERNEL_TIMERS.setdefault(name, []).append((s, e, work))
     s.record()
-    return e
+    check(fn(*args), what)
+    e.record()
 
 
 def gemm_nt(A, B, out=None, bias=None, residual=None, aux_in=None, aux_out=None, epilogue=EPI_BF16, alpha=1.0,
@@ -313,13 +324,11 @@ def gemm_nt(A, B, out=None, bias=None, residual=None, aux_in=None, aux_out=None,
     if out is None:
         out = torch.empty((M, N), dtype=F32 if epilogue == EPI_F32 else BF16, device=A.device)
     aux = aux_in if aux_in is not None else aux_out
-    _ev = _timed("gemm_nt", 2.0 * M * N * K)
-    check(lib.vj_gemm_bf16_nt(_ptr(A), A.stride(0), _ptr(B), B.stride(0), _ptr(out), out.stride(0), M, N, K,
-                              _ptr(bias), _ptr(residual), 0 if residual is None else residual.stride(0),
-                              _ptr(aux_in), _ptr(aux_out), 0 if aux is None else aux.stride(0), epilogue, alpha, beta,
-                              GEMM_FLAGS if flags is None else flags, _stream(stream)), "vj_gemm_bf16_nt")
-    if _ev is not None:
-        _ev.record()
+    _timed("gemm_nt", 2.0 * M * N * K, "vj_gemm_bf16_nt", lib.vj_gemm_bf16_nt,
+           _ptr(A), A.stride(0), _ptr(B), B.stride(0), _ptr(out), out.stride(0), M, N, K,
+           _ptr(bias), _ptr(residual), 0 if residual is None else residual.stride(0),
+           _ptr(aux_in), _ptr(aux_out), 0 if aux is None else aux.stride(0), epilogue, alpha, beta,
+           GEMM_FLAGS if flags is None else flags, _stream(stream))
     return out
 
 
@@ -376,12 +385,9 @@ def gemm_wgrad(dyT, xT, out, alpha=1.0, beta=0.0, flags=None, stream=None):
     M, K = dyT.shape
     N = xT.shape[0]
     ws = Scratch.get(WGRAD_WS_BYTES, dyT.device, "wgrad", stream=stream)
-    _ev = _timed("gemm_nt", 2.0 * M * N * K)
-    check(lib.vj_gemm_bf16_nt_splitk(_ptr(dyT), dyT.stride(0), _ptr(xT), xT.stride(0), _ptr(out), out.stride(0), M, N,
-                                     K, alpha, beta, GEMM_FLAGS if flags is None else flags, _ptr(ws), WGRAD_WS_BYTES,
-                                     _stream(stream)), "vj_gemm_bf16_nt_splitk")
-    if _ev is not None:
-        _ev.record()
+    _timed("gemm_nt", 2.0 * M * N * K, "vj_gemm_bf16_nt_splitk", lib.vj_gemm_bf16_nt_splitk,
+           _ptr(dyT), dyT.stride(0), _ptr(xT), xT.stride(0), _ptr(out), out.stride(0), M, N, K, alpha, beta,
+           GEMM_FLAGS if flags is None else flags, _ptr(ws), WGRAD_WS_BYTES, _stream(stream))
     return out
 
 
@@ -398,11 +404,9 @@ def gemm_wgrad_tn_grouped(problems, alpha=1.0, beta=0.0, stream=None):
         flat += [dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), dy.shape[1], x.shape[1]]
     arr = (ctypes.c_int64 * len(flat))(*[int(v) for v in flat])
     ws = Scratch.get(GROUP_WS_BYTES, problems[0][0].device, "wgrad_group", stream=stream)
-    _ev = _timed("gemm_nt", sum(2.0 * T * dy.shape[1] * x.shape[1] for dy, x, _ in problems))
-    check(lib.vj_gemm_bf16_tn_grouped(ctypes.addressof(arr), len(problems), T, alpha, beta, _ptr(ws), GROUP_WS_BYTES,
-                                      _stream(stream)), "vj_gemm_bf16_tn_grouped")
-    if _ev is not None:
-        _ev.record()
+    _timed("gemm_nt", sum(2.0 * T * dy.shape[1] * x.shape[1] for dy, x, _ in problems), "vj_gemm_bf16_tn_grouped",
+           lib.vj_gemm_bf16_tn_grouped, ctypes.addressof(arr), len(problems), T, alpha, beta, _ptr(ws), GROUP_WS_BYTES,
+           _stream(stream))
 
 
 def gemm_wgrad_tn(dy, x, out, alpha=1.0, beta=0.0, stream=None):
@@ -413,11 +417,9 @@ def gemm_wgrad_tn(dy, x, out, alpha=1.0, beta=0.0, stream=None):
     T, N1 = dy.shape
     N2 = x.shape[1]
     ws = Scratch.get(WGRAD_WS_BYTES, dy.device, "wgrad", stream=stream)
-    _ev = _timed("gemm_nt", 2.0 * T * N1 * N2)
-    check(lib.vj_gemm_bf16_tn_splitk(_ptr(dy), dy.stride(0), _ptr(x), x.stride(0), _ptr(out), out.stride(0), T, N1, N2,
-                                     alpha, beta, _ptr(ws), WGRAD_WS_BYTES, _stream(stream)), "vj_gemm_bf16_tn_splitk")
-    if _ev is not None:
-        _ev.record()
+    _timed("gemm_nt", 2.0 * T * N1 * N2, "vj_gemm_bf16_tn_splitk", lib.vj_gemm_bf16_tn_splitk,
+           _ptr(dy), dy.stride(0), _ptr(x), x.stride(0), _ptr(out), out.stride(0), T, N1, N2, alpha, beta, _ptr(ws), WGRAD_WS_BYTES,
+           _stream(stream))
     return out
 
 
@@ -480,33 +482,49 @@ def attn_fwd(qkv, B, S, H, hd, scale, save_lse=True, out=None, stream=None):
     _req(qkv, BF16, "qkv")
     o = torch.empty((B * S, H * hd), dtype=BF16, device=qkv.device) if out is None else out
     lse = torch.empty((B, H, S), dtype=F32, device=qkv.device) if save_lse else None
-    _ev = _timed("attn_fwd", 4.0 * B * H * S * S * hd)
-    check(lib.vj_attn_fwd(_ptr(qkv), _ptr(o), _ptr(lse), B, S, H, hd, scale, _stream(stream)), "vj_attn_fwd")
-    if _ev is not None:
-        _ev.record()
+    _timed("attn_fwd", 4.0 * B * H * S * S * hd, "vj_attn_fwd", lib.vj_attn_fwd,
+           _ptr(qkv), _ptr(o), _ptr(lse), B, S, H, hd, scale, _stream(stream))
     return o, lse
+
+
+def seg_array(segs):
+    """ctypes array of vj_seg_t over segments given as (row0, B, S) tuples or as objects with those fields (engine.layers.Seg)."""
+    arr = (VjSeg * len(segs))()
+    for i, s in enumerate(segs):
+        arr[i] = VjSeg(*s) if isinstance(s, tuple) else VjSeg(s.row0, s.B, s.S)
+    return arr
+
+
+_seg_array = seg_array
+
+
+def _attn_bwd_bufs(qkv, segs, H, hd, colsum, stream):
+    """What an attention backward over `segs` needs next to its operands: (seg_arr, ws, nws, colq, colkv) -- the stream's "attn"
+    scratch and, with colsum, the fp32 column partials of dqkv, the segments' rows one after the other."""
+    lib = load_library()
+    seg_arr = seg_array(segs)
+    nws = lib.vj_attn_bwd_segs_ws_bytes(seg_arr, len(segs), H, hd)
+    ws = Scratch.get(nws, qkv.device, "attn", stream=stream)
+    colq = colkv = None
+    if colsum:
+        rq_t = rkv_t = 0
+        rq, rkv = ctypes.c_int64(0), ctypes.c_int64(0)
+        for sg in seg_arr:
+            check(lib.vj_attn_bwd_colsum_rows(sg.B, sg.S, hd, ctypes.byref(rq), ctypes.byref(rkv)), "vj_attn_bwd_colsum_rows")
+            rq_t, rkv_t = rq_t + (rq.value if sg.B * sg.S else 0), rkv_t + (rkv.value if sg.B * sg.S else 0)
+        colq = torch.empty((rq_t, H * hd), dtype=F32, device=qkv.device)
+        colkv = torch.empty((rkv_t, 2 * H * hd), dtype=F32, device=qkv.device)
+    return seg_arr, ws, nws, colq, colkv
 
 
 def attn_bwd(qkv, o, dout, lse, B, S, H, hd, scale, out=None, stream=None):
     lib = load_library()
     _req(dout, BF16, "dout")
     dqkv = torch.empty_like(qkv) if out is None else out
-    nws = lib.vj_attn_bwd_segs_ws_bytes(_seg_array([(0, B, S)]), 1, H, hd)
-    ws = Scratch.get(nws, qkv.device, "attn", stream=stream)
-    _ev = _timed("attn_bwd", 8.0 * B * H * S * S * hd)
-    check(lib.vj_attn_bwd(_ptr(qkv), _ptr(o), _ptr(dout), _ptr(lse), _ptr(dqkv), B, S, H, hd, scale, _ptr(ws), nws,
-                          _stream(stream)), "vj_attn_bwd")
-    if _ev is not None:
-        _ev.record()
+    _, ws, nws, _, _ = _attn_bwd_bufs(qkv, [(0, B, S)], H, hd, False, stream)
+    _timed("attn_bwd", 8.0 * B * H * S * S * hd, "vj_attn_bwd", lib.vj_attn_bwd,
+           _ptr(qkv), _ptr(o), _ptr(dout), _ptr(lse), _ptr(dqkv), B, S, H, hd, scale, _ptr(ws), nws, _stream(stream))
     return dqkv
-
-
-def _seg_array(segs):
-    from .lib import VjSeg
-    arr = (VjSeg * len(segs))()
-    for i, (row0, B, S) in enumerate(segs):
-        arr[i] = VjSeg(row0, B, S)
-    return arr
 
 
 def attn_fwd_segs(qkv, segs, H, hd, scale, save_lse=True, stream=None):
@@ -517,7 +535,7 @@ def attn_fwd_segs(qkv, segs, H, hd, scale, save_lse=True, stream=None):
     M = qkv.shape[0]
     o = torch.empty((M, H * hd), dtype=BF16, device=qkv.device)
     lse = torch.empty((H * M,), dtype=F32, device=qkv.device) if save_lse else None
-    check(lib.vj_attn_fwd_segs(_ptr(qkv), _ptr(o), _ptr(lse), _seg_array(segs), len(segs), H, hd, scale, _stream(stream)),
+    check(lib.vj_attn_fwd_segs(_ptr(qkv), _ptr(o), _ptr(lse), seg_array(segs), len(segs), H, hd, scale, _stream(stream)),
           "vj_attn_fwd_segs")
     return o, lse
 
@@ -525,23 +543,10 @@ def attn_fwd_segs(qkv, segs, H, hd, scale, save_lse=True, stream=None):
 def attn_bwd_segs(qkv, o, dout, lse, segs, H, hd, scale, colsum=False, stream=None):
     """Backward of attn_fwd_segs in one launch pair (vj_attn_bwd_segs) -> dqkv [, colq, colkv: the segments' column partials one
     after the other]."""
-    import ctypes
     lib = load_library()
     _req(dout, BF16, "dout")
-    M = qkv.shape[0]
     dqkv = torch.empty_like(qkv)
-    seg_arr = _seg_array(segs)
-    nws = lib.vj_attn_bwd_segs_ws_bytes(seg_arr, len(segs), H, hd)
-    ws = Scratch.get(nws, qkv.device, "attn", stream=stream)
-    colq = colkv = None
-    if colsum:
-        rq_t = rkv_t = 0
-        for _, B, S in segs:
-            rq, rkv = ctypes.c_int64(0), ctypes.c_int64(0)
-            check(lib.vj_attn_bwd_colsum_rows(B, S, hd, ctypes.byref(rq), ctypes.byref(rkv)), "vj_attn_bwd_colsum_rows")
-            rq_t, rkv_t = rq_t + (rq.value if B * S else 0), rkv_t + (rkv.value if B * S else 0)
-        colq = torch.empty((rq_t, H * hd), dtype=F32, device=qkv.device)
-        colkv = torch.empty((rkv_t, 2 * H * hd), dtype=F32, device=qkv.device)
+    seg_arr, ws, nws, colq, colkv = _attn_bwd_bufs(qkv, segs, H, hd, colsum, stream)
     check(lib.vj_attn_bwd_segs(_ptr(qkv), _ptr(o), _ptr(dout), _ptr(lse), _ptr(dqkv), seg_arr, len(segs), H, hd, scale,
                                _ptr(ws), nws, _ptr(colq), _ptr(colkv), _stream(stream)), "vj_attn_bwd_segs")
     return (dqkv, colq, colkv) if colsum else dqkv
@@ -550,16 +555,10 @@ def attn_bwd_segs(qkv, o, dout, lse, segs, H, hd, scale, colsum=False, stream=No
 def attn_bwd_colsum(qkv, o, dout, lse, B, S, H, hd, scale, out=None, stream=None):
     """attn_bwd + fp32 column partials of dqkv over this segment (vj_attn_bwd_colsum): returns (dqkv, colq [rows_q, H*hd],
     colkv [rows_kv, 2*H*hd]); the qkv bias gradient is colq.sum(0) | colkv.sum(0) (reduce_segments on the product path)."""
-    import ctypes
     lib = load_library()
     _req(dout, BF16, "dout")
     dqkv = torch.empty_like(qkv) if out is None else out
-    rq, rkv = ctypes.c_int64(0), ctypes.c_int64(0)
-    check(lib.vj_attn_bwd_colsum_rows(B, S, hd, ctypes.byref(rq), ctypes.byref(rkv)), "vj_attn_bwd_colsum_rows")
-    colq = torch.empty((rq.value, H * hd), dtype=F32, device=qkv.device)
-    colkv = torch.empty((rkv.value, 2 * H * hd), dtype=F32, device=qkv.device)
-    nws = lib.vj_attn_bwd_segs_ws_bytes(_seg_array([(0, B, S)]), 1, H, hd)
-    ws = Scratch.get(nws, qkv.device, "attn", stream=stream)
+    _, ws, nws, colq, colkv = _attn_bwd_bufs(qkv, [(0, B, S)], H, hd, True, stream)
     check(lib.vj_attn_bwd_colsum(_ptr(qkv), _ptr(o), _ptr(dout), _ptr(lse), _ptr(dqkv), B, S, H, hd, scale, _ptr(ws), nws,
                                  _ptr(colq), _ptr(colkv), _stream(stream)), "vj_attn_bwd_colsum")
     return dqkv, colq, colkv
@@ -568,7 +567,6 @@ def attn_bwd_colsum(qkv, o, dout, lse, B, S, H, hd, scale, out=None, stream=None
 def gemm_dgelu_colsum(dy, wT, aux_in, stream=None):
     """fc2 dgrad with fc1's bias-gradient partials (vj_gemm_bf16_nt_dgelu_colsum): returns (du bf16 [M, N], colpart fp32
     [rows, N] or None when the fused kernel did not take the problem -- du is the plain GEMM's either way)."""
-    import ctypes
     lib = load_library()
     _req(dy, BF16, "dy")
     M, K = dy.shape
@@ -586,7 +584,6 @@ def gemm_dgelu_colsum(dy, wT, aux_in, stream=None):
 def reduce_segments(segs, alpha=1.0, accumulate=False, stream=None):
     """segs: list of (part fp32 [P, stride] (a 2-D tensor or a column slice of one), out fp32 [N]) -> out = alpha * column sums
     (+ old when accumulating), all in ONE launch (vj_reduce_segments)."""
-    from .lib import VjReduceSeg
     lib = load_library()
     arr = (VjReduceSeg * len(segs))()
     for i, (part, out) in enumerate(segs):

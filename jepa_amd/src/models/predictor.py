@@ -94,10 +94,7 @@ class VisionTransformerPredictor(nn.Module, hipmodule.HipModule):
         for c in ctxt:
             hipmodule.require_gpu(c, "VisionTransformerPredictor.forward")
         z = torch.cat([c.reshape(-1, D) for c in ctxt], dim=0) if len(ctxt) > 1 else ctxt[0].reshape(-1, D)
-        enc_segs, r = [], 0
-        for c in ctxt:
-            enc_segs.append(Seg(r, B, c.shape[1]))
-            r += B * c.shape[1]
+        enc_segs = Seg.table(B, [c.shape[1] for c in ctxt])
         masks_ctxt = [m.contiguous() for m in masks_ctxt]
         masks_tgt = [m.contiguous() for m in masks_tgt]
         args = (enc_segs, masks_ctxt, masks_tgt, first_mask_index)

@@ -17,12 +17,14 @@ bicubically at other square sizes (vj_pos_interp2d_bicubic) and FrameAggregation
 `forward_frames`.
 """
 import math
+import weakref
 from functools import partial
 
 import torch
 import torch.nn as nn
 
 from ...engine import hipmodule
+from ...engine.chain import Workspace
 from ...engine.layers import encoder_backward, encoder_forward
 from ..utils.tensors import trunc_normal_
 from .utils.modules import Block
@@ -197,24 +199,29 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         B = x.shape[0]
         return [out[s.row0:s.row0 + s.rows].view(B, s.S, self.embed_dim) for s in segs]
 
+    def _needs_grad(self):
+        return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+
+    def _frozen_only(self, what, then=""):
+        """Refuse `what` while a backward would be recorded: it is a feature of the frozen / no-grad path."""
+        if self._needs_grad():
+            raise NotImplementedError(f"{what} on the frozen / no-grad path only (torch.no_grad() or parameters with "
+                                      f"requires_grad=False){then}")
+
     def _pos_table(self, x):
         """None at the native clip size (the arena's table is used), otherwise the fp32 [N', D] table of x's token grid.  Still
         images and off-native sizes are frozen-path features: with gradients enabled they raise."""
         T, H, W = self._input_size(x)
         if not self.is_video:
             return self._image_pos_table(H, W)
-        native = H == self.input_size and W == self.input_size and T == self.num_frames
-        if (x.dim() == 4 or not native) and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError("still-image [B,C,H,W] and off-native-size inputs run on the frozen / no-grad path only "
-                                      "(torch.no_grad() or parameters with requires_grad=False); with gradients enabled the "
-                                      "encoder runs at its native clip size, as the pretraining step does")
+        if x.dim() == 4 or not (H == self.input_size and W == self.input_size and T == self.num_frames):
+            self._frozen_only("still-image [B,C,H,W] and off-native-size inputs run", "; with gradients enabled the encoder runs "
+                              "at its native clip size, as the pretraining step does")
         pos = self.interpolate_pos_encoding(x, self.pos_embed)
         return None if pos is self.pos_embed else pos.view(-1, self.embed_dim)
 
     def _image_pos_table(self, H, W):
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError("the image (num_frames=1) encoder runs on the frozen / no-grad path only (torch.no_grad() "
-                                      "or parameters with requires_grad=False)")
+        self._frozen_only("the image (num_frames=1) encoder runs")
         pos = self._interpolate_image(H, W, self.pos_embed)
         return None if pos is self.pos_embed else pos.view(-1, self.embed_dim)
 
@@ -258,7 +265,7 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
             x = x.contiguous().float()
         if masks is not None:
             masks = [m.contiguous() for m in masks]
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if self._needs_grad():
             return hipmodule.run_with_autograd(self, _enc_fwd, _enc_bwd, (x, masks))
         # inference: one C call per trunk (no saved activations, a private workspace) and, because nothing else shares the
         # GPU with this stream, the two-workgroups-per-CU GEMM (gemm4w.hip; see DESIGN.md section 6 for why training does not)
@@ -268,8 +275,6 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         flags = INFER_GEMM_FLAGS if self.embed_dim <= 1024 else 0
         tag = f"infer{id(self)}:"
         if "_hip_ws_finalizer" not in self.__dict__:   # the workspace dies with the module
-            import weakref
-            from ...engine.chain import Workspace
             self.__dict__["_hip_ws_finalizer"] = weakref.finalize(self, Workspace.release, tag)
         out, segs, _ = encoder_forward(ew, x, masks, save=False, ws_tag=tag, gemm_flags=flags, pos=pos)
         return out, segs
