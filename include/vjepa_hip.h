@@ -90,6 +90,26 @@ int vj_clip_transform_pre(const uint8_t* frames, int64_t frames_bytes, const int
  * batch is erased) launches nothing.  B < 65536, 3*T*S*S < 2^31. */
 int vj_clip_erase(float* clips, const int32_t* ebox, const float* noise, int64_t noise_elems, const int64_t* noise_off, int64_t B,
                   int64_t T, int64_t S, vj_stream_t stream);
+/* RandAugment on the decoded uint8 frames, before everything else        evals/video_classification_frozen/utils.py:233-237,256-259
+ * RandAugment.__call__ / AugmentOp.__call__ and the 15 operations         src/datasets/utils/video/randaugment.py:51-179,324-369,449-465
+ * (PIL behind them: ImageOps, ImageEnhance, ImageFilter.SMOOTH, Image.transform(AFFINE, BICUBIC, fillcolor=(128,128,128))).
+ * The draws stay on the host (jepa_amd/app/vjepa/randaugment.py: which operations, whether each runs, magnitudes, signs, and the
+ * affine coefficients); this is the pixel work, in place, byte for byte what PIL gives.
+ *   frames  the flat buffer of vj_clip_transform (clip b: [T,Hs,Ws,3] interleaved RGB); 16-byte aligned, frames_bytes < 2^31
+ *   desc    int64 [B,4] = (byte offset, Hs, Ws, unused), the table vj_clip_transform takes; offsets are multiples of 16
+ *   ops     int32 [B,L], L <= 8: operation code of clip b in layer l, applied in order (layer l+1 reads layer l's output):
+ *           0 nothing, 1 AutoContrast, 2 Equalize, 3 Invert, 4 Rotate, 5 Posterize, 6 Solarize, 7 SolarizeAdd, 8 Color, 9 Contrast,
+ *           10 Brightness, 11 Sharpness, 12 ShearX, 13 ShearY, 14 TranslateXRel, 15 TranslateYRel
+ *   args    double [B,L,6]: the six affine coefficients (4, 12..15), else in [0] the factor (8..11), the bits kept (5), the
+ *           threshold (6) or the addend (7)
+ *   ws      workspace of vj_clip_randaug_ws_bytes(frames_bytes, B, T) bytes, 16-byte aligned: a second copy of the frame buffer
+ *           (layers read one copy and write the other) and one [3][256] byte table per (clip, frame)
+ * Two launches per layer and one more when L is odd; callers drop the layers in which no clip has an operation before they upload
+ * the tables.  A clip whose row is all zeros, the padding between clips, and a clip whose extent leaves the buffer are not
+ * changed by one byte.  An augmented clip must not share its bytes with another row.  B == 0 or L == 0 launches nothing. */
+int vj_clip_randaug(uint8_t* frames, int64_t frames_bytes, const int64_t* desc, int64_t B, int64_t T, const int32_t* ops,
+                    const double* args, int64_t L, void* ws, int64_t ws_bytes, vj_stream_t stream);
+int64_t vj_clip_randaug_ws_bytes(int64_t frames_bytes, int64_t B, int64_t T);
 
 /* ---- still-image front end of the video encoder and position-table interpolation ------------------------------
  * input.unsqueeze(2).repeat(1, 1, frames_per_clip, 1, 1) + patch_embed    evals/image_classification_frozen/eval.py:452-455

@@ -12,7 +12,9 @@ Supported: the transform of the three pretrain configs -- auto_augment false, re
 scale / aspect ratio, crop size, motion_shift false and true.  `auto_augment=True` (PIL RandAugment) and `reprob > 0`
 (RandomErasing) raise NotImplementedError here.  The RandomErasing draw itself (`draw_erase`) and the tables that carry it to
 `vj_clip_erase` live in this module; the frozen eval's transforms (evals/video_classification_frozen/utils.py), which set
-reprob 0.25, use them, together with the normalise-first flag and per-clip view boxes of `RawClip` / `RawClipBatch`.
+reprob 0.25, use them, together with the normalise-first flag and per-clip view boxes of `RawClip` / `RawClipBatch`.  Those two
+also carry the optional RandAugment plan of a clip (drawn by randaugment.RandAugmentDraw, carried out by `vj_clip_randaug`), which
+the eval's training transform attaches behind its `rand_augment` attribute.
 """
 import math
 import random
@@ -20,6 +22,8 @@ import random
 import numpy as np
 import torch
 from torch.utils.data._utils.collate import default_collate_fn_map
+
+from .randaugment import MAX_LAYERS, MIN_SIDE, NUM_ARGS, NUM_OPS
 
 ALIGN = 16   # every clip of a RawClipBatch starts on a 16-byte boundary of the flat buffer
 
@@ -96,13 +100,20 @@ class RawClip:
     """One undecorated clip on its way to the device: uint8 frames [T,H,W,3], int32 boxes [T,4] = (i, j, h, w) -- or [V,T,4], one
     table per spatial view of the same frames --, the flip flag, and the constants of the transform that drew them (output side,
     mean and std).  `pre` selects the frozen eval's normalise-first arithmetic (mean / std in 0..1 units; otherwise 0..255).
-    `ebox` = (top, left, h, w) and `noise` fp32 [T,3,h,w] are the RandomErasing draw of the clip (h == 0 / None: not erased)."""
-    __slots__ = ("frames", "boxes", "flip", "crop_size", "mean", "std", "pre", "ebox", "noise")
+    `ebox` = (top, left, h, w) and `noise` fp32 [T,3,h,w] are the RandomErasing draw of the clip (h == 0 / None: not erased).
+    `aug_ops` int32 [8] and `aug_args` float64 [8,6] are its RandAugment plan (randaugment.RandAugmentDraw.draw; None: none), which
+    the device carries out on the uint8 frames before anything else."""
+    __slots__ = ("frames", "boxes", "flip", "crop_size", "mean", "std", "pre", "ebox", "noise", "aug_ops", "aug_args")
 
-    def __init__(self, frames, boxes, flip, crop_size, mean, std, pre=False, ebox=(0, 0, 0, 0), noise=None):
+    def __init__(self, frames, boxes, flip, crop_size, mean, std, pre=False, ebox=(0, 0, 0, 0), noise=None, aug_ops=None,
+                 aug_args=None):
         self.frames, self.boxes, self.flip = frames, boxes, bool(flip)
         self.crop_size, self.mean, self.std = int(crop_size), tuple(mean), tuple(std)
         self.pre, self.ebox, self.noise = bool(pre), tuple(int(v) for v in ebox), noise
+        if (aug_ops is None) != (aug_args is None):
+            raise ValueError("RawClip: aug_ops and aug_args come together")
+        self.aug_ops = None if aug_ops is None else torch.as_tensor(aug_ops, dtype=torch.int32).reshape(-1)
+        self.aug_args = None if aug_args is None else torch.as_tensor(aug_args, dtype=torch.float64).reshape(-1, NUM_ARGS)
 
     @property
     def num_views(self):
@@ -117,11 +128,15 @@ class RawClipBatch:
         ebox       int32 [R,4]      (top, left, h, w) of the erased box; h == 0: none
         noise      fp32 [n]         per erased row one [T,3,h,w] block
         noise_off  int64 [R]        where the row's block starts in `noise`
+        aug_ops    int32 [R,8]      RandAugment operation codes, layer by layer; 0: nothing (None: no row has a plan)
+        aug_args   float64 [R,8,6]  their arguments (randaugment.py)
     R = num_views * B rows, view-major: rows [v*B, (v+1)*B) are view v of the B clips, and the rows of one clip share its byte
     offset.  `pre`: the normalise-first form (mean / std in 0..1 units)."""
 
-    def __init__(self, frames, desc, boxes, crop_size, mean, std, pre=False, num_views=1, ebox=None, noise=None, noise_off=None):
+    def __init__(self, frames, desc, boxes, crop_size, mean, std, pre=False, num_views=1, ebox=None, noise=None, noise_off=None,
+                 aug_ops=None, aug_args=None):
         self.frames, self.desc, self.boxes = frames, desc, boxes
+        self.aug_ops, self.aug_args = aug_ops, aug_args
         self.crop_size, self.mean, self.std = int(crop_size), tuple(mean), tuple(std)
         self.pre, self.num_views = bool(pre), int(num_views)
         R = desc.shape[0]
@@ -140,6 +155,37 @@ class RawClipBatch:
     def erased(self):
         """Whether any row of the batch carries an erase box (decided on the host: no launch otherwise)."""
         return self.noise.numel() > 0 and bool((self.ebox[:, 2] > 0).any())
+
+    @property
+    def augmented(self):
+        """Whether any row of the batch carries a RandAugment operation (decided on the host: no upload and no launch otherwise)."""
+        return self.aug_ops is not None and bool((self.aug_ops != 0).any())
+
+    def _validate_aug(self):
+        ao, aa, d = self.aug_ops, self.aug_args, self.desc
+        if (ao is None) != (aa is None):
+            raise ValueError("RawClipBatch: aug_ops and aug_args come together")
+        if ao is None:
+            return
+        R = d.shape[0]
+        if ao.dtype != torch.int32 or tuple(ao.shape) != (R, MAX_LAYERS) or aa.dtype != torch.float64 \
+                or tuple(aa.shape) != (R, MAX_LAYERS, NUM_ARGS):
+            raise ValueError(f"RawClipBatch: malformed RandAugment tables aug_ops {tuple(ao.shape)} {ao.dtype}, aug_args "
+                             f"{tuple(aa.shape)} {aa.dtype}")
+        if bool(((ao < 0) | (ao > NUM_OPS)).any()):
+            raise ValueError(f"RawClipBatch: unknown RandAugment operation code in {ao[((ao < 0) | (ao > NUM_OPS)).any(1)][0].tolist()}")
+        if not bool(torch.isfinite(aa).all()):
+            raise ValueError("RawClipBatch: non-finite RandAugment argument")
+        on = (ao != 0).any(1)
+        small = on & ((d[:, 1] < MIN_SIDE) | (d[:, 2] < MIN_SIDE))
+        if bool(small.any()):
+            b = int(small.nonzero()[0])
+            raise ValueError(f"RawClipBatch: augmented clip {b} of {int(d[b, 1])}x{int(d[b, 2])} has a side below {MIN_SIDE}")
+        offs = d[:, 0].tolist()
+        for b in on.nonzero().reshape(-1).tolist():
+            if offs.count(offs[b]) > 1:
+                raise ValueError(f"RawClipBatch: augmented clip {b} shares its byte offset {offs[b]} with another row (the pass is "
+                                 "in place)")
 
     def validate(self):
         """Refuse, on the host, anything that would send the kernels outside a frame, a clip or a buffer."""
@@ -185,6 +231,7 @@ class RawClipBatch:
             b = int(bad.nonzero()[0])
             raise ValueError(f"RawClipBatch: the noise block of clip {b} ({T}x3x{int(eh[b])}x{int(ew[b])} values at {int(no[b])}) "
                              f"leaves the noise buffer of {nz.numel()} values")
+        self._validate_aug()
         return self
 
     def clip_frames(self, b):
@@ -197,6 +244,8 @@ class RawClipBatch:
         self.frames, self.desc, self.boxes = self.frames.pin_memory(), self.desc.pin_memory(), self.boxes.pin_memory()
         self.ebox, self.noise_off = self.ebox.pin_memory(), self.noise_off.pin_memory()
         self.noise = self.noise.pin_memory() if self.noise.numel() else self.noise
+        if self.aug_ops is not None:
+            self.aug_ops, self.aug_args = self.aug_ops.pin_memory(), self.aug_args.pin_memory()
         return self
 
     def to(self, device):
@@ -233,8 +282,18 @@ def collate_raw_clips(batch, *, collate_fn_map=None):
             blocks.append(c.noise.to(torch.float32).reshape(-1))
             n += blocks[-1].numel()
     noise = torch.cat(blocks) if blocks else torch.zeros(0, dtype=torch.float32)
+    aug_ops = aug_args = None
+    if any(c.aug_ops is not None for c in batch):      # rows of clips without a plan stay zero: no work
+        aug_ops = torch.zeros((len(rows), MAX_LAYERS), dtype=torch.int32)
+        aug_args = torch.zeros((len(rows), MAX_LAYERS, NUM_ARGS), dtype=torch.float64)
+        for r, (c, _, _) in enumerate(rows):
+            if c.aug_ops is not None:
+                if tuple(c.aug_ops.shape) != (MAX_LAYERS,) or tuple(c.aug_args.shape) != (MAX_LAYERS, NUM_ARGS):
+                    raise ValueError(f"collate: a RandAugment plan is int32 [{MAX_LAYERS}] / float64 [{MAX_LAYERS},{NUM_ARGS}]")
+                aug_ops[r], aug_args[r] = c.aug_ops, c.aug_args
     return RawClipBatch(flat, desc, boxes, first.crop_size, first.mean, first.std, pre=first.pre, num_views=V, ebox=ebox,
-                        noise=noise, noise_off=torch.tensor(noise_off, dtype=torch.int64)).validate()
+                        noise=noise, noise_off=torch.tensor(noise_off, dtype=torch.int64), aug_ops=aug_ops,
+                        aug_args=aug_args).validate()
 
 
 default_collate_fn_map[RawClip] = collate_raw_clips

@@ -23,6 +23,8 @@ copy stream, after the copies, into the slot's fp32 [B,3,T,S,S] buffer; `ready` 
 The flat buffer changes size from batch to batch: its pinned and device staging buffers only ever grow.  A batch in the frozen
 eval's normalise-first form goes through `vj_clip_transform_pre`, and a batch that carries RandomErasing boxes also ships its
 noise and has `vj_clip_erase` write it, on the copy stream after the transform (no copy and no launch when no clip is erased).
+A batch whose clips carry RandAugment plans ships the two plan tables too, and `vj_clip_randaug` rewrites the uploaded uint8 frames
+in place on the copy stream BEFORE the transform, with a workspace kept in the slot (again nothing when no clip has an operation).
 
 `EvalPrefetcher` is the same machinery for the batch structure of the frozen video eval (a list over segments of `RawClipBatch`,
 labels, clip indices): it iterates like the loader it wraps and hands out what `run_one_epoch` takes.
@@ -84,7 +86,18 @@ class DevicePrefetcher:
         frames = self._stage(slot, ("raw", i), raw.frames, flat=True)
         desc = self._stage(slot, ("desc", i), raw.desc)
         boxes = self._stage(slot, ("boxes", i), raw.boxes)
-        shape = (len(raw), 3, raw.num_frames, raw.crop_size, raw.crop_size)
+        if raw.augmented:
+            # RandAugment comes first, on the uint8 frames, in place.  Only the layers in which some clip has an operation are
+            # uploaded (each costs two launches); the workspace is the slot's and only ever grows.
+            live = (raw.aug_ops != 0).any(0)
+            aug_ops = self._stage(slot, ("aug_ops", i), raw.aug_ops[:, live].reshape(-1), flat=True).view(len(raw), -1)
+            aug_args = self._stage(slot, ("aug_args", i), raw.aug_args[:, live].reshape(-1), flat=True).view(len(raw), -1, 6)
+            need = ops.clip_randaug_ws_bytes(frames.numel(), len(raw), raw.num_frames)
+            ws = self._dev[slot].get(("aug_ws", i))
+            if ws is None or ws.numel() < need:
+                ws = self._dev[slot][("aug_ws", i)] = torch.empty(need + need // 4, dtype=torch.uint8, device=self.device)
+            ops.clip_randaug(frames, desc, raw.num_frames, aug_ops, aug_args, stream=self.copy_stream.cuda_stream, ws=ws)
+        shape =(len(raw), 3, raw.num_frames, raw.crop_size, raw.crop_size)
         out = self._dev[slot].get(("clip", i))
         if out is None or tuple(out.shape) != shape or out.dtype != torch.float32:
             out = torch.empty(shape, dtype=torch.float32, device=self.device)

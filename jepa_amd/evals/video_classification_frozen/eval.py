@@ -16,8 +16,10 @@ arithmetic, CSV columns, checkpoint dictionary and folder / file names.  Differe
     per split, default 8 batches) and `data.num_workers` (default 0).
   - uint8 frames are what crosses to the device: the transforms only draw, the views are made by vj_clip_transform_pre and
     vj_clip_erase on a copy stream, and batch k+1 uploads while batch k's frozen forward runs (engine.input.EvalPrefetcher).
-    `auto_augment` is false where the reference's probe training sets it true (PIL RandAugment is not implemented; logged once),
-    and the short-side resize of the validation transforms is the loader's job (the synthetic frames have that short side).
+    `auto_augment` stays false where the reference's probe training sets it true; its RandAugment is opt-in instead: with the
+    extension key `data.rand_augment: true` (default false; `synthetic_frames` only) the training transform draws the reference's
+    plan per clip and vj_clip_randaug applies it to the uint8 frames on the device, byte for byte what PIL gives.  The short-side
+    resize of the validation transforms is the loader's job (the synthetic frames have that short side).
   - the classifier is wrapped in DistributedDataParallel only when a process group with more than one rank is active; its
     checkpoint keys carry the `module.` prefix either way, so checkpoints move between this package and the reference.
   - with `pretrain.frames_per_clip` == 1 the encoder is the 2-D image ViT under FrameAggregation, which (as in the reference) only
@@ -35,6 +37,7 @@ import torch
 import torch.nn.functional as F
 from torch.nn.parallel import DistributedDataParallel
 
+from ...app.vjepa.randaugment import RandAugmentDraw
 from ...engine.input import EvalPrefetcher
 from ...src.datasets.data_manager import SyntheticFramesClassification, SyntheticVideoClassification
 from ...src.models import vision_transformer as vit
@@ -92,6 +95,7 @@ def main(args_eval, resume_preempt=False):
     eval_num_views_per_segment = args_data.get('num_views_per_segment', 1)
     synthetic_length = args_data.get('synthetic_length', None)
     num_workers = args_data.get('num_workers', 0)
+    rand_augment = bool(args_data.get('rand_augment', False))
 
     # -- OPTIMIZATION
     args_opt = args_eval.get('optimization')
@@ -158,7 +162,7 @@ def main(args_eval, resume_preempt=False):
                   world_size=world_size, rank=rank, num_classes=num_classes, synthetic_length=synthetic_length,
                   num_workers=num_workers)
     train_loader = make_dataloader(root_path=train_data_path, num_segments=eval_num_segments if attend_across_segments else 1,
-                                   num_views_per_segment=1, training=True, **common)
+                                   num_views_per_segment=1, training=True, rand_augment=rand_augment, **common)
     val_loader = make_dataloader(root_path=val_data_path, num_segments=eval_num_segments,
                                  num_views_per_segment=eval_num_views_per_segment, training=False, **common)
     if str(dataset_type).lower() == 'synthetic_frames':
@@ -362,11 +366,13 @@ def load_pretrained(encoder, pretrained, checkpoint_key='target_encoder'):
 
 def make_dataloader(root_path, batch_size, world_size, rank, dataset_type='VideoDataset', resolution=224, frames_per_clip=16,
                     frame_step=4, num_segments=8, eval_duration=None, num_views_per_segment=1, allow_segment_overlap=True,
-                    training=False, num_workers=12, subset_file=None, num_classes=None, synthetic_length=None, seed=None):
+                    training=False, num_workers=12, subset_file=None, num_classes=None, synthetic_length=None, seed=None,
+                    rand_augment=False):
     """The reference's loader factory (eval.py:442-488) for `dataset_type: synthetic` (finished fp32 views) and
     `synthetic_frames` (uint8 frames through the eval's transforms, with the reference's arguments: eval.py:460-469 -- batches of
     RawClipBatch, one per segment, for engine.input.EvalPrefetcher); every real dataset type raises, as data_manager.init_data
-    does."""
+    does.  rand_augment (extension, `data.rand_augment`): the training transform of `synthetic_frames` also draws the reference's
+    RandAugment plan per clip ('rand-m7-n4-mstd0.5-inc1', utils.py:233-237), which the prefetcher carries out on the device."""
     kind = str(dataset_type).lower()
     if kind not in ('synthetic', 'synthetic_frames'):
         raise NotImplementedError(
@@ -374,17 +380,25 @@ def make_dataloader(root_path, batch_size, world_size, rank, dataset_type='Video
             "use data.dataset_type: synthetic or synthetic_frames, or pass your own loader to run_one_epoch")
     if num_classes is None:
         raise ValueError(f"make_dataloader(dataset_type={kind!r}) needs num_classes")
+    if rand_augment and kind != 'synthetic_frames':
+        raise ValueError(f"data.rand_augment needs uint8 frames (dataset_type: synthetic_frames); {kind!r} yields finished fp32 views")
     length = synthetic_length if synthetic_length is not None else 8 * batch_size * world_size
     seed = (0 if training else 1) if seed is None else seed
     if kind == 'synthetic_frames':
         global _randaugment_logged
-        if training and not _randaugment_logged:
+        if training and rand_augment:
+            logger.info("probe training: the reference's RandAugment (auto_augment=True, eval.py:465: rand-m7-n4-mstd0.5-inc1, "
+                        "bicubic) is applied on the device (data.rand_augment), before the random resized crop and RandomErasing")
+        elif training and not _randaugment_logged:
             _randaugment_logged = True
             logger.info("probe training: the reference's RandAugment (auto_augment=True, eval.py:465) is NOT applied -- it runs "
-                        "through PIL on the CPU; the random resized crop and RandomErasing (reprob 0.25) are")
+                        "through PIL on the CPU; the random resized crop and RandomErasing (reprob 0.25) are "
+                        "(data.rand_augment: true applies it on the device)")
         transform = make_transforms(training=training, num_views_per_clip=num_views_per_segment, random_horizontal_flip=False,
                                     random_resize_aspect_ratio=(0.75, 4/3), random_resize_scale=(0.08, 1.0), reprob=0.25,
                                     auto_augment=False, motion_shift=False, crop_size=resolution)
+        if training and rand_augment:
+            transform.rand_augment = RandAugmentDraw('rand-m7-n4-mstd0.5-inc1')
         short = None if training else (resolution if num_views_per_segment > 1 else int(resolution * 256 / 224))
         dataset = SyntheticFramesClassification(length, num_classes, frames_per_clip, resolution, transform,
                                                 num_segments=num_segments, short_side=short, frame_step=frame_step, seed=seed)

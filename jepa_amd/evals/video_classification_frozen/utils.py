@@ -9,8 +9,10 @@ view.
 `make_transforms`, `VideoTransform` and `EvalVideoTransform` (utils.py:162-323) keep the reference's names, signatures and DRAWS and
 do no pixel work: they take decoded uint8 [T,H,W,3] frames and return a `RawClip` (app/vjepa/transforms.py) in the eval's
 normalise-first form -- the frames as they came, the crop boxes of every view, the flip, the RandomErasing box and noise -- and
-`engine.input.EvalPrefetcher` makes the fp32 views on the device (vj_clip_transform_pre, vj_clip_erase).  Out of scope, raising:
-`auto_augment=True` (PIL RandAugment) and the short-side resize of the two validation forms (cv2.resize in the reference), which is
+`engine.input.EvalPrefetcher` makes the fp32 views on the device (vj_clip_transform_pre, vj_clip_erase).  RandAugment is opt-in
+behind the attribute `VideoTransform.rand_augment` (a `RandAugmentDraw` of app/vjepa/randaugment.py: the plan is drawn first, as
+the reference augments first, and vj_clip_randaug carries it out on the uint8 frames on the device).  Out of scope, raising:
+`auto_augment=True` in the constructors (PIL RandAugment on the CPU) and the short-side resize of the two validation forms (cv2.resize in the reference), which is
 the loader's job here.  The decord loader behind the transforms is not part of this package.
 """
 import numpy as np
@@ -257,6 +259,10 @@ class VideoTransform(object):
         self.motion_shift = motion_shift
         self.crop_size = crop_size
         self.reprob = reprob
+        # None, or a randaugment.RandAugmentDraw: training calls then draw a RandAugment plan first and attach it to the RawClip
+        # (the reference's auto_augment=True is RandAugmentDraw('rand-m7-n4-mstd0.5-inc1'), utils.py:233-237); set after
+        # construction, the constructor keeps the reference's signature
+        self.rand_augment = None
         self.mean, self.std = _normalize_constants(normalize)
         # box(es) and flip are drawn exactly as in pretraining (the same functions of src/datasets/utils/video/transforms.py)
         self._spatial = _PretrainVideoTransform(
@@ -273,11 +279,16 @@ class VideoTransform(object):
             y1 = int(round((H - S) / 2.))
             boxes = torch.tensor([y1, x1, S, S], dtype=torch.int32).repeat(1, T, 1)
             return RawClip(frames, boxes, False, S, self.mean, self.std, pre=True)
+        aug_ops = aug_args = None
+        if self.rand_augment is not None:
+            # the reference augments first (utils.py:258-259), so these draws come before the crop, flip and erase draws
+            aug_ops, aug_args = self.rand_augment.draw(H, W)
         boxes, flip = self._spatial.draw(T, H, W)
         ebox, noise = ((0, 0, 0, 0), None)
         if self.reprob > 0:
             ebox, noise = draw_erase(self.reprob, T, S, S)
-        return RawClip(frames, boxes, flip, S, self.mean, self.std, pre=True, ebox=ebox, noise=noise)
+        return RawClip(frames, boxes, flip, S, self.mean, self.std, pre=True, ebox=ebox, noise=noise, aug_ops=aug_ops,
+                       aug_args=aug_args)
 
 
 class EvalVideoTransform(object):

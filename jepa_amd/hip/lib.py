@@ -63,6 +63,8 @@ SIGNATURES = {
     "vj_clip_transform": (I32, [P, I64, P, P, P, I64, I64, I64, F32, F32, F32, F32, F32, F32, P]),
     "vj_clip_transform_pre": (I32, [P, I64, P, P, P, I64, I64, I64, F32, F32, F32, F32, F32, F32, P]),
     "vj_clip_erase": (I32, [P, P, P, I64, P, I64, I64, I64, P]),
+    "vj_clip_randaug": (I32, [P, I64, P, I64, I64, P, P, I64, P, I64, P]),
+    "vj_clip_randaug_ws_bytes": (I64, [I64, I64, I64]),
     "vj_image_pack": (I32, [P, P, P, I64, I64, I64, I64, I64, I64, I64, P]),
     "vj_add_pos_bcast": (I32, [P, P, P, I64, I64, I64, I64, P]),
     "vj_pos_interp3d": (I32, [P, P, I64, I64, I64, I64, F64, F64, F64, I64, I64, I64, P]),

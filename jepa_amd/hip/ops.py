@@ -208,6 +208,42 @@ def clip_erase(clips, ebox, noise, noise_off, stream=None):
     return clips
 
 
+def clip_randaug_ws_bytes(frames_bytes, B, T):
+    """Bytes of workspace clip_randaug needs for a frame buffer of frames_bytes bytes holding B rows of T frames."""
+    return int(load_library().vj_clip_randaug_ws_bytes(int(frames_bytes), int(B), int(T)))
+
+
+def clip_randaug(frames, desc, T, aug_ops, aug_args, stream=None, ws=None):
+    """RandAugment in place on the uint8 frames of a flat clip buffer (the arguments `frames`, `desc` of clip_transform; T frames
+    per clip): aug_ops int32 [B,L] and aug_args float64 [B,L,6], L <= 8, are the plans drawn by
+    jepa_amd.app.vjepa.randaugment.RandAugmentDraw, one layer per column, applied in order; callers drop the columns in which no
+    clip has an operation (every column costs two launches) and validate the tables on the host (RawClipBatch.validate).  Byte
+    for byte what the reference's PIL path gives.  ws: a uint8 device buffer of at least clip_randaug_ws_bytes(...) bytes
+    (default: this stream's scratch buffer)."""
+    lib = load_library()
+    _req(frames, torch.uint8, "frames")
+    _req(desc, I64, "desc")
+    _req(aug_ops, torch.int32, "aug_ops")
+    _req(aug_args, torch.float64, "aug_args")
+    if frames.dim() != 1 or desc.dim() != 2 or desc.shape[1] != 4 or aug_ops.dim() != 2 or aug_ops.shape[0] != desc.shape[0] \
+            or tuple(aug_args.shape) != (aug_ops.shape[0], aug_ops.shape[1], 6) or aug_ops.shape[1] > 8:
+        raise ValueError(f"clip_randaug: frames {tuple(frames.shape)} / desc {tuple(desc.shape)} / aug_ops {tuple(aug_ops.shape)} / "
+                         f"aug_args {tuple(aug_args.shape)}: expected [nbytes], [B,4], [B,L], [B,L,6] with L <= 8")
+    if int(T) <= 0:
+        raise ValueError(f"clip_randaug: T={T} frames per clip")
+    B, L = aug_ops.shape
+    need = clip_randaug_ws_bytes(frames.numel(), B, T)
+    if ws is None:
+        ws = Scratch.get(need, frames.device, tag="clip_randaug", stream=stream)
+    else:
+        _req(ws, torch.uint8, "ws")
+        if ws.numel() < need:
+            raise ValueError(f"clip_randaug: ws of {ws.numel()} bytes, {need} needed")
+    check(lib.vj_clip_randaug(_ptr(frames), frames.numel(), _ptr(desc), B, int(T), _ptr(aug_ops), _ptr(aug_args), L, _ptr(ws),
+                              ws.numel(), _stream(stream)), "vj_clip_randaug")
+    return frames
+
+
 def add_pos_bcast(y, pos, B, S, Gt, out=None, stream=None):
     """out[b, t*S+s] = bf16(y[b,s] + pos[t*S+s]), t < Gt; y bf16 [B*S, D], pos fp32 [Gt*S, D] -> bf16 [B*Gt*S, D]."""
     lib = load_library()

@@ -10,6 +10,16 @@ Settings: B = 24, T = 16, S = 224 (the ViT-L/16 recipe), sources 240x320, 256x34
 3. the time the compute stream waits in `prefetcher.next()` for `ready` in a loop of real ViT-L train steps, for both paths
    (events on the compute stream before and after next(); batches start in pinned host memory).
 Prints one JSON line per measurement; nothing here is a gate.
+
+    python tools/input_bench.py --randaug [--launches 30] [--steps 12] [--rounds 3]
+    python tools/input_bench.py --randaug-pil          (CPU only, needs PIL)
+
+--randaug measures the device-side RandAugment (vj_clip_randaug) on K400-shaped batches (16 frames of 256x340, B = 4 and 24):
+4. kernel time per layer class -- every clip of the batch with the same operation in two layers (two launches per layer, no copy
+   back), halved -- and of whole plans drawn by RandAugmentDraw('rand-m7-n4-mstd0.5-inc1') (live layers only, copy back included);
+5. the wait of the compute stream on the input edge (EvalPrefetcher, timing events) inside a loop of frozen ViT-L forwards over
+   B = 4 training clips, with and without the plans, the two arms interleaved round by round.
+--randaug-pil times, for scale, the same plans carried out through PIL on one CPU core, per clip.
 """
 import argparse
 import json
@@ -117,12 +127,178 @@ def step_loop(dev, steps):
                           "h2d_bytes_per_step": int((pf.bytes_copied - b0) / steps)}), flush=True)
 
 
+RA_T, RA_HW = 16, (256, 340)
+RA_CLASSES = (("copy through (no operation)", 0, 0.0), ("table (Invert)", 3, 0.0), ("table + histogram (AutoContrast)", 1, 0.0),
+              ("table + histogram (Equalize)", 2, 0.0), ("table + luma sum (Contrast)", 9, 1.63), ("Color", 8, 1.63),
+              ("Sharpness", 11, 1.63), ("affine (Rotate)", 4, 21.0))
+
+
+def _drawn_plans(n, seed=0):
+    from jepa_amd.app.vjepa.randaugment import RandAugmentDraw
+    random.seed(seed)
+    np.random.seed(seed)
+    draw = RandAugmentDraw()
+    plans = [draw.draw(*RA_HW) for _ in range(n)]
+    return np.stack([p[0] for p in plans]), np.stack([p[1] for p in plans])
+
+
+def _timed_us(fn, launches):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    us = []
+    for _ in range(launches):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        us.append(1e3 * e0.elapsed_time(e1))
+    return us
+
+
+def randaug_kernel_times(dev, launches):
+    from jepa_amd.app.vjepa.randaugment import rotation_coefficients
+    H, W = RA_HW
+    clip_bytes = RA_T * H * W * 3
+    assert clip_bytes % 16 == 0
+    g = torch.Generator().manual_seed(0)
+    for nb in (4, 24):
+        frames = torch.randint(0, 256, (nb * clip_bytes,), generator=g, dtype=torch.uint8).to(dev)
+        keep = frames.clone()
+        desc = torch.tensor([[b * clip_bytes, H, W, 0] for b in range(nb)], dtype=torch.int64, device=dev)
+        ws = torch.empty(ops.clip_randaug_ws_bytes(frames.numel(), nb, RA_T), dtype=torch.uint8, device=dev)
+        for name, code, arg in RA_CLASSES:
+            a = np.zeros((nb, 2, 6))
+            a[:, :, 0] = arg
+            if code == 4:
+                a[:] = rotation_coefficients(arg, H, W)
+            o = torch.full((nb, 2), code, dtype=torch.int32, device=dev)
+            a = torch.from_numpy(a).to(dev)
+            frames.copy_(keep)
+            us = _timed_us(lambda: ops.clip_randaug(frames, desc, RA_T, o, a, ws=ws), launches)
+            med = statistics.median(us) / 2
+            print(json.dumps({"what": "vj_clip_randaug, one layer (table + apply launches)", "class": name, "batch": nb, "frames": RA_T,
+                              "source": list(RA_HW), "launches": launches, "median_us_per_layer": round(med, 1),
+                              "min_us_per_layer": round(min(us) / 2, 1), "max_us_per_layer": round(max(us) / 2, 1),
+                              "TB_per_s_read_plus_written": round(2 * frames.numel() / (med * 1e-6) / 1e12, 3)}), flush=True)
+        po, pa = _drawn_plans(nb)
+        live = (po != 0).any(0)
+        o, a = torch.from_numpy(po[:, live].copy()).to(dev), torch.from_numpy(pa[:, live].copy()).to(dev)
+        frames.copy_(keep)
+        us = _timed_us(lambda: ops.clip_randaug(frames, desc, RA_T, o, a, ws=ws), launches)
+        print(json.dumps({"what": "vj_clip_randaug, drawn plans rand-m7-n4-mstd0.5-inc1 (copy back included when the layer count is odd)",
+                          "batch": nb, "live_layers": int(live.sum()), "applied_operations": int((po != 0).sum()),
+                          "median_us": round(statistics.median(us), 1), "min_us": round(min(us), 1), "max_us": round(max(us), 1)}),
+              flush=True)
+
+
+def randaug_edge(dev, steps, rounds, nb=4):
+    from jepa_amd.app.vjepa.randaugment import RandAugmentDraw
+    from jepa_amd.engine.input import EvalPrefetcher
+    from jepa_amd.evals.video_classification_frozen.utils import ClipAggregation
+    from jepa_amd.evals.video_classification_frozen.utils import make_transforms as eval_transforms
+    from jepa_amd.src.models import vision_transformer as vit
+    torch.manual_seed(0)
+    enc = ClipAggregation(vit.vit_large(img_size=S, patch_size=16, num_frames=RA_T, tubelet_size=2, uniform_power=True),
+                          tubelet_size=2, attend_across_segments=True).to(dev).eval()
+    for p in enc.parameters():
+        p.requires_grad = False
+    g = torch.Generator().manual_seed(1)
+    src = [torch.randint(0, 256, (RA_T,) + RA_HW + (3,), generator=g, dtype=torch.uint8) for _ in range(nb)]
+
+    def host_batch(aug):
+        random.seed(2)
+        np.random.seed(2)
+        torch.manual_seed(2)
+        tf = eval_transforms(training=True, random_horizontal_flip=False, random_resize_aspect_ratio=(0.75, 4 / 3),
+                             random_resize_scale=(0.08, 1.0), reprob=0.25, crop_size=S)
+        if aug:
+            tf.rand_augment = RandAugmentDraw()
+        raw = torch.utils.data.default_collate([tf(f) for f in src]).pin_memory()
+        return ([raw], torch.zeros(nb, dtype=torch.int64), [torch.arange(RA_T)])
+
+    arms = {"plain": host_batch(False), "randaug": host_batch(True)}
+    rows = []
+    for r in range(rounds):
+        row = {}
+        for arm in (("plain", "randaug") if r % 2 == 0 else ("randaug", "plain")):
+            pf = EvalPrefetcher([arms[arm]] * (steps + 1), dev, timing=True)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.no_grad():
+                for k, (clips, _, idx) in enumerate(pf):
+                    if k == 1:
+                        e0.record()
+                    enc(clips, idx)
+            e1.record()
+            torch.cuda.synchronize()
+            waits = [max(0.0, a.elapsed_time(b)) for a, b in pf.edge_events]
+            row[arm] = dict(edge_wait_ms_first=round(waits[0], 3), edge_wait_ms_rest_mean=round(statistics.mean(waits[1:]), 4),
+                            edge_wait_ms_rest_max=round(max(waits[1:]), 4), iteration_ms=round(e0.elapsed_time(e1) / steps, 3))
+        rows.append(row)
+    raw = arms["randaug"][0][0]
+    print(json.dumps({"what": "input-edge wait inside a loop of frozen ViT-L forwards, EvalPrefetcher, interleaved arms", "batch": nb,
+                      "frames": RA_T, "source": list(RA_HW), "steps": steps, "live_layers": int((raw.aug_ops != 0).any(0).sum()),
+                      "applied_operations": int((raw.aug_ops != 0).sum()), "rounds": rows}), flush=True)
+
+
+def randaug_pil(clips=8):
+    """The plans of RandAugmentDraw carried out by PIL, frame by frame, on one CPU core: seconds per clip of 16 frames of 256x340."""
+    import time
+
+    from PIL import Image, ImageEnhance, ImageOps
+    torch.set_num_threads(1)
+    H, W = RA_HW
+    po, pa = _drawn_plans(clips)
+    g = np.random.RandomState(0)
+    fill = dict(resample=Image.BICUBIC, fillcolor=(128, 128, 128))
+    enhance = {8: ImageEnhance.Color, 9: ImageEnhance.Contrast, 10: ImageEnhance.Brightness, 11: ImageEnhance.Sharpness}
+
+    def one(img, code, a):
+        if code in (4, 12, 13, 14, 15):
+            return img.transform(img.size, Image.AFFINE, tuple(a), **fill)
+        if code in enhance:
+            return enhance[code](img).enhance(a[0])
+        if code == 7:
+            return img.point([min(255, i + int(a[0])) if i < 128 else i for i in range(256)] * 3)
+        return {1: ImageOps.autocontrast, 2: ImageOps.equalize, 3: ImageOps.invert, 5: lambda i: ImageOps.posterize(i, int(a[0])),
+                6: lambda i: ImageOps.solarize(i, int(a[0]))}[code](img)
+
+    secs = []
+    for c in range(clips):
+        frames = g.randint(0, 256, (RA_T, H, W, 3)).astype(np.uint8)
+        t0 = time.perf_counter()
+        imgs = [Image.fromarray(f) for f in frames]
+        for code, a in zip(po[c], pa[c]):
+            if code:
+                imgs = [one(i, int(code), a) for i in imgs]
+        np.stack([np.asarray(i) for i in imgs])
+        secs.append(time.perf_counter() - t0)
+    print(json.dumps({"what": "the same plans through PIL on one CPU core (uint8 in, uint8 out; the reference's ToTensor comes on top)",
+                      "clips": clips, "frames": RA_T, "source": list(RA_HW), "applied_operations_per_clip": (po != 0).sum(1).tolist(),
+                      "ms_per_clip_mean": round(1e3 * statistics.mean(secs), 1), "ms_per_clip_max": round(1e3 * max(secs), 1),
+                      "ms_per_applied_operation": round(1e3 * sum(secs) / max(1, int((po != 0).sum())), 1)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=30)
     ap.add_argument("--steps", type=int, default=12)
     ap.add_argument("--no-step-loop", action="store_true")
+    ap.add_argument("--randaug", action="store_true", help="the device-side RandAugment: kernel times and the input-edge wait")
+    ap.add_argument("--randaug-pil", action="store_true", help="CPU only: the same plans through PIL, for scale")
+    ap.add_argument("--rounds", type=int, default=3)
     args = ap.parse_args()
+    if args.randaug_pil:
+        return randaug_pil()
+    if args.randaug:
+        assert torch.cuda.is_available(), "needs an MI355X"
+        dev = torch.device("cuda", 0)
+        randaug_kernel_times(dev, max(20, args.launches))
+        if not args.no_step_loop:
+            randaug_edge(dev, args.steps, args.rounds)
+        return
     assert torch.cuda.is_available(), "needs an MI355X"
     dev = torch.device("cuda", 0)
     kernel_times(dev, max(20, args.launches))
