@@ -15,7 +15,8 @@ arithmetic, CSV columns, checkpoint dictionary and folder / file names.  Differe
     reference feeds it (no pre-hook is registered there, eval.py:451); its table is interpolated bicubically at other square sizes
     (vj_pos_interp2d_bicubic).
   - bf16 compute, `use_bfloat16`, `use_silu` and the DistributedDataParallel wrapping are handled exactly as in the video eval
-    (..video_classification_frozen.eval, whose load_checkpoint, load_pretrained, init_model and init_opt are these files' too).
+    (..video_classification_frozen.eval, whose load_pretrained, init_model and init_opt are this file's too; what the two evals
+    share beyond those is in ..frozen).
   - there are no real image datasets: `data.dataset_name` must be `synthetic` (seeded labelled images,
     src/datasets/data_manager.py: SyntheticImageClassification); extension keys `data.synthetic_length` (items per split, default 8
     batches) and `data.num_workers` (default 0).
@@ -23,23 +24,20 @@ arithmetic, CSV columns, checkpoint dictionary and folder / file names.  Differe
     makes (frozen_features).
   - `main` returns a small record of the run (per-epoch accuracies, per-iteration training loss and learning rate).
 """
-import os
 import pprint
 
 import numpy as np
 import torch
-from torch.nn.parallel import DistributedDataParallel
 
-from ...hip import ops
 from ...src.datasets.data_manager import SyntheticImageClassification
 from ...src.models.attentive_pooler import AttentiveClassifier
-from ...src.utils.distributed import AllReduce, init_distributed
-from ...src.utils.logging import AverageMeter, CSVLogger, get_logger
-from ..multihead import parse_multihead_kwargs
+from ...src.utils.logging import get_logger
+from ..frozen import classifier_state_dict, load_checkpoint  # noqa: F401  (the reference's names in this file)
+from ..frozen import distributed as _distributed
+from ..frozen import (chunked_call, freeze, max_clips_per_call, parse_config, run_probe_epoch, setup_run, synthetic_dataloader,
+                      train_single_probe, widest_activation)
 from ..multihead import run as run_multihead
-from ..video_classification_frozen.eval import (_distributed, classifier_state_dict, init_model, init_opt,  # noqa: F401
-                                                load_checkpoint, load_pretrained)
-from ..video_classification_frozen.utils import _widest, max_clips_per_call
+from ..video_classification_frozen.eval import init_model, init_opt, load_pretrained  # noqa: F401
 
 logger = get_logger(__name__)
 
@@ -51,21 +49,8 @@ pp = pprint.PrettyPrinter(indent=4)
 
 
 def main(args_eval, resume_preempt=False):
-    # -- PRETRAIN
-    args_pretrain = args_eval.get('pretrain')
-    checkpoint_key = args_pretrain.get('checkpoint_key', 'target_encoder')
-    model_name = args_pretrain.get('model_name', None)
-    patch_size = args_pretrain.get('patch_size', None)
-    pretrain_folder = args_pretrain.get('folder', None)
-    ckp_fname = args_pretrain.get('checkpoint', None)
-    tag = args_pretrain.get('write_tag', None)
-    use_sdpa = args_pretrain.get('use_sdpa', True)
-    use_SiLU = args_pretrain.get('use_silu', False)
-    tight_SiLU = args_pretrain.get('tight_silu', True)
-    uniform_power = args_pretrain.get('uniform_power', False)
-    pretrained_path = os.path.join(pretrain_folder, ckp_fname)
-    tubelet_size = args_pretrain.get('tubelet_size', 2)
-    frames_per_clip = args_pretrain.get('frames_per_clip', 1)
+    cfg = parse_config(args_eval, resume_preempt)
+    multihead = cfg.multihead
 
     # -- DATA
     args_data = args_eval.get('data')
@@ -77,49 +62,15 @@ def main(args_eval, resume_preempt=False):
     synthetic_length = args_data.get('synthetic_length', None)
     num_workers = args_data.get('num_workers', 0)
 
-    # -- OPTIMIZATION
-    args_opt = args_eval.get('optimization')
-    batch_size = args_opt.get('batch_size')
-    num_epochs = args_opt.get('num_epochs')
-    wd = args_opt.get('weight_decay')
-    start_lr = args_opt.get('start_lr')
-    lr = args_opt.get('lr')
-    final_lr = args_opt.get('final_lr')
-    warmup = args_opt.get('warmup')
-    use_bfloat16 = args_opt.get('use_bfloat16')
-    multihead = parse_multihead_kwargs(args_opt)   # None: the single probe below; a list: one bank of probes (..multihead)
-
-    # -- EXPERIMENT-ID/TAG (optional)
-    resume_checkpoint = args_eval.get('resume_checkpoint', False) or resume_preempt
-    eval_tag = args_eval.get('tag', None)
-
-    if not torch.cuda.is_available():
-        raise RuntimeError("the frozen eval computes on the GPU through libvjepa_hip.so (there is no CPU path)")
-    device = torch.device('cuda:0')
-    torch.cuda.set_device(device)
-
-    world_size, rank = init_distributed()
-    logger.info(f'Initialized (rank/world-size) {rank}/{world_size}')
-
-    # -- log/checkpointing paths
-    folder = os.path.join(pretrain_folder, 'image_classification_frozen/')
-    if eval_tag is not None:
-        folder = os.path.join(folder, eval_tag)
-    os.makedirs(folder, exist_ok=True)
-    log_file = os.path.join(folder, f'{tag}_r{rank}.csv')
-    latest_path = os.path.join(folder, f'{tag}-latest.pth.tar')
-
-    if rank == 0 and multihead is None:
-        csv_logger = CSVLogger(log_file, ('%d', 'epoch'), ('%.5f', 'loss'), ('%.5f', 'acc'))
+    run = setup_run(cfg, 'image_classification_frozen/', csv=multihead is None)
+    device = run.device
 
     # -- pretrained encoder (frozen): the video ViT, or the image ViT with frames_per_clip == 1; both are fed [B,C,H,W] directly
-    encoder = init_model(crop_size=resolution, device=device, pretrained=pretrained_path, model_name=model_name,
-                         patch_size=patch_size, frames_per_clip=frames_per_clip, tubelet_size=tubelet_size,
-                         uniform_power=uniform_power, checkpoint_key=checkpoint_key, use_SiLU=use_SiLU, tight_SiLU=tight_SiLU,
-                         use_sdpa=use_sdpa)
-    encoder.eval()
-    for p in encoder.parameters():
-        p.requires_grad = False
+    encoder = init_model(crop_size=resolution, device=device, pretrained=cfg.pretrained_path, model_name=cfg.model_name,
+                         patch_size=cfg.patch_size, frames_per_clip=cfg.frames_per_clip, tubelet_size=cfg.tubelet_size,
+                         uniform_power=cfg.uniform_power, checkpoint_key=cfg.checkpoint_key, use_SiLU=cfg.use_SiLU,
+                         tight_SiLU=cfg.tight_SiLU, use_sdpa=cfg.use_sdpa)
+    freeze(encoder)
 
     # -- init classifier
     if multihead is None:
@@ -127,7 +78,7 @@ def main(args_eval, resume_preempt=False):
                                          num_classes=num_classes).to(device)
 
     common = dict(dataset_name=dataset_name, root_path=root_path, resolution=resolution, image_folder=image_folder,
-                  batch_size=batch_size, world_size=world_size, rank=rank, num_classes=num_classes,
+                  batch_size=cfg.batch_size, world_size=run.world_size, rank=run.rank, num_classes=num_classes,
                   synthetic_length=synthetic_length, num_workers=num_workers)
     train_loader = make_dataloader(training=True, **common)
     val_loader = make_dataloader(training=False, **common)
@@ -136,55 +87,24 @@ def main(args_eval, resume_preempt=False):
 
     if multihead is not None:
         return run_multihead(hps=multihead, init_opt=init_opt, features=_image_features, encoder=encoder,
-                             train_loader=train_loader, val_loader=val_loader, num_classes=num_classes, num_epochs=num_epochs,
-                             use_bfloat16=use_bfloat16, folder=folder, tag=tag, rank=rank, world_size=world_size,
-                             batch_size=batch_size, resume_checkpoint=resume_checkpoint, distributed=_distributed(), device=device)
+                             train_loader=train_loader, val_loader=val_loader, num_classes=num_classes,
+                             num_epochs=cfg.num_epochs, use_bfloat16=cfg.use_bfloat16, folder=run.folder, tag=cfg.tag,
+                             rank=run.rank, world_size=run.world_size, batch_size=cfg.batch_size,
+                             resume_checkpoint=cfg.resume_checkpoint, distributed=_distributed(), device=device)
 
     # -- optimizer and scheduler
-    optimizer, scaler, scheduler, wd_scheduler = init_opt(classifier=classifier, wd=wd, start_lr=start_lr, ref_lr=lr,
-                                                          final_lr=final_lr, iterations_per_epoch=ipe, warmup=warmup,
-                                                          num_epochs=num_epochs, use_bfloat16=use_bfloat16)
-    if _distributed():
-        classifier = DistributedDataParallel(classifier, static_graph=True)
+    opt = init_opt(classifier=classifier, wd=cfg.wd, start_lr=cfg.start_lr, ref_lr=cfg.lr, final_lr=cfg.final_lr,
+                   iterations_per_epoch=ipe, warmup=cfg.warmup, num_epochs=cfg.num_epochs, use_bfloat16=cfg.use_bfloat16)
 
-    # -- load training checkpoint
-    start_epoch = 0
-    if resume_checkpoint:
-        classifier, optimizer, scaler, start_epoch = load_checkpoint(device=device, r_path=latest_path, classifier=classifier,
-                                                                     opt=optimizer, scaler=scaler)
-        for _ in range(start_epoch * ipe):
-            scheduler.step()
-            wd_scheduler.step()
+    def train_epoch(**probe):
+        return run_one_epoch(device=device, training=True, encoder=encoder, data_loader=train_loader,
+                             use_bfloat16=cfg.use_bfloat16, **probe)
 
-    def save_checkpoint(epoch):
-        save_dict = {
-            'classifier': classifier_state_dict(classifier),
-            'opt': optimizer.state_dict(),
-            'scaler': None if scaler is None else scaler.state_dict(),
-            'epoch': epoch,
-            'batch_size': batch_size,
-            'world_size': world_size,
-            'lr': lr
-        }
-        if rank == 0:
-            torch.save(save_dict, latest_path)
+    def val_epoch(**probe):
+        return run_one_epoch(device=device, training=False, encoder=encoder, data_loader=val_loader,
+                             use_bfloat16=cfg.use_bfloat16, **probe)
 
-    record = dict(start_epoch=start_epoch, train_acc=[], val_acc=[], train_history=[])
-    for epoch in range(start_epoch, num_epochs):
-        logger.info('Epoch %d' % (epoch + 1))
-        train_acc = run_one_epoch(device=device, training=True, encoder=encoder, classifier=classifier, scaler=scaler,
-                                  optimizer=optimizer, scheduler=scheduler, wd_scheduler=wd_scheduler, data_loader=train_loader,
-                                  use_bfloat16=use_bfloat16, history=record['train_history'])
-        val_acc = run_one_epoch(device=device, training=False, encoder=encoder, classifier=classifier, scaler=scaler,
-                                optimizer=optimizer, scheduler=scheduler, wd_scheduler=wd_scheduler, data_loader=val_loader,
-                                use_bfloat16=use_bfloat16)
-        logger.info('[%5d] train: %.3f%% test: %.3f%%' % (epoch + 1, train_acc, val_acc))
-        if rank == 0:
-            csv_logger.log(epoch + 1, train_acc, val_acc)
-        save_checkpoint(epoch + 1)
-        record['train_acc'].append(train_acc)
-        record['val_acc'].append(val_acc)
-    return record
+    return train_single_probe(cfg, run, classifier, opt, ipe, train_epoch, val_epoch)
 
 
 def frozen_features(encoder, imgs):
@@ -193,21 +113,10 @@ def frozen_features(encoder, imgs):
     and the calls' outputs are joined by the bit-exact row copy."""
     if not (hasattr(encoder, 'patch_size') and hasattr(encoder, 'tubelet_size') and hasattr(encoder, 'num_frames')):
         return encoder(imgs)
-    B = imgs.shape[0]
     frames = encoder.num_frames if imgs.dim() == 4 else imgs.shape[2]
     depth = frames // encoder.tubelet_size if getattr(encoder, 'is_video', True) else 1     # the image model has no tubelets
     tokens = depth * (imgs.shape[-2] // encoder.patch_size) * (imgs.shape[-1] // encoder.patch_size)
-    cap = max_clips_per_call(_widest(encoder), max(tokens, 1))
-    if B <= cap:
-        return encoder(imgs)
-    out = None
-    for c0 in range(0, B, cap):
-        f = encoder(imgs[c0:c0 + cap])
-        if out is None:
-            out = torch.empty((B,) + tuple(f.shape[1:]), dtype=f.dtype, device=f.device)
-        N, D = f.shape[1], f.shape[2]
-        ops.copy_rows(f, out, 1, f.shape[0] * N, 0, B * N, c0 * N, f.shape[0] * N, D)
-    return out
+    return chunked_call(encoder, imgs, max_clips_per_call(widest_activation(encoder), max(tokens, 1)))
 
 
 def _image_features(encoder, data, device):
@@ -219,49 +128,21 @@ def run_one_epoch(device, training, encoder, classifier, scaler, optimizer, sche
                   *, history=None):
     """The reference's epoch (eval.py:262-317), same parameters in the same order.  history (keyword-only, optional list):
     (learning rate, loss) of each training iteration."""
-    classifier.train(mode=training)
     criterion = torch.nn.CrossEntropyLoss()
-    top1_meter = AverageMeter()
-    for itr, data in enumerate(data_loader):
 
-        if training:
-            scheduler.step()
-            wd_scheduler.step()
-
+    def features(data):
         imgs, labels = data[0].to(device, non_blocking=True), data[1].to(device)
-        with torch.no_grad():
-            outputs = frozen_features(encoder, imgs)
-            if not training:
-                outputs = classifier(outputs)
-        if training:
-            outputs = classifier(outputs)
+        return frozen_features(encoder, imgs), labels
 
+    def loss_and_top1(outputs, labels):
+        # the prediction is the arg-max of the logits
+        outputs = classifier(outputs)
         loss = criterion(outputs, labels)
         with torch.no_grad():
-            top1_acc = 100. * outputs.max(dim=1).indices.eq(labels).sum() / len(imgs)
-            top1_acc = float(AllReduce.apply(top1_acc))
-            top1_meter.update(top1_acc)
+            return loss, 100. * outputs.max(dim=1).indices.eq(labels).sum() / len(labels)
 
-        if training:
-            if use_bfloat16:
-                scaler.scale(loss).backward()
-                scaler.unscale_(optimizer)
-                torch.nn.utils.clip_grad_norm_(classifier.parameters(), 1.0)
-                scaler.step(optimizer)
-                scaler.update()
-            else:
-                loss.backward()
-                torch.nn.utils.clip_grad_norm_(classifier.parameters(), 1.0)
-                optimizer.step()
-            optimizer.zero_grad()
-            if history is not None:
-                history.append((optimizer.param_groups[0]['lr'], float(loss.detach())))
-
-        if itr % 20 == 0:
-            logger.info('[%5d] %.3f%% (loss: %.3f) [mem: %.2e]'
-                        % (itr, top1_meter.avg, float(loss.detach()), torch.cuda.max_memory_allocated() / 1024.**2))
-
-    return top1_meter.avg
+    return run_probe_epoch(training, classifier, scaler, optimizer, scheduler, wd_scheduler, data_loader, use_bfloat16, features,
+                           loss_and_top1, history=history)
 
 
 def make_dataloader(dataset_name, root_path, image_folder, batch_size, world_size, rank, resolution=224, training=False,
@@ -274,8 +155,8 @@ def make_dataloader(dataset_name, root_path, image_folder, batch_size, world_siz
             "part of this package; use data.dataset_name: synthetic, or pass your own loader to run_one_epoch")
     if num_classes is None:
         raise ValueError("make_dataloader(dataset_name='synthetic') needs num_classes")
-    length = synthetic_length if synthetic_length is not None else 8 * batch_size * world_size
-    dataset = SyntheticImageClassification(length, num_classes, resolution, seed=(0 if training else 1) if seed is None else seed)
-    sampler = torch.utils.data.distributed.DistributedSampler(dataset, num_replicas=world_size, rank=rank, shuffle=training)
-    return torch.utils.data.DataLoader(dataset, sampler=sampler, batch_size=batch_size, drop_last=False,
-                                       num_workers=num_workers, pin_memory=True, persistent_workers=False)
+
+    def make_dataset(length, seed):
+        return SyntheticImageClassification(length, num_classes, resolution, seed=seed)
+
+    return synthetic_dataloader(make_dataset, batch_size, world_size, rank, training, num_workers, synthetic_length, seed)

@@ -6,7 +6,9 @@ they run their own single-probe code, unchanged.
 One AttentiveClassifierBank on one frozen forward pass per iteration; per probe its own AdamW, LR / WD schedule and GradScaler
 (the evals' `init_opt`); ONE backward of the summed per-probe losses (the probes share no parameter, so each receives its own
 gradient); `clip_grad_norm_(1.0)`, accuracy meter and `{tag}_p{p}_r{rank}.csv` per probe; the checkpoint carries per-probe lists
-of classifier (reference format, `module.` prefix: the winner loads into the reference), optimizer and scaler state.
+of classifier (reference format, `module.` prefix: the winner loads into the reference), optimizer and scaler state.  The update
+of one probe, the prefix and the resume frame are the single-probe evals' too (.frozen); the epoch loop is this module's own: its
+meters, schedules and log line are per-probe lists.
 """
 import torch
 import torch.nn.functional as F
@@ -15,27 +17,10 @@ from torch.nn.parallel import DistributedDataParallel
 from ..src.models.attentive_pooler import AttentiveClassifierBank
 from ..src.utils.distributed import AllReduce
 from ..src.utils.logging import AverageMeter, CSVLogger, get_logger
+from .frozen import HP_KEYS, parse_multihead_kwargs  # noqa: F401  (this module's names)
+from .frozen import add_module_prefix, probe_update, resume, strip_module_prefix
 
 logger = get_logger(__name__)
-
-HP_KEYS = ('lr', 'start_lr', 'final_lr', 'weight_decay', 'warmup')
-
-
-def parse_multihead_kwargs(args_opt):
-    """-> None without the key (the single-probe eval), else one {lr, start_lr, final_lr, weight_decay, warmup} per probe with the
-    missing keys taken from `optimization`."""
-    entries = args_opt.get('multihead_kwargs', None)
-    if entries is None:
-        return None
-    if not isinstance(entries, (list, tuple)) or len(entries) == 0 or not all(isinstance(e, dict) for e in entries):
-        raise ValueError("optimization.multihead_kwargs must be a non-empty list of dictionaries")
-    hps = []
-    for i, e in enumerate(entries):
-        unknown = sorted(set(e) - set(HP_KEYS))
-        if unknown:
-            raise ValueError(f"optimization.multihead_kwargs[{i}]: unknown keys {unknown}; a probe may override {list(HP_KEYS)}")
-        hps.append({k: e.get(k, args_opt.get(k)) for k in HP_KEYS})
-    return hps
 
 
 def _probes(bank):
@@ -80,7 +65,7 @@ def run(*, hps, init_opt, features, encoder, train_loader, val_loader, num_class
                 csv_loggers[p].log(epoch + 1, train_acc[p], val_acc[p])
         if rank == 0:
             torch.save({
-                'classifier': [{'module.' + k: v for k, v in m.state_dict().items()} for m in _probes(bank)],
+                'classifier': [add_module_prefix(m.state_dict()) for m in _probes(bank)],
                 'opt': [o.state_dict() for o in optimizers],
                 'scaler': [None if s is None else s.state_dict() for s in scalers],
                 'epoch': epoch + 1,
@@ -131,15 +116,7 @@ def run_one_epoch(device, training, features, encoder, bank, scalers, optimizers
             else:
                 sum(losses).backward()
             for m, opt, scaler in zip(probes, optimizers, scalers):
-                if use_bfloat16:
-                    scaler.unscale_(opt)
-                    torch.nn.utils.clip_grad_norm_(m.parameters(), 1.0)
-                    scaler.step(opt)
-                    scaler.update()
-                else:
-                    torch.nn.utils.clip_grad_norm_(m.parameters(), 1.0)
-                    opt.step()
-                opt.zero_grad()
+                probe_update(m, opt, scaler, use_bfloat16)
             if history is not None:
                 history.append(([o.param_groups[0]['lr'] for o in optimizers], [float(ls.detach()) for ls in losses]))
         if itr % 20 == 0:
@@ -151,21 +128,16 @@ def run_one_epoch(device, training, features, encoder, bank, scalers, optimizers
 
 def load_checkpoint(r_path, bank, optimizers, scalers):
     """Restores every probe, optimizer and scaler from the per-probe lists -> the epoch to continue from (0 when nothing loads)."""
-    try:
-        checkpoint = torch.load(r_path, map_location=torch.device('cpu'))
-        epoch = checkpoint['epoch']
+    def restore(checkpoint, epoch):
         probes = _probes(bank)
         if len(checkpoint['classifier']) != len(probes):
             raise ValueError(f"checkpoint holds {len(checkpoint['classifier'])} probes, the config asks for {len(probes)}")
         for m, sd, opt, osd, scaler, ssd in zip(probes, checkpoint['classifier'], optimizers, checkpoint['opt'], scalers,
                                                 checkpoint['scaler']):
-            m.load_state_dict({(k[len('module.'):] if k.startswith('module.') else k): v for k, v in sd.items()})
+            m.load_state_dict(strip_module_prefix(sd))
             opt.load_state_dict(osd)
             if scaler is not None:
                 scaler.load_state_dict(ssd)
         logger.info(f'loaded {len(probes)} probes and their optimizers from epoch {epoch}; read-path: {r_path}')
-        del checkpoint
-    except Exception as e:
-        logger.info(f'Encountered exception when loading checkpoint {e}')
-        epoch = 0
-    return epoch
+
+    return resume(r_path, restore)

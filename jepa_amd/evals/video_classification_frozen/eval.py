@@ -28,24 +28,23 @@ arithmetic, CSV columns, checkpoint dictionary and folder / file names.  Differe
   - `optimization.multihead_kwargs` (optional list of dictionaries overriding lr / start_lr / final_lr / weight_decay / warmup)
     trains one probe per entry on the same frozen forward pass (..multihead); without the key nothing changes.
 """
-import os
 import pprint
 from functools import partial
 
 import numpy as np
 import torch
 import torch.nn.functional as F
-from torch.nn.parallel import DistributedDataParallel
 
 from ...app.vjepa.randaugment import RandAugmentDraw
 from ...engine.input import EvalPrefetcher
 from ...src.datasets.data_manager import SyntheticFramesClassification, SyntheticVideoClassification
 from ...src.models import vision_transformer as vit
 from ...src.models.attentive_pooler import AttentiveClassifier
-from ...src.utils.distributed import AllReduce, init_distributed
-from ...src.utils.logging import AverageMeter, CSVLogger, get_logger
+from ...src.utils.logging import get_logger
 from ...src.utils.schedulers import CosineWDSchedule, WarmupCosineSchedule
-from ..multihead import parse_multihead_kwargs
+from ..frozen import classifier_state_dict, load_checkpoint  # noqa: F401  (the reference's names in this file)
+from ..frozen import distributed as _distributed
+from ..frozen import freeze, parse_config, run_probe_epoch, setup_run, synthetic_dataloader, train_single_probe
 from ..multihead import run as run_multihead
 from .utils import ClipAggregation, FrameAggregation, make_transforms
 
@@ -60,27 +59,10 @@ pp = pprint.PrettyPrinter(indent=4)
 _randaugment_logged = False
 
 
-def _distributed():
-    import torch.distributed as dist
-    return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-
-
 def main(args_eval, resume_preempt=False):
-    # -- PRETRAIN
-    args_pretrain = args_eval.get('pretrain')
-    checkpoint_key = args_pretrain.get('checkpoint_key', 'target_encoder')
-    model_name = args_pretrain.get('model_name', None)
-    patch_size = args_pretrain.get('patch_size', None)
-    pretrain_folder = args_pretrain.get('folder', None)
-    ckp_fname = args_pretrain.get('checkpoint', None)
-    tag = args_pretrain.get('write_tag', None)
-    use_sdpa = args_pretrain.get('use_sdpa', True)
-    use_SiLU = args_pretrain.get('use_silu', False)
-    tight_SiLU = args_pretrain.get('tight_silu', True)
-    uniform_power = args_pretrain.get('uniform_power', False)
-    pretrained_path = os.path.join(pretrain_folder, ckp_fname)
-    tubelet_size = args_pretrain.get('tubelet_size', 2)
-    pretrain_frames_per_clip = args_pretrain.get('frames_per_clip', 1)
+    cfg = parse_config(args_eval, resume_preempt)
+    multihead = cfg.multihead
+    args_pretrain, args_opt = cfg.args_pretrain, cfg.args_opt
 
     # -- DATA
     args_data = args_eval.get('data')
@@ -97,60 +79,29 @@ def main(args_eval, resume_preempt=False):
     num_workers = args_data.get('num_workers', 0)
     rand_augment = bool(args_data.get('rand_augment', False))
 
-    # -- OPTIMIZATION
-    args_opt = args_eval.get('optimization')
+    # -- OPTIMIZATION (the video eval's own keys)
     resolution = args_opt.get('resolution', 224)
-    batch_size = args_opt.get('batch_size')
     attend_across_segments = args_opt.get('attend_across_segments', False)
-    num_epochs = args_opt.get('num_epochs')
-    wd = args_opt.get('weight_decay')
-    start_lr = args_opt.get('start_lr')
-    lr = args_opt.get('lr')
-    final_lr = args_opt.get('final_lr')
-    warmup = args_opt.get('warmup')
-    use_bfloat16 = args_opt.get('use_bfloat16')
-    multihead = parse_multihead_kwargs(args_opt)   # None: the single probe below; a list: one bank of probes (..multihead)
 
-    # -- EXPERIMENT-ID/TAG (optional)
-    resume_checkpoint = args_eval.get('resume_checkpoint', False) or resume_preempt
-    eval_tag = args_eval.get('tag', None)
-
-    if pretrain_frames_per_clip == 1 and not attend_across_segments:
+    if cfg.frames_per_clip == 1 and not attend_across_segments:
         raise ValueError("pretrain.frames_per_clip == 1 needs optimization.attend_across_segments: true: the reference's frame "
                          "aggregation only has the concatenated form (one [B, S*T*N, D] tensor per view), and the epoch loop of "
                          "attend_across_segments: false would iterate over the batch dimension of those tensors")
 
-    if not torch.cuda.is_available():
-        raise RuntimeError("the frozen eval computes on the GPU through libvjepa_hip.so (there is no CPU path)")
-    device = torch.device('cuda:0')
-    torch.cuda.set_device(device)
-
-    world_size, rank = init_distributed()
-    logger.info(f'Initialized (rank/world-size) {rank}/{world_size}')
-
-    # -- log/checkpointing paths
-    folder = os.path.join(pretrain_folder, 'video_classification_frozen/')
-    if eval_tag is not None:
-        folder = os.path.join(folder, eval_tag)
-    os.makedirs(folder, exist_ok=True)
-    log_file = os.path.join(folder, f'{tag}_r{rank}.csv')
-    latest_path = os.path.join(folder, f'{tag}-latest.pth.tar')
-
-    if rank == 0 and multihead is None:
-        csv_logger = CSVLogger(log_file, ('%d', 'epoch'), ('%.5f', 'loss'), ('%.5f', 'acc'))
+    run = setup_run(cfg, 'video_classification_frozen/', csv=multihead is None)
+    device = run.device
 
     # -- pretrained encoder (frozen)
-    encoder = init_model(crop_size=resolution, device=device, pretrained=pretrained_path, model_name=model_name,
-                         patch_size=patch_size, tubelet_size=tubelet_size, frames_per_clip=pretrain_frames_per_clip,
-                         uniform_power=uniform_power, checkpoint_key=checkpoint_key, use_SiLU=use_SiLU, tight_SiLU=tight_SiLU,
-                         use_sdpa=use_sdpa)
-    if pretrain_frames_per_clip == 1:
+    encoder = init_model(crop_size=resolution, device=device, pretrained=cfg.pretrained_path, model_name=cfg.model_name,
+                         patch_size=cfg.patch_size, tubelet_size=cfg.tubelet_size, frames_per_clip=cfg.frames_per_clip,
+                         uniform_power=cfg.uniform_power, checkpoint_key=cfg.checkpoint_key, use_SiLU=cfg.use_SiLU,
+                         tight_SiLU=cfg.tight_SiLU, use_sdpa=cfg.use_sdpa)
+    if cfg.frames_per_clip == 1:
         encoder = FrameAggregation(encoder).to(device)
     else:
-        encoder = ClipAggregation(encoder, tubelet_size=tubelet_size, attend_across_segments=attend_across_segments).to(device)
-    encoder.eval()
-    for p in encoder.parameters():
-        p.requires_grad = False
+        encoder = ClipAggregation(encoder, tubelet_size=cfg.tubelet_size,
+                                  attend_across_segments=attend_across_segments).to(device)
+    freeze(encoder)
 
     # -- init classifier
     if multihead is None:
@@ -158,9 +109,9 @@ def main(args_eval, resume_preempt=False):
                                          num_classes=num_classes).to(device)
 
     common = dict(dataset_type=dataset_type, resolution=resolution, frames_per_clip=eval_frames_per_clip,
-                  frame_step=eval_frame_step, eval_duration=eval_duration, allow_segment_overlap=True, batch_size=batch_size,
-                  world_size=world_size, rank=rank, num_classes=num_classes, synthetic_length=synthetic_length,
-                  num_workers=num_workers)
+                  frame_step=eval_frame_step, eval_duration=eval_duration, allow_segment_overlap=True,
+                  batch_size=cfg.batch_size, world_size=run.world_size, rank=run.rank, num_classes=num_classes,
+                  synthetic_length=synthetic_length, num_workers=num_workers)
     train_loader = make_dataloader(root_path=train_data_path, num_segments=eval_num_segments if attend_across_segments else 1,
                                    num_views_per_segment=1, training=True, rand_augment=rand_augment, **common)
     val_loader = make_dataloader(root_path=val_data_path, num_segments=eval_num_segments,
@@ -174,59 +125,24 @@ def main(args_eval, resume_preempt=False):
     if multihead is not None:
         return run_multihead(hps=multihead, init_opt=init_opt, features=partial(_view_features, attend_across_segments),
                              encoder=encoder, train_loader=train_loader, val_loader=val_loader, num_classes=num_classes,
-                             num_epochs=num_epochs, use_bfloat16=use_bfloat16, folder=folder, tag=tag, rank=rank,
-                             world_size=world_size, batch_size=batch_size, resume_checkpoint=resume_checkpoint,
-                             distributed=_distributed(), device=device)
+                             num_epochs=cfg.num_epochs, use_bfloat16=cfg.use_bfloat16, folder=run.folder, tag=cfg.tag,
+                             rank=run.rank, world_size=run.world_size, batch_size=cfg.batch_size,
+                             resume_checkpoint=cfg.resume_checkpoint, distributed=_distributed(), device=device)
 
     # -- optimizer and scheduler
-    optimizer, scaler, scheduler, wd_scheduler = init_opt(classifier=classifier, wd=wd, start_lr=start_lr, ref_lr=lr,
-                                                          final_lr=final_lr, iterations_per_epoch=ipe, warmup=warmup,
-                                                          num_epochs=num_epochs, use_bfloat16=use_bfloat16)
-    if _distributed():
-        classifier = DistributedDataParallel(classifier, static_graph=True)
+    opt = init_opt(classifier=classifier, wd=cfg.wd, start_lr=cfg.start_lr, ref_lr=cfg.lr, final_lr=cfg.final_lr,
+                   iterations_per_epoch=ipe, warmup=cfg.warmup, num_epochs=cfg.num_epochs, use_bfloat16=cfg.use_bfloat16)
+    epoch = dict(device=device, encoder=encoder, use_bfloat16=cfg.use_bfloat16, attend_across_segments=attend_across_segments)
 
-    # -- load training checkpoint
-    start_epoch = 0
-    if resume_checkpoint:
-        classifier, optimizer, scaler, start_epoch = load_checkpoint(device=device, r_path=latest_path, classifier=classifier,
-                                                                     opt=optimizer, scaler=scaler)
-        for _ in range(start_epoch * ipe):
-            scheduler.step()
-            wd_scheduler.step()
+    def train_epoch(**probe):
+        return run_one_epoch(training=True, num_temporal_views=eval_num_segments if attend_across_segments else 1,
+                             num_spatial_views=1, data_loader=train_loader, **epoch, **probe)
 
-    def save_checkpoint(epoch):
-        save_dict = {
-            'classifier': classifier_state_dict(classifier),
-            'opt': optimizer.state_dict(),
-            'scaler': None if scaler is None else scaler.state_dict(),
-            'epoch': epoch,
-            'batch_size': batch_size,
-            'world_size': world_size,
-            'lr': lr
-        }
-        if rank == 0:
-            torch.save(save_dict, latest_path)
+    def val_epoch(**probe):
+        return run_one_epoch(training=False, num_temporal_views=eval_num_segments,
+                             num_spatial_views=eval_num_views_per_segment, data_loader=val_loader, **epoch, **probe)
 
-    record = dict(start_epoch=start_epoch, train_acc=[], val_acc=[], train_history=[])
-    for epoch in range(start_epoch, num_epochs):
-        logger.info('Epoch %d' % (epoch + 1))
-        train_acc = run_one_epoch(device=device, training=True,
-                                  num_temporal_views=eval_num_segments if attend_across_segments else 1,
-                                  attend_across_segments=attend_across_segments, num_spatial_views=1, encoder=encoder,
-                                  classifier=classifier, scaler=scaler, optimizer=optimizer, scheduler=scheduler,
-                                  wd_scheduler=wd_scheduler, data_loader=train_loader, use_bfloat16=use_bfloat16,
-                                  history=record['train_history'])
-        val_acc = run_one_epoch(device=device, training=False, num_temporal_views=eval_num_segments,
-                                attend_across_segments=attend_across_segments, num_spatial_views=eval_num_views_per_segment,
-                                encoder=encoder, classifier=classifier, scaler=scaler, optimizer=optimizer, scheduler=scheduler,
-                                wd_scheduler=wd_scheduler, data_loader=val_loader, use_bfloat16=use_bfloat16)
-        logger.info('[%5d] train: %.3f%% test: %.3f%%' % (epoch + 1, train_acc, val_acc))
-        if rank == 0:
-            csv_logger.log(epoch + 1, train_acc, val_acc)
-        save_checkpoint(epoch + 1)
-        record['train_acc'].append(train_acc)
-        record['val_acc'].append(val_acc)
-    return record
+    return train_single_probe(cfg, run, classifier, opt, ipe, train_epoch, val_epoch)
 
 
 def _view_features(attend_across_segments, encoder, data, device):
@@ -241,104 +157,32 @@ def run_one_epoch(device, training, encoder, classifier, scaler, optimizer, sche
                   num_spatial_views, num_temporal_views, attend_across_segments, *, history=None):
     """The reference's epoch (eval.py:298-380), same parameters in the same order.  history (keyword-only, optional list):
     (learning rate, loss) of each training iteration."""
-    classifier.train(mode=training)
     criterion = torch.nn.CrossEntropyLoss()
-    top1_meter = AverageMeter()
-    for itr, data in enumerate(data_loader):
 
-        if training:
-            scheduler.step()
-            wd_scheduler.step()
-
+    def features(data):
         # Load data and put on GPU
         clips = [[dij.to(device, non_blocking=True) for dij in di] for di in data[0]]
         clip_indices = [d.to(device, non_blocking=True) for d in data[2]]
         labels = data[1].to(device)
-        batch_size = len(labels)
+        return encoder(clips, clip_indices), labels
 
-        # Forward and prediction
-        with torch.no_grad():
-            outputs = encoder(clips, clip_indices)
-            if not training:
-                if attend_across_segments:
-                    outputs = [classifier(o) for o in outputs]
-                else:
-                    outputs = [[classifier(ost) for ost in os] for os in outputs]
-        if training:
-            if attend_across_segments:
-                outputs = [classifier(o) for o in outputs]
-            else:
-                outputs = [[classifier(ost) for ost in os] for os in outputs]
-
-        # Compute loss
+    def loss_and_top1(outputs, labels):
+        # the prediction is the arg-max of the soft-max averaged over every view
         if attend_across_segments:
+            outputs = [classifier(o) for o in outputs]
             loss = sum([criterion(o, labels) for o in outputs]) / len(outputs)
+            with torch.no_grad():
+                probs = sum([F.softmax(o, dim=1) for o in outputs]) / len(outputs)
         else:
-            loss = sum([sum([criterion(ost, labels) for ost in os]) for os in outputs]) / len(outputs) / len(outputs[0])
+            outputs = [[classifier(ost) for ost in ov] for ov in outputs]
+            loss = sum([sum([criterion(ost, labels) for ost in ov]) for ov in outputs]) / len(outputs) / len(outputs[0])
+            with torch.no_grad():
+                probs = sum([sum([F.softmax(ost, dim=1) for ost in ov]) for ov in outputs]) / len(outputs) / len(outputs[0])
         with torch.no_grad():
-            if attend_across_segments:
-                outputs = sum([F.softmax(o, dim=1) for o in outputs]) / len(outputs)
-            else:
-                outputs = sum([sum([F.softmax(ost, dim=1) for ost in os]) for os in outputs]) / len(outputs) / len(outputs[0])
-            top1_acc = 100. * outputs.max(dim=1).indices.eq(labels).sum() / batch_size
-            top1_acc = float(AllReduce.apply(top1_acc))
-            top1_meter.update(top1_acc)
+            return loss, 100. * probs.max(dim=1).indices.eq(labels).sum() / len(labels)
 
-        if training:
-            if use_bfloat16:
-                scaler.scale(loss).backward()
-                scaler.unscale_(optimizer)
-                torch.nn.utils.clip_grad_norm_(classifier.parameters(), 1.0)
-                scaler.step(optimizer)
-                scaler.update()
-            else:
-                loss.backward()
-                torch.nn.utils.clip_grad_norm_(classifier.parameters(), 1.0)
-                optimizer.step()
-            optimizer.zero_grad()
-            if history is not None:
-                history.append((optimizer.param_groups[0]['lr'], float(loss.detach())))
-
-        if itr % 20 == 0:
-            logger.info('[%5d] %.3f%% (loss: %.3f) [mem: %.2e]'
-                        % (itr, top1_meter.avg, float(loss.detach()), torch.cuda.max_memory_allocated() / 1024.**2))
-
-    return top1_meter.avg
-
-
-def classifier_state_dict(classifier):
-    """The classifier's state dict with the `module.` prefix the reference's DDP-wrapped classifier writes."""
-    sd = classifier.state_dict()
-    if isinstance(classifier, DistributedDataParallel):
-        return sd
-    return {'module.' + k: v for k, v in sd.items()}
-
-
-def load_checkpoint(device, r_path, classifier, opt, scaler):
-    try:
-        checkpoint = torch.load(r_path, map_location=torch.device('cpu'))
-        epoch = checkpoint['epoch']
-
-        # -- loading classifier (`module.`-prefixed keys, as the reference writes them)
-        pretrained_dict = checkpoint['classifier']
-        if not isinstance(classifier, DistributedDataParallel):
-            pretrained_dict = {(k[len('module.'):] if k.startswith('module.') else k): v for k, v in pretrained_dict.items()}
-        msg = classifier.load_state_dict(pretrained_dict)
-        logger.info(f'loaded pretrained classifier from epoch {epoch} with msg: {msg}')
-
-        # -- loading optimizer
-        opt.load_state_dict(checkpoint['opt'])
-        if scaler is not None:
-            scaler.load_state_dict(checkpoint['scaler'])
-        logger.info(f'loaded optimizers from epoch {epoch}')
-        logger.info(f'read-path: {r_path}')
-        del checkpoint
-
-    except Exception as e:
-        logger.info(f'Encountered exception when loading checkpoint {e}')
-        epoch = 0
-
-    return classifier, opt, scaler, epoch
+    return run_probe_epoch(training, classifier, scaler, optimizer, scheduler, wd_scheduler, data_loader, use_bfloat16, features,
+                           loss_and_top1, history=history)
 
 
 def load_pretrained(encoder, pretrained, checkpoint_key='target_encoder'):
@@ -382,8 +226,6 @@ def make_dataloader(root_path, batch_size, world_size, rank, dataset_type='Video
         raise ValueError(f"make_dataloader(dataset_type={kind!r}) needs num_classes")
     if rand_augment and kind != 'synthetic_frames':
         raise ValueError(f"data.rand_augment needs uint8 frames (dataset_type: synthetic_frames); {kind!r} yields finished fp32 views")
-    length = synthetic_length if synthetic_length is not None else 8 * batch_size * world_size
-    seed = (0 if training else 1) if seed is None else seed
     if kind == 'synthetic_frames':
         global _randaugment_logged
         if training and rand_augment:
@@ -400,14 +242,15 @@ def make_dataloader(root_path, batch_size, world_size, rank, dataset_type='Video
         if training and rand_augment:
             transform.rand_augment = RandAugmentDraw('rand-m7-n4-mstd0.5-inc1')
         short = None if training else (resolution if num_views_per_segment > 1 else int(resolution * 256 / 224))
-        dataset = SyntheticFramesClassification(length, num_classes, frames_per_clip, resolution, transform,
-                                                num_segments=num_segments, short_side=short, frame_step=frame_step, seed=seed)
+
+        def make_dataset(length, seed):
+            return SyntheticFramesClassification(length, num_classes, frames_per_clip, resolution, transform,
+                                                 num_segments=num_segments, short_side=short, frame_step=frame_step, seed=seed)
     else:
-        dataset = SyntheticVideoClassification(length, num_classes, frames_per_clip, resolution, num_segments=num_segments,
-                                               num_views_per_segment=num_views_per_segment, frame_step=frame_step, seed=seed)
-    sampler = torch.utils.data.distributed.DistributedSampler(dataset, num_replicas=world_size, rank=rank, shuffle=training)
-    return torch.utils.data.DataLoader(dataset, sampler=sampler, batch_size=batch_size, drop_last=False,
-                                       num_workers=num_workers, pin_memory=True, persistent_workers=False)
+        def make_dataset(length, seed):
+            return SyntheticVideoClassification(length, num_classes, frames_per_clip, resolution, num_segments=num_segments,
+                                                num_views_per_segment=num_views_per_segment, frame_step=frame_step, seed=seed)
+    return synthetic_dataloader(make_dataset, batch_size, world_size, rank, training, num_workers, synthetic_length, seed)
 
 
 def init_model(device, pretrained, model_name, patch_size=16, crop_size=224, frames_per_clip=16, tubelet_size=2, use_sdpa=False,

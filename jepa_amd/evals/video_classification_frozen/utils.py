@@ -23,19 +23,7 @@ from ...app.vjepa.transforms import RawClip, draw_erase
 from ...app.vjepa.transforms import VideoTransform as _PretrainVideoTransform
 from ...hip import ops
 from ...src.models.utils.pos_embs import get_1d_sincos_pos_embed
-
-
-def max_clips_per_call(width, tokens_per_clip):
-    """Clips (or frames of an image encoder: tokens_per_clip is then one frame's tokens; with 1, token rows) per encoder call that
-    keep the widest activation (M token rows x `width` columns: fc1's output) below 2^31 elements."""
-    return max(1, (2 ** 31 - 1) // (width * tokens_per_clip))
-
-
-def _widest(model):
-    """Widest activation row of the encoder: fc1's output features (4 D for L / H, 48/11 D for ViT-g), at least 3 D (qkv)."""
-    blocks = getattr(model, "blocks", None)
-    fc1 = blocks[0].mlp.fc1.out_features if blocks is not None and len(blocks) else 4 * model.embed_dim
-    return max(fc1, 3 * model.embed_dim)
+from ..frozen import chunked_call, max_clips_per_call, widest_activation
 
 
 class FrameAggregation(nn.Module):
@@ -64,7 +52,7 @@ class FrameAggregation(nn.Module):
             sincos = get_1d_sincos_pos_embed(embed_dim, max_frames)
             self.pos_embed.data.copy_(torch.from_numpy(sincos).float().unsqueeze(0))
         # encoder call size in token rows: fc1's output of one call stays below 2^31 elements
-        self.max_tokens_per_call = max_clips_per_call(_widest(model), 1)
+        self.max_tokens_per_call = max_clips_per_call(widest_activation(model), 1)
 
     def _pieces(self, x, frames_per_call):
         """(clips [b,C,t,H,W], view, first sample, first frame of the output) in the reference's order, none above frames_per_call
@@ -146,15 +134,11 @@ class ClipAggregation(nn.Module):
                                       "implemented; no shipped eval config sets it (eval.py:172-176)")
         self.pos_embed = None
         # encoder call size: fc1's output of one call stays below 2^31 elements (91 clips for ViT-H/16 at 384)
-        self.max_clips_per_call = max_clips_per_call(_widest(model), model.num_patches)
+        self.max_clips_per_call = max_clips_per_call(widest_activation(model), model.num_patches)
 
-    def _features(self, x):
-        """x: [S*V*B, C, T, H, W] -> list of (first clip, bf16 [m, N, D]) over encoder calls of at most max_clips_per_call."""
-        out, M = [], x.shape[0]
-        for c0 in range(0, M, self.max_clips_per_call):
-            f = self.model(x[c0:c0 + self.max_clips_per_call])
-            out.append((c0, f if f.dtype == torch.bfloat16 else f.to(torch.bfloat16)))
-        return out
+    def _bf16(self, x):
+        f = self.model(x)
+        return f if f.dtype == torch.bfloat16 else f.to(torch.bfloat16)
 
     def forward(self, x, clip_indices=None):
         num_clips = len(x)
@@ -162,16 +146,13 @@ class ClipAggregation(nn.Module):
         B = x[0][0].shape[0]
         eff_B = B * num_views_per_clip
         # all spatial and temporal views along the batch dimension, in the reference's order
-        feats = self._features(torch.cat([torch.cat(xi, dim=0) for xi in x], dim=0))
-        N, D = feats[0][1].shape[1], feats[0][1].shape[2]
+        x = torch.cat([torch.cat(xi, dim=0) for xi in x], dim=0)
         if not self.attend_across_segments:
-            if len(feats) == 1:
-                f = feats[0][1]
-                return [[f[i * eff_B + j * B:i * eff_B + (j + 1) * B] for i in range(num_clips)] for j in range(num_views_per_clip)]
-            allf = torch.empty((num_clips * eff_B, N, D), dtype=torch.bfloat16, device=feats[0][1].device)
-            for c0, f in feats:
-                ops.copy_rows(f, allf, 1, f.shape[0] * N, 0, allf.shape[0] * N, c0 * N, f.shape[0] * N, D)
-            return [[allf[i * eff_B + j * B:i * eff_B + (j + 1) * B] for i in range(num_clips)] for j in range(num_views_per_clip)]
+            f = chunked_call(self._bf16, x, self.max_clips_per_call)
+            return [[f[i * eff_B + j * B:i * eff_B + (j + 1) * B] for i in range(num_clips)] for j in range(num_views_per_clip)]
+        # bf16 [m, N, D] of each encoder call of at most max_clips_per_call clips, with its first clip
+        feats = [(c0, self._bf16(x[c0:c0 + self.max_clips_per_call])) for c0 in range(0, x.shape[0], self.max_clips_per_call)]
+        N, D = feats[0][1].shape[1], feats[0][1].shape[2]
         # segment i of view j of sample b is clip i*eff_B + j*B + b; its tokens go to rows [i*N, (i+1)*N) of sample b of view j
         outs = [torch.empty((B, num_clips * N, D), dtype=torch.bfloat16, device=feats[0][1].device)
                 for _ in range(num_views_per_clip)]

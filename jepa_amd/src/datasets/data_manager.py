@@ -62,6 +62,35 @@ class SyntheticFrames(torch.utils.data.Dataset):
         return clips, 0, [np.arange(self.num_frames) for _ in range(self.num_clips)]
 
 
+def _label_and_generator(seed, i, num_classes):
+    """The label of classification item i of split `seed`, and the item's generator right after that draw."""
+    g = torch.Generator().manual_seed((seed * 1_000_003 + i) % (1 << 62))
+    return int(torch.randint(0, num_classes, (1,), generator=g)), g
+
+
+def _class_wave(pattern_seed, label, signal, sizes):
+    """The pattern of a class: one plane wave per channel over the axes of extents `sizes` -- (T, H, W) for clips, (H, W) for
+    images -- in relative coordinates, with frequency, phase and amplitude drawn from (pattern_seed, label) -> fp32 [3, *sizes]."""
+    g = torch.Generator().manual_seed((1 << 62) + pattern_seed * 1_000_003 + label)   # items use seeds < 2^62
+    n = len(sizes)
+    f = 1.0 + 3.0 * torch.rand(3, n, generator=g)                  # cycles along each axis, per channel
+    phase = 6.283185307179586 * torch.rand(3, generator=g)
+    amp = signal * (0.5 + torch.rand(3, generator=g))
+    per_channel = (3,) + (1,) * n
+    arg = None
+    for k, size in enumerate(sizes):                               # summed in axis order: the rounding of (t + h) + w
+        coord = (torch.arange(size, dtype=torch.float32) / size).reshape((1,) * (k + 1) + (size,) + (1,) * (n - 1 - k))
+        term = f[:, k].reshape(per_channel) * coord
+        arg = term if arg is None else arg + term
+    return amp.reshape(per_channel) * torch.cos(6.283185307179586 * arg + phase.reshape(per_channel))
+
+
+def _segment_indices(num_segments, frames, frame_step):
+    """Frame indices of consecutive segments of `frames` frames, `frame_step` apart: [S] of int64 [frames]."""
+    span = frames * frame_step
+    return [torch.arange(s * span, (s + 1) * span, frame_step, dtype=torch.int64) for s in range(num_segments)]
+
+
 class SyntheticVideoClassification(torch.utils.data.Dataset):
     """Seeded labelled clips for the frozen video-classification eval, in the item layout of the reference's VideoDataset
     under the eval transform (video_dataset.py:156-184, evals/video_classification_frozen/utils.py:172-190):
@@ -83,25 +112,14 @@ class SyntheticVideoClassification(torch.utils.data.Dataset):
         return self.length
 
     def _pattern(self, label):
-        g = torch.Generator().manual_seed((1 << 62) + self.pattern_seed * 1_000_003 + label)   # items use seeds < 2^62
-        f = 1.0 + 3.0 * torch.rand(3, 3, generator=g)                  # cycles per clip along (t, h, w), per channel
-        phase = 6.283185307179586 * torch.rand(3, generator=g)
-        amp = self.signal * (0.5 + torch.rand(3, generator=g))
-        t = torch.arange(self.frames, dtype=torch.float32) / self.frames
-        s = torch.arange(self.crop, dtype=torch.float32) / self.crop
-        arg = (f[:, 0, None, None, None] * t[None, :, None, None] + f[:, 1, None, None, None] * s[None, None, :, None]
-               + f[:, 2, None, None, None] * s[None, None, None, :])
-        return amp[:, None, None, None] * torch.cos(6.283185307179586 * arg + phase[:, None, None, None])
+        return _class_wave(self.pattern_seed, label, self.signal, (self.frames, self.crop, self.crop))
 
     def __getitem__(self, i):
-        g = torch.Generator().manual_seed((self.seed * 1_000_003 + i) % (1 << 62))
-        label = int(torch.randint(0, self.num_classes, (1,), generator=g))
+        label, g = _label_and_generator(self.seed, i, self.num_classes)
         pat = self._pattern(label)
         clips = [[torch.randn(3, self.frames, self.crop, self.crop, generator=g) + pat for _ in range(self.V)]
                  for _ in range(self.S)]
-        span = self.frames * self.frame_step
-        indices = [torch.arange(s * span, (s + 1) * span, self.frame_step, dtype=torch.int64) for s in range(self.S)]
-        return clips, label, indices
+        return clips, label, _segment_indices(self.S, self.frames, self.frame_step)
 
 
 class SyntheticFramesClassification(torch.utils.data.Dataset):
@@ -138,21 +156,11 @@ class SyntheticFramesClassification(torch.utils.data.Dataset):
         return self.sizes[(self.seed + i) % len(self.sizes)]
 
     def _pattern(self, label, H, W):
-        g = torch.Generator().manual_seed((1 << 62) + self.pattern_seed * 1_000_003 + label)   # items use seeds < 2^62
-        f = 1.0 + 3.0 * torch.rand(3, 3, generator=g)                  # cycles per clip along (t, h, w), per channel
-        phase = 6.283185307179586 * torch.rand(3, generator=g)
-        amp = self.signal * (0.5 + torch.rand(3, generator=g))
-        t = torch.arange(self.frames, dtype=torch.float32) / self.frames
-        y = torch.arange(H, dtype=torch.float32) / H
-        x = torch.arange(W, dtype=torch.float32) / W
-        arg = (f[:, 0, None, None, None] * t[None, :, None, None] + f[:, 1, None, None, None] * y[None, None, :, None]
-               + f[:, 2, None, None, None] * x[None, None, None, :])
-        return (amp[:, None, None, None] * torch.cos(6.283185307179586 * arg + phase[:, None, None, None])).permute(1, 2, 3, 0)
+        return _class_wave(self.pattern_seed, label, self.signal, (self.frames, H, W)).permute(1, 2, 3, 0)
 
     def frames_of(self, i):
         """(list over segments of uint8 [T,Hs,Ws,3] arrays, label) of item i, before the transform."""
-        g = torch.Generator().manual_seed((self.seed * 1_000_003 + i) % (1 << 62))
-        label = int(torch.randint(0, self.num_classes, (1,), generator=g))
+        label, g = _label_and_generator(self.seed, i, self.num_classes)
         H, W = self.source_size(i)
         pat = self._pattern(label, H, W)
         segs = [(127.5 + 48.0 * (torch.randn(self.frames, H, W, 3, generator=g) + pat)).clamp_(0, 255).to(torch.uint8).numpy()
@@ -161,9 +169,7 @@ class SyntheticFramesClassification(torch.utils.data.Dataset):
 
     def __getitem__(self, i):
         segs, label = self.frames_of(i)
-        span = self.frames * self.frame_step
-        indices = [torch.arange(s * span, (s + 1) * span, self.frame_step, dtype=torch.int64) for s in range(self.S)]
-        return [self.transform(f) for f in segs], label, indices
+        return [self.transform(f) for f in segs], label, _segment_indices(self.S, self.frames, self.frame_step)
 
 
 class SyntheticImageClassification(torch.utils.data.Dataset):
@@ -183,17 +189,10 @@ class SyntheticImageClassification(torch.utils.data.Dataset):
         return self.length
 
     def _pattern(self, label):
-        g = torch.Generator().manual_seed((1 << 62) + self.pattern_seed * 1_000_003 + label)   # items use seeds < 2^62
-        f = 1.0 + 3.0 * torch.rand(3, 2, generator=g)                  # cycles per image along (h, w), per channel
-        phase = 6.283185307179586 * torch.rand(3, generator=g)
-        amp = self.signal * (0.5 + torch.rand(3, generator=g))
-        s = torch.arange(self.crop, dtype=torch.float32) / self.crop
-        arg = f[:, 0, None, None] * s[None, :, None] + f[:, 1, None, None] * s[None, None, :]
-        return amp[:, None, None] * torch.cos(6.283185307179586 * arg + phase[:, None, None])
+        return _class_wave(self.pattern_seed, label, self.signal, (self.crop, self.crop))
 
     def __getitem__(self, i):
-        g = torch.Generator().manual_seed((self.seed * 1_000_003 + i) % (1 << 62))
-        label = int(torch.randint(0, self.num_classes, (1,), generator=g))
+        label, g = _label_and_generator(self.seed, i, self.num_classes)
         return torch.randn(3, self.crop, self.crop, generator=g) + self._pattern(label), label
 
 
