@@ -56,6 +56,38 @@ def reference_groups(enc_named, pred_named):
             ({"WD_exclude": True, "weight_decay": 0}, grp(pred_named, True))]
 
 
+def layer_id(name, depth):
+    """Layer of an encoder parameter for layer-wise learning-rate decay: patch_embed.* -> 0, blocks.i.* -> i + 1, everything else
+    (the final norm) -> depth + 1."""
+    parts = name.split(".")
+    if parts[0] == "patch_embed":
+        return 0
+    if parts[0] == "blocks":
+        return int(parts[1]) + 1
+    return depth + 1
+
+
+def layer_decay_groups(named, depth, layer_decay):
+    """[(group dict, [(name, param), ...])] of a stand-alone encoder that is fine-tuned with layer-wise learning-rate decay, from
+    named = module.named_parameters(): one group per (layer id, no-decay) in ascending layer order, the decayed tensors of a
+    layer before its bias / 1-D tensors (is_no_decay; weight_decay 0), empty groups left out.  Every group dict carries
+    `layer_id` and `lr_scale` = layer_decay ** (depth + 1 - layer_id), so the final norm trains at the full rate.  Frozen
+    tensors (the sincos `pos_embed`) are in no group.  In named_parameters() order a layer's tensors follow one another, so
+    every group is one contiguous range of layout()."""
+    by = {}
+    for n, p in named:
+        if not p.requires_grad or n.split(".")[-1] == "pos_embed":
+            continue
+        by.setdefault((layer_id(n, depth), is_no_decay(n, p)), []).append((n, p))
+    groups = []
+    for lid, nodecay in sorted(by):
+        g = {"layer_id": lid, "lr_scale": float(layer_decay) ** (depth + 1 - lid)}
+        if nodecay:
+            g.update({"WD_exclude": True, "weight_decay": 0})
+        groups.append((g, by[(lid, nodecay)]))
+    return groups
+
+
 def build_state_dict(param_groups, slot_of, M1, M2, step, betas, eps):
     """param_groups: list of dicts with 'params' (parameters, frozen ones included); slot_of: id(param) -> Slot for the
     trainable ones; M1 / M2: flat exp_avg / exp_avg_sq arenas; step: Adam step count t (0 = no state yet)."""

@@ -142,11 +142,14 @@ def probe_update(classifier, optimizer, scaler, use_bfloat16, loss=None):
 
 
 def run_probe_epoch(training, classifier, scaler, optimizer, scheduler, wd_scheduler, data_loader, use_bfloat16, features,
-                    loss_and_top1, history=None):
+                    loss_and_top1, history=None, features_grad=False, after_update=None):
     """One epoch of a single probe -> its average top-1.  What an eval brings: features(data) -> (frozen features, labels), run
     under no_grad, and loss_and_top1(features, labels) -> (loss, top-1 in percent of this batch), which applies the classifier
     (with gradients only when training) and holds the eval's own prediction arithmetic.  history (optional list): (learning rate,
-    loss) of each training iteration."""
+    loss) of each training iteration.  The fine-tuning eval's two additions, off by default: features_grad -- training iterations
+    compute the features with gradients enabled, so the probe's backward reaches the encoder; after_update(optimizer, grad_scale)
+    -- called after the probe's update of a training iteration (the encoder's step), with the factor the GradScaler had put on
+    the loss of that backward (1.0 without use_bfloat16)."""
     classifier.train(mode=training)
     top1_meter = AverageMeter()
     for itr, data in enumerate(data_loader):
@@ -155,7 +158,7 @@ def run_probe_epoch(training, classifier, scaler, optimizer, scheduler, wd_sched
             scheduler.step()
             wd_scheduler.step()
 
-        with torch.no_grad():
+        with torch.set_grad_enabled(training and features_grad):
             outputs, labels = features(data)
         with torch.set_grad_enabled(training):
             loss, top1_acc = loss_and_top1(outputs, labels)
@@ -164,7 +167,10 @@ def run_probe_epoch(training, classifier, scaler, optimizer, scheduler, wd_sched
             top1_meter.update(float(AllReduce.apply(top1_acc)))
 
         if training:
+            grad_scale = scaler.get_scale() if (use_bfloat16 and after_update is not None) else 1.0
             probe_update(classifier, optimizer, scaler, use_bfloat16, loss=loss)
+            if after_update is not None:
+                after_update(optimizer, grad_scale)
             if history is not None:
                 history.append((optimizer.param_groups[0]['lr'], float(loss.detach())))
 
@@ -205,7 +211,9 @@ def resume(r_path, restore):
     return epoch
 
 
-def load_checkpoint(device, r_path, classifier, opt, scaler):
+def load_checkpoint(device, r_path, classifier, opt, scaler, restore_extra=None):
+    """restore_extra(checkpoint) (optional): what the caller keeps in the checkpoint beside the probe (extra_state of
+    train_single_probe), restored with it -- if it raises, the run starts at epoch 0 like after any unreadable checkpoint."""
     def restore(checkpoint, epoch):
         # -- loading classifier (`module.`-prefixed keys, as the reference writes them)
         pretrained_dict = checkpoint['classifier']
@@ -218,6 +226,8 @@ def load_checkpoint(device, r_path, classifier, opt, scaler):
         opt.load_state_dict(checkpoint['opt'])
         if scaler is not None:
             scaler.load_state_dict(checkpoint['scaler'])
+        if restore_extra is not None:
+            restore_extra(checkpoint)
         logger.info(f'loaded optimizers from epoch {epoch}')
         logger.info(f'read-path: {r_path}')
 
@@ -226,10 +236,11 @@ def load_checkpoint(device, r_path, classifier, opt, scaler):
 
 # --------------------------------------------------------------------------------------------------------- single-probe training
 
-def train_single_probe(cfg, run, classifier, opt, ipe, train_epoch, val_epoch):
+def train_single_probe(cfg, run, classifier, opt, ipe, train_epoch, val_epoch, extra_state=None, restore_extra=None):
     """The training of a single probe.  opt: what the eval's init_opt returned for `classifier`; ipe: iterations per epoch;
     train_epoch(classifier=, scaler=, optimizer=, scheduler=, wd_scheduler=, history=) and val_epoch(the same without history)
-    run one epoch on the eval's loaders -> its top-1.  Returns the run's record."""
+    run one epoch on the eval's loaders -> its top-1.  Returns the run's record.  extra_state() -> dict (optional): further
+    entries of every checkpoint (the fine-tuned encoder and its optimizer state); restore_extra(checkpoint) reads them on resume."""
     optimizer, scaler, scheduler, wd_scheduler = opt
     if distributed():
         classifier = DistributedDataParallel(classifier, static_graph=True)
@@ -238,7 +249,8 @@ def train_single_probe(cfg, run, classifier, opt, ipe, train_epoch, val_epoch):
     start_epoch = 0
     if cfg.resume_checkpoint:
         classifier, optimizer, scaler, start_epoch = load_checkpoint(device=run.device, r_path=run.latest_path,
-                                                                     classifier=classifier, opt=optimizer, scaler=scaler)
+                                                                     classifier=classifier, opt=optimizer, scaler=scaler,
+                                                                     restore_extra=restore_extra)
         for _ in range(start_epoch * ipe):
             scheduler.step()
             wd_scheduler.step()
@@ -253,6 +265,8 @@ def train_single_probe(cfg, run, classifier, opt, ipe, train_epoch, val_epoch):
             'world_size': run.world_size,
             'lr': cfg.lr
         }
+        if extra_state is not None:
+            save_dict.update(extra_state())
         if run.rank == 0:
             torch.save(save_dict, run.latest_path)
 

@@ -1,0 +1,92 @@
+"""Fine-tuning of a pretrained video encoder end to end through the attentive probe:
+
+    from jepa_amd.evals.video_classification_finetune.eval import main
+    main(args_eval_dict_from_yaml, resume_preempt=False)
+
+The reference releases no such loop; this one is the frozen video eval (..video_classification_frozen.eval) with the encoder
+left trainable.  It takes that eval's dictionary -- the same keys, `data.dataset_type: synthetic` / `synthetic_frames`,
+`data.rand_augment` -- and one more section:
+
+    optimization:
+      finetune:
+        encoder_lr: 0.0001            # peak learning rate of the encoder's last layer (default: optimization.lr)
+        layer_decay: 0.75             # layer l of depth L trains at encoder_lr * layer_decay ** (L + 1 - l)
+        encoder_weight_decay: 0.05    # constant; biases and 1-D tensors get 0
+        clip_grad: null               # max global norm of the encoder's gradient
+
+A training iteration: the clips go through ClipAggregation with gradients enabled (one encoder call), the AttentiveClassifier,
+the cross-entropy and backward(); the probe's optimizer steps exactly as in the frozen eval; then engine.finetune.EncoderFineTuner
+steps the encoder at the probe's warm-up / cosine learning rate scaled by encoder_lr / lr.  Validation runs the encoder under
+no_grad.  The data, the probe, its update and schedules, the CSV log and the checkpoint are the frozen eval's (under
+`<pretrain folder>/video_classification_finetune/`); the checkpoint adds `encoder` (a state dict in the reference's names, which
+the frozen eval's load_pretrained(checkpoint_key='encoder') reads) and `encoder_opt` (Adam moments and step count in
+torch.optim.AdamW's format).
+
+Limits, all raising: one rank; video encoders at their native clip size (image encoders and off-native sizes are frozen-path
+features); the lone probe (`optimization.multihead_kwargs` is the frozen evals'); every clip of a batch in one encoder call.  Not
+implemented: stochastic depth (drop_path_rate > 0), mixup / cutmix / label smoothing.
+"""
+from types import SimpleNamespace
+
+from ...engine.finetune import EncoderFineTuner
+from ...src.utils.logging import get_logger
+from ..video_classification_frozen import eval as frozen_eval
+
+logger = get_logger(__name__)
+
+FOLDER_NAME = 'video_classification_finetune/'
+
+
+def parse_finetune(args_opt):
+    """The `optimization.finetune` section with its defaults."""
+    ft = args_opt.get('finetune', None) or {}
+    unknown = sorted(set(ft) - {'encoder_lr', 'layer_decay', 'encoder_weight_decay', 'clip_grad'})
+    if unknown:
+        raise ValueError(f"optimization.finetune: unknown keys {unknown}")
+    encoder_lr = ft.get('encoder_lr', None)
+    return SimpleNamespace(encoder_lr=args_opt.get('lr') if encoder_lr is None else encoder_lr,
+                           layer_decay=ft.get('layer_decay', 0.75),
+                           encoder_weight_decay=ft.get('encoder_weight_decay', 0.05),
+                           clip_grad=ft.get('clip_grad', None))
+
+
+class _FineTune:
+    """What frozen_eval.main takes to leave the encoder trainable."""
+
+    folder_name = FOLDER_NAME
+
+    def check(self, cfg):
+        if cfg.multihead is not None:
+            raise ValueError("optimization.multihead_kwargs: a bank of probes belongs to the frozen evals (features of a FROZEN "
+                             "encoder); fine-tuning trains the encoder through the lone probe")
+        if cfg.frames_per_clip == 1:
+            raise NotImplementedError("pretrain.frames_per_clip == 1: image encoders run on the frozen / no-grad path only")
+        self.ft = parse_finetune(cfg.args_opt)
+
+    def attach(self, cfg, run, aggregation):
+        ft, encoder = self.ft, aggregation.model
+        tuner = EncoderFineTuner(encoder, layer_decay=ft.layer_decay, world_size=run.world_size)
+        lr_ratio = ft.encoder_lr / cfg.lr
+
+        def after_update(optimizer, grad_scale):
+            # the probe's schedule has set this iteration's learning rate; the encoder follows its shape
+            tuner.step(optimizer.param_groups[0]['lr'] * lr_ratio, ft.encoder_weight_decay, clip=ft.clip_grad, grad_scale=grad_scale)
+
+        def extra_state():
+            return {'encoder': {k: v.detach().cpu().clone() for k, v in encoder.state_dict().items()},
+                    'encoder_opt': tuner.state_dict()}
+
+        def restore_extra(checkpoint):
+            msg = encoder.load_state_dict(checkpoint['encoder'])
+            tuner.sync_shadows()
+            tuner.load_state_dict(checkpoint['encoder_opt'])
+            logger.info(f'loaded fine-tuned encoder and its optimizer state with msg: {msg}')
+
+        logger.info(f'fine-tuning the encoder: lr {ft.encoder_lr} x {ft.layer_decay} ** (layers below the last), weight decay '
+                    f'{ft.encoder_weight_decay}, clip {ft.clip_grad}, {len(tuner.param_groups)} parameter ranges')
+        self.tuner = tuner
+        return dict(features_grad=True, after_update=after_update), extra_state, restore_extra
+
+
+def main(args_eval, resume_preempt=False):
+    return frozen_eval.main(args_eval, resume_preempt, finetune=_FineTune())

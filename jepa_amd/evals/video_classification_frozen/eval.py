@@ -59,9 +59,15 @@ pp = pprint.PrettyPrinter(indent=4)
 _randaugment_logged = False
 
 
-def main(args_eval, resume_preempt=False):
+def main(args_eval, resume_preempt=False, finetune=None):
+    """finetune (extension): None (the frozen eval), or what ..video_classification_finetune.eval brings to train the encoder
+    with the probe on this eval's data, probe, schedules and checkpoints: `folder_name`; check(cfg), called before anything is
+    set up; attach(cfg, run, encoder) -> (epoch keywords of the training run_one_epoch, extra_state, restore_extra of
+    frozen.train_single_probe), called on the ClipAggregation instead of freezing it."""
     cfg = parse_config(args_eval, resume_preempt)
     multihead = cfg.multihead
+    if finetune is not None:
+        finetune.check(cfg)
     args_pretrain, args_opt = cfg.args_pretrain, cfg.args_opt
 
     # -- DATA
@@ -88,7 +94,7 @@ def main(args_eval, resume_preempt=False):
                          "aggregation only has the concatenated form (one [B, S*T*N, D] tensor per view), and the epoch loop of "
                          "attend_across_segments: false would iterate over the batch dimension of those tensors")
 
-    run = setup_run(cfg, 'video_classification_frozen/', csv=multihead is None)
+    run = setup_run(cfg, 'video_classification_frozen/' if finetune is None else finetune.folder_name, csv=multihead is None)
     device = run.device
 
     # -- pretrained encoder (frozen)
@@ -101,7 +107,11 @@ def main(args_eval, resume_preempt=False):
     else:
         encoder = ClipAggregation(encoder, tubelet_size=cfg.tubelet_size,
                                   attend_across_segments=attend_across_segments).to(device)
-    freeze(encoder)
+    tune, extra = {}, {}
+    if finetune is None:
+        freeze(encoder)
+    else:
+        tune, extra['extra_state'], extra['restore_extra'] = finetune.attach(cfg, run, encoder)
 
     # -- init classifier
     if multihead is None:
@@ -136,13 +146,13 @@ def main(args_eval, resume_preempt=False):
 
     def train_epoch(**probe):
         return run_one_epoch(training=True, num_temporal_views=eval_num_segments if attend_across_segments else 1,
-                             num_spatial_views=1, data_loader=train_loader, **epoch, **probe)
+                             num_spatial_views=1, data_loader=train_loader, **epoch, **probe, **tune)
 
     def val_epoch(**probe):
         return run_one_epoch(training=False, num_temporal_views=eval_num_segments,
                              num_spatial_views=eval_num_views_per_segment, data_loader=val_loader, **epoch, **probe)
 
-    return train_single_probe(cfg, run, classifier, opt, ipe, train_epoch, val_epoch)
+    return train_single_probe(cfg, run, classifier, opt, ipe, train_epoch, val_epoch, **extra)
 
 
 def _view_features(attend_across_segments, encoder, data, device):
@@ -154,9 +164,11 @@ def _view_features(attend_across_segments, encoder, data, device):
 
 
 def run_one_epoch(device, training, encoder, classifier, scaler, optimizer, scheduler, wd_scheduler, data_loader, use_bfloat16,
-                  num_spatial_views, num_temporal_views, attend_across_segments, *, history=None):
+                  num_spatial_views, num_temporal_views, attend_across_segments, *, history=None, features_grad=False,
+                  after_update=None):
     """The reference's epoch (eval.py:298-380), same parameters in the same order.  history (keyword-only, optional list):
-    (learning rate, loss) of each training iteration."""
+    (learning rate, loss) of each training iteration.  features_grad / after_update (keyword-only, off by default): the
+    fine-tuning eval's encoder gradients and encoder step, see frozen.run_probe_epoch."""
     criterion = torch.nn.CrossEntropyLoss()
 
     def features(data):
@@ -182,7 +194,7 @@ def run_one_epoch(device, training, encoder, classifier, scaler, optimizer, sche
             return loss, 100. * probs.max(dim=1).indices.eq(labels).sum() / len(labels)
 
     return run_probe_epoch(training, classifier, scaler, optimizer, scheduler, wd_scheduler, data_loader, use_bfloat16, features,
-                           loss_and_top1, history=history)
+                           loss_and_top1, history=history, features_grad=features_grad, after_update=after_update)
 
 
 def load_pretrained(encoder, pretrained, checkpoint_key='target_encoder'):

@@ -119,8 +119,41 @@ class FrameAggregation(nn.Module):
         return outs
 
 
+class _PlaceSegments(torch.autograd.Function):
+    """ClipAggregation's concatenated form as an autograd node: bf16 features f [S*V*B, N, D] of ONE encoder call (clip
+    i*V*B + j*B + b is segment i of view j of sample b) -> V tensors [B, S*N, D], by the row copy the frozen path places them
+    with (vj_copy_rows).  The backward is the inverse copy: no torch.cat copies of the features either way."""
+
+    @staticmethod
+    def forward(ctx, f, S, V, B):
+        N, D = f.shape[1], f.shape[2]
+        outs = [torch.empty((B, S * N, D), dtype=f.dtype, device=f.device) for _ in range(V)]
+        for i in range(S):
+            for j in range(V):
+                c = (i * V + j) * B
+                ops.copy_rows(f[c:c + B], outs[j], B, N, 0, S * N, i * N, N, D)
+        ctx.dims = (S, V, B, N, D)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *douts):
+        S, V, B, N, D = ctx.dims
+        ref = next(d for d in douts if d is not None)
+        df = torch.empty((S * V * B, N, D), dtype=ref.dtype, device=ref.device)
+        for j, d in enumerate(douts):
+            d = None if d is None else d.contiguous()
+            for i in range(S):
+                c = (i * V + j) * B
+                if d is None:       # a view no loss reads
+                    df[c:c + B].zero_()
+                else:
+                    ops.copy_rows(d, df[c:c + B], B, S * N, i * N, N, 0, N, D)
+        return df, None, None, None
+
+
 class ClipAggregation(nn.Module):
-    """Process each clip independently and concatenate all tokens (utils.py:84-159)."""
+    """Process each clip independently and concatenate all tokens (utils.py:84-159).  With a trainable encoder and gradients
+    enabled (fine-tuning) the clips of a batch go through ONE encoder call, whose output stays on the autograd graph."""
 
     def __init__(self, model, tubelet_size=2, max_frames=10000, use_pos_embed=False, attend_across_segments=False):
         super().__init__()
@@ -147,6 +180,9 @@ class ClipAggregation(nn.Module):
         eff_B = B * num_views_per_clip
         # all spatial and temporal views along the batch dimension, in the reference's order
         x = torch.cat([torch.cat(xi, dim=0) for xi in x], dim=0)
+        needs_grad = getattr(self.model, "_needs_grad", None)
+        if needs_grad is not None and needs_grad():
+            return self._forward_with_grad(x, num_clips, num_views_per_clip, B)
         if not self.attend_across_segments:
             f = chunked_call(self._bf16, x, self.max_clips_per_call)
             return [[f[i * eff_B + j * B:i * eff_B + (j + 1) * B] for i in range(num_clips)] for j in range(num_views_per_clip)]
@@ -165,6 +201,20 @@ class ClipAggregation(nn.Module):
                 ops.copy_rows(f[k:k + n], outs[j][b:b + n], n, N, 0, num_clips * N, i * N, N, D)
                 k += n
         return outs
+
+
+    def _forward_with_grad(self, x, num_clips, num_views_per_clip, B):
+        """The same outputs with a backward recorded: one encoder call for all clips (a second call would overwrite the gradient
+        slots the first one's backward writes), slices of it or, concatenated, _PlaceSegments."""
+        if x.shape[0] > self.max_clips_per_call:
+            raise ValueError(f"ClipAggregation: {x.shape[0]} clips with gradients enabled need one encoder call, and one call takes "
+                             f"at most max_clips_per_call = {self.max_clips_per_call} clips (fc1's output stays below 2^31 "
+                             "elements); use a smaller batch or fewer segments")
+        f = self._bf16(x)
+        eff_B = B * num_views_per_clip
+        if not self.attend_across_segments:
+            return [[f[i * eff_B + j * B:i * eff_B + (j + 1) * B] for i in range(num_clips)] for j in range(num_views_per_clip)]
+        return list(_PlaceSegments.apply(f, num_clips, num_views_per_clip, B))
 
 
 def make_transforms(

@@ -3,7 +3,8 @@
 forward and backward run on the gfx950 kernels behind the C ABI (bf16 MFMA GEMMs with fused bias / GELU / residual epilogues,
 fp32-statistics LayerNorm, transpose-free weight gradients, the few-query cross-attention of csrc/xattn.hip) inside two autograd
 nodes, so `loss.backward()` + any torch optimizer of the reference's eval loop (evals/video_classification_frozen/eval.py:298-352)
-work unchanged.  Parameters stay fp32 nn.Parameters (the reference's layout); every step casts the five matrices to bf16.
+work unchanged.  Features that require grad (an encoder fine-tuned through the probe, evals/video_classification_finetune) get their
+gradient from the same backward: norm1's LayerNorm backward already forms it.  Parameters stay fp32 nn.Parameters (the reference's layout); every step casts the five matrices to bf16.
 Any number of feature tokens: attend_across_segments feeds all segments at once (36 864 tokens for ViT-H/16-384 K400 16x8x3), and the
 cross-attention runs split-key kernels where one workgroup cannot hold every score (ops.xattn_fwd / xattn_bwd pick the kernel).
 
@@ -148,6 +149,7 @@ class _PoolerFn(torch.autograd.Function):
         ctx.saved = (x2, xn, mean1, rstd1, kv, qh, q0, lse, wq, wkv, tail)
         ctx.meta = (B, N, D, heads, hd, eps)
         ctx.params = params
+        ctx.x_like = (x.shape, x.dtype)
         return q2.float().view(B, 1, D)
 
     @staticmethod
@@ -166,13 +168,15 @@ class _PoolerFn(torch.autograd.Function):
             dqh1 = torch.empty((1, D), dtype=torch.bfloat16, device=dev)
             ops.cast_bf16(g_qb, dqh1.view(-1))
             g_qw = _qproj_bwd(dqh1, q0, wq, qw, g_qt)
-            # kv = Linear(norm1(x)): weight / bias gradients, then norm1's affine parameters (x itself is frozen)
+            # kv = Linear(norm1(x)): weight / bias gradients, then norm1's affine parameters and, from the same launch, dx: x reaches
+            # the output through norm1 -> kv only, so this is its whole gradient (kept only where x asks for one: fine-tuning)
             g_kvw = ops.gemm_wgrad_tn(dkv, xn, _zeros_like_param(kvw))
             g_kvb = ops.colsum(dkv, _zeros_like_param(kvb))
             dxn = ops.gemm_nt(dkv, _wT(wkv))
             g_n1w, g_n1b = _zeros_like_param(n1w), _zeros_like_param(n1b)
-            ops.layernorm_bwd(dxn, x2, _f32(n1w), mean1, rstd1, g_n1w, g_n1b)
-        return (None, None, None, g_qt.view_as(qt), g_n1w, g_n1b, g_qw, None if qb is None else g_qb, g_kvw,
+            dx = ops.layernorm_bwd(dxn, x2, _f32(n1w), mean1, rstd1, g_n1w, g_n1b)
+            dx = dx.view(ctx.x_like[0]).to(ctx.x_like[1]) if ctx.needs_input_grad[0] else None
+        return (dx, None, None, g_qt.view_as(qt), g_n1w, g_n1b, g_qw, None if qb is None else g_qb, g_kvw,
                 None if kvb is None else g_kvb, *g_tail)
 
 
@@ -231,12 +235,10 @@ class AttentivePooler(nn.Module):
             nn.init.constant_(m.weight, 1.0)
 
     def forward(self, x):
-        """x: [B, N, D] frozen-encoder tokens (any float dtype, GPU) -> [B, 1, D] fp32."""
+        """x: [B, N, D] encoder tokens (any float dtype, GPU) -> [B, 1, D] fp32.  Where x requires grad (an encoder that is being
+        fine-tuned), the backward also returns its gradient, in x's shape and dtype."""
         if not x.is_cuda:
             raise ValueError("AttentivePooler: jepa_amd computes only on the GPU through libvjepa_hip.so (no CPU fallback)")
-        if x.requires_grad and torch.is_grad_enabled():
-            raise NotImplementedError("AttentivePooler: the features come from a FROZEN encoder (eval.py:330-337 runs it under "
-                                      "torch.no_grad()); no gradient is propagated into them")
         blk = self.cross_attention_block
         return _PoolerFn.apply(x, blk.xattn.num_heads, blk.norm1.eps, *_probe_params(self))
 
@@ -393,7 +395,8 @@ class AttentiveClassifierBank(nn.Module):
             raise ValueError("AttentiveClassifierBank: jepa_amd computes only on the GPU through libvjepa_hip.so (no CPU fallback)")
         if x.requires_grad and torch.is_grad_enabled():
             raise NotImplementedError("AttentiveClassifierBank: the features come from a FROZEN encoder (eval.py:330-337 runs it "
-                                      "under torch.no_grad()); no gradient is propagated into them")
+                                      "under torch.no_grad()); no gradient is propagated into them -- a bank of probes over one "
+                                      "trainable encoder is not a protocol (fine-tuning takes the lone AttentiveClassifier)")
         flat = [t for m in self.probes for t in _probe_params(m.pooler, (m.linear.weight, m.linear.bias))]
         return _BankFn.apply(x, self.num_heads, self.probes[0].pooler.cross_attention_block.norm1.eps, len(self.probes), *flat)
 

@@ -27,7 +27,13 @@ k+1 uploading under batch k's frozen forward), the two arms taking turns inside 
 host-to-device bytes per iteration, wall time per iteration, the wait at the input edge (fp32: the copies themselves, timed alone;
 uint8: how long the compute stream stood at the prefetcher's event), and the two kernels timed alone.  The host batches are built
 once, before the clock starts: what a loader costs to decode and draw is not part of these figures.
-python tools/eval_bench.py --uint8 [--rounds 3] [--reps 3]"""
+python tools/eval_bench.py --uint8 [--rounds 3] [--reps 3]
+
+--finetune: one fine-tuning iteration (jepa_amd/evals/video_classification_finetune: ClipAggregation with gradients, the probe's
+update, EncoderFineTuner.step) against the frozen iteration of the same config -- ViT-L/16 16x224x224, batch 4, attend_across_segments
+with --segments segments (default 1 and 8) -- the two arms taking turns inside this process in both orders; ms and peak memory
+of each, and EncoderFineTuner.step timed alone (its launches, ms, share of the iteration).
+python tools/eval_bench.py --finetune [--segments 1 8] [--rounds 4] [--reps 3]"""
 import argparse
 import json
 import os
@@ -416,8 +422,72 @@ def bench_uint8(reps, rounds, B=4, name="vitl16_k400_16x8x3"):
     return dict(config=name, batch=B, reps=reps, iterations_per_arm=reps + 1, **out)
 
 
+def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400):
+    import statistics
+    from jepa_amd.engine.finetune import EncoderFineTuner
+    dev = "cuda"
+    torch.manual_seed(0)
+
+    def make(trainable):
+        model = vit.__dict__[model_name](img_size=res, patch_size=16, num_frames=16, tubelet_size=2, uniform_power=True).to(dev)
+        agg = ClipAggregation(model, tubelet_size=2, attend_across_segments=True).to(dev)
+        tuner = None
+        if trainable:
+            tuner = EncoderFineTuner(model, layer_decay=0.75)
+        else:
+            agg.eval()
+            for p in agg.parameters():
+                p.requires_grad = False
+        clf = AttentiveClassifier(embed_dim=agg.embed_dim, num_heads=agg.num_heads, depth=1, num_classes=C).to(dev)
+        return agg, tuner, clf, init_opt(clf, iterations_per_epoch=1, start_lr=1e-4, ref_lr=1e-4, warmup=0, num_epochs=10 ** 6, wd=0.01)
+
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    enc_f, _, clf_f, (opt_f, scaler_f, sched_f, wd_f) = make(False)
+    enc_t, tuner, clf_t, (opt_t, scaler_t, sched_t, wd_t) = make(True)
+    labels = torch.randint(0, C, (B,))
+    train = ([[torch.randn(B, 3, 16, res, res, device=dev)] for _ in range(S)], labels, [torch.arange(16) for _ in range(S)])
+
+    def step(optimizer, grad_scale):
+        tuner.step(optimizer.param_groups[0]['lr'], 0.05, grad_scale=grad_scale)
+
+    arms = {"frozen": lambda: run_one_epoch(dev, True, enc_f, clf_f, scaler_f, opt_f, sched_f, wd_f, [train], False, 1, S, True),
+            "finetune": lambda: run_one_epoch(dev, True, enc_t, clf_t, scaler_t, opt_t, sched_t, wd_t, [train], False, 1, S, True,
+                                              features_grad=True, after_update=step)}
+    torch.cuda.synchronize()
+    resident = torch.cuda.memory_allocated() - base
+    peak = {}
+    for arm, fn in arms.items():    # warm-up (workspace growth, code load) and the peak memory of each arm on its own
+        torch.cuda.synchronize()
+        before = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        fn()
+        torch.cuda.synchronize()
+        peak[arm] = round((torch.cuda.max_memory_allocated() - before) / 2 ** 30, 2)
+    ms = {arm: [] for arm in arms}
+    for r in range(rounds):
+        for arm in (("frozen", "finetune") if r % 2 == 0 else ("finetune", "frozen")):
+            ms[arm].append(timed(arms[arm], reps))
+    mean = {arm: statistics.mean(v) for arm, v in ms.items()}
+    t_step = [timed(lambda: tuner.step(1e-4, 0.05), 10) for _ in range(3)]
+    t_refresh = timed(tuner.arena.refresh_transposed, 10)
+    upd = statistics.mean(t_step)
+    return dict(config=f"{model_name}_16x{res}_finetune", batch=B, segments=S, clips=S * B, rounds=rounds, reps=reps,
+                frozen_ms_rounds=[round(v, 2) for v in ms["frozen"]], finetune_ms_rounds=[round(v, 2) for v in ms["finetune"]],
+                frozen_iteration_ms=round(mean["frozen"], 2), finetune_iteration_ms=round(mean["finetune"], 2),
+                frozen_ms_spread=round(max(ms["frozen"]) - min(ms["frozen"]), 2),
+                finetune_ms_spread=round(max(ms["finetune"]) - min(ms["finetune"]), 2),
+                peak_mem_gib_frozen_iteration=peak["frozen"], peak_mem_gib_finetune_iteration=peak["finetune"],
+                resident_gib_both_models=round(resident / 2 ** 30, 2),
+                update_ranges=len(tuner.param_groups), update_launches=len(tuner.param_groups) + 4,
+                update_ms_runs=[round(v, 3) for v in t_step], update_ms=round(upd, 3), update_transposed_refresh_ms=round(t_refresh, 3),
+                update_share_of_iteration_pct=round(100 * upd / mean["finetune"], 2))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--finetune", action="store_true", help="one fine-tuning iteration against the frozen iteration (ViT-L/16, batch 4)")
+    ap.add_argument("--segments", nargs="*", type=int, default=[1, 8])
     ap.add_argument("--uint8", action="store_true", help="the video eval's input edge: fp32 views + .to(device) against uint8 frames + prefetch")
     ap.add_argument("--frames", action="store_true", help="FrameAggregation on the ViT-L/16 image model instead of the video eval")
     ap.add_argument("--image", action="store_true", help="the image-classification eval instead of the video one")
@@ -427,6 +497,11 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--bank", type=int, default=0, help="also time the training iteration with a bank of this many probes")
     a = ap.parse_args()
+    if a.finetune:
+        for S in a.segments:
+            print(json.dumps(bench_finetune(a.reps, a.rounds, S)), flush=True)
+            torch.cuda.empty_cache()
+        return
     if a.uint8:
         print(json.dumps(bench_uint8(a.reps, a.rounds)), flush=True)
         return
