@@ -151,6 +151,20 @@ int vj_pos_interp2d_bicubic(const float* table, float* out, int64_t Nh, int64_t 
 int vj_add_pos_frames(void* x_bf16, const float* pos, const int64_t* idx, int64_t B, int64_t F, int64_t N, int64_t D,
                       int64_t max_frames, vj_stream_t stream);
 
+/* ---- stochastic depth (drop path) of encoder fine-tuning ------------------------------------------------------
+ * The ViT lineage's `x = x + drop_path(branch(x))` at the two residual adds of a block, drop_path(v) = v * floor(keep + u) / keep
+ * with one u ~ U[0,1) per sample; the V-JEPA reference builds its blocks without it (src/models/utils/modules.py:114-120) and
+ * releases no fine-tuning loop.  These two replace the ATen broadcast multiply + add of that expression and the multiply autograd
+ * runs for it in the backward; the caller computes the per-sample scales s[b] (0 or 1 / keep) on the device.
+ * y <- bf16( fmaf(s[b], y, x) ) for the rows of sample b (rows b*S .. b*S+S-1); where s[b] == 0 the row becomes the bits of x and
+ * y is NOT read (it may hold anything, NaN included).  x, y bf16 [B*S, D], s fp32 [B] on the device.  D % 8 == 0; x and y distinct,
+ * 16-byte aligned.  B * S == 0 launches nothing; every argument is checked on the host before any HIP call. */
+int vj_drop_path_add(const void* x_bf16, void* y_bf16, const float* scale, int64_t B, int64_t S, int64_t D, vj_stream_t stream);
+/* out <- bf16( s[b] * dx ) (fp32 product, one rounding to bf16); where s[b] == 0 the row is +0 and dx is NOT read.  The scaled
+ * copy is the dY of the branch's last Linear (proj / fc2): its dgrad, weight gradient and bias gradient all read it.  Same shapes
+ * and conditions as vj_drop_path_add. */
+int vj_drop_path_scale(const void* dx_bf16, void* out_bf16, const float* scale, int64_t B, int64_t S, int64_t D, vj_stream_t stream);
+
 /* ---- LayerNorm ----------------------------------------------------------------------------------------------
  * nn.LayerNorm(eps=1e-6) (modules.py:97,106,115,119; vision_transformer.py:193; predictor.py:233).
  * bf16 in/out, fp32 statistics; mean/rstd (nullable pair) are saved for the backward. */

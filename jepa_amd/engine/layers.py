@@ -73,9 +73,29 @@ def _f32_mul(a: float, b: float) -> float:
 
 
 # =============================================================================================== block
-def block_forward(x, bw: BlockW, segs: List[Seg], heads: int, save: bool, fold=None):
+def _drop_residual(x, y, s, segs):
+    """y <- x + s[b] * y in place (stochastic depth: s fp32 [B], 0 or 1 / keep per sample; vj_drop_path_add).  A clip keeps its
+    scale in every segment: s is indexed by b within each Seg."""
+    for sg in segs:
+        ops.drop_path_add(_rows(x, sg), _rows(y, sg), s, sg.B, sg.S)
+    return y
+
+
+def _drop_grad(dx, s, segs):
+    """bf16(s[b] * dx): the gradient of a dropped branch's output, the dY of its last Linear (vj_drop_path_scale)."""
+    out = torch.empty_like(dx)
+    for sg in segs:
+        ops.drop_path_scale(_rows(dx, sg), s, sg.B, sg.S, out=_rows(out, sg))
+    return out
+
+
+def block_forward(x, bw: BlockW, segs: List[Seg], heads: int, save: bool, fold=None, drop=None):
     """x [M, D] bf16 -> x2 [M, D]; returns (x2, saved).  fold (FoldW, only with save = False): both LayerNorms folded into the
-    GEMMs that consume them -- the kernels and their order are those of vj_blocks_fwd_lnfold (bit-identical results)."""
+    GEMMs that consume them -- the kernels and their order are those of vj_blocks_fwd_lnfold (bit-identical results).
+    drop (stochastic depth): None, or (s_attn, s_mlp), each None or an fp32 [B] tensor of per-sample scales.  A branch with a scale
+    leaves its last GEMM without the fused residual (the branch is rounded to bf16 once) and _drop_residual finishes it in place
+    (the sum is rounded once); a branch without one issues exactly the launches of drop = None."""
+    s_attn, s_mlp = drop if drop is not None else (None, None)
     D = x.shape[1]
     hd = D // heads
     scale = hd ** -0.5
@@ -96,7 +116,10 @@ def block_forward(x, bw: BlockW, segs: List[Seg], heads: int, save: bool, fold=N
     for sg in segs:
         _, lse = ops.attn_fwd(_rows(qkv, sg), sg.B, sg.S, heads, hd, scale, save_lse=save, out=_rows(o, sg))
         lses.append(lse)
-    x1 = ops.gemm_nt(o, bw.proj.w, bias=bw.proj.b, residual=x)
+    if s_attn is None:
+        x1 = ops.gemm_nt(o, bw.proj.w, bias=bw.proj.b, residual=x)
+    else:
+        x1 = _drop_residual(x, ops.gemm_nt(o, bw.proj.w, bias=bw.proj.b), s_attn, segs)
     y2 = mean2 = rstd2 = u = None
     if fold is not None:
         g = ops.gemm_nt_lnfold(x1, fold.w_fc1, fold.b_fc1, ops.ln_rowstats(x1, LN_EPS), fold.c_fc1, epilogue=ops.EPI_GELU)
@@ -105,7 +128,10 @@ def block_forward(x, bw: BlockW, segs: List[Seg], heads: int, save: bool, fold=N
         # u: the fc1 epilogue saves gelu'(pre-activation) here (not the pre-activation): all the backward needs from it
         u = torch.empty((x.shape[0], bw.fc1.w.shape[0]), dtype=torch.bfloat16, device=x.device) if save else None
         g = ops.gemm_nt(y2, bw.fc1.w, bias=bw.fc1.b, aux_out=u, epilogue=ops.EPI_GELU)
-    x2 = ops.gemm_nt(g, bw.fc2.w, bias=bw.fc2.b, residual=x1)
+    if s_mlp is None:
+        x2 = ops.gemm_nt(g, bw.fc2.w, bias=bw.fc2.b, residual=x1)
+    else:
+        x2 = _drop_residual(x1, ops.gemm_nt(g, bw.fc2.w, bias=bw.fc2.b), s_mlp, segs)
     saved = (x, y1, mean1, rstd1, qkv, o, lses, x1, y2, mean2, rstd2, u, g) if save else None
     return x2, saved
 
@@ -178,11 +204,17 @@ def _linear_backward(dy, x_in, lw: LinearW, alpha: float, need_dx=True, dgelu_au
 
 
 def block_backward(dx2, saved, bw: BlockW, segs: List[Seg], heads: int, alpha: float, beta: float = 0.0,
-                   fc2_bias_done: bool = False, prev_fc2_gb=None):
+                   fc2_bias_done: bool = False, prev_fc2_gb=None, drop=None):
     """With transpose-free weight gradients the bias gradients of proj and of the PREVIOUS block's fc2 are the column
     sums of the two LayerNorm backward outputs and come out of those passes (vj_layernorm_bwd_colsum); `fc2_bias_done`
     says that this block's fc2 bias gradient was produced that way by the block above.  Same kernels, same order as
-    vj_blocks_bwd (csrc/chain.hip): bit-identical results."""
+    vj_blocks_bwd (csrc/chain.hip): bit-identical results.
+    drop = (s_attn, s_mlp) of the forward.  The dY of a scaled branch's last Linear is the scaled copy of the stream's gradient
+    (_drop_grad), which feeds its dgrad, weight and bias gradient, while the LayerNorm backward below still adds the unscaled
+    gradient as dres.  That Linear's bias gradient is then NOT the column sum of a LayerNorm backward's output: a scaled MLP branch
+    ignores fc2_bias_done (and the caller passes prev_fc2_gb = None to the block above it), a scaled attention branch takes
+    proj.gb from ops.colsum."""
+    s_attn, s_mlp = drop if drop is not None else (None, None)
     x, y1, mean1, rstd1, qkv, o, lses, x1, y2, mean2, rstd2, u, g = saved
     D = x.shape[1]
     hd = D // heads
@@ -192,11 +224,14 @@ def block_backward(dx2, saved, bw: BlockW, segs: List[Seg], heads: int, alpha: f
     acc = beta != 0.0
     fuse = _tn_ok(8, 8)
     defer = [] if _group_ok(bw) else None
-    du = _linear_backward(dx2, g, bw.fc2, alpha, dgelu_aux=u, beta=beta, bias_done=fuse and fc2_bias_done, defer=defer)   # fc2 dgrad fused with GELU'
+    dfc2 = dx2 if s_mlp is None else _drop_grad(dx2, s_mlp, segs)
+    du = _linear_backward(dfc2, g, bw.fc2, alpha, dgelu_aux=u, beta=beta, bias_done=fuse and fc2_bias_done and s_mlp is None,
+                          defer=defer)   # fc2 dgrad fused with GELU'
     dy2 = _linear_backward(du, y2, bw.fc1, alpha, beta=beta, defer=defer)
     dx1 = ops.layernorm_bwd(dy2, x1, bw.norm2.g, mean2, rstd2, bw.norm2.gg, bw.norm2.gb, dres=dx2, alpha=alpha,
-                            accumulate=acc, dxsum=bw.proj.gb if fuse else None)
-    do = _linear_backward(dx1, o, bw.proj, alpha, beta=beta, bias_done=fuse, defer=defer)
+                            accumulate=acc, dxsum=bw.proj.gb if fuse and s_attn is None else None)
+    dproj = dx1 if s_attn is None else _drop_grad(dx1, s_attn, segs)
+    do = _linear_backward(dproj, o, bw.proj, alpha, beta=beta, bias_done=fuse and s_attn is None, defer=defer)
     dqkv = torch.empty_like(qkv)
     for sg, lse in zip(segs, lses):
         ops.attn_bwd(_rows(qkv, sg), _rows(o, sg), _rows(do, sg), lse, sg.B, sg.S, heads, hd, scale,
@@ -239,21 +274,45 @@ def _chained(ws_tag) -> bool:
     return ws_tag is not None and USE_C_CHAIN
 
 
-def _trunk_forward(x, views, segs, save, ws_tag, gemm_flags=0, gates=None):
+def _scaled_mlp(drop, li) -> bool:
+    """Block li's MLP branch carries a stochastic-depth scale: its fc2 bias gradient takes no fused route."""
+    return bool(drop) and drop[li] is not None and drop[li][1] is not None
+
+
+def _check_drop(drop, n_blocks, B, ws_tag):
+    """A non-empty stochastic-depth list: one (s_attn, s_mlp) entry per block, each scale None or fp32 [B] on the device, and no
+    C launch chain (a caller with a workspace, ws_tag, is the Trainer, which has no stochastic depth)."""
+    if not drop:
+        return
+    if ws_tag is not None:
+        raise ValueError("stochastic depth runs on the per-kernel block chain only: the C launch chains (ws_tag) serve the "
+                         "Trainer, which has none")
+    if len(drop) != n_blocks:
+        raise ValueError(f"stochastic depth: {len(drop)} scale entries for {n_blocks} blocks")
+    for d in drop:
+        for s in (d or ()):
+            if s is not None and (s.dtype != torch.float32 or tuple(s.shape) != (B,)):
+                raise ValueError(f"stochastic depth: a scale is {s.dtype} {tuple(s.shape)}, expected float32 ({B},): one per clip")
+
+
+def _trunk_forward(x, views, segs, save, ws_tag, gemm_flags=0, gates=None, drop=None):
     """x through every block of `views` (EncoderW / PredictorW) -> (x, saved blocks): one C call per gated range, else the
-    per-kernel Python chain."""
+    per-kernel Python chain.  drop: None, or one entry per block (block_forward's drop); the per-kernel chain only."""
+    _check_drop(drop, len(views.blocks), segs[0].B if segs else 0, ws_tag)
     if _chained(ws_tag):
         return chain.blocks_forward(x, views, segs, save, ws_tag, LN_EPS, gemm_flags=gemm_flags, gates=gates)
     folds = None if save else getattr(views, "folds", None)
     saved_blocks = []
     for bi, bw in enumerate(views.blocks):
-        x, sv = block_forward(x, bw, segs, views.heads, save, fold=None if folds is None else folds[bi])
+        x, sv = block_forward(x, bw, segs, views.heads, save, fold=None if folds is None else folds[bi],
+                              drop=drop[bi] if drop else None)
         saved_blocks.append(sv)
     return x, saved_blocks
 
 
-def _trunk_backward(dx, saved_blocks, views, segs, tag, alpha, beta, on_layer_done, ws_tag, last_fc2_bias_done):
-    """The blocks of `views` in reverse, whichever chain the forward took; on_layer_done(tag, layer) after every block."""
+def _trunk_backward(dx, saved_blocks, views, segs, tag, alpha, beta, on_layer_done, ws_tag, last_fc2_bias_done, drop=None):
+    """The blocks of `views` in reverse, whichever chain the forward took; on_layer_done(tag, layer) after every block.
+    drop: the forward's per-block list; a block whose MLP branch is scaled gets its fc2 bias gradient from no LayerNorm backward."""
     done = None if on_layer_done is None else (lambda li: on_layer_done(tag, li))
     if isinstance(saved_blocks, chain.TrunkCtx):
         side = side_stream(dx.device)
@@ -262,8 +321,9 @@ def _trunk_backward(dx, saved_blocks, views, segs, tag, alpha, beta, on_layer_do
     nb = len(views.blocks)
     for li in range(nb - 1, -1, -1):
         dx = block_backward(dx, saved_blocks[li], views.blocks[li], segs, views.heads, alpha, beta,
-                            fc2_bias_done=li + 1 < nb or last_fc2_bias_done,
-                            prev_fc2_gb=views.blocks[li - 1].fc2.gb if li > 0 else None)
+                            fc2_bias_done=(li + 1 < nb or last_fc2_bias_done) and not _scaled_mlp(drop, li),
+                            prev_fc2_gb=views.blocks[li - 1].fc2.gb if li > 0 and not _scaled_mlp(drop, li - 1) else None,
+                            drop=drop[li] if drop else None)
         saved_blocks[li] = None
         if done is not None:
             done(li)      # bucket launch waits on the side stream's event, not on this stream
@@ -299,13 +359,14 @@ def _image_model_tokens(ew: EncoderW, clips, masks, N, kdim):
 
 
 def encoder_forward(ew: EncoderW, clips, masks: Optional[List[torch.Tensor]], save: bool, final_norm=True, ws_tag=None,
-                    gemm_flags=0, gates=None, pos=None):
+                    gemm_flags=0, gates=None, pos=None, drop=None):
     """clips fp32 [B,3,T,H,W], or still images [B,3,H,W] standing for the clip that repeats each image along time; for the image
     model (ew.image) images [B,3,H,W], or frames [B,3,T,H,W] (or a list of such clips) each encoded on its own (_image_model_tokens); masks:
     None (all N tokens) or a list of int64 [B,K_i] index tensors.  pos (fp32 [N, D], default ew.pos): the position table of
     the input's token grid (gt, gh, gw), N = gt*gh*gw; the grid is taken from the input (and, for a still image, gt from N).
     Returns (out [sum_i B*K_i, D] bf16, segs, saved).  With final_norm=False the last residual stream is returned
-    (the target path fuses the final norm into vj_target_rows).  gates: see _wait_gates.
+    (the target path fuses the final norm into vj_target_rows).  gates: see _wait_gates.  drop: stochastic depth, None or one
+    (s_attn, s_mlp) entry per block (block_forward); the scales are per clip, [B], shared by every mask segment.
 
     Still images: only the gh*gw distinct tubelets are packed and embedded (vj_image_pack, a GEMM on B*gh*gw rows) and the gt
     temporal slices differ only in their position rows (vj_add_pos_bcast); with masks, the kept rows are packed one by one
@@ -316,6 +377,10 @@ def encoder_forward(ew: EncoderW, clips, masks: Optional[List[torch.Tensor]], sa
     kdim = ew.patch.w.shape[1]
     pos = ew.pos if pos is None else pos
     N = pos.shape[0]
+    if drop:
+        if ew.image or clips.dim() != 5:
+            raise ValueError("encoder_forward: stochastic depth goes with a video encoder's clips [B,3,T,H,W]")
+        _check_drop(drop, len(ew.blocks), clips.shape[0], ws_tag)
     if ew.image:
         if save:
             raise ValueError("encoder_forward: the image model is a frozen (save=False) path")
@@ -346,11 +411,11 @@ def encoder_forward(ew: EncoderW, clips, masks: Optional[List[torch.Tensor]], sa
     else:
         for i, sg in enumerate(segs):
             ops.add_pos(_rows(x, sg), pos, sg.B, sg.S, idx=None if masks is None else masks[i])
-    x, saved_blocks = _trunk_forward(x, ew, segs, save, ws_tag, gemm_flags, gates)
+    x, saved_blocks = _trunk_forward(x, ew, segs, save, ws_tag, gemm_flags, gates, drop=drop or None)
     if not final_norm:
         return x, segs, None
     out, mean, rstd = ops.layernorm_fwd(x, ew.norm.g, ew.norm.b, LN_EPS, save_stats=save)
-    saved = (tok, saved_blocks, x, mean, rstd) if save else None
+    saved = (tok, saved_blocks, x, mean, rstd, drop or None) if save else None
     return out, segs, saved
 
 
@@ -358,13 +423,14 @@ def encoder_backward(dout, saved, ew: EncoderW, segs, alpha: float, on_layer_don
                      ws_tag="bwd_tmp"):
     """dout [M, D] bf16: gradient of the encoder output rows.  Pixels need no gradient.  Parameter gradients are written
     as alpha * grad + beta * old (beta = 1 accumulates micro-batches)."""
-    tok, saved_blocks, xl, mean, rstd = saved
+    tok, saved_blocks, xl, mean, rstd, drop = saved
     # dx of the final norm's backward is the dY of the last block's fc2: with the transpose-free route its bias gradient (the
     # column sums of dx) comes out of this pass like every other block's (round 4: no stand-alone column sum left in a trunk)
-    last_gb = ew.blocks[-1].fc2.gb if _tn_ok(8, 8) else None
+    # (not for a last block whose MLP branch is scaled by stochastic depth: its fc2's dY is the scaled copy of dx)
+    last_gb = ew.blocks[-1].fc2.gb if _tn_ok(8, 8) and not _scaled_mlp(drop, len(ew.blocks) - 1) else None
     dx = ops.layernorm_bwd(dout, xl, ew.norm.g, mean, rstd, ew.norm.gg, ew.norm.gb, alpha=alpha, accumulate=beta != 0.0,
                            dxsum=last_gb)
-    dx = _trunk_backward(dx, saved_blocks, ew, segs, "enc", alpha, beta, on_layer_done, ws_tag, last_gb is not None)
+    dx = _trunk_backward(dx, saved_blocks, ew, segs, "enc", alpha, beta, on_layer_done, ws_tag, last_gb is not None, drop=drop)
     _linear_backward(dx, tok, ew.patch, alpha, need_dx=False, beta=beta)
     side_stream(dout.device).join()
     if on_layer_done is not None:

@@ -13,18 +13,22 @@ left trainable.  It takes that eval's dictionary -- the same keys, `data.dataset
         layer_decay: 0.75             # layer l of depth L trains at encoder_lr * layer_decay ** (L + 1 - l)
         encoder_weight_decay: 0.05    # constant; biases and 1-D tensors get 0
         clip_grad: null               # max global norm of the encoder's gradient
+        drop_path: 0.0                # stochastic depth: block i of L drops each branch per clip at rate drop_path * i / (L - 1)
 
 A training iteration: the clips go through ClipAggregation with gradients enabled (one encoder call), the AttentiveClassifier,
 the cross-entropy and backward(); the probe's optimizer steps exactly as in the frozen eval; then engine.finetune.EncoderFineTuner
 steps the encoder at the probe's warm-up / cosine learning rate scaled by encoder_lr / lr.  Validation runs the encoder under
-no_grad.  The data, the probe, its update and schedules, the CSV log and the checkpoint are the frozen eval's (under
+no_grad.  With `drop_path` > 0 the encoder, which stays in training mode, applies stochastic depth to the training iterations'
+forward (VisionTransformer.set_drop_path_rate: one draw per clip, branch and block from the default CUDA generator, on the device);
+the no_grad validation forward drops nothing.  The generator's state is not part of the checkpoint: a resumed run draws another
+stream of drops than the uninterrupted one would have.  The data, the probe, its update and schedules, the CSV log and the checkpoint are the frozen eval's (under
 `<pretrain folder>/video_classification_finetune/`); the checkpoint adds `encoder` (a state dict in the reference's names, which
 the frozen eval's load_pretrained(checkpoint_key='encoder') reads) and `encoder_opt` (Adam moments and step count in
 torch.optim.AdamW's format).
 
 Limits, all raising: one rank; video encoders at their native clip size (image encoders and off-native sizes are frozen-path
-features); the lone probe (`optimization.multihead_kwargs` is the frozen evals'); every clip of a batch in one encoder call.  Not
-implemented: stochastic depth (drop_path_rate > 0), mixup / cutmix / label smoothing.
+features); the lone probe (`optimization.multihead_kwargs` is the frozen evals'); every clip of a batch in one encoder call;
+0 <= drop_path < 1.  Not implemented: mixup / cutmix / label smoothing.
 """
 from types import SimpleNamespace
 
@@ -40,14 +44,15 @@ FOLDER_NAME = 'video_classification_finetune/'
 def parse_finetune(args_opt):
     """The `optimization.finetune` section with its defaults."""
     ft = args_opt.get('finetune', None) or {}
-    unknown = sorted(set(ft) - {'encoder_lr', 'layer_decay', 'encoder_weight_decay', 'clip_grad'})
+    unknown = sorted(set(ft) - {'encoder_lr', 'layer_decay', 'encoder_weight_decay', 'clip_grad', 'drop_path'})
     if unknown:
         raise ValueError(f"optimization.finetune: unknown keys {unknown}")
     encoder_lr = ft.get('encoder_lr', None)
     return SimpleNamespace(encoder_lr=args_opt.get('lr') if encoder_lr is None else encoder_lr,
                            layer_decay=ft.get('layer_decay', 0.75),
                            encoder_weight_decay=ft.get('encoder_weight_decay', 0.05),
-                           clip_grad=ft.get('clip_grad', None))
+                           clip_grad=ft.get('clip_grad', None),
+                           drop_path=ft.get('drop_path', 0.0))
 
 
 class _FineTune:
@@ -65,6 +70,8 @@ class _FineTune:
 
     def attach(self, cfg, run, aggregation):
         ft, encoder = self.ft, aggregation.model
+        encoder.set_drop_path_rate(ft.drop_path)
+        aggregation.train()     # training iterations drop in training mode only; validation runs under no_grad and drops nothing
         tuner = EncoderFineTuner(encoder, layer_decay=ft.layer_decay, world_size=run.world_size)
         lr_ratio = ft.encoder_lr / cfg.lr
 
@@ -83,7 +90,8 @@ class _FineTune:
             logger.info(f'loaded fine-tuned encoder and its optimizer state with msg: {msg}')
 
         logger.info(f'fine-tuning the encoder: lr {ft.encoder_lr} x {ft.layer_decay} ** (layers below the last), weight decay '
-                    f'{ft.encoder_weight_decay}, clip {ft.clip_grad}, {len(tuner.param_groups)} parameter ranges')
+                    f'{ft.encoder_weight_decay}, clip {ft.clip_grad}, {len(tuner.param_groups)} parameter ranges, stochastic depth '
+                    f'{ft.drop_path} (per block: {", ".join("%.3f" % r for r in encoder.drop_path_rates)})')
         self.tuner = tuner
         return dict(features_grad=True, after_update=after_update), extra_state, restore_extra
 

@@ -70,6 +70,8 @@ SIGNATURES = {
     "vj_pos_interp3d": (I32, [P, P, I64, I64, I64, I64, F64, F64, F64, I64, I64, I64, P]),
     "vj_pos_interp2d_bicubic": (I32, [P, P, I64, I64, I64, F64, I64, I64, P]),
     "vj_add_pos_frames": (I32, [P, P, P, I64, I64, I64, I64, I64, P]),
+    "vj_drop_path_add": (I32, [P, P, P, I64, I64, I64, P]),
+    "vj_drop_path_scale": (I32, [P, P, P, I64, I64, I64, P]),
     "vj_layernorm_fwd": (I32, [P, P, P, P, P, P, I64, I64, F32, P]),
     "vj_layernorm_bwd_ws_bytes": (I64, [I64]),
     "vj_layernorm_bwd": (I32, [P, P, P, P, P, P, P, P, P, F32, F32, I64, I64, P, I64, P]),

@@ -299,6 +299,37 @@ def add_pos_frames(x, pos, idx, N, stream=None):
     return x
 
 
+# ---------------------------------------------------------------- stochastic depth
+def _drop_path_args(what, a, b, scale, B, S):
+    _req(a, BF16, what + ": rows")
+    _req(b, BF16, what + ": rows")
+    _req(scale, F32, what + ": scale")
+    D = a.shape[-1]
+    if a.numel() != B * S * D or b.shape != a.shape or scale.numel() != B:
+        raise ValueError(f"{what}: rows {tuple(a.shape)} / {tuple(b.shape)} and scale {tuple(scale.shape)} do not match B={B} S={S}")
+    return D
+
+
+def drop_path_add(x, y, scale, B, S, stream=None):
+    """y [B*S, D] bf16 <- bf16(x + scale[b] * y) on the S rows of sample b, in place (one fp32 fused multiply-add, one rounding);
+    where scale[b] == 0 the rows become x's bits and y is not read.  scale fp32 [B]."""
+    lib = load_library()
+    D = _drop_path_args("drop_path_add", x, y, scale, B, S)
+    check(lib.vj_drop_path_add(_ptr(x), _ptr(y), _ptr(scale), B, S, D, _stream(stream)), "vj_drop_path_add")
+    return y
+
+
+def drop_path_scale(dx, scale, B, S, out=None, stream=None):
+    """bf16(scale[b] * dx) on the S rows of sample b -> out (new unless given); where scale[b] == 0 the rows are +0 and dx is not
+    read.  dx bf16 [B*S, D], scale fp32 [B]."""
+    lib = load_library()
+    if out is None:
+        out = torch.empty_like(dx)
+    D = _drop_path_args("drop_path_scale", dx, out, scale, B, S)
+    check(lib.vj_drop_path_scale(_ptr(dx), _ptr(out), _ptr(scale), B, S, D, _stream(stream)), "vj_drop_path_scale")
+    return out
+
+
 # ---------------------------------------------------------------- layernorm
 def layernorm_fwd(x, gamma, beta, eps, save_stats=True, out=None, stream=None):
     lib = load_library()

@@ -5,7 +5,8 @@
     out = vit(clips)                  # [B, N, D]
     out = vit(clips, masks=[idx])     # [B*len(masks), K, D]   (reference contract: masks share K)
 
-`forward` is differentiable (one autograd node per call whose backward is the hand-written layer chain), but
+`forward` is differentiable (one autograd node per call whose backward is the hand-written layer chain; with `drop_path_rate` > 0
+a training-mode forward that records a backward applies stochastic depth, see set_drop_path_rate), but
 the pretraining step (jepa_amd.engine.step.Trainer) bypasses autograd entirely and shares this module's
 parameters through flat arenas.
 
@@ -38,8 +39,11 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
     def __init__(self, img_size=224, patch_size=16, num_frames=1, tubelet_size=2, in_chans=3, embed_dim=768,
                  depth=12, num_heads=12, mlp_ratio=4.0, qkv_bias=True, qk_scale=None, drop_rate=0.0,
                  attn_drop_rate=0.0, norm_layer=nn.LayerNorm, init_std=0.02, out_layers=None, uniform_power=False,
-                 **kwargs):
+                 drop_path_rate=0.0, **kwargs):
         super().__init__()
+        self.drop_path_generator = None     # a torch.Generator of the model's device for the draws; None: the default generator
+        self.last_drop_path_scales = None   # fp32 [L, 2, B]: the scales of the latest forward that dropped anything
+        self.set_drop_path_rate(drop_path_rate, depth)
         self.num_features = self.embed_dim = embed_dim
         self.num_heads = num_heads
         self.out_layers = out_layers
@@ -96,6 +100,56 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
 
     def get_num_layers(self):
         return len(self.blocks)
+
+    # ---- stochastic depth ---------------------------------------------------------------------------------
+    def set_drop_path_rate(self, rate, depth=None):
+        """Block i of L drops each of its two branches (attention, MLP) per sample with probability rate * i / (L - 1), the ViT
+        lineage's torch.linspace(0, rate, L) -- while the module is in training mode and the forward records a backward; the
+        frozen / no-grad path, eval() and the image encoder never drop."""
+        rate = float(rate)
+        if not 0.0 <= rate < 1.0:
+            raise ValueError(f"drop_path_rate={rate} must lie in [0, 1)")
+        depth = len(self.blocks) if depth is None else depth
+        self.drop_path_rate = rate
+        self.drop_path_rates = [rate * i / (depth - 1) if depth > 1 else 0.0 for i in range(depth)]
+        self.__dict__.pop("_drop_keep", None)
+
+    def set_drop_path_scales(self, scales):
+        """The next forward that records a backward in training mode takes these scales instead of drawing: fp32 [L, 2, B] on the
+        model's device, scales[i, 0] / scales[i, 1] multiplying the attention / MLP branch of block i per clip (0 drops it; a draw
+        gives 0 or 1 / keep_i).  Used once; None withdraws them."""
+        if scales is not None:
+            if scales.dim() != 3 or tuple(scales.shape[:2]) != (len(self.blocks), 2) or scales.dtype != torch.float32:
+                raise ValueError(f"set_drop_path_scales: expected float32 [{len(self.blocks)}, 2, B], got {scales.dtype} "
+                                 f"{tuple(scales.shape)}")
+            scales = scales.detach().contiguous()
+        self.__dict__["_drop_scales_next"] = scales
+
+    def _drop_path_entries(self, x):
+        """The per-block (s_attn, s_mlp) list of engine.layers for a grad-recording forward of clips x, or None: nothing drops.  One
+        torch.rand((L, 2, B)) on the device per forward, no host synchronisation; s = floor(keep + u) / keep.  A branch whose rate is
+        0 gets no scale and keeps the fused residual add.  `last_drop_path_scales` holds what the forward used."""
+        self.__dict__["last_drop_path_scales"] = None
+        if not self.training or isinstance(x, list) or x.dim() != 5:
+            return None
+        L, B = len(self.blocks), x.shape[0]
+        s = self.__dict__.get("_drop_scales_next")
+        if s is not None:
+            if s.shape[2] != B or s.device != x.device:
+                raise ValueError(f"set_drop_path_scales: scales {tuple(s.shape)} on {s.device} do not fit a batch of {B} clips on "
+                                 f"{x.device}")
+            self.__dict__["_drop_scales_next"] = None
+            self.__dict__["last_drop_path_scales"] = s
+            return [(s[i, 0], s[i, 1]) for i in range(L)]
+        if self.drop_path_rate == 0.0:
+            return None
+        keep = self.__dict__.get("_drop_keep")
+        if keep is None or keep.device != x.device:
+            keep = self.__dict__["_drop_keep"] = (1.0 - torch.tensor(self.drop_path_rates, dtype=torch.float32)).view(L, 1, 1).to(x.device)
+        u = torch.rand((L, 2, B), device=x.device, generator=self.drop_path_generator)
+        s = torch.floor(keep + u).clamp_(max=1.0) / keep      # (the clamp: keep + u can round up to 2 at u = 1 - 2^-24)
+        self.__dict__["last_drop_path_scales"] = s
+        return [(s[i, 0], s[i, 1]) if self.drop_path_rates[i] > 0.0 else None for i in range(L)]
 
     def no_weight_decay(self):
         return {}
@@ -256,6 +310,7 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         return out.view(x.shape[0], segs[0].S, self.embed_dim)
 
     def _run(self, x, masks, pos=None):
+        self.__dict__["last_drop_path_scales"] = None
         if isinstance(x, list):     # frames of the image model, clip by clip (forward_frames)
             for c in x:
                 hipmodule.require_gpu(c, "VisionTransformer.forward_frames")
@@ -266,7 +321,7 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         if masks is not None:
             masks = [m.contiguous() for m in masks]
         if self._needs_grad():
-            return hipmodule.run_with_autograd(self, _enc_fwd, _enc_bwd, (x, masks))
+            return hipmodule.run_with_autograd(self, _enc_fwd, _enc_bwd, (x, masks, self._drop_path_entries(x)))
         # inference: one C call per trunk (no saved activations, a private workspace) and, because nothing else shares the
         # GPU with this stream, the two-workgroups-per-CU GEMM (gemm4w.hip; see DESIGN.md section 6 for why training does not)
         ew = self._hip_views(train=False)
@@ -284,8 +339,8 @@ INFER_GEMM_FLAGS = 0x100
 
 
 def _enc_fwd(module, ew, args, diff):
-    x, masks = args
-    out, segs, saved = encoder_forward(ew, x, masks, save=True)
+    x, masks, drop = args
+    out, segs, saved = encoder_forward(ew, x, masks, save=True, drop=drop)
     return out, segs, (saved, segs)
 
 
@@ -295,41 +350,41 @@ def _enc_bwd(module, ew, ctx_saved, dout):
     return None
 
 
-def vit_tiny(patch_size=16, **kwargs):
+def vit_tiny(patch_size=16, drop_path_rate=0.0, **kwargs):
     return VisionTransformer(patch_size=patch_size, embed_dim=192, depth=12, num_heads=3, mlp_ratio=4,
-                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), **kwargs)
+                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), drop_path_rate=drop_path_rate, **kwargs)
 
 
-def vit_small(patch_size=16, **kwargs):
+def vit_small(patch_size=16, drop_path_rate=0.0, **kwargs):
     return VisionTransformer(patch_size=patch_size, embed_dim=384, depth=12, num_heads=6, mlp_ratio=4,
-                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), **kwargs)
+                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), drop_path_rate=drop_path_rate, **kwargs)
 
 
-def vit_base(patch_size=16, **kwargs):
+def vit_base(patch_size=16, drop_path_rate=0.0, **kwargs):
     return VisionTransformer(patch_size=patch_size, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4,
-                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), **kwargs)
+                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), drop_path_rate=drop_path_rate, **kwargs)
 
 
-def vit_large(patch_size=16, **kwargs):
+def vit_large(patch_size=16, drop_path_rate=0.0, **kwargs):
     return VisionTransformer(patch_size=patch_size, embed_dim=1024, depth=24, num_heads=16, mlp_ratio=4,
-                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), **kwargs)
+                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), drop_path_rate=drop_path_rate, **kwargs)
 
 
-def vit_huge(patch_size=16, **kwargs):
+def vit_huge(patch_size=16, drop_path_rate=0.0, **kwargs):
     return VisionTransformer(patch_size=patch_size, embed_dim=1280, depth=32, num_heads=16, mlp_ratio=4,
-                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), **kwargs)
+                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), drop_path_rate=drop_path_rate, **kwargs)
 
 
-def vit_giant(patch_size=16, **kwargs):
+def vit_giant(patch_size=16, drop_path_rate=0.0, **kwargs):
     return VisionTransformer(patch_size=patch_size, embed_dim=1408, depth=40, num_heads=16, mlp_ratio=48 / 11,
-                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), **kwargs)
+                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), drop_path_rate=drop_path_rate, **kwargs)
 
 
-def vit_gigantic(patch_size=14, **kwargs):
+def vit_gigantic(patch_size=14, drop_path_rate=0.0, **kwargs):
     # the reference passes a misspelt `mpl_ratio` here (vision_transformer.py:293), so its effective mlp_ratio is
     # the default 4.0; kept for checkpoint compatibility
     return VisionTransformer(patch_size=patch_size, embed_dim=1664, depth=48, num_heads=16, mlp_ratio=4.0,
-                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), **kwargs)
+                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), drop_path_rate=drop_path_rate, **kwargs)
 
 
 VIT_EMBED_DIMS = {

@@ -32,8 +32,10 @@ python tools/eval_bench.py --uint8 [--rounds 3] [--reps 3]
 --finetune: one fine-tuning iteration (jepa_amd/evals/video_classification_finetune: ClipAggregation with gradients, the probe's
 update, EncoderFineTuner.step) against the frozen iteration of the same config -- ViT-L/16 16x224x224, batch 4, attend_across_segments
 with --segments segments (default 1 and 8) -- the two arms taking turns inside this process in both orders; ms and peak memory
-of each, and EncoderFineTuner.step timed alone (its launches, ms, share of the iteration).
-python tools/eval_bench.py --finetune [--segments 1 8] [--rounds 4] [--reps 3]"""
+of each, and EncoderFineTuner.step timed alone (its launches, ms, share of the iteration).  --drop-path R adds a third arm taking
+turns with the two: the same fine-tuning iteration with stochastic depth at rate R (the fine-tuning arm itself runs at rate 0), and
+times vj_drop_path_add / vj_drop_path_scale alone on the trunk's M x D rows, every sample kept, beside vj_copy_rows (ms, bytes/s).
+python tools/eval_bench.py --finetune [--segments 1 8] [--rounds 4] [--reps 3] [--drop-path 0.1]"""
 import argparse
 import json
 import os
@@ -422,7 +424,26 @@ def bench_uint8(reps, rounds, B=4, name="vitl16_k400_16x8x3"):
     return dict(config=name, batch=B, reps=reps, iterations_per_arm=reps + 1, **out)
 
 
-def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400):
+def bench_drop_path_kernels(M, D, B, reps=20):
+    """The two stochastic-depth kernels and vj_copy_rows alone on M x D bf16 rows of B samples, every sample kept (the most
+    bytes: a dropped sample's branch rows are not read): ms and bytes/s by the bytes each must move."""
+    from jepa_amd.hip import ops
+    dev = "cuda"
+    x = torch.randn(M, D, device=dev).to(torch.bfloat16)
+    y = torch.randn(M, D, device=dev).to(torch.bfloat16)
+    out = torch.empty_like(x)
+    s = torch.ones(B, device=dev)          # y <- x + y: stays finite over the repetitions
+    S = M // B
+    ms = dict(drop_path_add=(timed(lambda: ops.drop_path_add(x, y, s, B, S), reps), 3),
+              drop_path_scale=(timed(lambda: ops.drop_path_scale(x, s, B, S, out=out), reps), 2),
+              copy_rows=(timed(lambda: ops.copy_rows(x, out, 1, M, 0, M, 0, M, D), reps), 2))
+    res = {}
+    for k, (t, streams) in ms.items():
+        res[k] = dict(ms=round(t, 4), streams=streams, tb_per_s=round(streams * M * D * 2 / (t * 1e-3) / 1e12, 3))
+    return dict(rows=M, cols=D, samples=B, **res)
+
+
+def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400, drop_path=None):
     import statistics
     from jepa_amd.engine.finetune import EncoderFineTuner
     dev = "cuda"
@@ -451,9 +472,17 @@ def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400)
     def step(optimizer, grad_scale):
         tuner.step(optimizer.param_groups[0]['lr'], 0.05, grad_scale=grad_scale)
 
+    def finetune_at(rate):
+        def run():
+            enc_t.model.set_drop_path_rate(rate)
+            run_one_epoch(dev, True, enc_t, clf_t, scaler_t, opt_t, sched_t, wd_t, [train], False, 1, S, True,
+                          features_grad=True, after_update=step)
+        return run
+
     arms = {"frozen": lambda: run_one_epoch(dev, True, enc_f, clf_f, scaler_f, opt_f, sched_f, wd_f, [train], False, 1, S, True),
-            "finetune": lambda: run_one_epoch(dev, True, enc_t, clf_t, scaler_t, opt_t, sched_t, wd_t, [train], False, 1, S, True,
-                                              features_grad=True, after_update=step)}
+            "finetune": finetune_at(0.0)}
+    if drop_path:
+        arms["finetune_drop"] = finetune_at(drop_path)
     torch.cuda.synchronize()
     resident = torch.cuda.memory_allocated() - base
     peak = {}
@@ -465,10 +494,23 @@ def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400)
         torch.cuda.synchronize()
         peak[arm] = round((torch.cuda.max_memory_allocated() - before) / 2 ** 30, 2)
     ms = {arm: [] for arm in arms}
+    names = list(arms)
     for r in range(rounds):
-        for arm in (("frozen", "finetune") if r % 2 == 0 else ("finetune", "frozen")):
+        # two arms: the two orders in turn; three: the order rotates, reversed every other round
+        order = names[r % len(names):] + names[:r % len(names)]
+        for arm in (order if r % 2 == 0 or len(names) == 2 else order[::-1]):
             ms[arm].append(timed(arms[arm], reps))
+    enc_t.model.set_drop_path_rate(0.0)
     mean = {arm: statistics.mean(v) for arm, v in ms.items()}
+    drop = {}
+    if drop_path:
+        d = ms["finetune_drop"]
+        drop = dict(drop_path=drop_path, finetune_drop_ms_rounds=[round(v, 2) for v in d],
+                    finetune_drop_iteration_ms=round(mean["finetune_drop"], 2), finetune_drop_ms_spread=round(max(d) - min(d), 2),
+                    drop_minus_rate0_ms_rounds=[round(a - b, 2) for a, b in zip(d, ms["finetune"])],
+                    drop_minus_rate0_ms=round(mean["finetune_drop"] - mean["finetune"], 2),
+                    peak_mem_gib_finetune_drop_iteration=peak["finetune_drop"],
+                    drop_path_kernels=bench_drop_path_kernels(S * B * enc_t.model.num_patches, enc_t.embed_dim, S * B))
     t_step = [timed(lambda: tuner.step(1e-4, 0.05), 10) for _ in range(3)]
     t_refresh = timed(tuner.arena.refresh_transposed, 10)
     upd = statistics.mean(t_step)
@@ -481,13 +523,14 @@ def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400)
                 resident_gib_both_models=round(resident / 2 ** 30, 2),
                 update_ranges=len(tuner.param_groups), update_launches=len(tuner.param_groups) + 4,
                 update_ms_runs=[round(v, 3) for v in t_step], update_ms=round(upd, 3), update_transposed_refresh_ms=round(t_refresh, 3),
-                update_share_of_iteration_pct=round(100 * upd / mean["finetune"], 2))
+                update_share_of_iteration_pct=round(100 * upd / mean["finetune"], 2), **drop)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--finetune", action="store_true", help="one fine-tuning iteration against the frozen iteration (ViT-L/16, batch 4)")
     ap.add_argument("--segments", nargs="*", type=int, default=[1, 8])
+    ap.add_argument("--drop-path", type=float, default=None, help="with --finetune: a third arm, fine-tuning with stochastic depth at this rate")
     ap.add_argument("--uint8", action="store_true", help="the video eval's input edge: fp32 views + .to(device) against uint8 frames + prefetch")
     ap.add_argument("--frames", action="store_true", help="FrameAggregation on the ViT-L/16 image model instead of the video eval")
     ap.add_argument("--image", action="store_true", help="the image-classification eval instead of the video one")
@@ -499,7 +542,7 @@ def main():
     a = ap.parse_args()
     if a.finetune:
         for S in a.segments:
-            print(json.dumps(bench_finetune(a.reps, a.rounds, S)), flush=True)
+            print(json.dumps(bench_finetune(a.reps, a.rounds, S, drop_path=a.drop_path)), flush=True)
             torch.cuda.empty_cache()
         return
     if a.uint8:
