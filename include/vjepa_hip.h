@@ -165,6 +165,29 @@ int vj_drop_path_add(const void* x_bf16, void* y_bf16, const float* scale, int64
  * and conditions as vj_drop_path_add. */
 int vj_drop_path_scale(const void* dx_bf16, void* out_bf16, const float* scale, int64_t B, int64_t S, int64_t D, vj_stream_t stream);
 
+/* ---- mixup / cutmix / label smoothing of encoder fine-tuning ----------------------------------------------------
+ * The ViT lineage's batch-mode mixup and cutmix (x = lam * x + (1 - lam) * x.flip(0); x[..., y0:y1, x0:x1] = x.flip(0)[..., y0:y1,
+ * x0:x1]) and its soft-target cross-entropy; the V-JEPA reference has neither (its probes train on hard labels,
+ * evals/video_classification_frozen/eval.py:309) and releases no fine-tuning loop.  The draws stay on the host (jepa_amd/evals/mix.py).
+ * vj_clip_mix replaces the ATen flip / multiply / add / slice-assign of those expressions without a second copy of the batch:
+ *   x    fp32 [B,P,H,W] (P = 3*T planes of a clip), mixed IN PLACE: sample i with sample B-1-i, both directions by one thread per
+ *        16-byte chunk of the pair; the middle sample of an odd B, and B == 1, keep their bits
+ *   lam  fp32 [B], box int32 [B,4] = (y0, y1, x0, x1) per sample (batch mode gives a pair equal rows; the kernel does not assume it)
+ * per element of sample i: inside box_i the bits of x_j; outside it with lam_i == 1 the bits of x_i (not written; a pair with lam == 1
+ * and empty boxes on both sides is not read); otherwise fmaf(lam_i, x_i, (1 - lam_i) * x_j) in fp32 (1 - lam_i and the product are
+ * rounded on their own).  W % 4 == 0, x 16-byte aligned, P*H*W < 2^33; callers validate 0 <= y0 <= y1 <= H, 0 <= x0 <= x1 <= W on the
+ * host before they copy the table (the kernel only compares against it: no box makes it leave x).  Every argument is checked on the
+ * host before any HIP call. */
+int vj_clip_mix(float* x, const float* lam, const int32_t* box, int64_t B, int64_t P, int64_t H, int64_t W, vj_stream_t stream);
+/* sum(-t * log_softmax(z), dim=-1) per row for the target t_c = eps / C + (1 - eps) * (lam * [c == a] + (1 - lam) * [c == b]), which
+ * is never materialised: loss[r] = lse - (1 - eps) * (lam * z_a + (1 - lam) * z_b) - (eps / C) * sum_c z_c, dlogits[r,:] = softmax(z) - t
+ * (d loss[r] / d z; a == b gives the one column the whole 1 - eps), probs (nullable) = softmax(z).  One wave per row, three passes
+ * (maximum; sum exp(z - max) and sum z in fp32; the outputs).  logits fp32 [R,C] with row stride ld >= C; label_a, label_b int32 [R];
+ * lam fp32 [R]; loss fp32 [R]; dlogits, probs fp32 [R,C] contiguous.  0 <= smoothing < 1, C >= 1.  Callers validate the labels on the
+ * host (the kernel clamps them into [0, C) all the same).  eps = 0, lam = 1 is nn.CrossEntropyLoss(reduction='none'). */
+int vj_soft_ce(const float* logits, int64_t ld, const int32_t* label_a, const int32_t* label_b, const float* lam, float smoothing,
+               int64_t R, int64_t C, float* loss, float* dlogits, float* probs, vj_stream_t stream);
+
 /* ---- LayerNorm ----------------------------------------------------------------------------------------------
  * nn.LayerNorm(eps=1e-6) (modules.py:97,106,115,119; vision_transformer.py:193; predictor.py:233).
  * bf16 in/out, fp32 statistics; mean/rstd (nullable pair) are saved for the backward. */

@@ -14,6 +14,13 @@ left trainable.  It takes that eval's dictionary -- the same keys, `data.dataset
         encoder_weight_decay: 0.05    # constant; biases and 1-D tensors get 0
         clip_grad: null               # max global norm of the encoder's gradient
         drop_path: 0.0                # stochastic depth: block i of L drops each branch per clip at rate drop_path * i / (L - 1)
+        mix:                          # absent (the default): off.  Present: the sub-keys left out take these values
+          mixup_alpha: 0.8            # lam ~ Beta(alpha, alpha): x_i <- lam x_i + (1 - lam) x_(B-1-i); 0: no mixup
+          cutmix_alpha: 1.0           # a box of area (1 - lam) S^2 of x_(B-1-i) replaces that of x_i; 0: no cutmix
+          prob: 1.0                   # a batch is mixed with this probability
+          switch_prob: 0.5            # a mixed batch is cutmix with this probability (when both alphas are > 0)
+          label_smoothing: 0.1        # eps of the target eps / C + (1 - eps) (lam onehot(y_i) + (1 - lam) onehot(y_(B-1-i)))
+          seed: 0                     # of the draws' own np.random.RandomState
 
 A training iteration: the clips go through ClipAggregation with gradients enabled (one encoder call), the AttentiveClassifier,
 the cross-entropy and backward(); the probe's optimizer steps exactly as in the frozen eval; then engine.finetune.EncoderFineTuner
@@ -21,19 +28,26 @@ steps the encoder at the probe's warm-up / cosine learning rate scaled by encode
 no_grad.  With `drop_path` > 0 the encoder, which stays in training mode, applies stochastic depth to the training iterations'
 forward (VisionTransformer.set_drop_path_rate: one draw per clip, branch and block from the default CUDA generator, on the device);
 the no_grad validation forward drops nothing.  The generator's state is not part of the checkpoint: a resumed run draws another
-stream of drops than the uninterrupted one would have.  The data, the probe, its update and schedules, the CSV log and the checkpoint are the frozen eval's (under
+stream of drops than the uninterrupted one would have.  With a `mix` section (..mix: the draws and their order) every training batch
+is mixed with its flipped self on the device, in place in the loader's buffers (vj_clip_mix: one plan per batch, the same tables for
+every segment of a clip), and the loss is the soft-target cross-entropy with label smoothing (vj_soft_ce) per view; the semantics
+are the ViT lineage's batch-mode mixup / cutmix, the random stream is this package's own (no bit-parity with timm's is claimed) and,
+like the drop-path generator, not part of the checkpoint.  The training top-1 is counted against each clip's own label, a lower
+bound under mixing; validation is untouched.  A section with both alphas and the smoothing at 0 counts as absent, and without the
+key an iteration issues the launches it issued before.  The data, the probe, its update and schedules, the CSV log and the checkpoint are the frozen eval's (under
 `<pretrain folder>/video_classification_finetune/`); the checkpoint adds `encoder` (a state dict in the reference's names, which
 the frozen eval's load_pretrained(checkpoint_key='encoder') reads) and `encoder_opt` (Adam moments and step count in
 torch.optim.AdamW's format).
 
 Limits, all raising: one rank; video encoders at their native clip size (image encoders and off-native sizes are frozen-path
 features); the lone probe (`optimization.multihead_kwargs` is the frozen evals'); every clip of a batch in one encoder call;
-0 <= drop_path < 1.  Not implemented: mixup / cutmix / label smoothing.
+0 <= drop_path < 1; `mix`: alphas >= 0, probabilities in [0, 1], 0 <= label_smoothing < 1, unknown sub-keys raise.
 """
 from types import SimpleNamespace
 
 from ...engine.finetune import EncoderFineTuner
 from ...src.utils.logging import get_logger
+from ..mix import MixDraw
 from ..video_classification_frozen import eval as frozen_eval
 
 logger = get_logger(__name__)
@@ -41,10 +55,43 @@ logger = get_logger(__name__)
 FOLDER_NAME = 'video_classification_finetune/'
 
 
+MIX_DEFAULTS = {'mixup_alpha': 0.8, 'cutmix_alpha': 1.0, 'prob': 1.0, 'switch_prob': 0.5, 'label_smoothing': 0.1, 'seed': 0}
+
+
+def parse_mix(section):
+    """The `optimization.finetune.mix` section -> the keywords of MixDraw (without num_classes), or None when the key is absent
+    or switches nothing on (both alphas and the smoothing 0).  A present section takes the recipe's values for the sub-keys it
+    leaves out."""
+    if section is None:
+        return None
+    if not isinstance(section, dict):
+        raise ValueError(f"optimization.finetune.mix: expected a mapping of {sorted(MIX_DEFAULTS)}, got {section!r}")
+    unknown = sorted(set(section) - set(MIX_DEFAULTS))
+    if unknown:
+        raise ValueError(f"optimization.finetune.mix: unknown keys {unknown}")
+    mix = {**MIX_DEFAULTS, **section}
+    for k in ('mixup_alpha', 'cutmix_alpha', 'prob', 'switch_prob', 'label_smoothing'):
+        if isinstance(mix[k], bool) or not isinstance(mix[k], (int, float)) or mix[k] != mix[k]:
+            raise ValueError(f"optimization.finetune.mix.{k}: expected a number, got {mix[k]!r}")
+    for k in ('mixup_alpha', 'cutmix_alpha'):
+        if mix[k] < 0 or mix[k] == float('inf'):
+            raise ValueError(f"optimization.finetune.mix.{k}={mix[k]} must be >= 0 and finite")
+    for k in ('prob', 'switch_prob'):
+        if not 0.0 <= mix[k] <= 1.0:
+            raise ValueError(f"optimization.finetune.mix.{k}={mix[k]} must lie in [0, 1]")
+    if not 0.0 <= mix['label_smoothing'] < 1.0:
+        raise ValueError(f"optimization.finetune.mix.label_smoothing={mix['label_smoothing']} must lie in [0, 1)")
+    if isinstance(mix['seed'], bool) or not isinstance(mix['seed'], int) or not 0 <= mix['seed'] < 2 ** 32:
+        raise ValueError(f"optimization.finetune.mix.seed={mix['seed']!r} must be an integer in [0, 2^32)")
+    if mix['mixup_alpha'] == 0 and mix['cutmix_alpha'] == 0 and mix['label_smoothing'] == 0:
+        return None
+    return mix
+
+
 def parse_finetune(args_opt):
     """The `optimization.finetune` section with its defaults."""
     ft = args_opt.get('finetune', None) or {}
-    unknown = sorted(set(ft) - {'encoder_lr', 'layer_decay', 'encoder_weight_decay', 'clip_grad', 'drop_path'})
+    unknown = sorted(set(ft) - {'encoder_lr', 'layer_decay', 'encoder_weight_decay', 'clip_grad', 'drop_path', 'mix'})
     if unknown:
         raise ValueError(f"optimization.finetune: unknown keys {unknown}")
     encoder_lr = ft.get('encoder_lr', None)
@@ -52,7 +99,8 @@ def parse_finetune(args_opt):
                            layer_decay=ft.get('layer_decay', 0.75),
                            encoder_weight_decay=ft.get('encoder_weight_decay', 0.05),
                            clip_grad=ft.get('clip_grad', None),
-                           drop_path=ft.get('drop_path', 0.0))
+                           drop_path=ft.get('drop_path', 0.0),
+                           mix=parse_mix(ft.get('mix', None)))
 
 
 class _FineTune:
@@ -93,7 +141,12 @@ class _FineTune:
                     f'{ft.encoder_weight_decay}, clip {ft.clip_grad}, {len(tuner.param_groups)} parameter ranges, stochastic depth '
                     f'{ft.drop_path} (per block: {", ".join("%.3f" % r for r in encoder.drop_path_rates)})')
         self.tuner = tuner
-        return dict(features_grad=True, after_update=after_update), extra_state, restore_extra
+        epoch = dict(features_grad=True, after_update=after_update)
+        if ft.mix is not None:
+            epoch['mix'] = self.mix = MixDraw(num_classes=cfg.num_classes, **ft.mix)
+            logger.info('mixing the training batches with their flipped selves: ' + ', '.join(f'{k} {v}' for k, v in ft.mix.items())
+                        + ' (soft-target cross-entropy; the training top-1 is counted against the clips\' own labels)')
+        return epoch, extra_state, restore_extra
 
 
 def main(args_eval, resume_preempt=False):

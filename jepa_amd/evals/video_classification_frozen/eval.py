@@ -45,6 +45,7 @@ from ...src.utils.schedulers import CosineWDSchedule, WarmupCosineSchedule
 from ..frozen import classifier_state_dict, load_checkpoint  # noqa: F401  (the reference's names in this file)
 from ..frozen import distributed as _distributed
 from ..frozen import freeze, parse_config, run_probe_epoch, setup_run, synthetic_dataloader, train_single_probe
+from ..mix import SoftTargetCrossEntropy, mix_batch
 from ..multihead import run as run_multihead
 from .utils import ClipAggregation, FrameAggregation, make_transforms
 
@@ -75,7 +76,7 @@ def main(args_eval, resume_preempt=False, finetune=None):
     train_data_path = [args_data.get('dataset_train')]
     val_data_path = [args_data.get('dataset_val')]
     dataset_type = args_data.get('dataset_type', 'VideoDataset')
-    num_classes = args_data.get('num_classes')
+    num_classes = cfg.num_classes = args_data.get('num_classes')
     eval_num_segments = args_data.get('num_segments', 1)
     eval_frames_per_clip = args_data.get('frames_per_clip', 16)
     eval_frame_step = args_pretrain.get('frame_step', 4)
@@ -165,20 +166,40 @@ def _view_features(attend_across_segments, encoder, data, device):
 
 def run_one_epoch(device, training, encoder, classifier, scaler, optimizer, scheduler, wd_scheduler, data_loader, use_bfloat16,
                   num_spatial_views, num_temporal_views, attend_across_segments, *, history=None, features_grad=False,
-                  after_update=None):
+                  after_update=None, mix=None):
     """The reference's epoch (eval.py:298-380), same parameters in the same order.  history (keyword-only, optional list):
     (learning rate, loss) of each training iteration.  features_grad / after_update (keyword-only, off by default): the
-    fine-tuning eval's encoder gradients and encoder step, see frozen.run_probe_epoch."""
+    fine-tuning eval's encoder gradients and encoder step, see frozen.run_probe_epoch.  mix (keyword-only, a ..mix.MixDraw or
+    None): training iterations mix the batch with its flipped self in place (mixup / cutmix, vj_clip_mix on every view with the
+    batch's one plan; the tensors are the loader's device buffers or this function's own copies) and take the soft-target
+    cross-entropy with label smoothing (vj_soft_ce) instead of the hard one.  The training top-1 is still counted against each
+    clip's own label: under mixing it is a lower bound of what the model knows, since a mixed clip's partner label may be the
+    right answer.  Validation ignores `mix`."""
     criterion = torch.nn.CrossEntropyLoss()
+    mix = mix if training else None
 
     def features(data):
         # Load data and put on GPU
         clips = [[dij.to(device, non_blocking=True) for dij in di] for di in data[0]]
         clip_indices = [d.to(device, non_blocking=True) for d in data[2]]
         labels = data[1].to(device)
+        if mix is not None:
+            tables = mix_batch(mix, clips, data[1], device)     # (labels, labels.flip(0), lam), validated on the host
+            return encoder(clips, clip_indices), (labels, tables)
         return encoder(clips, clip_indices), labels
 
+    def soft_loss_and_top1(outputs, labels, tables):
+        # the same arithmetic as below with the soft-target loss, whose kernel also gives the soft-max of each view
+        views = outputs if attend_across_segments else [ost for ov in outputs for ost in ov]
+        results = [SoftTargetCrossEntropy.apply(classifier(o), *tables, mix.label_smoothing, True) for o in views]
+        loss = sum([ls for ls, _ in results]) / len(results)
+        with torch.no_grad():
+            probs = sum([p for _, p in results]) / len(results)
+            return loss, 100. * probs.max(dim=1).indices.eq(labels).sum() / len(labels)
+
     def loss_and_top1(outputs, labels):
+        if mix is not None:
+            return soft_loss_and_top1(outputs, *labels)
         # the prediction is the arg-max of the soft-max averaged over every view
         if attend_across_segments:
             outputs = [classifier(o) for o in outputs]

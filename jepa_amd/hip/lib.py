@@ -72,6 +72,8 @@ SIGNATURES = {
     "vj_add_pos_frames": (I32, [P, P, P, I64, I64, I64, I64, I64, P]),
     "vj_drop_path_add": (I32, [P, P, P, I64, I64, I64, P]),
     "vj_drop_path_scale": (I32, [P, P, P, I64, I64, I64, P]),
+    "vj_clip_mix": (I32, [P, P, P, I64, I64, I64, I64, P]),
+    "vj_soft_ce": (I32, [P, I64, P, P, P, F32, I64, I64, P, P, P, P]),
     "vj_layernorm_fwd": (I32, [P, P, P, P, P, P, I64, I64, F32, P]),
     "vj_layernorm_bwd_ws_bytes": (I64, [I64]),
     "vj_layernorm_bwd": (I32, [P, P, P, P, P, P, P, P, P, F32, F32, I64, I64, P, I64, P]),

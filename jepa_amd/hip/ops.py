@@ -14,6 +14,7 @@ from .lib import VjReduceSeg, VjSeg, check, load_library
 BF16 = torch.bfloat16
 F32 = torch.float32
 I64 = torch.int64
+I32 = torch.int32
 
 EPI_BF16, EPI_GELU, EPI_DGELU, EPI_F32 = 0, 1, 2, 3
 EPI_QKV = 4   # EPI_BF16 whose first N/3 output columns (the q part of a qkv projection) are multiplied by alpha before the rounding
@@ -328,6 +329,105 @@ def drop_path_scale(dx, scale, B, S, out=None, stream=None):
     D = _drop_path_args("drop_path_scale", dx, out, scale, B, S)
     check(lib.vj_drop_path_scale(_ptr(dx), _ptr(out), _ptr(scale), B, S, D, _stream(stream)), "vj_drop_path_scale")
     return out
+
+
+# ---------------------------------------------------------------- mixup / cutmix / soft-target cross-entropy
+def _host_table(t, dtype, name):
+    t = torch.as_tensor(t)
+    if t.is_cuda:
+        raise ValueError(f"{name}: a host table is expected here (it is validated on the host and then uploaded)")
+    return t.to(dtype).contiguous()
+
+
+def _checked(t, name, helper):
+    """The record a device table carries from the helper that validated its host copy before uploading it."""
+    mark = getattr(t, "_vj_checked", None)
+    if mark is None:
+        raise ValueError(f"{name}: not a table uploaded by ops.{helper} (the kernels trust these tables: they are validated on the host "
+                         "before the upload, never read back)")
+    return mark
+
+
+def mix_tables(lam, box, H, W, device):
+    """The two per-sample tables of clip_mix, validated on the host and uploaded: lam [B] -> fp32, box [B,4] = (y0, y1, x0, x1) ->
+    int32 with 0 <= y0 <= y1 <= H and 0 <= x0 <= x1 <= W in every row.  Returns the device tensors (lam, box)."""
+    lam, box = _host_table(lam, F32, "lam"), _host_table(box, I32, "box")
+    if lam.dim() != 1 or tuple(box.shape) != (lam.shape[0], 4):
+        raise ValueError(f"mix_tables: lam {tuple(lam.shape)} / box {tuple(box.shape)}: expected [B], [B,4]")
+    if not bool(torch.isfinite(lam).all()):
+        raise ValueError("mix_tables: lam must be finite")
+    y0, y1, x0, x1 = box.unbind(1)
+    if not bool(((0 <= y0) & (y0 <= y1) & (y1 <= H) & (0 <= x0) & (x0 <= x1) & (x1 <= W)).all()):
+        raise ValueError(f"mix_tables: every box needs 0 <= y0 <= y1 <= {H} and 0 <= x0 <= x1 <= {W}, got {box.tolist()}")
+    lam_d, box_d = lam.to(device, non_blocking=True), box.to(device, non_blocking=True)
+    box_d._vj_checked = (int(H), int(W))
+    return lam_d, box_d
+
+
+def clip_mix(x, lam, box, stream=None):
+    """Mixup / cutmix of a batch with its flipped self, in place (vj_clip_mix): x fp32 [B, ..., H, W]; sample i is mixed with sample
+    B-1-i under lam[i] and box[i] = (y0, y1, x0, x1): inside the box the partner's bits, outside it with lam == 1 its own bits, else
+    fmaf(lam, x_i, (1 - lam) * x_j).  lam fp32 [B], box int32 [B,4]: the device tables of mix_tables for this H, W."""
+    lib = load_library()
+    _req(x, F32, "x")
+    _req(lam, F32, "lam")
+    _req(box, I32, "box")
+    if x.dim() < 3:
+        raise ValueError(f"clip_mix: x {tuple(x.shape)}: expected [B, ..., H, W]")
+    B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    if tuple(lam.shape) != (B,) or tuple(box.shape) != (B, 4):
+        raise ValueError(f"clip_mix: lam {tuple(lam.shape)} / box {tuple(box.shape)} do not match x {tuple(x.shape)}: expected [B], [B,4]")
+    if _checked(box, "clip_mix: box", "mix_tables") != (H, W):
+        raise ValueError(f"clip_mix: box was validated for {box._vj_checked}, x has H, W = {(H, W)}")
+    P = math.prod(x.shape[1:-2])
+    check(lib.vj_clip_mix(_ptr(x), _ptr(lam), _ptr(box), B, P, H, W, _stream(stream)), "vj_clip_mix")
+    return x
+
+
+def soft_ce_tables(label_a, label_b, lam, C, device):
+    """The three per-row tables of soft_ce, validated on the host and uploaded: label_a, label_b [R] -> int32 in [0, C), lam [R] ->
+    fp32.  Returns the device tensors (label_a, label_b, lam)."""
+    a, b, lam = _host_table(label_a, I32, "label_a"), _host_table(label_b, I32, "label_b"), _host_table(lam, F32, "lam")
+    if a.dim() != 1 or b.shape != a.shape or lam.shape != a.shape:
+        raise ValueError(f"soft_ce_tables: label_a {tuple(a.shape)} / label_b {tuple(b.shape)} / lam {tuple(lam.shape)}: expected [R] each")
+    if not bool(((0 <= a) & (a < C) & (0 <= b) & (b < C)).all()):
+        raise ValueError(f"soft_ce_tables: labels must lie in [0, {C}), got {a.tolist()} / {b.tolist()}")
+    if not bool(torch.isfinite(lam).all()):
+        raise ValueError("soft_ce_tables: lam must be finite")
+    out = tuple(t.to(device, non_blocking=True) for t in (a, b, lam))
+    out[0]._vj_checked = out[1]._vj_checked = int(C)
+    return out
+
+
+def soft_ce(logits, label_a, label_b, lam, smoothing, probs=False, stream=None):
+    """Soft-target cross-entropy per row (vj_soft_ce) for the target eps / C + (1 - eps) * (lam * onehot(a) + (1 - lam) * onehot(b)):
+    logits fp32 [R,C] (rows may be strided) -> (loss [R], dlogits [R,C] = softmax - target, the soft-max [R,C] or None).
+    label_a, label_b int32 [R], lam fp32 [R]: the device tables of soft_ce_tables for this C."""
+    lib = load_library()
+    for t, dt, name in ((logits, F32, "logits"), (label_a, I32, "label_a"), (label_b, I32, "label_b"), (lam, F32, "lam")):
+        if t.dtype != dt:
+            raise TypeError(f"{name}: expected {dt}, got {t.dtype}")
+        if not t.is_cuda:
+            raise ValueError(f"{name}: must live on the GPU (jepa_amd has no CPU compute path)")
+    if logits.dim() != 2 or logits.shape[1] < 1 or (logits.shape[0] > 1 and logits.stride(0) < logits.shape[1]) or logits.stride(1) != 1:
+        raise ValueError(f"soft_ce: logits {tuple(logits.shape)} with strides {logits.stride()}: expected [R,C], C >= 1, unit column stride")
+    R, C = logits.shape
+    for t, name in ((label_a, "label_a"), (label_b, "label_b"), (lam, "lam")):
+        if tuple(t.shape) != (R,) or not t.is_contiguous():
+            raise ValueError(f"soft_ce: {name} {tuple(t.shape)}: expected a contiguous [{R}]")
+    for t, name in ((label_a, "label_a"), (label_b, "label_b")):
+        if _checked(t, "soft_ce: " + name, "soft_ce_tables") != C:
+            raise ValueError(f"soft_ce: {name} was validated for {t._vj_checked} classes, logits have {C}")
+    smoothing = float(smoothing)
+    if not 0.0 <= smoothing < 1.0:
+        raise ValueError(f"soft_ce: smoothing={smoothing} must lie in [0, 1)")
+    loss = torch.empty((R,), dtype=F32, device=logits.device)
+    dlogits = torch.empty((R, C), dtype=F32, device=logits.device)
+    p = torch.empty((R, C), dtype=F32, device=logits.device) if probs else None
+    ld = logits.stride(0) if R > 1 else max(logits.stride(0), C)
+    check(lib.vj_soft_ce(_ptr(logits), ld, _ptr(label_a), _ptr(label_b), _ptr(lam), smoothing, R, C, _ptr(loss), _ptr(dlogits), _ptr(p),
+                         _stream(stream)), "vj_soft_ce")
+    return loss, dlogits, p
 
 
 # ---------------------------------------------------------------- layernorm

@@ -35,7 +35,11 @@ with --segments segments (default 1 and 8) -- the two arms taking turns inside t
 of each, and EncoderFineTuner.step timed alone (its launches, ms, share of the iteration).  --drop-path R adds a third arm taking
 turns with the two: the same fine-tuning iteration with stochastic depth at rate R (the fine-tuning arm itself runs at rate 0), and
 times vj_drop_path_add / vj_drop_path_scale alone on the trunk's M x D rows, every sample kept, beside vj_copy_rows (ms, bytes/s).
-python tools/eval_bench.py --finetune [--segments 1 8] [--rounds 4] [--reps 3] [--drop-path 0.1]"""
+--mix adds another arm in the same rotation: the fine-tuning iteration (rate 0) with `optimization.finetune.mix` at the recipe's
+values (mixup 0.8, cutmix 1.0, prob 1, switch 0.5, label smoothing 0.1: vj_clip_mix on every segment, vj_soft_ce for the loss), and
+times vj_clip_mix alone on one segment batch [4,3,16,224,224] (a mixup plan, which moves every byte, and a cutmix plan with a box of
+half the side) beside vj_copy_rows on the same bytes, and vj_soft_ce at R = 4, C in {400, 1000}.
+python tools/eval_bench.py --finetune [--segments 1 8] [--rounds 4] [--reps 3] [--drop-path 0.1] [--mix]"""
 import argparse
 import json
 import os
@@ -443,7 +447,40 @@ def bench_drop_path_kernels(M, D, B, reps=20):
     return dict(rows=M, cols=D, samples=B, **res)
 
 
-def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400, drop_path=None):
+MIX_RECIPE = dict(mixup_alpha=0.8, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5, label_smoothing=0.1, seed=0)
+
+
+def bench_mix_kernels(B=4, T=16, res=224, reps=20):
+    """vj_clip_mix alone on one segment batch [B,3,T,res,res] -- a mixup plan (every byte is read and written once) and a cutmix
+    plan with a centred box of half the side (a quarter of the bytes) -- beside vj_copy_rows on the bytes of the batch (read and
+    written once each as well); vj_soft_ce with the soft-max output at R = B rows of 400 and 1000 classes."""
+    from jepa_amd.hip import ops
+    dev = "cuda"
+    x = torch.randn(B, 3, T, res, res, device=dev)
+    nbytes = x.numel() * 4
+    D = 1024
+    M = nbytes // (2 * D)
+    src, dst = torch.randn(M, D, device=dev).to(torch.bfloat16), torch.empty(M, D, device=dev, dtype=torch.bfloat16)
+    q = res // 4
+    mixup = ops.mix_tables([0.5] * B, [[0, 0, 0, 0]] * B, res, res, dev)
+    cutmix = ops.mix_tables([1.0] * B, [[q, 3 * q, q, 3 * q]] * B, res, res, dev)
+    t_mixup = timed(lambda: ops.clip_mix(x, *mixup), reps)
+    t_cutmix = timed(lambda: ops.clip_mix(x, *cutmix), reps)
+    t_copy = timed(lambda: ops.copy_rows(src, dst, 1, M, 0, M, 0, M, D), reps)
+    res_ = dict(shape=list(x.shape), mbytes=round(nbytes / 1e6, 1),
+                clip_mix_mixup=dict(ms=round(t_mixup, 4), tb_per_s=round(2 * nbytes / (t_mixup * 1e-3) / 1e12, 3)),
+                clip_mix_cutmix_quarter=dict(ms=round(t_cutmix, 4), tb_per_s=round(2 * (nbytes // 4) / (t_cutmix * 1e-3) / 1e12, 3)),
+                copy_rows=dict(ms=round(t_copy, 4), tb_per_s=round(2 * M * D * 2 / (t_copy * 1e-3) / 1e12, 3)))
+    for C in (400, 1000):
+        z = torch.randn(B, C, device=dev)
+        labels = torch.randint(0, C, (B,))
+        tables = ops.soft_ce_tables(labels, labels.flip(0), [0.5] * B, C, dev)
+        res_[f"soft_ce_C{C}_ms"] = round(timed(lambda: ops.soft_ce(z, *tables, 0.1, probs=True), reps), 4)
+    return res_
+
+
+def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400, drop_path=None, mix=False):
+    from jepa_amd.evals.mix import MixDraw
     import statistics
     from jepa_amd.engine.finetune import EncoderFineTuner
     dev = "cuda"
@@ -472,17 +509,20 @@ def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400,
     def step(optimizer, grad_scale):
         tuner.step(optimizer.param_groups[0]['lr'], 0.05, grad_scale=grad_scale)
 
-    def finetune_at(rate):
+    def finetune_at(rate, mix=None):
         def run():
             enc_t.model.set_drop_path_rate(rate)
             run_one_epoch(dev, True, enc_t, clf_t, scaler_t, opt_t, sched_t, wd_t, [train], False, 1, S, True,
-                          features_grad=True, after_update=step)
+                          features_grad=True, after_update=step, mix=mix)
         return run
 
     arms = {"frozen": lambda: run_one_epoch(dev, True, enc_f, clf_f, scaler_f, opt_f, sched_f, wd_f, [train], False, 1, S, True),
             "finetune": finetune_at(0.0)}
     if drop_path:
         arms["finetune_drop"] = finetune_at(drop_path)
+    if mix:
+        # (the clips are mixed in place iteration after iteration: convex combinations and swaps, they stay what they were in scale)
+        arms["finetune_mix"] = finetune_at(0.0, MixDraw(num_classes=C, **MIX_RECIPE))
     torch.cuda.synchronize()
     resident = torch.cuda.memory_allocated() - base
     peak = {}
@@ -511,6 +551,13 @@ def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400,
                     drop_minus_rate0_ms=round(mean["finetune_drop"] - mean["finetune"], 2),
                     peak_mem_gib_finetune_drop_iteration=peak["finetune_drop"],
                     drop_path_kernels=bench_drop_path_kernels(S * B * enc_t.model.num_patches, enc_t.embed_dim, S * B))
+    if mix:
+        d = ms["finetune_mix"]
+        drop.update(mix=MIX_RECIPE, finetune_mix_ms_rounds=[round(v, 2) for v in d],
+                    finetune_mix_iteration_ms=round(mean["finetune_mix"], 2), finetune_mix_ms_spread=round(max(d) - min(d), 2),
+                    mix_minus_plain_ms_rounds=[round(a - b, 2) for a, b in zip(d, ms["finetune"])],
+                    mix_minus_plain_ms=round(mean["finetune_mix"] - mean["finetune"], 2),
+                    peak_mem_gib_finetune_mix_iteration=peak["finetune_mix"], mix_kernels=bench_mix_kernels(B=B, res=res))
     t_step = [timed(lambda: tuner.step(1e-4, 0.05), 10) for _ in range(3)]
     t_refresh = timed(tuner.arena.refresh_transposed, 10)
     upd = statistics.mean(t_step)
@@ -531,6 +578,7 @@ def main():
     ap.add_argument("--finetune", action="store_true", help="one fine-tuning iteration against the frozen iteration (ViT-L/16, batch 4)")
     ap.add_argument("--segments", nargs="*", type=int, default=[1, 8])
     ap.add_argument("--drop-path", type=float, default=None, help="with --finetune: a third arm, fine-tuning with stochastic depth at this rate")
+    ap.add_argument("--mix", action="store_true", help="with --finetune: another arm, fine-tuning with mixup / cutmix / label smoothing")
     ap.add_argument("--uint8", action="store_true", help="the video eval's input edge: fp32 views + .to(device) against uint8 frames + prefetch")
     ap.add_argument("--frames", action="store_true", help="FrameAggregation on the ViT-L/16 image model instead of the video eval")
     ap.add_argument("--image", action="store_true", help="the image-classification eval instead of the video one")
@@ -542,7 +590,7 @@ def main():
     a = ap.parse_args()
     if a.finetune:
         for S in a.segments:
-            print(json.dumps(bench_finetune(a.reps, a.rounds, S, drop_path=a.drop_path)), flush=True)
+            print(json.dumps(bench_finetune(a.reps, a.rounds, S, drop_path=a.drop_path, mix=a.mix)), flush=True)
             torch.cuda.empty_cache()
         return
     if a.uint8:
