@@ -27,6 +27,85 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert lib.vj_abi_version() == 1
 
 
+def _prototypes():
+    """name -> (return type, [parameter types]) as C type strings, parsed out of include/vjepa_hip.h: comments, preprocessor lines,
+    struct typedefs, enums and the remaining typedefs are stripped first; every statement that is left must be a prototype."""
+    text = open(os.path.join(ROOT, "include", "vjepa_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^\s*#.*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{', " ", text)
+    text = re.sub(r"\b(?:typedef\s+struct\s+\w+|enum)\s*\{.*?\}\s*\w*\s*;", " ", text, flags=re.S)
+    text = re.sub(r"\btypedef\b[^;{}]*;", " ", text)
+    protos = {}
+    for stmt in (s.strip() for s in text.split(";")):
+        if stmt in ("", "}"):       # "}" closes extern "C"
+            continue
+        m = re.fullmatch(r"([\w\s\*]+?)\s*\b(vj_\w+)\s*\(([^()]*)\)", stmt, flags=re.S)
+        assert m, f"not a prototype: {stmt!r}"
+        ret, name, params = m.groups()
+        assert name not in protos, f"{name} declared twice"
+        params = [] if params.strip() in ("", "void") else [p.strip() for p in params.split(",")]
+        types = []
+        for p in params:
+            pm = re.fullmatch(r"(.*?[\s\*])(\w+)\s*(\[\s*\])?", p, flags=re.S)    # type, name, optional []
+            assert pm, f"{name}: parameter {p!r}"
+            types.append(pm.group(1).strip() + ("*" if pm.group(3) else ""))
+        protos[name] = (" ".join(ret.split()), types)
+    return protos
+
+
+_POINTER_TYPEDEFS = {"vj_stream_t", "vj_comm_t", "vj_layer_cb_t"}
+_C_SCALARS = {"int64_t": "int64", "int": "int", "float": "float", "double": "double", "void": "void"}
+
+
+def _c_class(ctype):
+    t = " ".join(re.sub(r"\bconst\b", " ", ctype).split())
+    if "*" in t or t in _POINTER_TYPEDEFS:
+        return "pointer"
+    assert t in _C_SCALARS, f"C type {ctype!r} has no class"
+    return _C_SCALARS[t]
+
+
+def _ctypes_class(t):
+    import ctypes
+    if t is None:
+        return "void"
+    scalars = {ctypes.c_int64: "int64", ctypes.c_int: "int", ctypes.c_float: "float", ctypes.c_double: "double"}
+    if t in scalars:
+        return scalars[t]
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, (ctypes._Pointer, ctypes._CFuncPtr)):
+        return "pointer"
+    raise AssertionError(f"ctypes type {t!r} has no class")
+
+
+def test_signatures_match_the_header_type_by_type():
+    """SIGNATURES against the prototypes of include/vjepa_hip.h: the same names, and per name the same return class and the same
+    class for every parameter (pointer / int64 / int / float / double) -- an int bound as c_int64 or a float bound as c_double
+    would pass the by-name test above and corrupt arguments at run time."""
+    from jepa_amd.hip import lib as L
+    protos = _prototypes()
+    assert set(protos) == set(L.SIGNATURES), sorted(set(protos) ^ set(L.SIGNATURES))
+    assert sorted(protos) == _declared()
+    wrong = []
+    for name, (ret, params) in sorted(protos.items()):
+        res, args = L.SIGNATURES[name]
+        want = [_c_class(ret)] + [_c_class(p) for p in params]
+        have = [_ctypes_class(res)] + [_ctypes_class(a) for a in args]
+        if want != have:
+            wrong.append(f"{name}: header {want}, SIGNATURES {have}")
+    assert not wrong, "\n".join(wrong)
+
+
+def test_type_classes_tell_the_widths_apart():
+    """The classifier itself: the mistakes it exists for land in different classes."""
+    import ctypes
+    assert _ctypes_class(ctypes.c_int) != _ctypes_class(ctypes.c_int64)
+    assert _ctypes_class(ctypes.c_float) != _ctypes_class(ctypes.c_double)
+    assert _c_class("const int64_t*") == _c_class("vj_stream_t") == _c_class("vj_comm_t*") == "pointer"
+    assert [_c_class(t) for t in ("int64_t", "int", "float", "double", "const char*")] == ["int64", "int", "float", "double", "pointer"]
+
+
 def test_no_cpu_fallback_in_ops():
     """The product path must fail loudly on CPU tensors instead of silently computing somewhere else."""
     import pytest
