@@ -125,6 +125,12 @@ int vj_image_pack(const float* images, void* out_bf16, const int64_t* idx, int64
  * out[b, t*S+s, :] = bf16(float(y[b,s,:]) + pos[t*S+s, :]).  Same fp32 add and single rounding as vj_add_pos. */
 int vj_add_pos_bcast(const void* y_bf16, const float* pos, void* out_bf16, int64_t B, int64_t S, int64_t Gt, int64_t D,
                      vj_stream_t stream);
+/* The adjoint of vj_add_pos_bcast (the backward of the still-image front end; the position table is a constant): the gradient of
+ * the S distinct patch embeddings is the sum of the gradients of the Gt temporal slices.  dx bf16 [B,Gt*S,D] -> dy bf16 [B,S,D]:
+ * dy[b,s,:] = bf16( sum_{t<Gt} float(dx[b, t*S+s, :]) ), accumulated in fp32 from slice 0 in ascending t with plain adds (a fixed
+ * order: the result is reproducible bit for bit) and rounded once; Gt == 1 copies the bits.  D % 8 == 0, dx and dy 16-byte
+ * aligned and distinct.  B*S*Gt == 0 launches nothing. */
+int vj_slice_sum(const void* dx_bf16, void* dy_bf16, int64_t B, int64_t S, int64_t Gt, int64_t D, vj_stream_t stream);
 /* nn.functional.interpolate(pos_embed [1,D,Nt,Nh,Nw], scale_factor=(T/N_t, H/N_h, W/N_w), mode='trilinear')
  *                                                                         src/models/vision_transformer.py:221-227
  * on the token-major table: fp32 [Nt,Nh,Nw,D] -> [To,Ho,Wo,D].  align_corners=False with the scale factors given (the

@@ -1,5 +1,6 @@
 // Token-row movers and position adds of the V-JEPA step, one wave per row: bit-exact mask gather / scatter and row-window copy,
-// positional-embedding add (plain, broadcast over the temporal slices of a still image, per frame) and predictor token assembly.
+// positional-embedding add (plain, broadcast over the temporal slices of a still image and that broadcast's adjoint, the sum over
+// the slices; per frame) and predictor token assembly.
 //
 // Reference behaviour restated (never copied):
 //   apply_masks                      src/masks/utils.py:11-23      (gather of kept token rows)
@@ -178,6 +179,71 @@ extern "C" int vj_add_pos_bcast(const void* y_bf16, const float* pos, void* out_
   hipLaunchKernelGGL(add_pos_bcast_kernel, dim3(rows_grid(rows)), dim3(256), 0, stream, (const bf16_t*)y_bf16, pos,
                      (bf16_t*)out_bf16, rows, S, Gt, (int)D);
   VJ_LAUNCH_CHECK("vj_add_pos_bcast");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// slice_sum: dy[b,s,:] = bf16(sum_{t<Gt} float(dx[b, t*S + s, :])), the adjoint of add_pos_bcast: the gradient of the S distinct
+// patch embeddings of a still image is the sum of the gradients of the Gt temporal slices they were fanned out to.  fp32, slice 0
+// first and then one plain add per slice in ascending t (no tree: the order is part of the contract), one rounding at the end;
+// Gt == 1 moves the bits.  One wave per output row (b,s), one lane per 16-byte chunk of it; the lane's Gt source chunks sit S*D
+// elements apart and are fetched four at a time before they are added, so four 16-byte loads are in flight per lane.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void slice_sum_kernel(const bf16_t* __restrict__ dx, bf16_t* __restrict__ dy, int64_t rows,
+                                                        int64_t S, int64_t Gt, int64_t D) {
+  const int lane = wave_lane();
+  const int64_t wave = wave_row(), nw = wave_row_step();
+  const int64_t step = S * D;
+  for (int64_t r = wave; r < rows; r += nw) {
+    const int64_t b = r / S, s = r - b * S;
+    const bf16_t* sp = dx + (b * Gt * S + s) * D;   // slice 0 of this row; slice t is t * step further on
+    bf16_t* op = dy + r * D;
+    for (int64_t c = (int64_t)lane * 8; c < D; c += 512) {
+      const u32x4_t w0 = *(const u32x4_t*)(sp + c);
+      if (Gt == 1) {   // (kernel argument: uniform)
+        *(u32x4_t*)(op + c) = w0;
+        continue;
+      }
+      float acc[8], v[8];
+      unpack8(w0, acc);
+      int64_t t = 1;
+      for (; t + 4 <= Gt; t += 4) {
+        u32x4_t w[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) w[i] = *(const u32x4_t*)(sp + (t + i) * step + c);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          unpack8(w[i], v);
+#pragma unroll
+          for (int j = 0; j < 8; j++) acc[j] = acc[j] + v[j];
+        }
+      }
+      for (; t < Gt; t++) {
+        load8(sp + t * step + c, v);
+#pragma unroll
+        for (int j = 0; j < 8; j++) acc[j] = acc[j] + v[j];
+      }
+      store8(op + c, acc);
+    }
+  }
+}
+
+extern "C" int vj_slice_sum(const void* dx_bf16, void* dy_bf16, int64_t B, int64_t S, int64_t Gt, int64_t D, hipStream_t stream) {
+  VJ_CHECK_ARG(B >= 0 && S >= 0 && Gt >= 0 && D > 0, "vj_slice_sum: bad dims B=%ld S=%ld Gt=%ld D=%ld", (long)B, (long)S, (long)Gt,
+               (long)D);
+  VJ_CHECK_ARG(D % 8 == 0, "vj_slice_sum: D=%ld must be a multiple of 8", (long)D);
+  const int64_t rows = B * S;
+  if (rows * Gt == 0) return 0;
+  int64_t n = 0;
+  VJ_CHECK_ARG(!__builtin_mul_overflow(B, S, &n) && !__builtin_mul_overflow(n, Gt, &n) && !__builtin_mul_overflow(n, D, &n) &&
+                   n <= INT64_MAX / 2,
+               "vj_slice_sum: B=%ld S=%ld Gt=%ld D=%ld overflows the element offsets", (long)B, (long)S, (long)Gt, (long)D);
+  VJ_CHECK_ARG(dx_bf16 != nullptr && dy_bf16 != nullptr, "vj_slice_sum: null pointer");
+  VJ_CHECK_ARG(dx_bf16 != dy_bf16, "vj_slice_sum: dx and dy must differ (the sum is not done in place)");
+  VJ_CHECK_ARG(((uintptr_t)dx_bf16 | (uintptr_t)dy_bf16) % 16 == 0, "vj_slice_sum: dx and dy must be 16-byte aligned");
+  hipLaunchKernelGGL(slice_sum_kernel, dim3(rows_grid(rows)), dim3(256), 0, stream, (const bf16_t*)dx_bf16, (bf16_t*)dy_bf16, rows,
+                     S, Gt, D);
+  VJ_LAUNCH_CHECK("vj_slice_sum");
   return 0;
 }
 

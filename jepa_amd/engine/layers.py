@@ -19,7 +19,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from ..hip import ops
+from ..hip import ops, ops_still
 from ..hip.lib import get_option
 from . import chain
 from .streams import (SideStream, _INDEP_LOG, independent_stream, low_priority_stream, side_stream,  # noqa: F401  (re-exported)
@@ -366,7 +366,9 @@ def encoder_forward(ew: EncoderW, clips, masks: Optional[List[torch.Tensor]], sa
     the input's token grid (gt, gh, gw), N = gt*gh*gw; the grid is taken from the input (and, for a still image, gt from N).
     Returns (out [sum_i B*K_i, D] bf16, segs, saved).  With final_norm=False the last residual stream is returned
     (the target path fuses the final norm into vj_target_rows).  gates: see _wait_gates.  drop: stochastic depth, None or one
-    (s_attn, s_mlp) entry per block (block_forward); the scales are per clip, [B], shared by every mask segment.
+    (s_attn, s_mlp) entry per block (block_forward); the scales are per clip, [B], shared by every mask segment -- per image for a
+    video encoder's still images, whose repeated clip is one sequence like any clip.  save: keep what encoder_backward needs; the
+    saved tuple ends with the still front end's fan-out (B, cells, gt), None for every other input.
 
     Still images: only the gh*gw distinct tubelets are packed and embedded (vj_image_pack, a GEMM on B*gh*gw rows) and the gt
     temporal slices differ only in their position rows (vj_add_pos_bcast); with masks, the kept rows are packed one by one
@@ -378,8 +380,8 @@ def encoder_forward(ew: EncoderW, clips, masks: Optional[List[torch.Tensor]], sa
     pos = ew.pos if pos is None else pos
     N = pos.shape[0]
     if drop:
-        if ew.image or clips.dim() != 5:
-            raise ValueError("encoder_forward: stochastic depth goes with a video encoder's clips [B,3,T,H,W]")
+        if ew.image or clips.dim() not in (4, 5):
+            raise ValueError("encoder_forward: stochastic depth goes with a video encoder's clips [B,3,T,H,W] or still images [B,3,H,W]")
         _check_drop(drop, len(ew.blocks), clips.shape[0], ws_tag)
     if ew.image:
         if save:
@@ -391,8 +393,6 @@ def encoder_forward(ew: EncoderW, clips, masks: Optional[List[torch.Tensor]], sa
         still = clips.dim() == 4
         cells = (clips.shape[-2] // ew.patch_size) * (clips.shape[-1] // ew.patch_size)
         if still:
-            if save:
-                raise ValueError("encoder_forward: still-image input is a frozen (save=False) path")
             if cells == 0 or N % cells != 0:
                 raise ValueError(f"encoder_forward: position table of {N} rows does not fit images of {cells} cells")
         elif (clips.shape[2] // ew.tubelet) * cells != N:
@@ -415,15 +415,22 @@ def encoder_forward(ew: EncoderW, clips, masks: Optional[List[torch.Tensor]], sa
     if not final_norm:
         return x, segs, None
     out, mean, rstd = ops.layernorm_fwd(x, ew.norm.g, ew.norm.b, LN_EPS, save_stats=save)
-    saved = (tok, saved_blocks, x, mean, rstd, drop or None) if save else None
+    fan = (B, cells, N // cells) if still and masks is None else None
+    saved = (tok, saved_blocks, x, mean, rstd, drop or None, fan) if save else None
     return out, segs, saved
 
 
 def encoder_backward(dout, saved, ew: EncoderW, segs, alpha: float, on_layer_done=None, beta: float = 0.0,
                      ws_tag="bwd_tmp"):
     """dout [M, D] bf16: gradient of the encoder output rows.  Pixels need no gradient.  Parameter gradients are written
-    as alpha * grad + beta * old (beta = 1 accumulates micro-batches)."""
-    tok, saved_blocks, xl, mean, rstd, drop = saved
+    as alpha * grad + beta * old (beta = 1 accumulates micro-batches).
+
+    Still images without masks (the saved fan-out (B, cells, gt)): the forward embedded B*cells packed rows and fanned them out
+    over the gt temporal slices (vj_add_pos_bcast), so the gradient of those embeddings is the sum of the trunk's input gradient
+    over the slices (vj_slice_sum, rounded to bf16 once) and the patch embedding's weight and bias gradients come from B*cells
+    rows.  Still images with masks packed their kept rows one by one: tok has one row per gradient row, as a clip's, and the
+    plain backward below is already right."""
+    tok, saved_blocks, xl, mean, rstd, drop, fan = saved
     # dx of the final norm's backward is the dY of the last block's fc2: with the transpose-free route its bias gradient (the
     # column sums of dx) comes out of this pass like every other block's (round 4: no stand-alone column sum left in a trunk)
     # (not for a last block whose MLP branch is scaled by stochastic depth: its fc2's dY is the scaled copy of dx)
@@ -431,6 +438,8 @@ def encoder_backward(dout, saved, ew: EncoderW, segs, alpha: float, on_layer_don
     dx = ops.layernorm_bwd(dout, xl, ew.norm.g, mean, rstd, ew.norm.gg, ew.norm.gb, alpha=alpha, accumulate=beta != 0.0,
                            dxsum=last_gb)
     dx = _trunk_backward(dx, saved_blocks, ew, segs, "enc", alpha, beta, on_layer_done, ws_tag, last_gb is not None, drop=drop)
+    if fan is not None:
+        dx = ops_still.slice_sum(dx, *fan)
     _linear_backward(dx, tok, ew.patch, alpha, need_dx=False, beta=beta)
     side_stream(dout.device).join()
     if on_layer_done is not None:

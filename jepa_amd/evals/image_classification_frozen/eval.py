@@ -23,6 +23,8 @@ arithmetic, CSV columns, checkpoint dictionary and folder / file names.  Differe
   - one encoder call never holds more images than keep fc1's output below 2^31 elements, counted from the tokens the actual input
     makes (frozen_features).
   - `main` returns a small record of the run (per-epoch accuracies, per-iteration training loss and learning rate).
+  - `main(finetune=...)` and run_one_epoch's `features_grad`, `after_update` and `mix` are what ..image_classification_finetune.eval
+    brings to train the encoder with the probe; without them this eval runs what it always ran.
 """
 import pprint
 
@@ -36,6 +38,7 @@ from ..frozen import classifier_state_dict, load_checkpoint  # noqa: F401  (the 
 from ..frozen import distributed as _distributed
 from ..frozen import (chunked_call, freeze, max_clips_per_call, parse_config, run_probe_epoch, setup_run, synthetic_dataloader,
                       train_single_probe, widest_activation)
+from ..mix import SoftTargetCrossEntropy, mix_batch
 from ..multihead import run as run_multihead
 from ..video_classification_frozen.eval import init_model, init_opt, load_pretrained  # noqa: F401
 
@@ -48,21 +51,27 @@ torch.manual_seed(_GLOBAL_SEED)
 pp = pprint.PrettyPrinter(indent=4)
 
 
-def main(args_eval, resume_preempt=False):
+def main(args_eval, resume_preempt=False, finetune=None):
+    """finetune (extension): None (the frozen eval), or what ..image_classification_finetune.eval brings to train the encoder with
+    the probe on this eval's data, probe, schedules and checkpoints: `folder_name`; check(cfg), called before anything is set up;
+    attach(cfg, run, encoder) -> (epoch keywords of the training run_one_epoch, extra_state, restore_extra of
+    frozen.train_single_probe), called on the encoder instead of freezing it."""
     cfg = parse_config(args_eval, resume_preempt)
     multihead = cfg.multihead
+    if finetune is not None:
+        finetune.check(cfg)
 
     # -- DATA
     args_data = args_eval.get('data')
     dataset_name = args_data.get('dataset_name')
-    num_classes = args_data.get('num_classes')
+    num_classes = cfg.num_classes = args_data.get('num_classes')
     root_path = args_data.get('root_path', None)
     image_folder = args_data.get('image_folder', None)
     resolution = args_data.get('resolution', 224)
     synthetic_length = args_data.get('synthetic_length', None)
     num_workers = args_data.get('num_workers', 0)
 
-    run = setup_run(cfg, 'image_classification_frozen/', csv=multihead is None)
+    run = setup_run(cfg, 'image_classification_frozen/' if finetune is None else finetune.folder_name, csv=multihead is None)
     device = run.device
 
     # -- pretrained encoder (frozen): the video ViT, or the image ViT with frames_per_clip == 1; both are fed [B,C,H,W] directly
@@ -70,7 +79,11 @@ def main(args_eval, resume_preempt=False):
                          patch_size=cfg.patch_size, frames_per_clip=cfg.frames_per_clip, tubelet_size=cfg.tubelet_size,
                          uniform_power=cfg.uniform_power, checkpoint_key=cfg.checkpoint_key, use_SiLU=cfg.use_SiLU,
                          tight_SiLU=cfg.tight_SiLU, use_sdpa=cfg.use_sdpa)
-    freeze(encoder)
+    tune, extra = {}, {}
+    if finetune is None:
+        freeze(encoder)
+    else:
+        tune, extra['extra_state'], extra['restore_extra'] = finetune.attach(cfg, run, encoder)
 
     # -- init classifier
     if multihead is None:
@@ -98,25 +111,41 @@ def main(args_eval, resume_preempt=False):
 
     def train_epoch(**probe):
         return run_one_epoch(device=device, training=True, encoder=encoder, data_loader=train_loader,
-                             use_bfloat16=cfg.use_bfloat16, **probe)
+                             use_bfloat16=cfg.use_bfloat16, **probe, **tune)
 
     def val_epoch(**probe):
         return run_one_epoch(device=device, training=False, encoder=encoder, data_loader=val_loader,
                              use_bfloat16=cfg.use_bfloat16, **probe)
 
-    return train_single_probe(cfg, run, classifier, opt, ipe, train_epoch, val_epoch)
+    return train_single_probe(cfg, run, classifier, opt, ipe, train_epoch, val_epoch, **extra)
 
 
 def frozen_features(encoder, imgs):
     """encoder(imgs) in calls small enough that the widest activation of one call (token rows x fc1's width) stays below 2^31
     elements.  The rows are counted from the tokens THIS input makes -- the model's num_patches describes its native size only --
     and the calls' outputs are joined by the bit-exact row copy."""
+    cap = images_per_call(encoder, imgs)
+    return encoder(imgs) if cap is None else chunked_call(encoder, imgs, cap)
+
+
+def images_per_call(encoder, imgs):
+    """The images of `imgs` one encoder call may hold (frozen_features), None for an encoder that does not describe its grid."""
     if not (hasattr(encoder, 'patch_size') and hasattr(encoder, 'tubelet_size') and hasattr(encoder, 'num_frames')):
-        return encoder(imgs)
+        return None
     frames = encoder.num_frames if imgs.dim() == 4 else imgs.shape[2]
     depth = frames // encoder.tubelet_size if getattr(encoder, 'is_video', True) else 1     # the image model has no tubelets
     tokens = depth * (imgs.shape[-2] // encoder.patch_size) * (imgs.shape[-1] // encoder.patch_size)
-    return chunked_call(encoder, imgs, max_clips_per_call(widest_activation(encoder), max(tokens, 1)))
+    return max_clips_per_call(widest_activation(encoder), max(tokens, 1))
+
+
+def trainable_features(encoder, imgs):
+    """encoder(imgs) with a backward recorded: ONE encoder call for the batch (a second call would overwrite the gradient slots the
+    first one's backward writes)."""
+    cap = images_per_call(encoder, imgs)
+    if cap is not None and imgs.shape[0] > cap:
+        raise ValueError(f"{imgs.shape[0]} images with gradients enabled need one encoder call, and one call takes at most "
+                         f"max_clips_per_call = {cap} images of this size (fc1's output stays below 2^31 elements); use a smaller batch")
+    return encoder(imgs)
 
 
 def _image_features(encoder, data, device):
@@ -125,24 +154,41 @@ def _image_features(encoder, data, device):
 
 
 def run_one_epoch(device, training, encoder, classifier, scaler, optimizer, scheduler, wd_scheduler, data_loader, use_bfloat16,
-                  *, history=None):
+                  *, history=None, features_grad=False, after_update=None, mix=None):
     """The reference's epoch (eval.py:262-317), same parameters in the same order.  history (keyword-only, optional list):
-    (learning rate, loss) of each training iteration."""
+    (learning rate, loss) of each training iteration.  features_grad / after_update (keyword-only, off by default): the
+    fine-tuning eval's encoder gradients and encoder step, see frozen.run_probe_epoch; the batch then goes through one encoder call
+    (trainable_features).  mix (keyword-only, a ..mix.MixDraw or None): training iterations mix the batch with its flipped self in
+    place (mixup / cutmix: vj_clip_mix on the images viewed as one-frame clips, three planes per image) and take the soft-target
+    cross-entropy with label smoothing (vj_soft_ce) instead of the hard one; the training top-1 is still counted against each
+    image's own label.  Validation ignores `mix`."""
     criterion = torch.nn.CrossEntropyLoss()
+    mix = mix if training else None
+    encode = trainable_features if training and features_grad else frozen_features
 
     def features(data):
         imgs, labels = data[0].to(device, non_blocking=True), data[1].to(device)
-        return frozen_features(encoder, imgs), labels
+        if mix is not None:
+            if imgs.shape[-1] % 4:
+                raise ValueError(f"mix: images of width {imgs.shape[-1]}: vj_clip_mix moves four pixels at a time, the width must be "
+                                 "a multiple of 4")
+            tables = mix_batch(mix, [[imgs.unsqueeze(2)]], data[1], device)     # (labels, labels.flip(0), lam), validated on the host
+            return encode(encoder, imgs), (labels, tables)
+        return encode(encoder, imgs), labels
 
     def loss_and_top1(outputs, labels):
         # the prediction is the arg-max of the logits
         outputs = classifier(outputs)
-        loss = criterion(outputs, labels)
+        if mix is not None:
+            labels, tables = labels
+            loss, _ = SoftTargetCrossEntropy.apply(outputs, *tables, mix.label_smoothing, False)
+        else:
+            loss = criterion(outputs, labels)
         with torch.no_grad():
             return loss, 100. * outputs.max(dim=1).indices.eq(labels).sum() / len(labels)
 
     return run_probe_epoch(training, classifier, scaler, optimizer, scheduler, wd_scheduler, data_loader, use_bfloat16, features,
-                           loss_and_top1, history=history)
+                           loss_and_top1, history=history, features_grad=features_grad, after_update=after_update)
 
 
 def make_dataloader(dataset_name, root_path, image_folder, batch_size, world_size, rank, resolution=224, training=False,

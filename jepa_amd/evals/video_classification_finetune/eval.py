@@ -39,8 +39,9 @@ key an iteration issues the launches it issued before.  The data, the probe, its
 the frozen eval's load_pretrained(checkpoint_key='encoder') reads) and `encoder_opt` (Adam moments and step count in
 torch.optim.AdamW's format).
 
-Limits, all raising: one rank; video encoders at their native clip size (image encoders and off-native sizes are frozen-path
-features); the lone probe (`optimization.multihead_kwargs` is the frozen evals'); every clip of a batch in one encoder call;
+Limits, all raising: one rank; video encoders at their native clip size (image encoders are frozen-path features, and so are still
+images and off-native sizes unless the module opted in -- VisionTransformer.train_on_any_input, which this eval leaves off and
+..image_classification_finetune.eval switches on); the lone probe (`optimization.multihead_kwargs` is the frozen evals'); every clip of a batch in one encoder call;
 0 <= drop_path < 1; `mix`: alphas >= 0, probabilities in [0, 1], 0 <= label_smoothing < 1, unknown sub-keys raise.
 """
 from types import SimpleNamespace
@@ -104,9 +105,14 @@ def parse_finetune(args_opt):
 
 
 class _FineTune:
-    """What frozen_eval.main takes to leave the encoder trainable."""
+    """What frozen_eval.main takes to leave the encoder trainable.  The image fine-tuning eval (..image_classification_finetune.eval)
+    derives from it: `folder_name` and `encoder_of` are what differs."""
 
     folder_name = FOLDER_NAME
+
+    def encoder_of(self, module):
+        """The VisionTransformer inside what the frozen eval calls: here the ClipAggregation's model."""
+        return module.model
 
     def check(self, cfg):
         if cfg.multihead is not None:
@@ -117,7 +123,7 @@ class _FineTune:
         self.ft = parse_finetune(cfg.args_opt)
 
     def attach(self, cfg, run, aggregation):
-        ft, encoder = self.ft, aggregation.model
+        ft, encoder = self.ft, self.encoder_of(aggregation)
         encoder.set_drop_path_rate(ft.drop_path)
         aggregation.train()     # training iterations drop in training mode only; validation runs under no_grad and drops nothing
         tuner = EncoderFineTuner(encoder, layer_decay=ft.layer_decay, world_size=run.world_size)

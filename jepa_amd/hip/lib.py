@@ -67,6 +67,7 @@ SIGNATURES = {
     "vj_clip_randaug_ws_bytes": (I64, [I64, I64, I64]),
     "vj_image_pack": (I32, [P, P, P, I64, I64, I64, I64, I64, I64, I64, P]),
     "vj_add_pos_bcast": (I32, [P, P, P, I64, I64, I64, I64, P]),
+    "vj_slice_sum": (I32, [P, P, I64, I64, I64, I64, P]),
     "vj_pos_interp3d": (I32, [P, P, I64, I64, I64, I64, F64, F64, F64, I64, I64, I64, P]),
     "vj_pos_interp2d_bicubic": (I32, [P, P, I64, I64, I64, F64, I64, I64, P]),
     "vj_add_pos_frames": (I32, [P, P, P, I64, I64, I64, I64, I64, P]),

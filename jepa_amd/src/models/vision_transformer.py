@@ -8,7 +8,8 @@
 `forward` is differentiable (one autograd node per call whose backward is the hand-written layer chain; with `drop_path_rate` > 0
 a training-mode forward that records a backward applies stochastic depth, see set_drop_path_rate), but
 the pretraining step (jepa_amd.engine.step.Trainer) bypasses autograd entirely and shares this module's
-parameters through flat arenas.
+parameters through flat arenas.  With gradients enabled the video model takes clips of its native size; still images [B,3,H,W] and
+other clip sizes are frozen / no-grad inputs unless the module opted in (train_on_any_input).
 
     img = vit_large(img_size=224, patch_size=16)       # num_frames=1: the 2-D image ViT (Conv2d patch embed, 2-D sincos table)
     out = img(images)                                  # [B, N, D] from fp32 [B,3,H,W]; frozen / no-grad path only
@@ -44,6 +45,7 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         self.drop_path_generator = None     # a torch.Generator of the model's device for the draws; None: the default generator
         self.last_drop_path_scales = None   # fp32 [L, 2, B]: the scales of the latest forward that dropped anything
         self.set_drop_path_rate(drop_path_rate, depth)
+        self.any_input_trains = False       # train_on_any_input: still images and off-native sizes with gradients enabled
         self.num_features = self.embed_dim = embed_dim
         self.num_heads = num_heads
         self.out_layers = out_layers
@@ -130,7 +132,7 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         torch.rand((L, 2, B)) on the device per forward, no host synchronisation; s = floor(keep + u) / keep.  A branch whose rate is
         0 gets no scale and keeps the fused residual add.  `last_drop_path_scales` holds what the forward used."""
         self.__dict__["last_drop_path_scales"] = None
-        if not self.training or isinstance(x, list) or x.dim() != 5:
+        if not self.training or isinstance(x, list) or not self.is_video or x.dim() not in (4, 5):
             return None
         L, B = len(self.blocks), x.shape[0]
         s = self.__dict__.get("_drop_scales_next")
@@ -150,6 +152,15 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         s = torch.floor(keep + u).clamp_(max=1.0) / keep      # (the clamp: keep + u can round up to 2 at u = 1 - 2^-24)
         self.__dict__["last_drop_path_scales"] = s
         return [(s[i, 0], s[i, 1]) if self.drop_path_rates[i] > 0.0 else None for i in range(L)]
+
+    def train_on_any_input(self, flag=True):
+        """Opt in (per module, default off, not part of the state dict) to recording a backward for every input the frozen path
+        takes: still images [B,C,H,W], whose backward sums the gradient over the temporal slices (vj_slice_sum) and takes the
+        patch embedding's gradients from the B*gh*gw distinct rows, and clips of another size than the model's, whose interpolated
+        position table is a constant.  Off, such inputs raise while gradients are enabled, as they always have.  The image model
+        (num_frames=1) keeps raising either way."""
+        self.any_input_trains = bool(flag)
+        return self
 
     def no_weight_decay(self):
         return {}
@@ -264,11 +275,12 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
 
     def _pos_table(self, x):
         """None at the native clip size (the arena's table is used), otherwise the fp32 [N', D] table of x's token grid.  Still
-        images and off-native sizes are frozen-path features: with gradients enabled they raise."""
+        images and off-native sizes are frozen-path features: with gradients enabled they raise unless the module opted in
+        (train_on_any_input)."""
         T, H, W = self._input_size(x)
         if not self.is_video:
             return self._image_pos_table(H, W)
-        if x.dim() == 4 or not (H == self.input_size and W == self.input_size and T == self.num_frames):
+        if not self.any_input_trains and (x.dim() == 4 or not (H == self.input_size and W == self.input_size and T == self.num_frames)):
             self._frozen_only("still-image [B,C,H,W] and off-native-size inputs run", "; with gradients enabled the encoder runs "
                               "at its native clip size, as the pretraining step does")
         pos = self.interpolate_pos_encoding(x, self.pos_embed)
@@ -321,7 +333,7 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         if masks is not None:
             masks = [m.contiguous() for m in masks]
         if self._needs_grad():
-            return hipmodule.run_with_autograd(self, _enc_fwd, _enc_bwd, (x, masks, self._drop_path_entries(x)))
+            return hipmodule.run_with_autograd(self, _enc_fwd, _enc_bwd, (x, masks, self._drop_path_entries(x), pos))
         # inference: one C call per trunk (no saved activations, a private workspace) and, because nothing else shares the
         # GPU with this stream, the two-workgroups-per-CU GEMM (gemm4w.hip; see DESIGN.md section 6 for why training does not)
         ew = self._hip_views(train=False)
@@ -339,8 +351,8 @@ INFER_GEMM_FLAGS = 0x100
 
 
 def _enc_fwd(module, ew, args, diff):
-    x, masks, drop = args
-    out, segs, saved = encoder_forward(ew, x, masks, save=True, drop=drop)
+    x, masks, drop, pos = args     # pos: None (the arena's table) or the interpolated table of x's grid, a constant
+    out, segs, saved = encoder_forward(ew, x, masks, save=True, drop=drop, pos=pos)
     return out, segs, (saved, segs)
 
 

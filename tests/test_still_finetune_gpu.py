@@ -1,0 +1,346 @@
+"""GPU: fine-tuning the video encoder on still images (VisionTransformer.train_on_any_input, engine.layers' still branch of
+encoder_backward over vj_slice_sum, evals/image_classification_finetune).
+
+The micro encoder of tests/test_still_input_gpu.py (64 x 64, 8 frames, tubelet 2: Gt = 4 temporal slices of S = 16 cells) under an
+EncoderFineTuner with the probe of tests/test_finetune_gpu.py.  The still route is held against the materialised repeated clip on
+the same module -- the forward and every gradient behind the patch embedding bit for bit, the two patch-embed gradients by rel-L2
+(the routes differ there by one bf16 rounding of the summed gradient and by the GEMM's summation order: 32 rows instead of 128)
+-- and against the fp32 CPU oracle run on the repeated clip.
+
+Bounds.  Each is min(2 x the value measured on MI355X, BOUND of tests/test_finetune_gpu.py); the measured values stand beside
+their names below."""
+import csv
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tests.golden_util import MICRO, load_micro, micro_weights, rel_l2  # noqa: E402
+from tests.test_finetune_gpu import BOUND, C, _classifier, _encoder, _micro_vit, _oracle_grads  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+T, GT, S = MICRO["frames"], MICRO["frames"] // MICRO["tubelet"], (MICRO["crop"] // MICRO["patch"]) ** 2
+PATCH = ("patch_embed.proj.weight", "patch_embed.proj.bias")
+
+# measured on MI355X, rel-L2 of the still route's gradient against the repeated-clip route's: patch_embed.proj.weight, .bias
+MEASURED_ROUTES = {"patch_embed.proj.weight": 1.706e-3, "patch_embed.proj.bias": 6.682e-4}      # bounds 3.41e-3, 1.34e-3
+# measured on MI355X, worst rel-L2 of an encoder gradient against the fp32 CPU oracle: still images at the native size (there the
+# patch embedding's two stand at 5.99e-3 and 6.34e-3; twice the worst exceeds BOUND, which therefore is the bound), and the
+# off-native 8 x 96 x 96 clip (bound 1.21e-2)
+MEASURED_ORACLE = (8.90e-3, "blocks.1.norm1.bias")
+MEASURED_OFF_NATIVE = (6.06e-3, "patch_embed.proj.weight")
+
+
+def _bound(measured):
+    return min(2 * measured, BOUND)
+
+
+def _repeat(images, frames=T):
+    return images.unsqueeze(2).repeat(1, 1, frames, 1, 1).contiguous()
+
+
+def _images(B=2, seed=3, size=MICRO["crop"]):
+    return torch.randn(B, 3, size, size, generator=torch.Generator().manual_seed(seed))
+
+
+@pytest.fixture(scope="module")
+def setup():
+    """One encoder under a tuner with the opt-in on, one classifier, the fixture's weights for the oracle, and the oracle's loss
+    and gradients for the repeated clip of the shared images (computed once)."""
+    from jepa_amd.engine.finetune import EncoderFineTuner
+    enc_w = micro_weights(load_micro())[0]
+    enc = _encoder()
+    tuner = EncoderFineTuner(enc, layer_decay=0.75)
+    enc.train_on_any_input()
+    clf = _classifier()
+    images, labels = _images(), torch.tensor([3, 7])
+    ref = _oracle_grads(enc_w, clf, [_repeat(images)], labels, True)
+    return enc_w, enc, tuner, clf, images, labels, ref
+
+
+def _grads(tuner):
+    return {n: tuner.arena.grad(n).clone() for n in tuner.arena.slots}
+
+
+def _backward(enc, clf, x, labels):
+    clf.zero_grad(set_to_none=True)
+    out = enc(x.to(DEV))
+    loss = F.cross_entropy(clf(out), labels.to(DEV))
+    loss.backward()
+    return out.detach(), float(loss.detach())
+
+
+def test_opt_in(setup):
+    _, enc, _, _, images, _, _ = setup
+    x = images.to(DEV)
+    assert _micro_vit().any_input_trains is False          # off by default
+    enc.train_on_any_input(False)
+    try:
+        with pytest.raises(NotImplementedError, match="frozen"):
+            enc(x)
+        with pytest.raises(NotImplementedError, match="frozen"):
+            enc(torch.randn(1, 3, 8, 96, 96, device=DEV))
+    finally:
+        enc.train_on_any_input()
+    assert "any_input_trains" not in enc.state_dict()
+    out = enc(x)
+    assert out.requires_grad and out.shape == (2, GT * S, MICRO["embed_dim"])
+    assert torch.equal(out, enc(_repeat(images).to(DEV)))
+    with torch.no_grad():
+        assert torch.equal(out, enc(x))
+
+
+def test_gradients_equal_the_repeated_clips(setup):
+    """Behind the patch embedding both routes run the same kernels on the same bits, so every gradient but the patch embedding's two
+    is bit-identical -- provided the repeated route agrees with itself, which is asserted first (no launch of the backward adds in
+    an order that depends on timing: the split-K weight gradients reduce their partials in a fixed order)."""
+    _, enc, tuner, clf, images, labels, _ = setup
+    rep = _repeat(images)
+    out_a, loss_a = _backward(enc, clf, rep, labels)
+    g_a = _grads(tuner)
+    _backward(enc, clf, rep, labels)
+    g_b = _grads(tuner)
+    for n in g_a:
+        assert torch.equal(g_a[n], g_b[n]), ("the repeated-clip route does not agree with itself", n)
+    tuner.arena.G.fill_(7.0)                     # a gradient nobody writes shows
+    out_s, loss_s = _backward(enc, clf, images, labels)
+    g_s = _grads(tuner)
+    assert torch.equal(out_s, out_a) and loss_s == loss_a
+    for n in g_a:
+        if n in PATCH:
+            e = rel_l2(g_s[n].float().cpu(), g_a[n].float().cpu())
+            print(f"still route against repeated-clip route: {n} rel-L2 {e:.3e}")
+            assert e < _bound(MEASURED_ROUTES[n]), (n, e)
+        else:
+            assert torch.equal(g_s[n], g_a[n]), n
+    assert set(PATCH) <= set(g_a)
+
+
+def test_masked_still_images_equal_the_masked_repeated_clip(setup):
+    """With masks the kept rows are packed one by one and the plain backward runs: everything is bit-identical, patch embed included."""
+    _, enc, tuner, _, images, _, _ = setup
+    g = torch.Generator().manual_seed(9)
+    masks = [torch.stack([torch.randperm(GT * S, generator=g)[:K].sort().values for _ in range(2)]).to(DEV) for K in (20, 37)]
+    cg = torch.Generator().manual_seed(4)
+    cots = [torch.randn(2, K, MICRO["embed_dim"], generator=cg).to(torch.bfloat16).to(DEV) for K in (20, 37)]
+    res = []
+    for x in (_repeat(images), images):
+        tuner.arena.G.fill_(7.0)
+        outs = enc.forward_masks(x.to(DEV), masks)
+        assert [tuple(o.shape) for o in outs] == [tuple(c.shape) for c in cots] and all(o.requires_grad for o in outs)
+        torch.autograd.backward(outs, cots)
+        res.append(([o.detach() for o in outs], _grads(tuner)))
+    for o_r, o_s in zip(res[0][0], res[1][0]):
+        assert torch.equal(o_r, o_s)
+    for n in res[0][1]:
+        assert torch.equal(res[0][1][n], res[1][1][n]), n
+
+
+def test_still_gradients_against_the_oracle(setup):
+    _, enc, tuner, clf, images, labels, (ref_loss, ref) = setup
+    _, loss = _backward(enc, clf, images, labels)
+    print(f"still images: loss {loss:.6f} oracle {ref_loss:.6f}")
+    assert abs(loss - ref_loss) < 2e-2 * abs(ref_loss)
+    errs = {n: rel_l2(tuner.arena.grad(n).float().cpu(), g) for n, g in ref.items()}
+    assert set(errs) == set(tuner.arena.slots)
+    worst = max((e, n) for n, e in errs.items())
+    print("still images: worst encoder gradient rel-L2 against the oracle", worst,
+          {n: "%.3e" % errs[n] for n in PATCH})
+    assert worst[0] < _bound(MEASURED_ORACLE[0]), worst
+
+
+def test_off_native_clip_with_gradients_against_the_oracle(setup):
+    """[1,3,8,96,96] through the 64 x 64 model: the position table is the trilinear interpolation the reference would use, a
+    constant of the backward; the oracle gets F.interpolate's table as its pos_embed."""
+    enc_w, enc, tuner, clf, _, _, _ = setup
+    clip = torch.randn(1, 3, 8, 96, 96, generator=torch.Generator().manual_seed(21))
+    label = torch.tensor([5])
+    D, g = MICRO["embed_dim"], MICRO["crop"] // MICRO["patch"]
+    table = enc_w["pos_embed"].reshape(1, GT, g, g, D).permute(0, 4, 1, 2, 3)
+    table = F.interpolate(table, scale_factor=(1.0, 96 / 64, 96 / 64), mode='trilinear')
+    w = dict(enc_w, pos_embed=table.permute(0, 2, 3, 4, 1).reshape(1, -1, D).contiguous())
+    assert w["pos_embed"].shape == (1, GT * 36, D)
+    ref_loss, ref = _oracle_grads(w, clf, [clip], label, True)
+    tuner.arena.G.fill_(7.0)
+    out, loss = _backward(enc, clf, clip, label)
+    assert out.shape == (1, GT * 36, D)
+    print(f"off-native clip: loss {loss:.6f} oracle {ref_loss:.6f}")
+    assert abs(loss - ref_loss) < 2e-2 * abs(ref_loss)
+    errs = {n: rel_l2(tuner.arena.grad(n).float().cpu(), gr) for n, gr in ref.items()}
+    assert set(errs) == set(tuner.arena.slots)
+    worst = max((e, n) for n, e in errs.items())
+    print("off-native clip: worst encoder gradient rel-L2 against the oracle", worst)
+    assert worst[0] < _bound(MEASURED_OFF_NATIVE[0]), worst
+
+
+def test_stochastic_depth_on_still_images(setup):
+    """Explicit scales, one per image: image 0 loses every branch, so its rows are the final LayerNorm of its embedded tokens (the
+    branch-free computation, here from the kernels on the repeated clip); the whole output and every gradient behind the patch
+    embedding equal the repeated clip's under the same scales; the gradients are finite."""
+    from jepa_amd.hip import ops
+    _, enc, tuner, clf, images, labels, _ = setup
+    L = MICRO["depth"]
+    scales = torch.full((L, 2, 2), 1.0 / 0.9)
+    scales[:, :, 0] = 0.0
+    scales = scales.to(DEV)
+    enc.train()
+    res = []
+    for x in (_repeat(images), images):
+        enc.set_drop_path_scales(scales)
+        tuner.arena.G.fill_(7.0)
+        out, _ = _backward(enc, clf, x, labels)
+        assert torch.equal(enc.last_drop_path_scales, scales)
+        res.append((out, _grads(tuner)))
+    (out_r, g_r), (out_s, g_s) = res
+    assert torch.equal(out_s, out_r)
+    ew = enc._hip_views(train=True)
+    x0 = ops.gemm_nt(ops.tubelet_pack(_repeat(images).to(DEV), MICRO["tubelet"], MICRO["patch"]), ew.patch.w, bias=ew.patch.b)
+    ops.add_pos(x0, ew.pos, 2, GT * S)
+    ln = ops.layernorm_fwd(x0, ew.norm.g, ew.norm.b, 1e-6, save_stats=False)[0].view(2, GT * S, -1)
+    assert torch.equal(out_s[0].view(torch.int16), ln[0].view(torch.int16))
+    assert not torch.equal(out_s[1].view(torch.int16), ln[1].view(torch.int16))
+    for n in g_s:
+        assert bool(torch.isfinite(g_s[n]).all()), n
+        if n not in PATCH:
+            assert torch.equal(g_s[n], g_r[n]), n
+    # scales that do not fit the batch of images are refused
+    enc.set_drop_path_scales(torch.ones(L, 2, 3, device=DEV))
+    try:
+        with pytest.raises(ValueError, match="do not fit a batch of 2"):
+            enc(images.to(DEV))
+    finally:
+        enc.set_drop_path_scales(None)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the eval
+def _eval_cfg(folder, **finetune):
+    """The micro encoder on synthetic 64 x 64 images: 4 items, batches of 2, two epochs of two iterations."""
+    return {
+        'pretrain': {'model_name': 'vit_micro', 'checkpoint_key': 'target_encoder', 'patch_size': 16, 'folder': folder,
+                     'checkpoint': 'micro-latest.pth.tar', 'write_tag': 'micro', 'tubelet_size': 2, 'frames_per_clip': 8,
+                     'uniform_power': True, 'use_sdpa': True, 'use_silu': False, 'tight_silu': False},
+        'data': {'dataset_name': 'synthetic', 'num_classes': C, 'root_path': None, 'image_folder': None, 'resolution': 64,
+                 'synthetic_length': 4},
+        'optimization': {'batch_size': 2, 'num_epochs': 2, 'weight_decay': 0.01, 'start_lr': 0.002, 'lr': 0.01, 'final_lr': 0.0,
+                         'warmup': 0.25, 'use_bfloat16': False,
+                         'finetune': dict({'encoder_lr': 1e-3, 'layer_decay': 0.75, 'encoder_weight_decay': 0.05}, **finetune)},
+        'tag': 'micro_ft',
+    }
+
+
+def _out(folder):
+    return os.path.join(str(folder), "image_classification_finetune", "micro_ft")
+
+
+def _final_state(folder):
+    ck = torch.load(os.path.join(_out(folder), "micro-latest.pth.tar"), map_location="cpu", weights_only=False)
+    return ck, {**{"encoder." + k: v for k, v in ck["encoder"].items()}, **{"classifier." + k: v for k, v in ck["classifier"].items()}}
+
+
+@pytest.fixture
+def micro_runs(tmp_path, monkeypatch):
+    from jepa_amd.src.models import vision_transformer as vit
+    monkeypatch.setattr(vit, "vit_micro", lambda **kw: _micro_vit(), raising=False)
+    enc_w = micro_weights(load_micro())[0]
+
+    def folder(name):
+        os.makedirs(tmp_path / name, exist_ok=True)
+        torch.save({'target_encoder': {'module.backbone.' + k: v for k, v in enc_w.items()}, 'epoch': 10},
+                   tmp_path / name / 'micro-latest.pth.tar')
+        return str(tmp_path / name)
+
+    return enc_w, folder
+
+
+def test_main_trains_the_encoder_checkpoints_and_resumes(micro_runs, monkeypatch):
+    from jepa_amd.evals.image_classification_finetune import eval as FT
+    from jepa_amd.evals.image_classification_frozen import eval as E
+    enc_w, folder = micro_runs
+    assert FT.FOLDER_NAME == 'image_classification_finetune/'
+
+    # -- two uninterrupted epochs of two iterations
+    torch.manual_seed(0)
+    rec = FT.main(_eval_cfg(folder("a")))
+    hist = rec['train_history']
+    assert rec['start_epoch'] == 0 and len(hist) == 4 and all(np.isfinite(ls) for _, ls in hist)
+    rows = list(csv.reader(open(os.path.join(_out(folder("a")), "micro_r0.csv"))))
+    assert rows[0] == ["epoch", "loss", "acc"] and [r[0] for r in rows[1:]] == ["1", "2"]
+    ck, state_a = _final_state(folder("a"))
+    assert sorted(ck) == ['batch_size', 'classifier', 'encoder', 'encoder_opt', 'epoch', 'lr', 'opt', 'scaler', 'world_size']
+    assert ck['epoch'] == 2 and list(ck['encoder']) == list(_micro_vit().state_dict())
+    assert float(ck['encoder_opt']['state'][0]['step']) == 4.0
+    moved = [n for n, v in ck['encoder'].items() if not torch.equal(v, enc_w[n])]
+    assert sorted(moved) == sorted(n for n in enc_w if n != 'pos_embed')       # every trainable tensor moved, the table did not
+    # the frozen image eval reads the fine-tuned encoder back
+    loaded = E.load_pretrained(_micro_vit(), os.path.join(_out(folder("a")), "micro-latest.pth.tar"), checkpoint_key='encoder')
+    for n, v in ck['encoder'].items():
+        assert torch.equal(loaded.state_dict()[n], v), n
+    cfg = _eval_cfg(_out(folder("a")))
+    del cfg['optimization']['finetune']
+    cfg['pretrain']['checkpoint_key'] = 'encoder'
+    cfg['optimization']['num_epochs'] = 1
+    frozen = E.main(cfg)
+    assert len(frozen['train_history']) == 2 and all(np.isfinite(ls) for _, ls in frozen['train_history'])
+
+    # -- the same run again: is the loop bit-reproducible?
+    torch.manual_seed(0)
+    FT.main(_eval_cfg(folder("a2")))
+    _, state_a2 = _final_state(folder("a2"))
+    spread = {n: float((state_a[n].double() - state_a2[n].double()).abs().max()) for n in state_a}
+    reproducible = all(torch.equal(state_a[n], state_a2[n]) for n in state_a)
+    print("two uninterrupted runs bit-identical:", reproducible, "max spread", max(spread.values()))
+
+    # -- 1 + 1: preempted at the start of epoch 2 (the 3rd epoch call: a training and a validation call per epoch), then resumed
+    real, calls = E.run_one_epoch, []
+
+    def preempt(*a, **kw):
+        calls.append(1)
+        if len(calls) == 3:
+            raise KeyboardInterrupt("preempted")
+        return real(*a, **kw)
+
+    monkeypatch.setattr(E, "run_one_epoch", preempt)
+    torch.manual_seed(0)
+    with pytest.raises(KeyboardInterrupt):
+        FT.main(_eval_cfg(folder("b")))
+    monkeypatch.setattr(E, "run_one_epoch", real)
+    rec_b = FT.main(_eval_cfg(folder("b")), resume_preempt=True)
+    assert rec_b['start_epoch'] == 1 and len(rec_b['train_history']) == 2
+    assert [lr for lr, _ in rec_b['train_history']] == [lr for lr, _ in hist[2:]]
+    _, state_b = _final_state(folder("b"))
+    if reproducible:
+        assert [ls for _, ls in rec_b['train_history']] == [ls for _, ls in hist[2:]]
+        for n in state_a:
+            assert torch.equal(state_b[n], state_a[n]), n
+    else:                 # a third run may lie as far from the first as the second does, and somewhat further: 4 x their spread
+        for n in state_a:
+            d = float((state_b[n].double() - state_a[n].double()).abs().max())
+            assert d <= 4 * spread[n] + 1e-12, (n, d, spread[n])
+
+
+def test_main_with_mix_and_its_limits(micro_runs, monkeypatch):
+    from jepa_amd.evals.image_classification_finetune import eval as FT
+    from jepa_amd.evals.image_classification_frozen import eval as E
+    from jepa_amd.hip import ops
+    _, folder = micro_runs
+    names = []
+    real = ops._launch
+    monkeypatch.setattr(ops, "_launch", lambda name, *a, **kw: (names.append(name), real(name, *a, **kw))[1])
+    torch.manual_seed(0)
+    rec = FT.main(_eval_cfg(folder("mixed"), mix={'prob': 1.0, 'seed': 0}, drop_path=0.1))
+    assert len(rec['train_history']) == 4 and all(np.isfinite(ls) for _, ls in rec['train_history'])
+    assert names.count("vj_clip_mix") == 4 and names.count("vj_soft_ce") == 4       # one per training iteration, none in validation
+    assert names.count("vj_slice_sum") == 4 and "vj_drop_path_add" in names
+    # without the section and the rate: none of the three
+    del names[:]
+    FT.main(_eval_cfg(folder("plain")))
+    assert names.count("vj_slice_sum") == 4 and not {"vj_clip_mix", "vj_soft_ce", "vj_drop_path_add"} & set(names)
+    # a batch that needs a second encoder call
+    monkeypatch.setattr(E, "max_clips_per_call", lambda width, tokens: 1)
+    with pytest.raises(ValueError, match="max_clips_per_call = 1"):
+        FT.main(_eval_cfg(folder("split")))

@@ -39,7 +39,14 @@ times vj_drop_path_add / vj_drop_path_scale alone on the trunk's M x D rows, eve
 values (mixup 0.8, cutmix 1.0, prob 1, switch 0.5, label smoothing 0.1: vj_clip_mix on every segment, vj_soft_ce for the loss), and
 times vj_clip_mix alone on one segment batch [4,3,16,224,224] (a mixup plan, which moves every byte, and a cutmix plan with a box of
 half the side) beside vj_copy_rows on the same bytes, and vj_soft_ce at R = 4, C in {400, 1000}.
-python tools/eval_bench.py --finetune [--segments 1 8] [--rounds 4] [--reps 3] [--drop-path 0.1] [--mix]"""
+python tools/eval_bench.py --finetune [--segments 1 8] [--rounds 4] [--reps 3] [--drop-path 0.1] [--mix]
+
+--image --finetune: one fine-tuning iteration of the image eval (jepa_amd/evals/image_classification_finetune: batch 16, 1000 classes,
+ViT-L/16-224 and ViT-H/16-384 at 16 frames) on still images, the same iteration on the materialised repeated clip (the ATen repeat
+inside it) and the frozen iteration, the three arms taking turns inside this process in rotating order: ms and peak memory of each,
+the rows the patch-embed GEMM and its weight gradient see on either route, and vj_slice_sum alone beside vj_copy_rows moving the same
+bytes (ms, GB/s).
+python tools/eval_bench.py --image --finetune [--image-configs vitl16_in1k vith16_384_in1k] [--rounds 4] [--reps 3]"""
 import argparse
 import json
 import os
@@ -222,6 +229,105 @@ def bench_image(name, reps, rounds, B=16, frames=16):
                 train_iteration_ms=round(it_train, 2), val_iteration_ms=round(it_val, 2),
                 peak_mem_gib_forward_still=peak["still"], peak_mem_gib_forward_repeat=peak["repeat"],
                 peak_mem_gib_iterations=round((torch.cuda.max_memory_allocated() - base) / 2 ** 30, 3))
+
+
+def bench_slice_sum(B, S, Gt, D, reps=20):
+    """vj_slice_sum alone on the trunk's input gradient [B*Gt*S, D] beside vj_copy_rows moving the same number of bytes (reads plus
+    writes): ms and GB/s by the bytes each must move."""
+    from jepa_amd.hip import ops, ops_still
+    dev = "cuda"
+    dx = torch.randn(B * Gt * S, D, device=dev).to(torch.bfloat16)
+    dy = torch.empty(B * S, D, device=dev, dtype=torch.bfloat16)
+    nbytes = (dx.numel() + dy.numel()) * 2
+    M = nbytes // (2 * 2 * D)
+    src, dst = torch.randn(M, D, device=dev).to(torch.bfloat16), torch.empty(M, D, device=dev, dtype=torch.bfloat16)
+    t_sum = timed(lambda: ops_still.slice_sum(dx, B, S, Gt, out=dy), reps)
+    t_copy = timed(lambda: ops.copy_rows(src, dst, 1, M, 0, M, 0, M, D), reps)
+    return dict(shape=[B, S, Gt, D], mbytes=round(nbytes / 1e6, 1),
+                slice_sum=dict(ms=round(t_sum, 4), gb_per_s=round(nbytes / (t_sum * 1e-3) / 1e9, 1)),
+                copy_rows=dict(ms=round(t_copy, 4), gb_per_s=round(2 * M * D * 2 / (t_copy * 1e-3) / 1e9, 1)))
+
+
+def bench_image_finetune(name, reps, rounds, B=16, frames=16):
+    """One fine-tuning iteration of the image eval on still images against the same iteration on the materialised repeated clip (the
+    ATen repeat inside the iteration: the only route there was) and against the frozen iteration, the three arms taking turns inside
+    this process in rotating order; ms and peak memory of each, the rows the patch-embed GEMM and its weight gradient see, and
+    vj_slice_sum alone beside vj_copy_rows."""
+    import statistics
+    from jepa_amd.engine.finetune import EncoderFineTuner
+    from jepa_amd.evals.image_classification_frozen import eval as IE
+    model_name, res, C = IMAGE_CONFIGS[name]
+    dev = "cuda"
+    torch.manual_seed(0)
+
+    def make(trainable):
+        enc = vit.__dict__[model_name](img_size=res, patch_size=16, num_frames=frames, tubelet_size=2, uniform_power=True).to(dev)
+        tuner = None
+        if trainable:
+            tuner = EncoderFineTuner(enc, layer_decay=0.75)
+            enc.train_on_any_input()
+        else:
+            enc.eval()
+            for p in enc.parameters():
+                p.requires_grad = False
+        clf = AttentiveClassifier(embed_dim=enc.embed_dim, num_heads=enc.num_heads, depth=1, num_classes=C).to(dev)
+        return enc, tuner, clf, IE.init_opt(clf, iterations_per_epoch=1, start_lr=1e-4, ref_lr=1e-4, warmup=0, num_epochs=10 ** 6, wd=0.01)
+
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    enc_f, _, clf_f, opt_f = make(False)
+    enc_t, tuner, clf_t, opt_t = make(True)
+    images = torch.randn(B, 3, res, res, device=dev)
+    labels = torch.randint(0, C, (B,))
+
+    def step(optimizer, grad_scale):
+        tuner.step(optimizer.param_groups[0]['lr'], 0.05, grad_scale=grad_scale)
+
+    def repeated(imgs):     # a plain callable: run_one_epoch hands it the batch as it is
+        return enc_t(imgs.unsqueeze(2).repeat(1, 1, frames, 1, 1))
+
+    def iteration(encoder, clf, opt, **kw):
+        optimizer, scaler, sched, wd_sched = opt
+        return lambda: IE.run_one_epoch(dev, True, encoder, clf, scaler, optimizer, sched, wd_sched, [(images, labels)], False, **kw)
+
+    tune = dict(features_grad=True, after_update=step)
+    arms = {"still": iteration(enc_t, clf_t, opt_t, **tune), "repeat": iteration(repeated, clf_t, opt_t, **tune),
+            "frozen": iteration(enc_f, clf_f, opt_f)}
+    torch.cuda.synchronize()
+    resident = torch.cuda.memory_allocated() - base
+    for fn in arms.values():        # warm-up: code load, and what stays allocated afterwards (workspaces, scratch, the probes' .grad
+        fn()                        # tensors and Adam state) is in place before any arm's peak is taken
+    peak = {}
+    for arm, fn in arms.items():    # the peak memory of each arm's iteration on its own, above what is resident
+        torch.cuda.synchronize()
+        before = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        fn()
+        torch.cuda.synchronize()
+        peak[arm] = round((torch.cuda.max_memory_allocated() - before) / 2 ** 30, 3)
+    ms = {arm: [] for arm in arms}
+    names = list(arms)
+    for r in range(rounds):
+        order = names[r % 3:] + names[:r % 3]
+        for arm in (order if r % 2 == 0 else order[::-1]):
+            ms[arm].append(timed(arms[arm], reps))
+    mean = {arm: statistics.mean(v) for arm, v in ms.items()}
+    cells, gt = (res // 16) ** 2, frames // 2
+    out = dict(config=f"{name}_finetune", batch=B, frames=frames, rounds=rounds, reps=reps, tokens_per_image=gt * cells,
+               patch_embed_rows_still=B * cells, patch_embed_rows_repeat=B * gt * cells,
+               packed_token_mib_still=round(B * cells * 1536 * 2 / 2 ** 20, 1),
+               packed_token_mib_repeat=round(B * gt * cells * 1536 * 2 / 2 ** 20, 1),
+               repeated_clip_mib=round(B * 3 * frames * res * res * 4 / 2 ** 20, 1),
+               resident_gib_both_models=round(resident / 2 ** 30, 2))
+    for arm in arms:
+        out[f"{arm}_ms_rounds"] = [round(v, 2) for v in ms[arm]]
+        out[f"{arm}_iteration_ms"] = round(mean[arm], 2)
+        out[f"{arm}_ms_spread"] = round(max(ms[arm]) - min(ms[arm]), 2)
+        out[f"peak_mem_gib_{arm}_iteration"] = peak[arm]
+    out["still_minus_repeat_ms_rounds"] = [round(a - b, 2) for a, b in zip(ms["still"], ms["repeat"])]
+    out["still_minus_repeat_ms"] = round(mean["still"] - mean["repeat"], 2)
+    out["slice_sum_kernel"] = bench_slice_sum(B, cells, gt, enc_t.embed_dim)
+    return out
 
 
 def bench_interp():
@@ -588,6 +694,11 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--bank", type=int, default=0, help="also time the training iteration with a bank of this many probes")
     a = ap.parse_args()
+    if a.image and a.finetune:
+        for name in a.image_configs:
+            print(json.dumps(bench_image_finetune(name, a.reps, a.rounds)), flush=True)
+            torch.cuda.empty_cache()
+        return
     if a.finetune:
         for S in a.segments:
             print(json.dumps(bench_finetune(a.reps, a.rounds, S, drop_path=a.drop_path, mix=a.mix)), flush=True)
