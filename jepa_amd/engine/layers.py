@@ -14,12 +14,12 @@ Reference semantics restated (never copied):
 """
 import os
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import Any, List, NamedTuple, Optional
 
 import numpy as np
 import torch
 
-from ..hip import ops, ops_still
+from ..hip import ops
 from ..hip.lib import get_option
 from . import chain
 from .streams import (SideStream, _INDEP_LOG, independent_stream, low_priority_stream, side_stream,  # noqa: F401  (re-exported)
@@ -72,7 +72,50 @@ def _f32_mul(a: float, b: float) -> float:
     return float(np.float32(np.float32(a) * np.float32(b)))
 
 
+# =============================================================================================== saved state
+# What a forward with save=True hands its backward.  Built by keyword, read by name; opaque to everything outside this module.
+class BlockSaved(NamedTuple):
+    x: Any          # the block's input [M, D]
+    y1: Any         # norm1(x), with its row statistics
+    mean1: Any
+    rstd1: Any
+    qkv: Any
+    o: Any          # attention output, before proj
+    lses: Any       # one log-sum-exp tensor per segment
+    x1: Any         # x + attention branch
+    y2: Any         # norm2(x1), with its row statistics
+    mean2: Any
+    rstd2: Any
+    u: Any          # gelu'(fc1 pre-activation)
+    g: Any          # gelu(fc1 pre-activation), the input of fc2
+
+
+class EncoderSaved(NamedTuple):
+    tok: Any        # the packed patch rows, the patch GEMM's input
+    blocks: Any     # [BlockSaved] (each dropped as soon as its backward has run), or the C chain's TrunkCtx
+    x: Any          # the last residual stream, the final norm's input, with its row statistics
+    mean: Any
+    rstd: Any
+    drop: Any       # the forward's drop-path plan (_drop_plan)
+    fan: Any        # the still front end's fan-out (B, cells, gt); None for every other input
+
+
+class PredictorSaved(NamedTuple):
+    z: Any          # the context-encoder output rows, predictor_embed's input
+    e_shape: Any    # shape of the embedded context rows
+    segs: Any       # whole sequences: context + target rows
+    tsegs: Any      # target rows
+    blocks: Any     # as EncoderSaved.blocks
+    t: Any          # the trunk's target rows, the predictor norm's input, with its output and row statistics
+    tn: Any
+    mean: Any
+    rstd: Any
+
+
 # =============================================================================================== block
+_UNSCALED = (None, None)    # a block's entry of a drop-path plan when neither branch carries a stochastic-depth scale
+
+
 def _drop_residual(x, y, s, segs):
     """y <- x + s[b] * y in place (stochastic depth: s fp32 [B], 0 or 1 / keep per sample; vj_drop_path_add).  A clip keeps its
     scale in every segment: s is indexed by b within each Seg."""
@@ -89,13 +132,13 @@ def _drop_grad(dx, s, segs):
     return out
 
 
-def block_forward(x, bw: BlockW, segs: List[Seg], heads: int, save: bool, fold=None, drop=None):
+def block_forward(x, bw: BlockW, segs: List[Seg], heads: int, save: bool, fold=None, drop=_UNSCALED):
     """x [M, D] bf16 -> x2 [M, D]; returns (x2, saved).  fold (FoldW, only with save = False): both LayerNorms folded into the
     GEMMs that consume them -- the kernels and their order are those of vj_blocks_fwd_lnfold (bit-identical results).
-    drop (stochastic depth): None, or (s_attn, s_mlp), each None or an fp32 [B] tensor of per-sample scales.  A branch with a scale
-    leaves its last GEMM without the fused residual (the branch is rounded to bf16 once) and _drop_residual finishes it in place
-    (the sum is rounded once); a branch without one issues exactly the launches of drop = None."""
-    s_attn, s_mlp = drop if drop is not None else (None, None)
+    drop (stochastic depth): the block's entry of a drop-path plan, (s_attn, s_mlp), each None or an fp32 [B] tensor of per-sample
+    scales.  A branch with a scale leaves its last GEMM without the fused residual (the branch is rounded to bf16 once) and
+    _drop_residual finishes it in place (the sum is rounded once); a branch without one issues exactly the launches of no drop."""
+    s_attn, s_mlp = drop
     D = x.shape[1]
     hd = D // heads
     scale = hd ** -0.5
@@ -132,7 +175,8 @@ def block_forward(x, bw: BlockW, segs: List[Seg], heads: int, save: bool, fold=N
         x2 = ops.gemm_nt(g, bw.fc2.w, bias=bw.fc2.b, residual=x1)
     else:
         x2 = _drop_residual(x1, ops.gemm_nt(g, bw.fc2.w, bias=bw.fc2.b), s_mlp, segs)
-    saved = (x, y1, mean1, rstd1, qkv, o, lses, x1, y2, mean2, rstd2, u, g) if save else None
+    saved = BlockSaved(x=x, y1=y1, mean1=mean1, rstd1=rstd1, qkv=qkv, o=o, lses=lses, x1=x1, y2=y2, mean2=mean2, rstd2=rstd2, u=u,
+                       g=g) if save else None
     return x2, saved
 
 
@@ -204,46 +248,46 @@ def _linear_backward(dy, x_in, lw: LinearW, alpha: float, need_dx=True, dgelu_au
 
 
 def block_backward(dx2, saved, bw: BlockW, segs: List[Seg], heads: int, alpha: float, beta: float = 0.0,
-                   fc2_bias_done: bool = False, prev_fc2_gb=None, drop=None):
+                   fc2_bias_done: bool = False, prev_fc2_gb=None, drop=_UNSCALED):
     """With transpose-free weight gradients the bias gradients of proj and of the PREVIOUS block's fc2 are the column
     sums of the two LayerNorm backward outputs and come out of those passes (vj_layernorm_bwd_colsum); `fc2_bias_done`
-    says that this block's fc2 bias gradient was produced that way by the block above.  Same kernels, same order as
-    vj_blocks_bwd (csrc/chain.hip): bit-identical results.
+    says that this block's fc2 bias gradient was produced that way by the block above, and `prev_fc2_gb` is what this block's
+    last pass fills for the block below.  Both are final: _fc2_gb_route decided them (_trunk_backward).  Same kernels, same order
+    as vj_blocks_bwd (csrc/chain.hip): bit-identical results.
     drop = (s_attn, s_mlp) of the forward.  The dY of a scaled branch's last Linear is the scaled copy of the stream's gradient
     (_drop_grad), which feeds its dgrad, weight and bias gradient, while the LayerNorm backward below still adds the unscaled
-    gradient as dres.  That Linear's bias gradient is then NOT the column sum of a LayerNorm backward's output: a scaled MLP branch
-    ignores fc2_bias_done (and the caller passes prev_fc2_gb = None to the block above it), a scaled attention branch takes
+    gradient as dres.  That Linear's bias gradient is then NOT the column sum of a LayerNorm backward's output: for a scaled MLP
+    branch the caller passes fc2_bias_done = False (and prev_fc2_gb = None to the block above it), a scaled attention branch takes
     proj.gb from ops.colsum."""
-    s_attn, s_mlp = drop if drop is not None else (None, None)
-    x, y1, mean1, rstd1, qkv, o, lses, x1, y2, mean2, rstd2, u, g = saved
-    D = x.shape[1]
+    s_attn, s_mlp = drop
+    D = saved.x.shape[1]
     hd = D // heads
     scale = hd ** -0.5
     if _q_prescaled(D):
         scale = -scale       # the forward stored q pre-scaled (option attn_softmax = 2)
     acc = beta != 0.0
-    fuse = _tn_ok(8, 8)
+    proj_gb = bw.proj.gb if _tn_ok(8, 8) and s_attn is None else None    # the attention branch's route: a one-block fact
     defer = [] if _group_ok(bw) else None
     dfc2 = dx2 if s_mlp is None else _drop_grad(dx2, s_mlp, segs)
-    du = _linear_backward(dfc2, g, bw.fc2, alpha, dgelu_aux=u, beta=beta, bias_done=fuse and fc2_bias_done and s_mlp is None,
+    du = _linear_backward(dfc2, saved.g, bw.fc2, alpha, dgelu_aux=saved.u, beta=beta, bias_done=fc2_bias_done,
                           defer=defer)   # fc2 dgrad fused with GELU'
-    dy2 = _linear_backward(du, y2, bw.fc1, alpha, beta=beta, defer=defer)
-    dx1 = ops.layernorm_bwd(dy2, x1, bw.norm2.g, mean2, rstd2, bw.norm2.gg, bw.norm2.gb, dres=dx2, alpha=alpha,
-                            accumulate=acc, dxsum=bw.proj.gb if fuse and s_attn is None else None)
+    dy2 = _linear_backward(du, saved.y2, bw.fc1, alpha, beta=beta, defer=defer)
+    dx1 = ops.layernorm_bwd(dy2, saved.x1, bw.norm2.g, saved.mean2, saved.rstd2, bw.norm2.gg, bw.norm2.gb, dres=dx2, alpha=alpha,
+                            accumulate=acc, dxsum=proj_gb)
     dproj = dx1 if s_attn is None else _drop_grad(dx1, s_attn, segs)
-    do = _linear_backward(dproj, o, bw.proj, alpha, beta=beta, bias_done=fuse and s_attn is None, defer=defer)
-    dqkv = torch.empty_like(qkv)
-    for sg, lse in zip(segs, lses):
-        ops.attn_bwd(_rows(qkv, sg), _rows(o, sg), _rows(do, sg), lse, sg.B, sg.S, heads, hd, scale,
+    do = _linear_backward(dproj, saved.o, bw.proj, alpha, beta=beta, bias_done=proj_gb is not None, defer=defer)
+    dqkv = torch.empty_like(saved.qkv)
+    for sg, lse in zip(segs, saved.lses):
+        ops.attn_bwd(_rows(saved.qkv, sg), _rows(saved.o, sg), _rows(do, sg), lse, sg.B, sg.S, heads, hd, scale,
                      out=_rows(dqkv, sg))
     if defer is not None:
-        defer.append((dqkv, y1, bw.qkv, False))
+        defer.append((dqkv, saved.y1, bw.qkv, False))
         _wgrad_group(defer, alpha, beta)
         dy1 = ops.gemm_nt(dqkv, bw.qkv.wT)
     else:
-        dy1 = _linear_backward(dqkv, y1, bw.qkv, alpha, beta=beta)
-    return ops.layernorm_bwd(dy1, x, bw.norm1.g, mean1, rstd1, bw.norm1.gg, bw.norm1.gb, dres=dx1, alpha=alpha,
-                             accumulate=acc, dxsum=prev_fc2_gb if fuse else None)
+        dy1 = _linear_backward(dqkv, saved.y1, bw.qkv, alpha, beta=beta)
+    return ops.layernorm_bwd(dy1, saved.x, bw.norm1.g, saved.mean1, saved.rstd1, bw.norm1.gg, bw.norm1.gb, dres=dx1, alpha=alpha,
+                             accumulate=acc, dxsum=prev_fc2_gb)
 
 
 # =============================================================================================== encoder
@@ -274,9 +318,8 @@ def _chained(ws_tag) -> bool:
     return ws_tag is not None and USE_C_CHAIN
 
 
-def _scaled_mlp(drop, li) -> bool:
-    """Block li's MLP branch carries a stochastic-depth scale: its fc2 bias gradient takes no fused route."""
-    return bool(drop) and drop[li] is not None and drop[li][1] is not None
+_DROP_ON_C_CHAIN = ("stochastic depth runs on the per-kernel block chain only: the C launch chains (ws_tag) serve the Trainer, which "
+                    "has none")
 
 
 def _check_drop(drop, n_blocks, B, ws_tag):
@@ -285,8 +328,7 @@ def _check_drop(drop, n_blocks, B, ws_tag):
     if not drop:
         return
     if ws_tag is not None:
-        raise ValueError("stochastic depth runs on the per-kernel block chain only: the C launch chains (ws_tag) serve the "
-                         "Trainer, which has none")
+        raise ValueError(_DROP_ON_C_CHAIN)
     if len(drop) != n_blocks:
         raise ValueError(f"stochastic depth: {len(drop)} scale entries for {n_blocks} blocks")
     for d in drop:
@@ -295,128 +337,162 @@ def _check_drop(drop, n_blocks, B, ws_tag):
                 raise ValueError(f"stochastic depth: a scale is {s.dtype} {tuple(s.shape)}, expected float32 ({B},): one per clip")
 
 
+def _drop_plan(ew: EncoderW, clips, drop, ws_tag):
+    """The caller's stochastic-depth list, validated and normalised once per encoder call: None (no list, or an empty one), or one
+    (s_attn, s_mlp) pair per block, _UNSCALED standing for a block whose entry is None.  The scales are per clip, [B], shared by
+    every mask segment -- per image for a video encoder's still images, whose repeated clip is one sequence like any clip.  The
+    trunk walkers, block_forward, block_backward and _fc2_gb_route take this form as it is."""
+    if not drop:
+        return None
+    if ew.image or clips.dim() not in (4, 5):
+        raise ValueError("encoder_forward: stochastic depth goes with a video encoder's clips [B,3,T,H,W] or still images [B,3,H,W]")
+    _check_drop(drop, len(ew.blocks), clips.shape[0], ws_tag)
+    return [_UNSCALED if d is None else d for d in drop]
+
+
+def _fc2_gb_route(views, li, plan):
+    """The one owner of "which LayerNorm backward writes block li's fc2 bias gradient": the tensor that the LayerNorm backward
+    producing block li's fc2 dY (norm1 of block li + 1; the final norm for the last block) must fill as `dxsum`, or None when that
+    bias gradient takes the column-sum route of _wgrad instead (and for li = -1: block 0 has no block below it).  It is fc2.gb
+    when the weight gradients are transpose-free and the block's MLP branch carries no stochastic-depth scale: a scaled branch's
+    fc2 dY is the scaled copy of that dx (block_backward), not the dx whose columns the pass sums.  A wrong answer doubles the bias
+    gradient or leaves it unwritten, so nobody else decides this."""
+    if li < 0 or not _tn_ok(8, 8) or (plan is not None and plan[li][1] is not None):
+        return None
+    return views.blocks[li].fc2.gb
+
+
 def _trunk_forward(x, views, segs, save, ws_tag, gemm_flags=0, gates=None, drop=None):
     """x through every block of `views` (EncoderW / PredictorW) -> (x, saved blocks): one C call per gated range, else the
-    per-kernel Python chain.  drop: None, or one entry per block (block_forward's drop); the per-kernel chain only."""
-    _check_drop(drop, len(views.blocks), segs[0].B if segs else 0, ws_tag)
+    per-kernel Python chain.  drop: None, or a drop-path plan as _drop_plan returns it -- a plan only: a caller's raw list is
+    neither validated nor normalised here.  A plan goes with the per-kernel chain only; the guard below keeps one from being
+    dropped silently in front of the C chain."""
+    if drop is not None and ws_tag is not None:
+        raise ValueError(_DROP_ON_C_CHAIN)
     if _chained(ws_tag):
         return chain.blocks_forward(x, views, segs, save, ws_tag, LN_EPS, gemm_flags=gemm_flags, gates=gates)
     folds = None if save else getattr(views, "folds", None)
     saved_blocks = []
     for bi, bw in enumerate(views.blocks):
         x, sv = block_forward(x, bw, segs, views.heads, save, fold=None if folds is None else folds[bi],
-                              drop=drop[bi] if drop else None)
+                              drop=_UNSCALED if drop is None else drop[bi])
         saved_blocks.append(sv)
     return x, saved_blocks
 
 
-def _trunk_backward(dx, saved_blocks, views, segs, tag, alpha, beta, on_layer_done, ws_tag, last_fc2_bias_done, drop=None):
-    """The blocks of `views` in reverse, whichever chain the forward took; on_layer_done(tag, layer) after every block.
-    drop: the forward's per-block list; a block whose MLP branch is scaled gets its fc2 bias gradient from no LayerNorm backward."""
+def _trunk_backward(dx, saved_blocks, views, segs, tag, alpha, beta, on_layer_done, ws_tag, drop=None):
+    """The blocks of `views` in reverse, whichever chain the forward took; on_layer_done(tag, layer) after every block.  The caller's
+    LayerNorm backward, which produced dx, filled _fc2_gb_route(views, last block, drop).  drop: the forward's drop-path plan."""
     done = None if on_layer_done is None else (lambda li: on_layer_done(tag, li))
+    nb = len(views.blocks)
+    fc2_gb = _fc2_gb_route(views, nb - 1, drop)
     if isinstance(saved_blocks, chain.TrunkCtx):
         side = side_stream(dx.device)
         return chain.blocks_backward(dx, saved_blocks, views, alpha, side.stream.cuda_stream if side.enabled else None, done,
-                                     beta_acc=beta, tag=ws_tag, last_fc2_bias_done=last_fc2_bias_done)
-    nb = len(views.blocks)
+                                     beta_acc=beta, tag=ws_tag, last_fc2_bias_done=fc2_gb is not None)
     for li in range(nb - 1, -1, -1):
+        prev_fc2_gb = _fc2_gb_route(views, li - 1, drop)
         dx = block_backward(dx, saved_blocks[li], views.blocks[li], segs, views.heads, alpha, beta,
-                            fc2_bias_done=(li + 1 < nb or last_fc2_bias_done) and not _scaled_mlp(drop, li),
-                            prev_fc2_gb=views.blocks[li - 1].fc2.gb if li > 0 and not _scaled_mlp(drop, li - 1) else None,
-                            drop=drop[li] if drop else None)
-        saved_blocks[li] = None
+                            fc2_bias_done=fc2_gb is not None, prev_fc2_gb=prev_fc2_gb, drop=_UNSCALED if drop is None else drop[li])
+        saved_blocks[li] = None     # the block's record goes as soon as its backward has run
+        fc2_gb = prev_fc2_gb
         if done is not None:
             done(li)      # bucket launch waits on the side stream's event, not on this stream
     return dx
 
 
-def _image_model_tokens(ew: EncoderW, clips, masks, N, kdim):
-    """Patch rows of the image model's input (tok bf16 [rows, 3*p*p], segs): images [B,3,H,W], or frames given as one clip tensor
-    [B,3,T,H,W] or a list of such tensors of one frame size.  vj_tubelet_pack with tubelet 1 emits a clip's rows in (b,t,h,w) order,
-    which is frame-major: every frame becomes its own sequence of N tokens, the frames of a list following one another part by part,
-    and no [B*T,3,H,W] copy of the pixels is made.  Masks address one image's token grid and go with images only.  The shapes were
-    validated by VisionTransformer.forward / forward_frames; this only packs."""
-    parts = list(clips) if isinstance(clips, (list, tuple)) else [clips]
-    parts = [c.unsqueeze(2) if c.dim() == 4 else c for c in parts]      # a view: an image is its own one-frame clip
-    p = ew.patch_size
-    if (parts[0].shape[-2] // p) * (parts[0].shape[-1] // p) != N:     # the callers checked that the parts share one frame size
-        raise ValueError(f"encoder_forward: position table of {N} rows does not fit images of "
-                         f"{parts[0].shape[-2] // p}x{parts[0].shape[-1] // p} cells")
-    frames = [c.shape[0] * c.shape[2] for c in parts]
-    if masks is None:
+def _pack_tokens(ew: EncoderW, clips, masks, N):
+    """The front end of encoder_forward: (ew, input, masks, rows N of the position table) -> (tok bf16 [rows, kdim], segs, fan): the
+    packed patch rows, the segment table and, for a video encoder's still images without masks, the fan-out (B, cells, gt) of the
+    B*cells packed rows over the gt temporal slices (None for every other input).  All shape validation of the three input kinds is
+    here, and nothing but the packing kernels is launched.
+
+    The image model (ew.image): images [B,3,H,W], or frames given as one clip tensor [B,3,T,H,W] or a list of such tensors of one
+    frame size (VisionTransformer.forward_frames checked that they share it).  vj_tubelet_pack with tubelet 1 emits a clip's rows in
+    (b,t,h,w) order, which is frame-major: every frame becomes its own sequence of N tokens, the frames of a list following one
+    another part by part, and no [B*T,3,H,W] copy of the pixels is made.  Masks address one image's token grid and go with images
+    only.
+
+    A video encoder's clips [B,3,T,H,W]: vj_tubelet_pack, every row or the rows each mask keeps, mask after mask.
+
+    A video encoder's still images [B,3,H,W], standing for the clip that repeats each image along time (gt is taken from N): only
+    the gh*gw distinct tubelets are packed (vj_image_pack); with masks, the kept rows are packed one by one (vj_image_pack with idx)
+    and tok has one row per output row, as a clip's."""
+    p, kdim = ew.patch_size, ew.patch.w.shape[1]
+    if ew.image:
+        parts = list(clips) if isinstance(clips, (list, tuple)) else [clips]
+        parts = [c.unsqueeze(2) if c.dim() == 4 else c for c in parts]      # a view: an image is its own one-frame clip
+        if (parts[0].shape[-2] // p) * (parts[0].shape[-1] // p) != N:
+            raise ValueError(f"encoder_forward: position table of {N} rows does not fit images of "
+                             f"{parts[0].shape[-2] // p}x{parts[0].shape[-1] // p} cells")
+        if masks is not None:
+            if len(parts) != 1 or parts[0].shape[2] != 1:
+                raise ValueError("encoder_forward: masks address one image's token grid; frames [B,C,T,H,W] take none")
+            return (*_pack_masked(ops.tubelet_pack, parts[0], 1, p, masks, kdim), None)
+        frames = [c.shape[0] * c.shape[2] for c in parts]
         segs = [Seg(0, sum(frames), N)]
         if len(parts) == 1:
-            return ops.tubelet_pack(parts[0], 1, p), segs
+            return ops.tubelet_pack(parts[0], 1, p), segs, None
         tok = torch.empty((sum(frames) * N, kdim), dtype=torch.bfloat16, device=parts[0].device)
         r = 0
         for c, f in zip(parts, frames):
             ops.tubelet_pack(c, 1, p, out=tok[r:r + f * N])
             r += f * N
-        return tok, segs
-    if len(parts) != 1 or parts[0].shape[2] != 1:
-        raise ValueError("encoder_forward: masks address one image's token grid; frames [B,C,T,H,W] take none")
-    return _pack_masked(ops.tubelet_pack, parts[0], 1, p, masks, kdim)
+        return tok, segs, None
+    B, still = clips.shape[0], clips.dim() == 4
+    cells = (clips.shape[-2] // p) * (clips.shape[-1] // p)
+    if still:
+        if cells == 0 or N % cells != 0:
+            raise ValueError(f"encoder_forward: position table of {N} rows does not fit images of {cells} cells")
+    elif (clips.shape[2] // ew.tubelet) * cells != N:
+        raise ValueError(f"encoder_forward: position table of {N} rows does not fit the input's token grid "
+                         f"{clips.shape[2] // ew.tubelet}x{clips.shape[-2] // p}x{clips.shape[-1] // p}")
+    pack = ops.image_pack if still else ops.tubelet_pack
+    if masks is not None:
+        return (*_pack_masked(pack, clips, ew.tubelet, p, masks, kdim), None)
+    return pack(clips, ew.tubelet, p), [Seg(0, B, N)], (B, cells, N // cells) if still else None
+
+
+def _add_positions(x, pos, segs, masks, fan):
+    """The position rows onto the embedded tokens x.  With a fan-out (still images without masks) x holds B*cells rows and the gt
+    temporal slices differ only in their position rows: vj_add_pos_bcast writes the B*gt*cells rows of the trunk's input.  Every other
+    input has its rows already and takes vj_add_pos in place, segment by segment, through its mask's indices."""
+    if fan is not None:
+        return ops.add_pos_bcast(x, pos, *fan)
+    for i, sg in enumerate(segs):
+        ops.add_pos(_rows(x, sg), pos, sg.B, sg.S, idx=None if masks is None else masks[i])
+    return x
 
 
 def encoder_forward(ew: EncoderW, clips, masks: Optional[List[torch.Tensor]], save: bool, final_norm=True, ws_tag=None,
                     gemm_flags=0, gates=None, pos=None, drop=None):
     """clips fp32 [B,3,T,H,W], or still images [B,3,H,W] standing for the clip that repeats each image along time; for the image
-    model (ew.image) images [B,3,H,W], or frames [B,3,T,H,W] (or a list of such clips) each encoded on its own (_image_model_tokens); masks:
+    model (ew.image) images [B,3,H,W], or frames [B,3,T,H,W] (or a list of such clips) each encoded on its own (_pack_tokens); masks:
     None (all N tokens) or a list of int64 [B,K_i] index tensors.  pos (fp32 [N, D], default ew.pos): the position table of
     the input's token grid (gt, gh, gw), N = gt*gh*gw; the grid is taken from the input (and, for a still image, gt from N).
     Returns (out [sum_i B*K_i, D] bf16, segs, saved).  With final_norm=False the last residual stream is returned
     (the target path fuses the final norm into vj_target_rows).  gates: see _wait_gates.  drop: stochastic depth, None or one
-    (s_attn, s_mlp) entry per block (block_forward); the scales are per clip, [B], shared by every mask segment -- per image for a
-    video encoder's still images, whose repeated clip is one sequence like any clip.  save: keep what encoder_backward needs; the
-    saved tuple ends with the still front end's fan-out (B, cells, gt), None for every other input.
+    (s_attn, s_mlp) entry per block, each entry or scale possibly None (_drop_plan).  save: keep what encoder_backward needs, an
+    EncoderSaved whose `fan` is the still front end's fan-out (B, cells, gt), None for every other input.
 
-    Still images: only the gh*gw distinct tubelets are packed and embedded (vj_image_pack, a GEMM on B*gh*gw rows) and the gt
-    temporal slices differ only in their position rows (vj_add_pos_bcast); with masks, the kept rows are packed one by one
-    (vj_image_pack with idx) and go through the same GEMM and vj_add_pos as a clip's.  Both equal the materialised repeated
-    clip bit for bit: the packed rows hold the same bf16 pixels, the NT GEMM accumulates a row's dot product in the same K
-    order in every execution form, and the position add is the same single fp32 rounding."""
-    D = ew.patch.w.shape[0]
-    kdim = ew.patch.w.shape[1]
+    Still images: only the gh*gw distinct tubelets are packed and embedded (_pack_tokens, then a GEMM on B*gh*gw rows) and the gt
+    temporal slices differ only in their position rows (_add_positions); with masks, the kept rows are packed one by one and go
+    through the same GEMM and vj_add_pos as a clip's.  Both equal the materialised repeated clip bit for bit: the packed rows hold
+    the same bf16 pixels, the NT GEMM accumulates a row's dot product in the same K order in every execution form (DESIGN.md
+    section 5), and the position add is the same single fp32 rounding."""
     pos = ew.pos if pos is None else pos
-    N = pos.shape[0]
-    if drop:
-        if ew.image or clips.dim() not in (4, 5):
-            raise ValueError("encoder_forward: stochastic depth goes with a video encoder's clips [B,3,T,H,W] or still images [B,3,H,W]")
-        _check_drop(drop, len(ew.blocks), clips.shape[0], ws_tag)
-    if ew.image:
-        if save:
-            raise ValueError("encoder_forward: the image model is a frozen (save=False) path")
-        still = False
-        tok, segs = _image_model_tokens(ew, clips, masks, N, kdim)
-    else:
-        B = clips.shape[0]
-        still = clips.dim() == 4
-        cells = (clips.shape[-2] // ew.patch_size) * (clips.shape[-1] // ew.patch_size)
-        if still:
-            if cells == 0 or N % cells != 0:
-                raise ValueError(f"encoder_forward: position table of {N} rows does not fit images of {cells} cells")
-        elif (clips.shape[2] // ew.tubelet) * cells != N:
-            raise ValueError(f"encoder_forward: position table of {N} rows does not fit the input's token grid "
-                             f"{clips.shape[2] // ew.tubelet}x{clips.shape[-2] // ew.patch_size}x{clips.shape[-1] // ew.patch_size}")
-        pack = ops.image_pack if still else ops.tubelet_pack
-        if masks is None:
-            segs = [Seg(0, B, N)]
-            tok = pack(clips, ew.tubelet, ew.patch_size)
-        else:
-            tok, segs = _pack_masked(pack, clips, ew.tubelet, ew.patch_size, masks, kdim)
+    plan = _drop_plan(ew, clips, drop, ws_tag)
+    if ew.image and save:
+        raise ValueError("encoder_forward: the image model is a frozen (save=False) path")
+    tok, segs, fan = _pack_tokens(ew, clips, masks, pos.shape[0])     # (the packing launches go out before the gates are waited for)
     _wait_gates(gates, _chained(ws_tag))
     x = ops.gemm_nt(tok, ew.patch.w, bias=ew.patch.b, flags=(gemm_flags & 0xffff if not gemm_flags >> 16 else 0) or None)
-    if still and masks is None:
-        x = ops.add_pos_bcast(x, pos, B, cells, N // cells)
-    else:
-        for i, sg in enumerate(segs):
-            ops.add_pos(_rows(x, sg), pos, sg.B, sg.S, idx=None if masks is None else masks[i])
-    x, saved_blocks = _trunk_forward(x, ew, segs, save, ws_tag, gemm_flags, gates, drop=drop or None)
+    x = _add_positions(x, pos, segs, masks, fan)
+    x, saved_blocks = _trunk_forward(x, ew, segs, save, ws_tag, gemm_flags, gates, drop=plan)
     if not final_norm:
         return x, segs, None
     out, mean, rstd = ops.layernorm_fwd(x, ew.norm.g, ew.norm.b, LN_EPS, save_stats=save)
-    fan = (B, cells, N // cells) if still and masks is None else None
-    saved = (tok, saved_blocks, x, mean, rstd, drop or None, fan) if save else None
+    saved = EncoderSaved(tok=tok, blocks=saved_blocks, x=x, mean=mean, rstd=rstd, drop=plan, fan=fan) if save else None
     return out, segs, saved
 
 
@@ -430,17 +506,15 @@ def encoder_backward(dout, saved, ew: EncoderW, segs, alpha: float, on_layer_don
     over the slices (vj_slice_sum, rounded to bf16 once) and the patch embedding's weight and bias gradients come from B*cells
     rows.  Still images with masks packed their kept rows one by one: tok has one row per gradient row, as a clip's, and the
     plain backward below is already right."""
-    tok, saved_blocks, xl, mean, rstd, drop, fan = saved
     # dx of the final norm's backward is the dY of the last block's fc2: with the transpose-free route its bias gradient (the
     # column sums of dx) comes out of this pass like every other block's (round 4: no stand-alone column sum left in a trunk)
     # (not for a last block whose MLP branch is scaled by stochastic depth: its fc2's dY is the scaled copy of dx)
-    last_gb = ew.blocks[-1].fc2.gb if _tn_ok(8, 8) and not _scaled_mlp(drop, len(ew.blocks) - 1) else None
-    dx = ops.layernorm_bwd(dout, xl, ew.norm.g, mean, rstd, ew.norm.gg, ew.norm.gb, alpha=alpha, accumulate=beta != 0.0,
-                           dxsum=last_gb)
-    dx = _trunk_backward(dx, saved_blocks, ew, segs, "enc", alpha, beta, on_layer_done, ws_tag, last_gb is not None, drop=drop)
-    if fan is not None:
-        dx = ops_still.slice_sum(dx, *fan)
-    _linear_backward(dx, tok, ew.patch, alpha, need_dx=False, beta=beta)
+    dx = ops.layernorm_bwd(dout, saved.x, ew.norm.g, saved.mean, saved.rstd, ew.norm.gg, ew.norm.gb, alpha=alpha,
+                           accumulate=beta != 0.0, dxsum=_fc2_gb_route(ew, len(ew.blocks) - 1, saved.drop))
+    dx = _trunk_backward(dx, saved.blocks, ew, segs, "enc", alpha, beta, on_layer_done, ws_tag, drop=saved.drop)
+    if saved.fan is not None:
+        dx = ops.slice_sum(dx, *saved.fan)
+    _linear_backward(dx, saved.tok, ew.patch, alpha, need_dx=False, beta=beta)
     side_stream(dout.device).join()
     if on_layer_done is not None:
         on_layer_done("enc", -1)
@@ -472,31 +546,32 @@ def predictor_forward(pw: PredictorW, z, enc_segs: List[Seg], masks_enc, masks_p
         ops.copy_rows(_rows(x, psg), _rows(t, tsg), psg.B, psg.S, sg.S, tsg.S, 0, tsg.S, Dp)
     tn, mean, rstd = ops.layernorm_fwd(t, pw.norm.g, pw.norm.b, LN_EPS, save_stats=save)
     zhat = ops.gemm_nt(tn, pw.proj.w, bias=pw.proj.b)
-    saved = (z, e.shape, segs, tsegs, saved_blocks, t, tn, mean, rstd) if save else None
+    saved = PredictorSaved(z=z, e_shape=e.shape, segs=segs, tsegs=tsegs, blocks=saved_blocks, t=t, tn=tn, mean=mean,
+                           rstd=rstd) if save else None
     return zhat, tsegs, saved
 
 
 def predictor_backward(dzhat, saved, pw: PredictorW, enc_segs, alpha: float, on_layer_done=None, beta: float = 0.0,
                        ws_tag="bwd_tmp"):
     """dzhat [sum_i B*Kp_i, D] bf16 -> returns dz [sum_i B*Ke_i, D] bf16 (gradient of the encoder output)."""
-    z, e_shape, segs, tsegs, saved_blocks, t, tn, mean, rstd = saved
+    segs, tsegs = saved.segs, saved.tsegs
     Dp = pw.embed.w.shape[0]
     n_tok = len(pw.mask_tokens)
     acc = beta != 0.0
-    dtn = _linear_backward(dzhat, tn, pw.proj, alpha, beta=beta)
+    dtn = _linear_backward(dzhat, saved.tn, pw.proj, alpha, beta=beta)
     # the trunk's output gradient is dt on the target rows and zero on the context rows, so the last block's fc2 bias gradient
     # (column sums over ALL rows of that gradient) is the column sum of dt: it comes out of this LayerNorm backward
-    last_gb = pw.blocks[-1].fc2.gb if _tn_ok(8, 8) else None
-    dt = ops.layernorm_bwd(dtn, t, pw.norm.g, mean, rstd, pw.norm.gg, pw.norm.gb, alpha=alpha, accumulate=acc, dxsum=last_gb)
+    dt = ops.layernorm_bwd(dtn, saved.t, pw.norm.g, saved.mean, saved.rstd, pw.norm.gg, pw.norm.gb, alpha=alpha, accumulate=acc,
+                           dxsum=_fc2_gb_route(pw, len(pw.blocks) - 1, None))
     dx = torch.empty((_total_rows(segs), Dp), dtype=torch.bfloat16, device=dzhat.device)
     for sg, psg, tsg in zip(enc_segs, segs, tsegs):
         ops.copy_rows(None, _rows(dx, psg), psg.B, 0, 0, psg.S, 0, sg.S, Dp)   # context rows start at zero grad (no ATen fill on the step)
         ops.copy_rows(_rows(dt, tsg), _rows(dx, psg), psg.B, tsg.S, 0, psg.S, sg.S, tsg.S, Dp)
     if on_layer_done is not None:
         on_layer_done("pred", len(pw.blocks))
-    dx = _trunk_backward(dx, saved_blocks, pw, segs, "pred", alpha, beta, on_layer_done, ws_tag, last_gb is not None)
+    dx = _trunk_backward(dx, saved.blocks, pw, segs, "pred", alpha, beta, on_layer_done, ws_tag)
     # token assembly backward: mask-token grads = sum of the target rows; context rows flow to predictor_embed
-    de = torch.empty(e_shape, dtype=torch.bfloat16, device=dzhat.device)
+    de = torch.empty(saved.e_shape, dtype=torch.bfloat16, device=dzhat.device)
     used = set()
     for i, (sg, psg) in enumerate(zip(enc_segs, segs)):
         ti = i % n_tok
@@ -507,7 +582,7 @@ def predictor_backward(dzhat, saved, pw: PredictorW, enc_segs, alpha: float, on_
     for ti in range(n_tok):
         if ti not in used and not acc:
             pw.g_mask_tokens[ti].zero_()
-    dz = _linear_backward(de, z, pw.embed, alpha, beta=beta)
+    dz = _linear_backward(de, saved.z, pw.embed, alpha, beta=beta)
     side_stream(dzhat.device).join()
     if on_layer_done is not None:
         on_layer_done("pred", -1)

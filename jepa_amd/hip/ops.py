@@ -304,6 +304,21 @@ def add_pos_bcast(y, pos, B, S, Gt, out=None, stream=None):
     return out
 
 
+def slice_sum(dx, B, S, Gt, out=None, stream=None):
+    """out[b, s] = bf16(sum_{t<Gt} dx[b, t*S+s]) in fp32, slice 0 first and then ascending t, one rounding; dx bf16 [B*Gt*S, D] ->
+    bf16 [B*S, D].  The adjoint of add_pos_bcast: the gradient of a still image's S distinct patch embeddings."""
+    _req(dx, BF16, "dx")
+    _opt(out, BF16, "out")
+    D = dx.shape[-1]
+    if dx.numel() != B * Gt * S * D or (out is not None and out.numel() != B * S * D):
+        raise ValueError(f"slice_sum: dx {tuple(dx.shape)} / out {None if out is None else tuple(out.shape)} do not match B={B} S={S} "
+                         f"Gt={Gt}")
+    if out is None:
+        out = torch.empty((B * S, D), dtype=BF16, device=dx.device)
+    _launch("vj_slice_sum", _ptr(dx), _ptr(out), B, S, Gt, D, stream=stream)
+    return out
+
+
 def pos_interp3d(table, scale_factor, stream=None):
     """Trilinear F.interpolate(scale_factor=..., align_corners=False) of an fp32 position table [Nt,Nh,Nw,D] along its three grid
     axes -> [floor(Nt*st), floor(Nh*sh), floor(Nw*sw), D]."""

@@ -21,6 +21,7 @@ bicubically at other square sizes (vj_pos_interp2d_bicubic) and FrameAggregation
 import math
 import weakref
 from functools import partial
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -32,6 +33,16 @@ from ..utils.tensors import trunc_normal_
 from .utils.modules import Block
 from .utils.patch_embed import PatchEmbed, PatchEmbed3D
 from .utils.pos_embs import get_2d_sincos_pos_embed, get_3d_sincos_pos_embed
+
+
+class _Input(NamedTuple):
+    """What VisionTransformer._describe found an input to be."""
+    T: int          # the clip the input stands for
+    H: int
+    W: int
+    still: bool     # a video encoder's still images [B,C,H,W]
+    native: bool    # (T, H, W) is the size the model was built for: the arena's position table fits
+    drops: bool     # stochastic depth applies: a video encoder's clips and still images; never the image model
 
 
 class VisionTransformer(nn.Module, hipmodule.HipModule):
@@ -127,12 +138,13 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
             scales = scales.detach().contiguous()
         self.__dict__["_drop_scales_next"] = scales
 
-    def _drop_path_entries(self, x):
-        """The per-block (s_attn, s_mlp) list of engine.layers for a grad-recording forward of clips x, or None: nothing drops.  One
-        torch.rand((L, 2, B)) on the device per forward, no host synchronisation; s = floor(keep + u) / keep.  A branch whose rate is
-        0 gets no scale and keeps the fused residual add.  `last_drop_path_scales` holds what the forward used."""
+    def _drop_path_entries(self, x, inp):
+        """The per-block (s_attn, s_mlp) list of engine.layers for a grad-recording forward of the input x that `inp` describes, or
+        None: nothing drops.  One torch.rand((L, 2, B)) on the device per forward, no host synchronisation; s = floor(keep + u) /
+        keep.  A branch whose rate is 0 gets no scale and keeps the fused residual add.  `last_drop_path_scales` holds what the
+        forward used."""
         self.__dict__["last_drop_path_scales"] = None
-        if not self.training or isinstance(x, list) or not self.is_video or x.dim() not in (4, 5):
+        if not self.training or not inp.drops:
             return None
         L, B = len(self.blocks), x.shape[0]
         s = self.__dict__.get("_drop_scales_next")
@@ -169,29 +181,39 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         self.__dict__.pop("_pos_interp_cache", None)    # .to() / .cuda() / .float(): interpolated tables follow pos_embed
         return super()._apply(fn, *args, **kwargs)
 
-    def _input_size(self, x):
-        """(T, H, W) of the clip an input stands for: a 4-D [B,C,H,W] still image is its repetition over num_frames frames."""
-        if not self.is_video:
+    def _describe(self, x, frames=False):
+        """What kind of input x is, asked once per call (_Input): the (T, H, W) of the clip it stands for -- a video encoder's 4-D
+        [B,C,H,W] still image is its repetition over num_frames frames, an image or a frame of the image model its own one-frame
+        clip -- and whether that is the model's native size.  frames: x is the validated clip list of forward_frames."""
+        if frames:
+            T, H, W, still = 1, x[0].shape[3], x[0].shape[4], False
+        elif not self.is_video:
             if x.dim() != 4:
                 raise ValueError(f"the image model (num_frames=1) takes images [B,C,H,W], got {tuple(x.shape)}; frames of a clip "
                                  "go through FrameAggregation")
-            return 1, x.shape[2], x.shape[3]
-        if x.dim() == 4:
-            return self.num_frames, x.shape[2], x.shape[3]
-        if x.dim() != 5:
+            T, H, W, still = 1, x.shape[2], x.shape[3], False
+        elif x.dim() == 4:
+            T, H, W, still = self.num_frames, x.shape[2], x.shape[3], True
+        elif x.dim() == 5:
+            T, H, W, still = x.shape[2], x.shape[3], x.shape[4], False
+        else:
             raise ValueError(f"expected clips [B,C,T,H,W] or still images [B,C,H,W], got {tuple(x.shape)}")
-        return x.shape[2], x.shape[3], x.shape[4]
+        return _Input(T, H, W, still=still, native=(T, H, W) == (self.num_frames, self.input_size, self.input_size),
+                      drops=self.is_video)
 
     def interpolate_pos_encoding(self, x, pos_embed):
         """The position table of x's token grid (reference: vision_transformer.py:197-228): the parameter itself at the native
         size, otherwise its trilinear interpolation [1, T'*H'*W', D] in fp32 (vj_pos_interp3d), computed once per (T, H, W) and
         kept until pos_embed is reloaded or moved.  Image model (vision_transformer.py:230-246): bicubic interpolation by
         scale_factor = sqrt(npatch / N) to the square grid of x (vj_pos_interp2d_bicubic)."""
-        T, H, W = self._input_size(x)
-        if not self.is_video:
-            return self._interpolate_image(H, W, pos_embed)
-        if H == self.input_size and W == self.input_size and T == self.num_frames:
+        return self._interpolate(self._describe(x), pos_embed)
+
+    def _interpolate(self, inp, pos_embed):
+        if inp.native:
             return pos_embed
+        if not self.is_video:
+            return self._interpolate_image(inp.H, inp.W, pos_embed)
+        T, H, W = inp.T, inp.H, inp.W
         if T % self.tubelet_size or H % self.patch_size or W % self.patch_size or min(T, H, W) <= 0:
             raise ValueError(f"input of {T}x{H}x{W} is not divisible into tubelets of {self.tubelet_size}x{self.patch_size}x"
                              f"{self.patch_size}")
@@ -222,8 +244,6 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         return cache
 
     def _interpolate_image(self, H, W, pos_embed):
-        if H == self.input_size and W == self.input_size:
-            return pos_embed
         p = self.patch_size
         if H % p or W % p or min(H, W) <= 0:
             raise ValueError(f"input of {H}x{W} is not divisible into patches of {p}x{p}")
@@ -260,7 +280,7 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
 
     def forward_masks(self, x, masks):
         """All masks through one fused chain; returns a list with one [B, K_i, D] tensor per mask."""
-        out, segs = self._run(x, masks, self._pos_table(x))
+        out, segs = self._run(x, masks, self._describe(x))
         B = x.shape[0]
         return [out[s.row0:s.row0 + s.rows].view(B, s.S, self.embed_dim) for s in segs]
 
@@ -273,22 +293,16 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
             raise NotImplementedError(f"{what} on the frozen / no-grad path only (torch.no_grad() or parameters with "
                                       f"requires_grad=False){then}")
 
-    def _pos_table(self, x):
-        """None at the native clip size (the arena's table is used), otherwise the fp32 [N', D] table of x's token grid.  Still
-        images and off-native sizes are frozen-path features: with gradients enabled they raise unless the module opted in
-        (train_on_any_input)."""
-        T, H, W = self._input_size(x)
+    def _pos_table(self, inp):
+        """None at the native size (the arena's table is used), otherwise the fp32 [N', D] table of the input's token grid.  The
+        image model, and a video encoder's still images and off-native sizes, are frozen-path features: with gradients enabled
+        the image model raises, and the video encoder does unless the module opted in (train_on_any_input)."""
         if not self.is_video:
-            return self._image_pos_table(H, W)
-        if not self.any_input_trains and (x.dim() == 4 or not (H == self.input_size and W == self.input_size and T == self.num_frames)):
+            self._frozen_only("the image (num_frames=1) encoder runs")
+        elif not self.any_input_trains and (inp.still or not inp.native):
             self._frozen_only("still-image [B,C,H,W] and off-native-size inputs run", "; with gradients enabled the encoder runs "
                               "at its native clip size, as the pretraining step does")
-        pos = self.interpolate_pos_encoding(x, self.pos_embed)
-        return None if pos is self.pos_embed else pos.view(-1, self.embed_dim)
-
-    def _image_pos_table(self, H, W):
-        self._frozen_only("the image (num_frames=1) encoder runs")
-        pos = self._interpolate_image(H, W, self.pos_embed)
+        pos = self._interpolate(inp, self.pos_embed)
         return None if pos is self.pos_embed else pos.view(-1, self.embed_dim)
 
     def forward_frames(self, x):
@@ -302,7 +316,7 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         for c in parts:
             if c.dim() != 5 or c.shape[1:2] + c.shape[3:] != parts[0].shape[1:2] + parts[0].shape[3:]:    # the one shape check of the frames route
                 raise ValueError(f"forward_frames expects clips [B,C,T,H,W] of one frame size, got {[tuple(q.shape) for q in parts]}")
-        out, segs = self._run(parts if len(parts) > 1 else parts[0], None, self._image_pos_table(parts[0].shape[3], parts[0].shape[4]))
+        out, segs = self._run(parts if len(parts) > 1 else parts[0], None, self._describe(parts, frames=True))
         N, views, r = segs[0].S, [], 0
         for c in parts:
             rows = c.shape[0] * c.shape[2] * N
@@ -318,10 +332,11 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
             masks = [masks]
         if masks is not None:
             return torch.cat(self.forward_masks(x, masks), dim=0)
-        out, segs = self._run(x, None, self._pos_table(x))
+        out, segs = self._run(x, None, self._describe(x))
         return out.view(x.shape[0], segs[0].S, self.embed_dim)
 
-    def _run(self, x, masks, pos=None):
+    def _run(self, x, masks, inp):
+        pos = self._pos_table(inp)
         self.__dict__["last_drop_path_scales"] = None
         if isinstance(x, list):     # frames of the image model, clip by clip (forward_frames)
             for c in x:
@@ -333,7 +348,7 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         if masks is not None:
             masks = [m.contiguous() for m in masks]
         if self._needs_grad():
-            return hipmodule.run_with_autograd(self, _enc_fwd, _enc_bwd, (x, masks, self._drop_path_entries(x), pos))
+            return hipmodule.run_with_autograd(self, _enc_fwd, _enc_bwd, (x, masks, self._drop_path_entries(x, inp), pos))
         # inference: one C call per trunk (no saved activations, a private workspace) and, because nothing else shares the
         # GPU with this stream, the two-workgroups-per-CU GEMM (gemm4w.hip; see DESIGN.md section 6 for why training does not)
         ew = self._hip_views(train=False)
@@ -362,49 +377,37 @@ def _enc_bwd(module, ew, ctx_saved, dout):
     return None
 
 
-def vit_tiny(patch_size=16, drop_path_rate=0.0, **kwargs):
-    return VisionTransformer(patch_size=patch_size, embed_dim=192, depth=12, num_heads=3, mlp_ratio=4,
-                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), drop_path_rate=drop_path_rate, **kwargs)
-
-
-def vit_small(patch_size=16, drop_path_rate=0.0, **kwargs):
-    return VisionTransformer(patch_size=patch_size, embed_dim=384, depth=12, num_heads=6, mlp_ratio=4,
-                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), drop_path_rate=drop_path_rate, **kwargs)
-
-
-def vit_base(patch_size=16, drop_path_rate=0.0, **kwargs):
-    return VisionTransformer(patch_size=patch_size, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4,
-                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), drop_path_rate=drop_path_rate, **kwargs)
-
-
-def vit_large(patch_size=16, drop_path_rate=0.0, **kwargs):
-    return VisionTransformer(patch_size=patch_size, embed_dim=1024, depth=24, num_heads=16, mlp_ratio=4,
-                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), drop_path_rate=drop_path_rate, **kwargs)
-
-
-def vit_huge(patch_size=16, drop_path_rate=0.0, **kwargs):
-    return VisionTransformer(patch_size=patch_size, embed_dim=1280, depth=32, num_heads=16, mlp_ratio=4,
-                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), drop_path_rate=drop_path_rate, **kwargs)
-
-
-def vit_giant(patch_size=16, drop_path_rate=0.0, **kwargs):
-    return VisionTransformer(patch_size=patch_size, embed_dim=1408, depth=40, num_heads=16, mlp_ratio=48 / 11,
-                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), drop_path_rate=drop_path_rate, **kwargs)
-
-
-def vit_gigantic(patch_size=14, drop_path_rate=0.0, **kwargs):
+# name -> (embed_dim, depth, num_heads, mlp_ratio, default patch_size): the one table of the factories and of VIT_EMBED_DIMS
+VIT_SIZES = {
+    'vit_tiny': (192, 12, 3, 4, 16),
+    'vit_small': (384, 12, 6, 4, 16),
+    'vit_base': (768, 12, 12, 4, 16),
+    'vit_large': (1024, 24, 16, 4, 16),
+    'vit_huge': (1280, 32, 16, 4, 16),
+    'vit_giant': (1408, 40, 16, 48 / 11, 16),
     # the reference passes a misspelt `mpl_ratio` here (vision_transformer.py:293), so its effective mlp_ratio is
     # the default 4.0; kept for checkpoint compatibility
-    return VisionTransformer(patch_size=patch_size, embed_dim=1664, depth=48, num_heads=16, mlp_ratio=4.0,
-                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), drop_path_rate=drop_path_rate, **kwargs)
-
-
-VIT_EMBED_DIMS = {
-    'vit_tiny': 192,
-    'vit_small': 384,
-    'vit_base': 768,
-    'vit_large': 1024,
-    'vit_huge': 1280,
-    'vit_giant': 1408,
-    'vit_gigantic': 1664,
+    'vit_gigantic': (1664, 48, 16, 4.0, 14),
 }
+
+
+def _factory(name):
+    embed_dim, depth, num_heads, mlp_ratio, patch = VIT_SIZES[name]
+
+    def make(patch_size=patch, drop_path_rate=0.0, **kwargs):
+        return VisionTransformer(patch_size=patch_size, embed_dim=embed_dim, depth=depth, num_heads=num_heads, mlp_ratio=mlp_ratio,
+                                 qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), drop_path_rate=drop_path_rate, **kwargs)
+    make.__name__ = make.__qualname__ = name
+    return make
+
+
+# module-level functions: the evals look them up by name (vit.__dict__[model_name])
+vit_tiny = _factory('vit_tiny')
+vit_small = _factory('vit_small')
+vit_base = _factory('vit_base')
+vit_large = _factory('vit_large')
+vit_huge = _factory('vit_huge')
+vit_giant = _factory('vit_giant')
+vit_gigantic = _factory('vit_gigantic')
+
+VIT_EMBED_DIMS = {name: size[0] for name, size in VIT_SIZES.items()}

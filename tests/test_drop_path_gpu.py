@@ -23,7 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests import drop_path_ref_util as R  # noqa: E402
 from tests.golden_util import MICRO, load_micro, micro_weights, rel_l2  # noqa: E402
 from tests.step_util import oracle_cfg  # noqa: E402
-from tests.test_finetune_gpu import HEADS, _classifier, _clips, _eval_cfg  # noqa: E402
+from tests.finetune_util import HEADS, _classifier, _clips, _eval_cfg  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"

@@ -57,7 +57,7 @@ def test_stream_log_is_one_list():
         assert getattr(layers, name) is getattr(streams, name), name
 
 
-OPS_PUBLIC = """gather_rows scatter_rows copy_rows tubelet_pack add_pos image_pack clip_transform clip_erase add_pos_bcast pos_interp3d
+OPS_PUBLIC = """gather_rows scatter_rows copy_rows tubelet_pack add_pos image_pack clip_transform clip_erase add_pos_bcast slice_sum pos_interp3d
 pos_interp2d_bicubic add_pos_frames layernorm_fwd layernorm_bwd gemm_nt ln_rowstats ln_fold_weights gemm_nt_lnfold gemm_wgrad
 gemm_wgrad_tn_grouped gemm_wgrad_tn transpose_colsum pad64 transpose transpose_multi colsum attn_fwd attn_bwd attn_fwd_segs attn_bwd_segs
 attn_bwd_colsum gemm_dgelu_colsum reduce_segments xattn_fwd xattn_bwd pool_softmax_fwd pool_softmax_bwd pred_assemble target_rows

@@ -26,7 +26,7 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests import mix_ref_util as R  # noqa: E402
 from tests.golden_util import MICRO, load_micro, micro_weights  # noqa: E402
-from tests.test_finetune_gpu import BOUND, C, _classifier, _clips, _encoder, _eval_cfg, _micro_vit, _oracle_grads, _worst  # noqa: E402
+from tests.finetune_util import BOUND, C, _classifier, _clips, _encoder, _eval_cfg, _micro_vit, _oracle_grads, _worst  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"

@@ -81,6 +81,7 @@ ROWS = {
     "clip_erase": lambda: ops.clip_erase(f(1, 3, 1, 4, 4), i32(1, 4), f(1), i64(1)),
     "clip_randaug": lambda: ops.clip_randaug(u8(48), i64(1, 4), 1, i32(1, 1), torch.zeros(1, 1, 6, dtype=torch.float64)),
     "add_pos_bcast": lambda: ops.add_pos_bcast(b(1, 4), f(1, 4), 1, 1, 1),
+    "slice_sum": lambda: ops.slice_sum(b(1, 8), 1, 1, 1),
     "pos_interp3d": lambda: ops.pos_interp3d(f(1, 1, 1, 4), (1, 1, 1)),
     "pos_interp2d_bicubic": lambda: ops.pos_interp2d_bicubic(f(1, 1, 4), 1.0),
     "add_pos_frames": lambda: ops.add_pos_frames(b(1, 1, 4), f(1, 4), i64(1, 1), 1),

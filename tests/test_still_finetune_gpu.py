@@ -20,7 +20,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests.golden_util import MICRO, load_micro, micro_weights, rel_l2  # noqa: E402
-from tests.test_finetune_gpu import BOUND, C, _classifier, _encoder, _micro_vit, _oracle_grads  # noqa: E402
+from tests.finetune_util import BOUND, C, _classifier, _encoder, _micro_vit, _oracle_grads  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"

@@ -1,4 +1,4 @@
-"""CPU: the host side of fine-tuning on still images -- vj_slice_sum's argument checks, ops_still.slice_sum on a recorder in place
+"""CPU: the host side of fine-tuning on still images -- vj_slice_sum's argument checks, ops.slice_sum on a recorder in place
 of the library, what the image fine-tuning eval refuses before it creates a folder, the opt-in's default, and the still branch of
 engine.layers.encoder_backward on stubbed wrappers."""
 import inspect
@@ -47,32 +47,25 @@ def rec(monkeypatch):
 
 
 def test_wrapper_refuses_host_tensors_and_mismatched_shapes(rec):
-    from jepa_amd.hip import ops_still
+    from jepa_amd.hip import ops
     with pytest.raises(ValueError, match="GPU"):
-        ops_still.slice_sum(b(2 * 4 * 3, 8), 2, 3, 4)
+        ops.slice_sum(b(2 * 4 * 3, 8), 2, 3, 4)
     with pytest.raises(ValueError, match="GPU"):
-        ops_still.slice_sum(gpu(b(2 * 4 * 3, 8)), 2, 3, 4, out=b(6, 8))
+        ops.slice_sum(gpu(b(2 * 4 * 3, 8)), 2, 3, 4, out=b(6, 8))
     assert rec.launches() == []
     with pytest.raises(ValueError, match="do not match B=2 S=3 Gt=5"):
-        ops_still.slice_sum(gpu(b(2 * 4 * 3, 8)), 2, 3, 5)
+        ops.slice_sum(gpu(b(2 * 4 * 3, 8)), 2, 3, 5)
     with pytest.raises(ValueError, match="do not match"):
-        ops_still.slice_sum(gpu(b(2 * 4 * 3, 8)), 2, 3, 4, out=gpu(b(5, 8)))
+        ops.slice_sum(gpu(b(2 * 4 * 3, 8)), 2, 3, 4, out=gpu(b(5, 8)))
     with pytest.raises(TypeError):
-        ops_still.slice_sum(gpu(b(2 * 4 * 3, 8).float()), 2, 3, 4)
+        ops.slice_sum(gpu(b(2 * 4 * 3, 8).float()), 2, 3, 4)
     with pytest.raises(ValueError, match="contiguous"):
-        ops_still.slice_sum(gpu(b(2 * 4 * 3, 16))[:, :8], 2, 3, 4)
+        ops.slice_sum(gpu(b(2 * 4 * 3, 16))[:, :8], 2, 3, 4)
     assert rec.launches() == []
     dx, out = gpu(b(2 * 4 * 3, 8)), gpu(b(6, 8))
-    assert ops_still.slice_sum(dx, 2, 3, 4, out=out) is out
+    assert ops.slice_sum(dx, 2, 3, 4, out=out) is out
     (name, args), = rec.calls
     assert name == "vj_slice_sum" and (args[0].value, args[1].value) == (dx.data_ptr(), out.data_ptr()) and args[2:6] == (2, 3, 4, 8)
-
-
-def test_wrapper_has_no_pointer_spelling_or_library_of_its_own():
-    from jepa_amd.hip import ops_still
-    src = inspect.getsource(ops_still)
-    assert "data_ptr(" not in src and "load_library(" not in src
-    assert [n for n, f in vars(ops_still).items() if inspect.isfunction(f) and not n.startswith("_")] == ["slice_sum"]
 
 
 # ---------------------------------------------------------------------------------------------------------------------- the eval
@@ -174,8 +167,7 @@ def test_still_branch_of_encoder_backward(monkeypatch):
     def linear_backward(dy, x_in, lw, alpha, need_dx=True, beta=0.0, **kw):
         calls.append(("patch", tuple(dy.shape), tuple(x_in.shape), lw, need_dx, beta))
 
-    monkeypatch.setattr(layers, "ops_still", SimpleNamespace(slice_sum=slice_sum))
-    monkeypatch.setattr(layers, "ops", SimpleNamespace(layernorm_bwd=lambda dout, *a, **kw: dout))
+    monkeypatch.setattr(layers, "ops", SimpleNamespace(layernorm_bwd=lambda dout, *a, **kw: dout, slice_sum=slice_sum))
     monkeypatch.setattr(layers, "_tn_ok", lambda n, k: False)
     monkeypatch.setattr(layers, "_trunk_backward", lambda dx, *a, **kw: dx)
     monkeypatch.setattr(layers, "_linear_backward", linear_backward)
@@ -184,11 +176,11 @@ def test_still_branch_of_encoder_backward(monkeypatch):
     ew = SimpleNamespace(norm=norm, blocks=[SimpleNamespace(fc2=SimpleNamespace(gb=None))], patch="patch-embed")
     dout = torch.zeros(B * gt * cells, D, dtype=torch.bfloat16)
     tok = torch.zeros(B * cells, kdim, dtype=torch.bfloat16)
-    layers.encoder_backward(dout, (tok, [None], dout, None, None, None, (B, cells, gt)), ew, [layers.Seg(0, B, gt * cells)], alpha=1.0,
-                            beta=1.0)
+    saved = layers.EncoderSaved(tok=tok, blocks=[None], x=dout, mean=None, rstd=None, drop=None, fan=(B, cells, gt))
+    layers.encoder_backward(dout, saved, ew, [layers.Seg(0, B, gt * cells)], alpha=1.0, beta=1.0)
     assert calls == [("slice_sum", (B * gt * cells, D), (B, cells, gt)),
                      ("patch", (B * cells, D), (B * cells, kdim), "patch-embed", False, 1.0)]
     del calls[:]
     tok = torch.zeros(B * gt * cells, kdim, dtype=torch.bfloat16)
-    layers.encoder_backward(dout, (tok, [None], dout, None, None, None, None), ew, [layers.Seg(0, B, gt * cells)], alpha=1.0)
+    layers.encoder_backward(dout, saved._replace(tok=tok, fan=None), ew, [layers.Seg(0, B, gt * cells)], alpha=1.0)
     assert calls == [("patch", (B * gt * cells, D), (B * gt * cells, kdim), "patch-embed", False, 0.0)]

@@ -234,14 +234,14 @@ def bench_image(name, reps, rounds, B=16, frames=16):
 def bench_slice_sum(B, S, Gt, D, reps=20):
     """vj_slice_sum alone on the trunk's input gradient [B*Gt*S, D] beside vj_copy_rows moving the same number of bytes (reads plus
     writes): ms and GB/s by the bytes each must move."""
-    from jepa_amd.hip import ops, ops_still
+    from jepa_amd.hip import ops
     dev = "cuda"
     dx = torch.randn(B * Gt * S, D, device=dev).to(torch.bfloat16)
     dy = torch.empty(B * S, D, device=dev, dtype=torch.bfloat16)
     nbytes = (dx.numel() + dy.numel()) * 2
     M = nbytes // (2 * 2 * D)
     src, dst = torch.randn(M, D, device=dev).to(torch.bfloat16), torch.empty(M, D, device=dev, dtype=torch.bfloat16)
-    t_sum = timed(lambda: ops_still.slice_sum(dx, B, S, Gt, out=dy), reps)
+    t_sum = timed(lambda: ops.slice_sum(dx, B, S, Gt, out=dy), reps)
     t_copy = timed(lambda: ops.copy_rows(src, dst, 1, M, 0, M, 0, M, D), reps)
     return dict(shape=[B, S, Gt, D], mbytes=round(nbytes / 1e6, 1),
                 slice_sum=dict(ms=round(t_sum, 4), gb_per_s=round(nbytes / (t_sum * 1e-3) / 1e9, 1)),
