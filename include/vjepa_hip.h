@@ -110,6 +110,32 @@ int vj_clip_erase(float* clips, const int32_t* ebox, const float* noise, int64_t
 int vj_clip_randaug(uint8_t* frames, int64_t frames_bytes, const int64_t* desc, int64_t B, int64_t T, const int32_t* ops,
                     const double* args, int64_t L, void* ws, int64_t ws_bytes, vj_stream_t stream);
 int64_t vj_clip_randaug_ws_bytes(int64_t frames_bytes, int64_t B, int64_t T);
+/* The input edge of the image evals: random-resized crop (bicubic) of training, Resize (bilinear, short side) + CenterCrop of
+ * validation                                                                 evals/image_classification_frozen/eval.py:379-423
+ * as PIL does them on 8-bit RGB: Image.crop(box).resize((OW, OH), filter), an antialiased two-pass resample whose support widens
+ * with the reduction ratio, with 22-bit integer coefficients and a uint8 intermediate between the horizontal (first) and the
+ * vertical pass.  Byte for byte what PIL gives; csrc/image_resample.hip states the arithmetic.  The draws stay on the host
+ * (jepa_amd/evals/image_classification_frozen/transforms.py).
+ *   frames  the flat buffer of vj_clip_transform holding image after image, each [Hs,Ws,3] interleaved RGB; 16-byte aligned; only read
+ *   desc    int64 [B,4] = (byte offset, Hs, Ws, unused); offsets are multiples of 16
+ *   geom    int32 [B,8] = (i, j, h, w, OH, OW, wy, wx): the crop box top i, left j, height h, width w is resampled to OH x OW, and
+ *           the S x S window of that result whose corner is (wy, wx) is written -- only the window is computed.  Training: OH = OW = S,
+ *           window (0, 0); validation: the box is the image, (OH, OW) the short-side size, the window the centre crop
+ *   out     uint8 [B,S,S,3], S % 4 == 0: a buffer of one-frame clips with Hs = Ws = S at offsets b*S*S*3, which vj_clip_transform_pre
+ *           (and vj_clip_randaug) takes
+ *   filter  0 bilinear (support 1), 1 bicubic (a = -0.5, support 2)
+ *   taps_x, taps_y, rows   capacities of the workspace, maxima over the batch: taps an output index can have per axis,
+ *           int(ceil(support * max(n / m, 1))) * 2 + 1, and source rows the window's vertical taps span.  Tap loops are bounded at
+ *           run time; there is no compile-time cap on the reduction ratio
+ *   ws      workspace of vj_image_resample_ws_bytes(B, S, taps_x, taps_y, rows) bytes, 16-byte aligned: bounds and coefficient
+ *           tables and the intermediate
+ * Three launches.  Callers validate desc and geom on the host before copying them (RawImageBatch.validate); the kernels clamp every
+ * source index into the crop and write zeros for an image that leaves the buffer, whose box leaves the image, whose window leaves
+ * OH x OW or that needs more than the capacities.  B == 0 launches nothing.  B < 65536, sides below 32768. */
+int vj_image_resample(const uint8_t* frames, int64_t frames_bytes, const int64_t* desc, const int32_t* geom, uint8_t* out, int64_t B,
+                      int64_t S, int filter, int64_t taps_x, int64_t taps_y, int64_t rows, void* ws, int64_t ws_bytes,
+                      vj_stream_t stream);
+int64_t vj_image_resample_ws_bytes(int64_t B, int64_t S, int64_t taps_x, int64_t taps_y, int64_t rows);
 
 /* ---- still-image front end of the video encoder and position-table interpolation ------------------------------
  * input.unsqueeze(2).repeat(1, 1, frames_per_clip, 1, 1) + patch_embed    evals/image_classification_frozen/eval.py:452-455

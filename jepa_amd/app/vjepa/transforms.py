@@ -120,6 +120,78 @@ class RawClip:
         return self.boxes.shape[0] if self.boxes.dim() == 3 else 1
 
 
+def buffer_offsets(sizes):
+    """(byte offsets, total bytes) of buffers of `sizes` bytes laid out one after the other, each on a 16-byte boundary."""
+    offs, total = [], 0
+    for n in sizes:
+        offs.append(total)
+        total += -(-n // ALIGN) * ALIGN
+    return offs, total
+
+
+def pack_buffers(tensors):
+    """uint8 tensors -> (one flat uint8 buffer that holds them one after the other, each on a 16-byte boundary, their byte offsets):
+    the packing of RawClipBatch and of the image evals' RawImageBatch."""
+    offs, total = buffer_offsets([t.numel() for t in tensors])
+    flat = torch.zeros(total, dtype=torch.uint8)
+    for t, off in zip(tensors, offs):
+        n = t.numel()
+        flat[off:off + n] = t.reshape(-1)
+    return flat, offs
+
+
+def collate_erase(rows):
+    """(ebox int32 [R,4], noise fp32 [n], noise_off int64 [R]) of rows that carry `.ebox` and `.noise` (None: not erased)."""
+    ebox = torch.tensor([c.ebox if c.noise is not None else (0, 0, 0, 0) for c in rows], dtype=torch.int32).reshape(len(rows), 4)
+    noise_off, blocks, n = [], [], 0
+    for c in rows:
+        noise_off.append(n if c.noise is not None else 0)
+        if c.noise is not None:
+            blocks.append(c.noise.to(torch.float32).reshape(-1))
+            n += blocks[-1].numel()
+    noise = torch.cat(blocks) if blocks else torch.zeros(0, dtype=torch.float32)
+    return ebox, noise, torch.tensor(noise_off, dtype=torch.int64)
+
+
+def check_erase_tables(who, eb, nz, no, R):
+    if eb.dtype != torch.int32 or tuple(eb.shape) != (R, 4) or nz.dtype != torch.float32 or nz.dim() != 1 \
+            or no.dtype != torch.int64 or tuple(no.shape) != (R,):
+        raise ValueError(f"{who}: malformed erase tables ebox {tuple(eb.shape)} {eb.dtype}, noise {tuple(nz.shape)} "
+                         f"{nz.dtype}, noise_off {tuple(no.shape)} {no.dtype}")
+
+
+def check_constants(who, crop_size, mean, std):
+    if crop_size <= 0 or crop_size % 4 != 0:
+        raise ValueError(f"{who}: crop_size={crop_size} must be a positive multiple of 4")
+    if len(mean) != 3 or len(std) != 3 or any(s == 0 for s in std):
+        raise ValueError(f"{who}: mean / std need three values each and a non-zero std")
+
+
+def check_extents(who, f, d, T, what="clip"):
+    """Every row of desc names T frames of Hs x Ws x 3 bytes that lie inside the flat buffer f on a 16-byte boundary."""
+    off, Hs, Ws = d[:, 0], d[:, 1], d[:, 2]
+    if T <= 0 or bool((Hs <= 0).any()) or bool((Ws <= 0).any()):
+        raise ValueError(f"{who}: empty {what}")
+    if bool((off < 0).any()) or bool((off % ALIGN != 0).any()) or bool((off + T * Hs * Ws * 3 > f.numel()).any()):
+        raise ValueError(f"{who}: a {what} does not lie inside the frame buffer on a 16-byte boundary")
+
+
+def check_erase(who, eb, nz, no, T, S, what="clip"):
+    """Every erase box lies inside its S x S output and its [T,3,h,w] noise block inside the noise buffer."""
+    e64 = eb.to(torch.int64)
+    top, left, eh, ew = e64[:, 0], e64[:, 1], e64[:, 2], e64[:, 3]
+    on = eh != 0
+    bad = on & ((top < 0) | (left < 0) | (eh < 0) | (ew <= 0) | (top + eh > S) | (left + ew > S))
+    if bool(bad.any()):
+        b = int(bad.nonzero()[0])
+        raise ValueError(f"{who}: erase box {eb[b].tolist()} of {what} {b} leaves its {S}x{S} {what}")
+    bad = on & ((no < 0) | (no + T * 3 * eh * ew > nz.numel()))
+    if bool(bad.any()):
+        b = int(bad.nonzero()[0])
+        raise ValueError(f"{who}: the noise block of {what} {b} ({T}x3x{int(eh[b])}x{int(ew[b])} values at {int(no[b])}) "
+                         f"leaves the noise buffer of {nz.numel()} values")
+
+
 class RawClipBatch:
     """A collated list of RawClips, all CPU tensors:
         frames     uint8 [nbytes]   clip after clip, each [T,Hs,Ws,3], each starting on a 16-byte boundary, each ONCE
@@ -195,42 +267,22 @@ class RawClipBatch:
             raise ValueError(f"RawClipBatch: malformed tables frames {tuple(f.shape)} {f.dtype}, desc {tuple(d.shape)} "
                              f"{d.dtype}, boxes {tuple(bx.shape)} {bx.dtype}")
         eb, nz, no = self.ebox, self.noise, self.noise_off
-        if eb.dtype != torch.int32 or tuple(eb.shape) != (d.shape[0], 4) or nz.dtype != torch.float32 or nz.dim() != 1 \
-                or no.dtype != torch.int64 or tuple(no.shape) != (d.shape[0],):
-            raise ValueError(f"RawClipBatch: malformed erase tables ebox {tuple(eb.shape)} {eb.dtype}, noise {tuple(nz.shape)} "
-                             f"{nz.dtype}, noise_off {tuple(no.shape)} {no.dtype}")
-        if self.crop_size <= 0 or self.crop_size % 4 != 0:
-            raise ValueError(f"RawClipBatch: crop_size={self.crop_size} must be a positive multiple of 4")
-        if len(self.mean) != 3 or len(self.std) != 3 or any(s == 0 for s in self.std):
-            raise ValueError("RawClipBatch: mean / std need three values each and a non-zero std")
+        check_erase_tables("RawClipBatch", eb, nz, no, d.shape[0])
+        check_constants("RawClipBatch", self.crop_size, self.mean, self.std)
         if self.num_views <= 0 or d.shape[0] % self.num_views != 0:
             raise ValueError(f"RawClipBatch: {d.shape[0]} rows are not {self.num_views} views of a whole number of clips")
         if d.shape[0] == 0:
             return self
         T = bx.shape[1]
-        off, Hs, Ws = d[:, 0], d[:, 1], d[:, 2]
-        if T <= 0 or bool((Hs <= 0).any()) or bool((Ws <= 0).any()):
-            raise ValueError("RawClipBatch: empty clip")
-        if bool((off < 0).any()) or bool((off % ALIGN != 0).any()) or bool((off + T * Hs * Ws * 3 > f.numel()).any()):
-            raise ValueError("RawClipBatch: a clip does not lie inside the frame buffer on a 16-byte boundary")
+        Hs, Ws = d[:, 1], d[:, 2]
+        check_extents("RawClipBatch", f, d, T)
         b64 = bx.to(torch.int64)
         i, j, h, w = b64[..., 0], b64[..., 1], b64[..., 2], b64[..., 3]
         bad = (i < 0) | (h <= 0) | (i + h > Hs[:, None]) | (j < 0) | (w <= 0) | (j + w > Ws[:, None])
         if bool(bad.any()):
             b, t = (int(v) for v in bad.nonzero()[0])
             raise ValueError(f"RawClipBatch: box {bx[b, t].tolist()} of clip {b} frame {t} leaves its {int(Hs[b])}x{int(Ws[b])} frame")
-        e64, S = eb.to(torch.int64), self.crop_size
-        top, left, eh, ew = e64[:, 0], e64[:, 1], e64[:, 2], e64[:, 3]
-        on = eh != 0
-        bad = on & ((top < 0) | (left < 0) | (eh < 0) | (ew <= 0) | (top + eh > S) | (left + ew > S))
-        if bool(bad.any()):
-            b = int(bad.nonzero()[0])
-            raise ValueError(f"RawClipBatch: erase box {eb[b].tolist()} of clip {b} leaves its {S}x{S} clip")
-        bad = on & ((no < 0) | (no + T * 3 * eh * ew > nz.numel()))
-        if bool(bad.any()):
-            b = int(bad.nonzero()[0])
-            raise ValueError(f"RawClipBatch: the noise block of clip {b} ({T}x3x{int(eh[b])}x{int(ew[b])} values at {int(no[b])}) "
-                             f"leaves the noise buffer of {nz.numel()} values")
+        check_erase("RawClipBatch", eb, nz, no, T, self.crop_size)
         self._validate_aug()
         return self
 
@@ -258,30 +310,17 @@ def collate_raw_clips(batch, *, collate_fn_map=None):
     view-major, over ONE copy of every clip's frames."""
     first = batch[0]
     T, V = first.frames.shape[0], first.num_views
-    offs, total = [], 0
     for c in batch:
         if c.frames.shape[0] != T or tuple(c.boxes.shape[-2:]) != (T, 4) or c.num_views != V:
             raise ValueError("collate: clips of one batch must have the same number of frames and views")
         if (c.crop_size, c.mean, c.std, c.pre) != (first.crop_size, first.mean, first.std, first.pre):
             raise ValueError("collate: clips of one batch must come from one transform (crop size, mean / std, normalise-first flag)")
-        offs.append(total)
-        total += -(-c.frames.numel() // ALIGN) * ALIGN
-    flat = torch.zeros(total, dtype=torch.uint8)
-    for c, off in zip(batch, offs):
-        n = c.frames.numel()
-        flat[off:off + n] = c.frames.reshape(-1)
+    flat, offs = pack_buffers([c.frames for c in batch])
     rows = [(c, off, v) for v in range(V) for c, off in zip(batch, offs)]
     desc = torch.tensor([[off, c.frames.shape[1], c.frames.shape[2], int(c.flip)] for c, off, _ in rows],
                         dtype=torch.int64).reshape(len(rows), 4)
     boxes = torch.stack([c.boxes.reshape(V, T, 4)[v] for c, _, v in rows])
-    ebox = torch.tensor([c.ebox if c.noise is not None else (0, 0, 0, 0) for c, _, _ in rows], dtype=torch.int32).reshape(len(rows), 4)
-    noise_off, blocks, n = [], [], 0
-    for c, _, _ in rows:
-        noise_off.append(n if c.noise is not None else 0)
-        if c.noise is not None:
-            blocks.append(c.noise.to(torch.float32).reshape(-1))
-            n += blocks[-1].numel()
-    noise = torch.cat(blocks) if blocks else torch.zeros(0, dtype=torch.float32)
+    ebox, noise, noise_off = collate_erase([c for c, _, _ in rows])
     aug_ops = aug_args = None
     if any(c.aug_ops is not None for c in batch):      # rows of clips without a plan stay zero: no work
         aug_ops = torch.zeros((len(rows), MAX_LAYERS), dtype=torch.int32)
@@ -292,7 +331,7 @@ def collate_raw_clips(batch, *, collate_fn_map=None):
                     raise ValueError(f"collate: a RandAugment plan is int32 [{MAX_LAYERS}] / float64 [{MAX_LAYERS},{NUM_ARGS}]")
                 aug_ops[r], aug_args[r] = c.aug_ops, c.aug_args
     return RawClipBatch(flat, desc, boxes, first.crop_size, first.mean, first.std, pre=first.pre, num_views=V, ebox=ebox,
-                        noise=noise, noise_off=torch.tensor(noise_off, dtype=torch.int64), aug_ops=aug_ops,
+                        noise=noise, noise_off=noise_off, aug_ops=aug_ops,
                         aug_args=aug_args).validate()
 
 

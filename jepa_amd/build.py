@@ -21,7 +21,9 @@ CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused
 EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                # RandAugment is compared byte for byte with PIL, whose x86-64 build has no fused multiply-add: every product and
                # sum of this file is rounded on its own
-               "clip_randaug.hip": ["-ffp-contract=off"]}
+               "clip_randaug.hip": ["-ffp-contract=off"],
+               # the same for PIL's resample: its fp64 coefficients are truncated to 22-bit integers
+               "image_resample.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

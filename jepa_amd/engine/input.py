@@ -27,11 +27,14 @@ A batch whose clips carry RandAugment plans ships the two plan tables too, and `
 in place on the copy stream BEFORE the transform, with a workspace kept in the slot (again nothing when no clip has an operation).
 
 `EvalPrefetcher` is the same machinery for the batch structure of the frozen video eval (a list over segments of `RawClipBatch`,
-labels, clip indices): it iterates like the loader it wraps and hands out what `run_one_epoch` takes.
+labels, clip indices): it iterates like the loader it wraps and hands out what `run_one_epoch` takes.  `ImagePrefetcher` is its
+sibling for the image evals: `(RawImageBatch, labels)` batches of decoded uint8 images, which `vj_image_resample` crops and resizes
+on the copy stream as PIL would before `vj_clip_transform_pre` normalises them.
 """
 import torch
 
 from ..app.vjepa.transforms import RawClipBatch
+from ..evals.image_classification_frozen.transforms import RawImageBatch
 from ..hip import ops
 from ..src.utils.tensors import repeat_interleave_batch
 
@@ -222,3 +225,51 @@ class EvalPrefetcher(DevicePrefetcher):
 
     def next(self, lookahead=True):
         raise TypeError("EvalPrefetcher is iterated like the loader it wraps")
+
+
+class ImagePrefetcher(EvalPrefetcher):
+    """The input edge of the image evals.  `loader` yields `(RawImageBatch, labels)` (decoded uint8 images of mixed sizes in one
+    flat buffer + descriptor and geometry tables: evals/image_classification_frozen/transforms.py); iterating the prefetcher yields
+    `(fp32 [B,3,S,S] images, labels)` on the device -- what the image evals' run_one_epoch builds from fp32 loader batches with
+    `.to(device)`, which is the identity on these.  On the copy stream, after the upload:
+        vj_image_resample        PIL's resample of every crop box into the slot's uint8 [B,S,S,3] buffer
+        vj_clip_transform_pre    that buffer as one-frame clips with identity boxes: (u / 255 - mean) / std and the flip
+        vj_clip_erase            the RandomErasing noise, when a box was drawn
+    so batch k+1 is fetched and transformed while batch k's forward runs, and fine-tuning's `mix` mixes in place in the slot's
+    buffer.  The resample workspace is kept in the slot and only ever grows."""
+
+    def _stage_images(self, slot, raw):
+        raw.validate()                                 # on the host, before anything is copied
+        B, S, stream = len(raw), raw.crop_size, self.copy_stream.cuda_stream
+        frames = self._stage(slot, "raw", raw.frames, flat=True)
+        desc = self._stage(slot, "desc", raw.desc)
+        geom = self._stage(slot, "geom", raw.geom)
+        dev = self._dev[slot]
+        u8 = dev.get("u8")
+        if u8 is None or tuple(u8.shape) != (B, S, S, 3):
+            u8 = dev["u8"] = torch.empty((B, S, S, 3), dtype=torch.uint8, device=self.device)
+        taps_x, taps_y, rows = raw.capacities()
+        need = ops.ImageResample.ws_bytes(B, S, taps_x, taps_y, rows) if B else 0
+        ws = dev.get("resample_ws")
+        if ws is None or ws.numel() < need:
+            ws = dev["resample_ws"] = torch.empty(max(need + need // 4, 16), dtype=torch.uint8, device=self.device)
+        ops.ImageResample.run(frames, desc, geom, S, raw.filter, taps_x, taps_y, rows, out=u8, stream=stream, ws=ws)
+        desc1, boxes1 = raw.resampled_tables()
+        desc1, boxes1 = self._stage(slot, "desc1", desc1), self._stage(slot, "boxes1", boxes1)
+        out = dev.get("images")
+        if out is None or tuple(out.shape) != (B, 3, 1, S, S):
+            out = dev["images"] = torch.empty((B, 3, 1, S, S), dtype=torch.float32, device=self.device)
+        ops.clip_transform(u8.view(-1), desc1, boxes1, S, raw.mean, raw.std, out=out, stream=stream, pre=True)
+        if raw.erased:
+            noise = self._stage(slot, "noise", raw.noise, flat=True)
+            ebox = self._stage(slot, "ebox", raw.ebox)
+            noise_off = self._stage(slot, "noise_off", raw.noise_off)
+            ops.clip_erase(out, ebox, noise, noise_off, stream=stream)
+        return out.view(B, 3, S, S)
+
+    def _stage_batch(self, slot, batch):
+        raw, labels = batch
+        if not isinstance(raw, RawImageBatch):
+            raise TypeError(f"ImagePrefetcher: the batch holds {type(raw).__name__}, expected the RawImageBatch that the image "
+                            "evals' transforms collate to (fp32 batches go to run_one_epoch as they are)")
+        return self._stage_images(slot, raw), self._stage(slot, "labels", torch.as_tensor(labels))

@@ -17,21 +17,30 @@ arithmetic, CSV columns, checkpoint dictionary and folder / file names.  Differe
   - bf16 compute, `use_bfloat16`, `use_silu` and the DistributedDataParallel wrapping are handled exactly as in the video eval
     (..video_classification_frozen.eval, whose load_pretrained, init_model and init_opt are this file's too; what the two evals
     share beyond those is in ..frozen).
-  - there are no real image datasets: `data.dataset_name` must be `synthetic` (seeded labelled images,
-    src/datasets/data_manager.py: SyntheticImageClassification); extension keys `data.synthetic_length` (items per split, default 8
-    batches) and `data.num_workers` (default 0).
+  - `data.dataset_name` is `synthetic` (seeded labelled fp32 images, src/datasets/data_manager.py: SyntheticImageClassification),
+    `synthetic_images` (seeded labelled uint8 images of mixed sizes) or `image_folder` (<root_path>/<image_folder>/{train,val}/
+    <class>/<file>, read with PIL; src/datasets/image_datasets.py).  The last two go through the reference's image transforms
+    (eval.py:379-423: random-resized crop bicubic, flip, RandomErasing 0.25 to train; Resize bilinear + CenterCrop to validate) as
+    draws on the host (.transforms) and pixel work on the device: uint8 bytes are uploaded, vj_image_resample does PIL's antialiased
+    resample byte for byte, vj_clip_transform_pre and vj_clip_erase the rest, on a copy stream one batch ahead of the forward
+    (engine.input.ImagePrefetcher).  The reference's own dataset classes (ImageNet, iNat21, Places205, `subset_file`) and timm's
+    auto-augment policy are not part of this package, and stream parity with timm / torchvision draws is not claimed.  Extension
+    keys `data.synthetic_length` (items per split, default 8 batches) and `data.num_workers` (default 0).
   - one encoder call never holds more images than keep fc1's output below 2^31 elements, counted from the tokens the actual input
     makes (frozen_features).
   - `main` returns a small record of the run (per-epoch accuracies, per-iteration training loss and learning rate).
   - `main(finetune=...)` and run_one_epoch's `features_grad`, `after_update` and `mix` are what ..image_classification_finetune.eval
     brings to train the encoder with the probe; without them this eval runs what it always ran.
 """
+import os
 import pprint
 
 import numpy as np
 import torch
 
+from ...engine.input import ImagePrefetcher
 from ...src.datasets.data_manager import SyntheticImageClassification
+from ...src.datasets.image_datasets import ImageFolder, SyntheticImages
 from ...src.models.attentive_pooler import AttentiveClassifier
 from ...src.utils.logging import get_logger
 from ..frozen import classifier_state_dict, load_checkpoint  # noqa: F401  (the reference's names in this file)
@@ -41,6 +50,7 @@ from ..frozen import (chunked_call, freeze, max_clips_per_call, parse_config, ru
 from ..mix import SoftTargetCrossEntropy, mix_batch
 from ..multihead import run as run_multihead
 from ..video_classification_frozen.eval import init_model, init_opt, load_pretrained  # noqa: F401
+from .transforms import make_transforms
 
 logger = get_logger(__name__)
 
@@ -95,6 +105,9 @@ def main(args_eval, resume_preempt=False, finetune=None):
                   synthetic_length=synthetic_length, num_workers=num_workers)
     train_loader = make_dataloader(training=True, **common)
     val_loader = make_dataloader(training=False, **common)
+    if str(dataset_name).lower() in UINT8_DATASETS:
+        # uint8 images cross PCIe; resample, normalisation, flip and erasing run on the device, one batch ahead of the forward
+        train_loader, val_loader = ImagePrefetcher(train_loader, device), ImagePrefetcher(val_loader, device)
     ipe = len(train_loader)
     logger.info(f'Dataloader created... iterations per epoch: {ipe}')
 
@@ -191,18 +204,44 @@ def run_one_epoch(device, training, encoder, classifier, scaler, optimizer, sche
                            loss_and_top1, history=history, features_grad=features_grad, after_update=after_update)
 
 
+UINT8_DATASETS = ('synthetic_images', 'image_folder')   # decoded uint8 images through the transform, staged by ImagePrefetcher
+
+
 def make_dataloader(dataset_name, root_path, image_folder, batch_size, world_size, rank, resolution=224, training=False,
                     subset_file=None, num_classes=None, synthetic_length=None, num_workers=0, seed=None):
-    """The reference's loader factory (eval.py:379-423) for `dataset_name: synthetic`; the real datasets raise, as
-    data_manager.init_data does."""
-    if str(dataset_name).lower() != 'synthetic':
+    """The reference's loader factory (eval.py:379-423) for
+        `dataset_name: synthetic`          finished fp32 images (SyntheticImageClassification);
+        `dataset_name: synthetic_images`   seeded uint8 images of mixed sizes through the eval's transform (SyntheticImages);
+        `dataset_name: image_folder`       <root_path>/<image_folder>/{train,val}/<class>/<file>, read with PIL, through the transform.
+    The last two yield `(RawImageBatch, labels)` for engine.input.ImagePrefetcher: the reference's transforms (random-resized crop
+    bicubic, flip, RandomErasing 0.25 to train; Resize bilinear + CenterCrop to validate) are drawn on the host and carried out on
+    the device (.transforms).  The reference's own dataset names raise, as data_manager.init_data does."""
+    kind = str(dataset_name).lower()
+    if kind not in ('synthetic',) + UINT8_DATASETS:
         raise NotImplementedError(
-            f"dataset_name={dataset_name!r}: the reference's timm / torchvision image pipeline (ImageNet, iNat21, Places205) is not "
-            "part of this package; use data.dataset_name: synthetic, or pass your own loader to run_one_epoch")
+            f"dataset_name={dataset_name!r}: the reference's ImageNet, iNat21 and Places205 dataset classes (their index files and "
+            "subset_file) are not part of this package; a directory of <split>/<class>/<file> images runs with "
+            "data.dataset_name: image_folder, seeded data with synthetic_images or synthetic, or pass your own loader to "
+            "run_one_epoch")
+    if kind == 'image_folder':
+        if subset_file is not None:
+            raise NotImplementedError("image_folder: the reference's subset_file is not implemented")
+        if root_path is None or image_folder is None:
+            raise ValueError("make_dataloader(dataset_name='image_folder') needs root_path and image_folder")
+        transform = make_transforms(training=training, resolution=resolution)
+        dataset = ImageFolder(os.path.join(root_path, image_folder, 'train' if training else 'val'), transform=transform)
+        sampler = torch.utils.data.distributed.DistributedSampler(dataset, num_replicas=world_size, rank=rank, shuffle=training)
+        return torch.utils.data.DataLoader(dataset, sampler=sampler, batch_size=batch_size, drop_last=False, num_workers=num_workers,
+                                           pin_memory=True, persistent_workers=False)
     if num_classes is None:
-        raise ValueError("make_dataloader(dataset_name='synthetic') needs num_classes")
+        raise ValueError(f"make_dataloader(dataset_name={kind!r}) needs num_classes")
+    if kind == 'synthetic_images':
+        transform = make_transforms(training=training, resolution=resolution)
 
-    def make_dataset(length, seed):
-        return SyntheticImageClassification(length, num_classes, resolution, seed=seed)
+        def make_dataset(length, seed):
+            return SyntheticImages(length, num_classes, resolution, transform, seed=seed)
+    else:
+        def make_dataset(length, seed):
+            return SyntheticImageClassification(length, num_classes, resolution, seed=seed)
 
     return synthetic_dataloader(make_dataset, batch_size, world_size, rank, training, num_workers, synthetic_length, seed)

@@ -291,6 +291,55 @@ def clip_randaug(frames, desc, T, aug_ops, aug_args, stream=None, ws=None):
     return frames
 
 
+BILINEAR, BICUBIC = 0, 1   # filter codes of ImageResample
+
+
+class ImageResample:
+    """vj_image_resample: PIL's antialiased resample of decoded uint8 images, the first kernel of the image evals' input edge.  A
+    namespace like Scratch: `ImageResample.run(...)` launches, `ImageResample.ws_bytes(...)` sizes its workspace."""
+
+    @staticmethod
+    def ws_bytes(B, S, taps_x, taps_y, rows):
+        """Bytes of workspace `run` needs for B images at output side S with those capacities."""
+        need = int(_query("vj_image_resample_ws_bytes", int(B), int(S), int(taps_x), int(taps_y), int(rows)))
+        if need < 0:
+            raise ValueError(f"ImageResample.ws_bytes: bad dims B={B} S={S} taps_x={taps_x} taps_y={taps_y} rows={rows}")
+        return need
+
+    @staticmethod
+    def run(frames, desc, geom, S, filter, taps_x, taps_y, rows, out=None, stream=None, ws=None):
+        """frames / desc as clip_transform takes them (image b: [Hs,Ws,3]); geom int32 [B,8] = (i, j, h, w, OH, OW, wy, wx): crop box ->
+        OH x OW -> the S x S window at (wy, wx) -> out uint8 [B,S,S,3], byte for byte Image.crop(box).resize((OW, OH), filter).
+        filter: BILINEAR or BICUBIC.  taps_x, taps_y, rows: the capacities of the batch (RawImageBatch.capacities); the tables must
+        have been validated on the host (RawImageBatch.validate).  ws: a uint8 device buffer of at least ws_bytes(...) bytes
+        (default: this stream's scratch buffer)."""
+        _req(frames, torch.uint8, "frames")
+        _req(desc, I64, "desc")
+        _req(geom, torch.int32, "geom")
+        _opt(out, torch.uint8, "out")
+        _opt(ws, torch.uint8, "ws")
+        if frames.dim() != 1 or desc.dim() != 2 or desc.shape[1] != 4 or tuple(geom.shape) != (desc.shape[0], 8):
+            raise ValueError(f"ImageResample: frames {tuple(frames.shape)} / desc {tuple(desc.shape)} / geom {tuple(geom.shape)}: "
+                             "expected [nbytes], [B,4], [B,8]")
+        B, S = desc.shape[0], int(S)
+        if S <= 0 or S % 4 != 0:
+            raise ValueError(f"ImageResample: S={S} must be a positive multiple of 4")
+        if out is None:
+            out = torch.empty((B, S, S, 3), dtype=torch.uint8, device=frames.device)
+        elif tuple(out.shape) != (B, S, S, 3):
+            raise ValueError(f"ImageResample: out {tuple(out.shape)} is not {(B, S, S, 3)}")
+        if B == 0:
+            return out
+        need = ImageResample.ws_bytes(B, S, taps_x, taps_y, rows)
+        if ws is None:
+            ws = Scratch.get(need, frames.device, tag="image_resample", stream=stream)
+        elif ws.numel() < need:
+            raise ValueError(f"ImageResample: ws of {ws.numel()} bytes, {need} needed")
+        _launch("vj_image_resample", _ptr(frames), frames.numel(), _ptr(desc), _ptr(geom), _ptr(out), B, S, int(filter), int(taps_x),
+                int(taps_y), int(rows), _ptr(ws), ws.numel(), stream=stream)
+        return out
+
+
 def add_pos_bcast(y, pos, B, S, Gt, out=None, stream=None):
     """out[b, t*S+s] = bf16(y[b,s] + pos[t*S+s]), t < Gt; y bf16 [B*S, D], pos fp32 [Gt*S, D] -> bf16 [B*Gt*S, D]."""
     _req(y, BF16, "y")
