@@ -110,6 +110,18 @@ int vj_clip_erase(float* clips, const int32_t* ebox, const float* noise, int64_t
 int vj_clip_randaug(uint8_t* frames, int64_t frames_bytes, const int64_t* desc, int64_t B, int64_t T, const int32_t* ops,
                     const double* args, int64_t L, void* ws, int64_t ws_bytes, vj_stream_t stream);
 int64_t vj_clip_randaug_ws_bytes(int64_t frames_bytes, int64_t B, int64_t T);
+/* vj_clip_randaug with the fill colour of the affine family (Rotate, ShearX/Y, TranslateX/YRel) as an argument: the colour PIL's
+ * Image.transform / Image.rotate write where the source has no pixel.  timm's AutoAugment / RandAugment for images fill with the
+ * dataset mean, img_mean = tuple(min(255, round(255 * m)) for m in mean) = (124, 116, 104) for the ImageNet mean (timm
+ * transforms_factory.py, the aa_params of create_transform -> auto_augment_transform, which the image evals' training transform is:
+ * evals/image_classification_frozen/eval.py:392-403); the reference's video RandAugment fills with (128, 128, 128)
+ * (src/datasets/utils/video/randaugment.py _FILL), which is what vj_clip_randaug passes here.  One kernel body serves both.
+ *   fill_r, fill_g, fill_b   the colour as three bytes, each passed as an int in 0..255 (anything else is an error)
+ * Every other argument, limit and guarantee is vj_clip_randaug's, the workspace that of vj_clip_randaug_ws_bytes.  The operations
+ * outside the affine family do not read the colour. */
+int vj_clip_randaug_fill(uint8_t* frames, int64_t frames_bytes, const int64_t* desc, int64_t B, int64_t T, const int32_t* ops,
+                         const double* args, int64_t L, void* ws, int64_t ws_bytes, int fill_r, int fill_g, int fill_b,
+                         vj_stream_t stream);
 /* The input edge of the image evals: random-resized crop (bicubic) of training, Resize (bilinear, short side) + CenterCrop of
  * validation                                                                 evals/image_classification_frozen/eval.py:379-423
  * as PIL does them on 8-bit RGB: Image.crop(box).resize((OW, OH), filter), an antialiased two-pass resample whose support widens
@@ -122,7 +134,7 @@ int64_t vj_clip_randaug_ws_bytes(int64_t frames_bytes, int64_t B, int64_t T);
  *           the S x S window of that result whose corner is (wy, wx) is written -- only the window is computed.  Training: OH = OW = S,
  *           window (0, 0); validation: the box is the image, (OH, OW) the short-side size, the window the centre crop
  *   out     uint8 [B,S,S,3], S % 4 == 0: a buffer of one-frame clips with Hs = Ws = S at offsets b*S*S*3, which vj_clip_transform_pre
- *           (and vj_clip_randaug) takes
+ *           (and vj_clip_randaug[_fill], vj_image_hflip) takes
  *   filter  0 bilinear (support 1), 1 bicubic (a = -0.5, support 2)
  *   taps_x, taps_y, rows   capacities of the workspace, maxima over the batch: taps an output index can have per axis,
  *           int(ceil(support * max(n / m, 1))) * 2 + 1, and source rows the window's vertical taps span.  Tap loops are bounded at
@@ -136,6 +148,17 @@ int vj_image_resample(const uint8_t* frames, int64_t frames_bytes, const int64_t
                       int64_t S, int filter, int64_t taps_x, int64_t taps_y, int64_t rows, void* ws, int64_t ws_bytes,
                       vj_stream_t stream);
 int64_t vj_image_resample_ws_bytes(int64_t B, int64_t S, int64_t taps_x, int64_t taps_y, int64_t rows);
+/* RandomHorizontalFlip of the S x S crop on the uint8 side, in place: PIL's Image.transpose(FLIP_LEFT_RIGHT), which timm's training
+ * pipeline applies BEFORE its AutoAugment policy (RandomResizedCrop -> RandomHorizontalFlip -> AutoAugment -> ToTensor -> Normalize ->
+ * RandomErasing; evals/image_classification_frozen/eval.py:392-403), so a batch that carries a policy plan is mirrored here and
+ * vj_clip_transform_pre then gets a zero flip column.  out[b, y, x, :] = in[b, y, S-1-x, :] for every flagged image b.
+ *   buf      uint8 [B,S,S,3], the output buffer of vj_image_resample; 16-byte aligned, S % 4 == 0, B*S*S*3 < 2^31
+ *   flags    int64 [B,4]: column 3 is the flip flag of image b (the descriptor table vj_clip_transform_pre takes); 8-byte aligned
+ *   flagged  how many images are flagged, as the host knows them (0 <= flagged <= B): only 0 is acted upon, it launches nothing
+ * Words are moved, never single bytes: a thread swaps a group of four pixels with its mirror group and permutes their bytes in
+ * registers.  An unflagged image, and anything outside [buf, buf + B*S*S*3), is not touched by one byte.  B == 0 launches nothing.
+ * Bit-exact. */
+int vj_image_hflip(uint8_t* buf, const int64_t* flags, int64_t B, int64_t S, int64_t flagged, vj_stream_t stream);
 
 /* ---- still-image front end of the video encoder and position-table interpolation ------------------------------
  * input.unsqueeze(2).repeat(1, 1, frames_per_clip, 1, 1) + patch_embed    evals/image_classification_frozen/eval.py:452-455

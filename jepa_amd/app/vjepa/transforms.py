@@ -192,6 +192,39 @@ def check_erase(who, eb, nz, no, T, S, what="clip"):
                          f"leaves the noise buffer of {nz.numel()} values")
 
 
+def check_aug_tables(who, ao, aa, R):
+    """The RandAugment / AutoAugment plan tables of R rows (None, None: no plan, returns False): int32 [R,8] codes in range and
+    float64 [R,8,6] finite arguments."""
+    if (ao is None) != (aa is None):
+        raise ValueError(f"{who}: aug_ops and aug_args come together")
+    if ao is None:
+        return False
+    if ao.dtype != torch.int32 or tuple(ao.shape) != (R, MAX_LAYERS) or aa.dtype != torch.float64 \
+            or tuple(aa.shape) != (R, MAX_LAYERS, NUM_ARGS):
+        raise ValueError(f"{who}: malformed RandAugment tables aug_ops {tuple(ao.shape)} {ao.dtype}, aug_args "
+                         f"{tuple(aa.shape)} {aa.dtype}")
+    if bool(((ao < 0) | (ao > NUM_OPS)).any()):
+        raise ValueError(f"{who}: unknown RandAugment operation code in {ao[((ao < 0) | (ao > NUM_OPS)).any(1)][0].tolist()}")
+    if not bool(torch.isfinite(aa).all()):
+        raise ValueError(f"{who}: non-finite RandAugment argument")
+    return True
+
+
+def collate_aug(rows):
+    """(aug_ops int32 [R,8], aug_args float64 [R,8,6]) of rows that carry `.aug_ops` / `.aug_args` (None: no plan, the row stays
+    zero: no work), or (None, None) when no row has a plan."""
+    if not any(c.aug_ops is not None for c in rows):
+        return None, None
+    aug_ops = torch.zeros((len(rows), MAX_LAYERS), dtype=torch.int32)
+    aug_args = torch.zeros((len(rows), MAX_LAYERS, NUM_ARGS), dtype=torch.float64)
+    for r, c in enumerate(rows):
+        if c.aug_ops is not None:
+            if tuple(c.aug_ops.shape) != (MAX_LAYERS,) or tuple(c.aug_args.shape) != (MAX_LAYERS, NUM_ARGS):
+                raise ValueError(f"collate: a RandAugment plan is int32 [{MAX_LAYERS}] / float64 [{MAX_LAYERS},{NUM_ARGS}]")
+            aug_ops[r], aug_args[r] = c.aug_ops, c.aug_args
+    return aug_ops, aug_args
+
+
 class RawClipBatch:
     """A collated list of RawClips, all CPU tensors:
         frames     uint8 [nbytes]   clip after clip, each [T,Hs,Ws,3], each starting on a 16-byte boundary, each ONCE
@@ -235,19 +268,8 @@ class RawClipBatch:
 
     def _validate_aug(self):
         ao, aa, d = self.aug_ops, self.aug_args, self.desc
-        if (ao is None) != (aa is None):
-            raise ValueError("RawClipBatch: aug_ops and aug_args come together")
-        if ao is None:
+        if not check_aug_tables("RawClipBatch", ao, aa, d.shape[0]):
             return
-        R = d.shape[0]
-        if ao.dtype != torch.int32 or tuple(ao.shape) != (R, MAX_LAYERS) or aa.dtype != torch.float64 \
-                or tuple(aa.shape) != (R, MAX_LAYERS, NUM_ARGS):
-            raise ValueError(f"RawClipBatch: malformed RandAugment tables aug_ops {tuple(ao.shape)} {ao.dtype}, aug_args "
-                             f"{tuple(aa.shape)} {aa.dtype}")
-        if bool(((ao < 0) | (ao > NUM_OPS)).any()):
-            raise ValueError(f"RawClipBatch: unknown RandAugment operation code in {ao[((ao < 0) | (ao > NUM_OPS)).any(1)][0].tolist()}")
-        if not bool(torch.isfinite(aa).all()):
-            raise ValueError("RawClipBatch: non-finite RandAugment argument")
         on = (ao != 0).any(1)
         small = on & ((d[:, 1] < MIN_SIDE) | (d[:, 2] < MIN_SIDE))
         if bool(small.any()):
@@ -321,15 +343,7 @@ def collate_raw_clips(batch, *, collate_fn_map=None):
                         dtype=torch.int64).reshape(len(rows), 4)
     boxes = torch.stack([c.boxes.reshape(V, T, 4)[v] for c, _, v in rows])
     ebox, noise, noise_off = collate_erase([c for c, _, _ in rows])
-    aug_ops = aug_args = None
-    if any(c.aug_ops is not None for c in batch):      # rows of clips without a plan stay zero: no work
-        aug_ops = torch.zeros((len(rows), MAX_LAYERS), dtype=torch.int32)
-        aug_args = torch.zeros((len(rows), MAX_LAYERS, NUM_ARGS), dtype=torch.float64)
-        for r, (c, _, _) in enumerate(rows):
-            if c.aug_ops is not None:
-                if tuple(c.aug_ops.shape) != (MAX_LAYERS,) or tuple(c.aug_args.shape) != (MAX_LAYERS, NUM_ARGS):
-                    raise ValueError(f"collate: a RandAugment plan is int32 [{MAX_LAYERS}] / float64 [{MAX_LAYERS},{NUM_ARGS}]")
-                aug_ops[r], aug_args[r] = c.aug_ops, c.aug_args
+    aug_ops, aug_args = collate_aug([c for c, _, _ in rows])
     return RawClipBatch(flat, desc, boxes, first.crop_size, first.mean, first.std, pre=first.pre, num_views=V, ebox=ebox,
                         noise=noise, noise_off=noise_off, aug_ops=aug_ops,
                         aug_args=aug_args).validate()

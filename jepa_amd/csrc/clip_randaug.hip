@@ -22,6 +22,10 @@
 //                          tiles of 16 x 4
 // Every index is clamped into its frame, and a clip whose extent does not lie inside the buffer on a 16-byte boundary is skipped
 // by every kernel: nothing outside [frames, frames + frames_bytes), the same range of the copy, and the tables is touched.
+//
+// The colour the affine family writes where the source has no pixel is an argument of the one kernel body: vj_clip_randaug passes
+// the reference's video _FILL (128, 128, 128), vj_clip_randaug_fill what its caller gives -- the image evals pass timm's
+// round(255 * mean) = (124, 116, 104) for the AutoAugment policy of   evals/image_classification_frozen/eval.py:392-403.
 #include "common.hpp"
 #include "../../include/vjepa_hip.h"
 
@@ -207,13 +211,13 @@ __global__ __launch_bounds__(512) void randaug_table_kernel(const uint8_t* __res
 typedef uint32_t ra_u32x4_t __attribute__((ext_vector_type(4), aligned(4)));
 
 __device__ __forceinline__ uint32_t ra_affine_pixel(const uint8_t* __restrict__ s, uint32_t frame, uint32_t clip_bytes, int H, int W,
-                                                    int x, int y, const double* a) {
+                                                    int x, int y, const double* a, uint32_t fill) {
   const double xc = (double)x + 0.5, yc = (double)y + 0.5;
   const double xa = a[0] * xc, xb = a[1] * yc;
   const double ya = a[3] * xc, yb = a[4] * yc;
   double xin = (xa + xb) + a[2];
   double yin = (ya + yb) + a[5];
-  if (!(xin >= 0.0 && xin < (double)W && yin >= 0.0 && yin < (double)H)) return 0x808080u;
+  if (!(xin >= 0.0 && xin < (double)W && yin >= 0.0 && yin < (double)H)) return fill;
   xin -= 0.5, yin -= 0.5;
   const double xf = floor(xin), yf = floor(yin);
   const double dx = xin - xf, dy = yin - yf;
@@ -305,7 +309,8 @@ __device__ __forceinline__ uint32_t ra_sharp_pixel(const uint8_t* __restrict__ s
 __global__ __launch_bounds__(256) void randaug_apply_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                             int64_t frames_bytes, const int64_t* __restrict__ desc,
                                                             const int32_t* __restrict__ ops, const double* __restrict__ args,
-                                                            int L, int layer, int T, const uint8_t* __restrict__ tables) {
+                                                            int L, int layer, int T, const uint8_t* __restrict__ tables,
+                                                            uint32_t fill) {
   const int64_t b = blockIdx.y;
   int64_t off;
   int H, W;
@@ -341,7 +346,7 @@ __global__ __launch_bounds__(256) void randaug_apply_kernel(const uint8_t* __res
       const int x = (int)(r % tx) * 16 + lx, y = (int)(r / tx) * 4 + ly;
       if (x >= W || y >= H) continue;
       const uint32_t px = op == RA_SHARPNESS ? ra_sharp_pixel(s, t * HW * 3u, npix * 3u, H, W, x, y, fct, convex)
-                                             : ra_affine_pixel(s, t * HW * 3u, npix * 3u, H, W, x, y, a);
+                                             : ra_affine_pixel(s, t * HW * 3u, npix * 3u, H, W, x, y, a, fill);
       uint8_t* o = d + (int64_t)t * HW * 3 + ((int64_t)y * W + x) * 3;
       o[0] = (uint8_t)px, o[1] = (uint8_t)(px >> 8), o[2] = (uint8_t)(px >> 16);
     }
@@ -393,8 +398,9 @@ extern "C" int64_t vj_clip_randaug_ws_bytes(int64_t frames_bytes, int64_t B, int
   return ra_align(frames_bytes) + ra_align(B * T * RA_TABLE_BYTES);
 }
 
-extern "C" int vj_clip_randaug(uint8_t* frames, int64_t frames_bytes, const int64_t* desc, int64_t B, int64_t T,
-                               const int32_t* ops, const double* args, int64_t L, void* ws, int64_t ws_bytes, hipStream_t stream) {
+// fill: the colour the affine family writes where the source has no pixel, packed as a pixel is (r | g << 8 | b << 16)
+static int ra_run(uint8_t* frames, int64_t frames_bytes, const int64_t* desc, int64_t B, int64_t T, const int32_t* ops,
+                  const double* args, int64_t L, void* ws, int64_t ws_bytes, uint32_t fill, hipStream_t stream) {
   VJ_CHECK_ARG(B >= 0 && B < 65536 && T > 0 && T < (1 << 20) && frames_bytes >= 0 && frames_bytes < (1ll << 31),
                "vj_clip_randaug: bad dims B=%ld T=%ld frames_bytes=%ld", (long)B, (long)T, (long)frames_bytes);
   VJ_CHECK_ARG(L >= 0 && L <= 8, "vj_clip_randaug: L=%ld layers, at most 8", (long)L);
@@ -417,13 +423,27 @@ extern "C" int vj_clip_randaug(uint8_t* frames, int64_t frames_bytes, const int6
     hipLaunchKernelGGL(randaug_table_kernel, dim3((unsigned)(B * T)), dim3(512), 0, stream, src, frames_bytes, desc, ops, args, (int)L,
                        layer, (int)T, tables);
     hipLaunchKernelGGL(randaug_apply_kernel, grid, dim3(256), 0, stream, src, dst, frames_bytes, desc, ops, args, (int)L, layer, (int)T,
-                       tables);
+                       tables, fill);
     uint8_t* swap = src;
     src = dst, dst = swap;
   }
   if (src != frames)
     hipLaunchKernelGGL(randaug_apply_kernel, grid, dim3(256), 0, stream, src, frames, frames_bytes, desc, (const int32_t*)nullptr, args,
-                       (int)L, 0, (int)T, tables);
+                       (int)L, 0, (int)T, tables, fill);
   VJ_LAUNCH_CHECK("vj_clip_randaug");
   return 0;
+}
+
+extern "C" int vj_clip_randaug(uint8_t* frames, int64_t frames_bytes, const int64_t* desc, int64_t B, int64_t T,
+                               const int32_t* ops, const double* args, int64_t L, void* ws, int64_t ws_bytes, hipStream_t stream) {
+  return ra_run(frames, frames_bytes, desc, B, T, ops, args, L, ws, ws_bytes, 0x808080u, stream);   // the reference's video _FILL
+}
+
+extern "C" int vj_clip_randaug_fill(uint8_t* frames, int64_t frames_bytes, const int64_t* desc, int64_t B, int64_t T,
+                                    const int32_t* ops, const double* args, int64_t L, void* ws, int64_t ws_bytes, int fill_r,
+                                    int fill_g, int fill_b, hipStream_t stream) {
+  VJ_CHECK_ARG(fill_r >= 0 && fill_r <= 255 && fill_g >= 0 && fill_g <= 255 && fill_b >= 0 && fill_b <= 255,
+               "vj_clip_randaug_fill: fill colour (%d, %d, %d), bytes are taken", fill_r, fill_g, fill_b);
+  return ra_run(frames, frames_bytes, desc, B, T, ops, args, L, ws, ws_bytes,
+                (uint32_t)fill_r | ((uint32_t)fill_g << 8) | ((uint32_t)fill_b << 16), stream);
 }

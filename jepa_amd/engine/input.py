@@ -29,12 +29,14 @@ in place on the copy stream BEFORE the transform, with a workspace kept in the s
 `EvalPrefetcher` is the same machinery for the batch structure of the frozen video eval (a list over segments of `RawClipBatch`,
 labels, clip indices): it iterates like the loader it wraps and hands out what `run_one_epoch` takes.  `ImagePrefetcher` is its
 sibling for the image evals: `(RawImageBatch, labels)` batches of decoded uint8 images, which `vj_image_resample` crops and resizes
-on the copy stream as PIL would before `vj_clip_transform_pre` normalises them.
+on the copy stream as PIL would before `vj_clip_transform_pre` normalises them.  A batch whose images carry AutoAugment / RandAugment
+plans (`data.auto_augment`) is mirrored on the uint8 side first (`vj_image_hflip`) and then augmented in place
+(`vj_clip_randaug_fill`), as the reference's pipeline flips before its policy.
 """
 import torch
 
 from ..app.vjepa.transforms import RawClipBatch
-from ..evals.image_classification_frozen.transforms import RawImageBatch
+from ..evals.image_classification_frozen.transforms import RawImageBatch, fill_colour
 from ..hip import ops
 from ..src.utils.tensors import repeat_interleave_batch
 
@@ -235,6 +237,11 @@ class ImagePrefetcher(EvalPrefetcher):
         vj_image_resample        PIL's resample of every crop box into the slot's uint8 [B,S,S,3] buffer
         vj_clip_transform_pre    that buffer as one-frame clips with identity boxes: (u / 255 - mean) / std and the flip
         vj_clip_erase            the RandomErasing noise, when a box was drawn
+    and, for a batch in which some image carries a plan (RawImageBatch.augmented), between the first two
+        vj_image_hflip           the flip, on the uint8 side: the policy sees the flipped crop (the flip column of the next but one
+                                 kernel is then zero)
+        vj_clip_randaug_fill     the plan on the [B,S,S,3] buffer as one-frame clips, fill colour round(255 * mean); only the layers
+                                 in which some image has an operation; its workspace is kept in the slot and only grows
     so batch k+1 is fetched and transformed while batch k's forward runs, and fine-tuning's `mix` mixes in place in the slot's
     buffer.  The resample workspace is kept in the slot and only ever grows."""
 
@@ -255,6 +262,20 @@ class ImagePrefetcher(EvalPrefetcher):
             ws = dev["resample_ws"] = torch.empty(max(need + need // 4, 16), dtype=torch.uint8, device=self.device)
         ops.ImageResample.run(frames, desc, geom, S, raw.filter, taps_x, taps_y, rows, out=u8, stream=stream, ws=ws)
         desc1, boxes1 = raw.resampled_tables()
+        if raw.augmented:
+            # the reference flips, then augments: mirror the uint8 crops now and hand the fp32 transform a zero flip column
+            flips = desc1[:, 3].clone()
+            desc_flip = self._stage(slot, "desc_flip", desc1)
+            ops.image_hflip(u8, desc_flip, flips, stream=stream)
+            desc1[:, 3] = 0
+            live = (raw.aug_ops != 0).any(0)
+            aug_ops = self._stage(slot, "aug_ops", raw.aug_ops[:, live].reshape(-1), flat=True).view(B, -1)
+            aug_args = self._stage(slot, "aug_args", raw.aug_args[:, live].reshape(-1), flat=True).view(B, -1, 6)
+            need = ops.clip_randaug_ws_bytes(u8.numel(), B, 1)
+            aug_ws = dev.get("aug_ws")
+            if aug_ws is None or aug_ws.numel() < need:
+                aug_ws = dev["aug_ws"] = torch.empty(need + need // 4, dtype=torch.uint8, device=self.device)
+            ops.clip_randaug(u8.view(-1), desc_flip, 1, aug_ops, aug_args, stream=stream, ws=aug_ws, fill=fill_colour(raw.mean))
         desc1, boxes1 = self._stage(slot, "desc1", desc1), self._stage(slot, "boxes1", boxes1)
         out = dev.get("images")
         if out is None or tuple(out.shape) != (B, 3, 1, S, S):

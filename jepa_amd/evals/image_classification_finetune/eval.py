@@ -22,12 +22,16 @@ The CSV log and the checkpoint are the frozen image eval's, under `<pretrain fol
 checkpoint adds `encoder` (a state dict in the reference's names, which the frozen evals' load_pretrained reads with
 `checkpoint_key: encoder`) and `encoder_opt` (Adam moments and step count in torch.optim.AdamW's format), as the video one does.
 
+`data.auto_augment` (null, 'original' or a `rand-...` string such as 'rand-m9-mstd0.5-inc1', the usual image fine-tuning recipe) is
+the frozen image eval's key, read by its parser (`parse_auto_augment`, re-exported here); `mix` still mixes the finished fp32 buffer.
+
 Limits, all raising: one rank; `pretrain.frames_per_clip` == 1 (the 2-D image encoder runs on the frozen / no-grad path only); the
 lone probe (`optimization.multihead_kwargs` is the frozen evals'); every image of a batch in one encoder call (max_clips_per_call);
 with `mix`, an image width that is a multiple of 4 (vj_clip_mix moves four pixels at a time) and square images; and those of the
 `finetune` section itself.
 """
 from ..image_classification_frozen import eval as frozen_eval
+from ..image_classification_frozen.eval import parse_auto_augment  # noqa: F401  (one parser for both image evals)
 from ..video_classification_finetune.eval import _FineTune
 
 FOLDER_NAME = 'image_classification_finetune/'

@@ -23,9 +23,15 @@ arithmetic, CSV columns, checkpoint dictionary and folder / file names.  Differe
     (eval.py:379-423: random-resized crop bicubic, flip, RandomErasing 0.25 to train; Resize bilinear + CenterCrop to validate) as
     draws on the host (.transforms) and pixel work on the device: uint8 bytes are uploaded, vj_image_resample does PIL's antialiased
     resample byte for byte, vj_clip_transform_pre and vj_clip_erase the rest, on a copy stream one batch ahead of the forward
-    (engine.input.ImagePrefetcher).  The reference's own dataset classes (ImageNet, iNat21, Places205, `subset_file`) and timm's
-    auto-augment policy are not part of this package, and stream parity with timm / torchvision draws is not claimed.  Extension
-    keys `data.synthetic_length` (items per split, default 8 batches) and `data.num_workers` (default 0).
+    (engine.input.ImagePrefetcher).  The reference's own dataset classes (ImageNet, iNat21, Places205, `subset_file`) are not part
+    of this package, and stream parity with timm / torchvision draws is not claimed.  Extension keys `data.synthetic_length` (items
+    per split, default 8 batches), `data.num_workers` (default 0) and `data.auto_augment` (default null: off).
+  - the reference's training transform also asks timm for `auto_augment='original'` (eval.py:392-403).  Here that is
+    `data.auto_augment: original` (or a `rand-...` string, timm's RandAugment form): the training transform then draws the policy's
+    plan for the flipped S x S crop and the device carries it out on the uint8 side (vj_image_hflip, vj_clip_randaug_fill with the
+    fill colour round(255 * mean)), byte for byte what PIL gives for that plan.  The policy table was not checked against a timm
+    install.  The key needs uint8 images: with `dataset_name: synthetic` it raises.  Without the key the eval issues the launches
+    and produces the bits it always did.
   - one encoder call never holds more images than keep fc1's output below 2^31 elements, counted from the tokens the actual input
     makes (frozen_features).
   - `main` returns a small record of the run (per-epoch accuracies, per-iteration training loss and learning rate).
@@ -50,6 +56,7 @@ from ..frozen import (chunked_call, freeze, max_clips_per_call, parse_config, ru
 from ..mix import SoftTargetCrossEntropy, mix_batch
 from ..multihead import run as run_multihead
 from ..video_classification_frozen.eval import init_model, init_opt, load_pretrained  # noqa: F401
+from ...app.vjepa.randaugment import auto_augment_draw
 from .transforms import make_transforms
 
 logger = get_logger(__name__)
@@ -59,6 +66,21 @@ np.random.seed(_GLOBAL_SEED)
 torch.manual_seed(_GLOBAL_SEED)
 
 pp = pprint.PrettyPrinter(indent=4)
+
+UINT8_DATASETS = ('synthetic_images', 'image_folder')   # decoded uint8 images through the transform, staged by ImagePrefetcher
+_auto_augment_logged = False
+
+
+def parse_auto_augment(args_data):
+    """`data.auto_augment` of both image evals (extension; absent / null: off, 'original', or a `rand-...` string), validated by the
+    one parser (app/vjepa/randaugment.auto_augment_draw) and against the dataset: finished fp32 images cannot be augmented."""
+    value = (args_data or {}).get('auto_augment', None)
+    auto_augment_draw(value)                      # raises ValueError naming what is accepted
+    kind = str((args_data or {}).get('dataset_name')).lower()
+    if value is not None and kind not in UINT8_DATASETS:
+        raise ValueError(f"data.auto_augment needs uint8 images (dataset_name: {' or '.join(UINT8_DATASETS)}); {kind!r} yields "
+                         "finished fp32 images")
+    return value
 
 
 def main(args_eval, resume_preempt=False, finetune=None):
@@ -80,6 +102,7 @@ def main(args_eval, resume_preempt=False, finetune=None):
     resolution = args_data.get('resolution', 224)
     synthetic_length = args_data.get('synthetic_length', None)
     num_workers = args_data.get('num_workers', 0)
+    auto_augment = parse_auto_augment(args_data)
 
     run = setup_run(cfg, 'image_classification_frozen/' if finetune is None else finetune.folder_name, csv=multihead is None)
     device = run.device
@@ -103,7 +126,7 @@ def main(args_eval, resume_preempt=False, finetune=None):
     common = dict(dataset_name=dataset_name, root_path=root_path, resolution=resolution, image_folder=image_folder,
                   batch_size=cfg.batch_size, world_size=run.world_size, rank=run.rank, num_classes=num_classes,
                   synthetic_length=synthetic_length, num_workers=num_workers)
-    train_loader = make_dataloader(training=True, **common)
+    train_loader = make_dataloader(training=True, auto_augment=auto_augment, **common)
     val_loader = make_dataloader(training=False, **common)
     if str(dataset_name).lower() in UINT8_DATASETS:
         # uint8 images cross PCIe; resample, normalisation, flip and erasing run on the device, one batch ahead of the forward
@@ -204,18 +227,16 @@ def run_one_epoch(device, training, encoder, classifier, scaler, optimizer, sche
                            loss_and_top1, history=history, features_grad=features_grad, after_update=after_update)
 
 
-UINT8_DATASETS = ('synthetic_images', 'image_folder')   # decoded uint8 images through the transform, staged by ImagePrefetcher
-
-
 def make_dataloader(dataset_name, root_path, image_folder, batch_size, world_size, rank, resolution=224, training=False,
-                    subset_file=None, num_classes=None, synthetic_length=None, num_workers=0, seed=None):
+                    subset_file=None, num_classes=None, synthetic_length=None, num_workers=0, seed=None, auto_augment=None):
     """The reference's loader factory (eval.py:379-423) for
         `dataset_name: synthetic`          finished fp32 images (SyntheticImageClassification);
         `dataset_name: synthetic_images`   seeded uint8 images of mixed sizes through the eval's transform (SyntheticImages);
         `dataset_name: image_folder`       <root_path>/<image_folder>/{train,val}/<class>/<file>, read with PIL, through the transform.
     The last two yield `(RawImageBatch, labels)` for engine.input.ImagePrefetcher: the reference's transforms (random-resized crop
     bicubic, flip, RandomErasing 0.25 to train; Resize bilinear + CenterCrop to validate) are drawn on the host and carried out on
-    the device (.transforms).  The reference's own dataset names raise, as data_manager.init_data does."""
+    the device (.transforms).  The reference's own dataset names raise, as data_manager.init_data does.  auto_augment (extension,
+    `data.auto_augment`): the training transform of the uint8 datasets also draws timm's policy plan per image."""
     kind = str(dataset_name).lower()
     if kind not in ('synthetic',) + UINT8_DATASETS:
         raise NotImplementedError(
@@ -223,12 +244,23 @@ def make_dataloader(dataset_name, root_path, image_folder, batch_size, world_siz
             "subset_file) are not part of this package; a directory of <split>/<class>/<file> images runs with "
             "data.dataset_name: image_folder, seeded data with synthetic_images or synthetic, or pass your own loader to "
             "run_one_epoch")
+    auto_augment = parse_auto_augment(dict(dataset_name=kind, auto_augment=auto_augment)) if training else None
+    if kind in UINT8_DATASETS and training:
+        global _auto_augment_logged
+        if auto_augment is not None:
+            logger.info(f"probe training: timm's auto_augment={auto_augment!r} (the reference asks for 'original', eval.py:392-403) is "
+                        "applied on the device (data.auto_augment), between the flip and the normalisation")
+        elif not _auto_augment_logged:
+            _auto_augment_logged = True
+            logger.info("probe training: the reference's auto_augment='original' policy (eval.py:392-403) is NOT applied; the random "
+                        "resized crop, flip and RandomErasing (re_prob 0.25) are (data.auto_augment: original applies it on the "
+                        "device)")
     if kind == 'image_folder':
         if subset_file is not None:
             raise NotImplementedError("image_folder: the reference's subset_file is not implemented")
         if root_path is None or image_folder is None:
             raise ValueError("make_dataloader(dataset_name='image_folder') needs root_path and image_folder")
-        transform = make_transforms(training=training, resolution=resolution)
+        transform = make_transforms(training=training, resolution=resolution, auto_augment=auto_augment)
         dataset = ImageFolder(os.path.join(root_path, image_folder, 'train' if training else 'val'), transform=transform)
         sampler = torch.utils.data.distributed.DistributedSampler(dataset, num_replicas=world_size, rank=rank, shuffle=training)
         return torch.utils.data.DataLoader(dataset, sampler=sampler, batch_size=batch_size, drop_last=False, num_workers=num_workers,
@@ -236,7 +268,7 @@ def make_dataloader(dataset_name, root_path, image_folder, batch_size, world_siz
     if num_classes is None:
         raise ValueError(f"make_dataloader(dataset_name={kind!r}) needs num_classes")
     if kind == 'synthetic_images':
-        transform = make_transforms(training=training, resolution=resolution)
+        transform = make_transforms(training=training, resolution=resolution, auto_augment=auto_augment)
 
         def make_dataset(length, seed):
             return SyntheticImages(length, num_classes, resolution, transform, seed=seed)

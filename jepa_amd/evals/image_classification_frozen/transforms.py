@@ -15,8 +15,18 @@ Normalize + flip) and vj_clip_erase on its copy stream.
 The crop box comes from app/vjepa/transforms.py's `_draw_box` and the erase box from its `draw_erase`, on the global generators
 (Python `random`, `np.random`, torch).  The semantics are the reference's (timm / torchvision); the random STREAM is this package's
 own: stream parity with timm / torchvision draws is not claimed.  The pixel arithmetic, given a box, is pinned byte for byte.
-Out of scope: timm's `auto_augment='original'` policy (the resampled uint8 buffer has the layout vj_clip_randaug takes, so it can
-follow), JPEG decoding on the device, non-RGB sources beyond `convert('RGB')`.
+
+The reference's training pipeline also applies timm's `auto_augment='original'` policy between the flip and ToTensor.  It is an
+extension key here, off by default (`data.auto_augment`: null, 'original' or a `rand-...` string; one parser,
+app/vjepa/randaugment.auto_augment_draw).  With it, `ImageTransform.draw` draws box, flip, PLAN at (S, S), erase -- the reference
+pipeline's order --, RawImage / RawImageBatch carry the plan tables (`aug_ops` int32 [B,8], `aug_args` float64 [B,8,6], None when no
+image has a plan), and the prefetcher, after the resample, mirrors the flagged images on the uint8 side (vj_image_hflip: timm
+augments the already flipped crop), runs the plan on the [B,S,S,3] buffer as one-frame clips with timm's fill colour
+round(255 * mean) = (124, 116, 104) (vj_clip_randaug_fill), and hands vj_clip_transform_pre a zero flip column.  The policy table
+was not checked against a timm install, and stream parity with timm's draws is not claimed, as for the box and erase draws; given a
+plan, the pixels are PIL's byte for byte (tests/golden/image_autoaug_micro.npz, made with the reference's own operation functions).
+Out of scope: timm's other policies ('originalr', 'v0', 'v0r', '3a', 'augmix-*', '-mstd' suffixes), JPEG decoding on the device,
+non-RGB sources beyond `convert('RGB')`.
 """
 import math
 
@@ -24,8 +34,9 @@ import numpy as np
 import torch
 from torch.utils.data._utils.collate import default_collate_fn_map
 
-from ...app.vjepa.transforms import (_draw_box, buffer_offsets, check_constants, check_erase, check_erase_tables, check_extents,
-                                     collate_erase, draw_erase, pack_buffers)
+from ...app.vjepa.randaugment import MIN_SIDE, NUM_ARGS, auto_augment_draw
+from ...app.vjepa.transforms import (_draw_box, buffer_offsets, check_aug_tables, check_constants, check_erase, check_erase_tables,
+                                     check_extents, collate_aug, collate_erase, draw_erase, pack_buffers)
 
 BILINEAR, BICUBIC = 0, 1          # the filter codes of vj_image_resample
 MAX_SIDE = 1 << 15                # sides the kernel takes (exclusive)
@@ -33,10 +44,15 @@ MAX_SIDE = 1 << 15                # sides the kernel takes (exclusive)
 
 def make_transforms(training=True, resolution=224, random_resize_scale=(0.08, 1.0), random_resize_aspect_ratio=(3 / 4, 4 / 3),
                     random_horizontal_flip=0.5, reprob=0.25,
-                    normalize=((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))):
+                    normalize=((0.485, 0.456, 0.406), (0.229, 0.224, 0.225)), auto_augment=None):
     return ImageTransform(training=training, resolution=resolution, random_resize_scale=random_resize_scale,
                           random_resize_aspect_ratio=random_resize_aspect_ratio, random_horizontal_flip=random_horizontal_flip,
-                          reprob=reprob, normalize=normalize)
+                          reprob=reprob, normalize=normalize, auto_augment=auto_augment)
+
+
+def fill_colour(mean):
+    """timm's fill colour of the affine operations: tuple(min(255, round(255 * m)) for m in mean) -- (124, 116, 104) for ImageNet."""
+    return tuple(min(255, round(255 * m)) for m in mean)
 
 
 def short_side_size(H, W, R):
@@ -72,13 +88,18 @@ def axis_span(n, m, filt, first, count):
 class RawImage:
     """One undecorated image on its way to the device: uint8 [H,W,3], its geometry (i, j, h, w, OH, OW, wy, wx), the flip flag, the
     output side, the filter code, mean / std (0..1 units) and the RandomErasing draw (`ebox` = (top, left, h, w), `noise` fp32
-    [1,3,h,w]; h == 0 / None: not erased)."""
-    __slots__ = ("image", "geom", "flip", "crop_size", "filter", "mean", "std", "ebox", "noise")
+    [1,3,h,w]; h == 0 / None: not erased).  `aug_ops` int32 [8] / `aug_args` float64 [8,6]: the AutoAugment / RandAugment plan of
+    the flipped S x S crop (randaugment.AutoAugmentDraw.draw; None: none)."""
+    __slots__ = ("image", "geom", "flip", "crop_size", "filter", "mean", "std", "ebox", "noise", "aug_ops", "aug_args")
 
-    def __init__(self, image, geom, flip, crop_size, filter, mean, std, ebox=(0, 0, 0, 0), noise=None):
+    def __init__(self, image, geom, flip, crop_size, filter, mean, std, ebox=(0, 0, 0, 0), noise=None, aug_ops=None, aug_args=None):
         self.image, self.geom, self.flip = image, tuple(int(v) for v in geom), bool(flip)
         self.crop_size, self.filter, self.mean, self.std = int(crop_size), int(filter), tuple(mean), tuple(std)
         self.ebox, self.noise = tuple(int(v) for v in ebox), noise
+        if (aug_ops is None) != (aug_args is None):
+            raise ValueError("RawImage: aug_ops and aug_args come together")
+        self.aug_ops = None if aug_ops is None else torch.as_tensor(aug_ops, dtype=torch.int32).reshape(-1)
+        self.aug_args = None if aug_args is None else torch.as_tensor(aug_args, dtype=torch.float64).reshape(-1, NUM_ARGS)
 
 
 class RawImageBatch:
@@ -87,10 +108,14 @@ class RawImageBatch:
         desc       int64 [B,4]      (byte offset, Hs, Ws, flip)
         geom       int32 [B,8]      (i, j, h, w, OH, OW, wy, wx)
         ebox / noise / noise_off    the erase tables of RawClipBatch, one frame per image
+        aug_ops    int32 [B,8]      plan of the flipped S x S crop, operation codes layer by layer (None: no image has a plan)
+        aug_args   float64 [B,8,6]  their arguments (app/vjepa/randaugment.py)
     with the output side, the filter code and mean / std (0..1 units: the normalise-first form of vj_clip_transform_pre)."""
 
-    def __init__(self, frames, desc, geom, crop_size, filter, mean, std, ebox=None, noise=None, noise_off=None):
+    def __init__(self, frames, desc, geom, crop_size, filter, mean, std, ebox=None, noise=None, noise_off=None, aug_ops=None,
+                 aug_args=None):
         self.frames, self.desc, self.geom = frames, desc, geom
+        self.aug_ops, self.aug_args = aug_ops, aug_args
         self.crop_size, self.filter, self.mean, self.std = int(crop_size), int(filter), tuple(mean), tuple(std)
         B = desc.shape[0]
         self.ebox = torch.zeros((B, 4), dtype=torch.int32) if ebox is None else ebox
@@ -104,6 +129,11 @@ class RawImageBatch:
     def erased(self):
         return self.noise.numel() > 0 and bool((self.ebox[:, 2] > 0).any())
 
+    @property
+    def augmented(self):
+        """Whether any image carries an operation (decided on the host: otherwise no upload, no launch, and the late flip)."""
+        return self.aug_ops is not None and bool((self.aug_ops != 0).any())
+
     def validate(self):
         """Refuse, on the host, anything that would send the kernels outside an image, its resize or a buffer."""
         who = "RawImageBatch"
@@ -116,6 +146,13 @@ class RawImageBatch:
         check_constants(who, self.crop_size, self.mean, self.std)
         if self.filter not in (BILINEAR, BICUBIC):
             raise ValueError(f"{who}: filter={self.filter} (0 bilinear, 1 bicubic)")
+        if check_aug_tables(who, self.aug_ops, self.aug_args, d.shape[0]) and self.augmented:
+            S = self.crop_size
+            if S < MIN_SIDE:
+                raise ValueError(f"{who}: augmented images of side {S}, below {MIN_SIDE}")
+            if d.shape[0] * S * S * 3 >= 1 << 31:
+                raise ValueError(f"{who}: {d.shape[0]} augmented images of {S}x{S} are {d.shape[0] * S * S * 3} bytes, below 2^31 "
+                                 "are taken")
         if d.shape[0] == 0:
             return self
         check_extents(who, f, d, 1, what="image")
@@ -163,6 +200,8 @@ class RawImageBatch:
         self.frames, self.desc, self.geom = self.frames.pin_memory(), self.desc.pin_memory(), self.geom.pin_memory()
         self.ebox, self.noise_off = self.ebox.pin_memory(), self.noise_off.pin_memory()
         self.noise = self.noise.pin_memory() if self.noise.numel() else self.noise
+        if self.aug_ops is not None:
+            self.aug_ops, self.aug_args = self.aug_ops.pin_memory(), self.aug_args.pin_memory()
         return self
 
 
@@ -180,8 +219,9 @@ def collate_raw_images(batch, *, collate_fn_map=None):
                         dtype=torch.int64).reshape(len(batch), 4)
     geom = torch.tensor([c.geom for c in batch], dtype=torch.int32).reshape(len(batch), 8)
     ebox, noise, noise_off = collate_erase(batch)
+    aug_ops, aug_args = collate_aug(batch)
     out = RawImageBatch(_extent_only(total), desc, geom, first.crop_size, first.filter, first.mean, first.std, ebox=ebox,
-                        noise=noise, noise_off=noise_off).validate()
+                        noise=noise, noise_off=noise_off, aug_ops=aug_ops, aug_args=aug_args).validate()
     out.frames, _ = pack_buffers([c.image for c in batch])
     return out
 
@@ -197,10 +237,13 @@ default_collate_fn_map[RawImage] = collate_raw_images
 class ImageTransform(object):
     """The reference's two image transforms as draws (module docstring).  training=True: the random-resized-crop box, the flip and
     the RandomErasing box and noise, in that order; the device resamples the box to S x S with the bicubic filter.  training=False:
-    no draw; the whole image is resampled to the short-side size with the bilinear filter and the centre window is taken."""
+    no draw; the whole image is resampled to the short-side size with the bilinear filter and the centre window is taken.
+    auto_augment (None, 'original' or a `rand-...` string: randaugment.auto_augment_draw): training also draws the policy's plan for
+    the flipped S x S crop, between the flip and the erase box; validation never draws."""
 
     def __init__(self, training=True, resolution=224, random_resize_scale=(0.08, 1.0), random_resize_aspect_ratio=(3 / 4, 4 / 3),
-                 random_horizontal_flip=0.5, reprob=0.25, normalize=((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))):
+                 random_horizontal_flip=0.5, reprob=0.25, normalize=((0.485, 0.456, 0.406), (0.229, 0.224, 0.225)),
+                 auto_augment=None):
         if resolution <= 0 or resolution % 4 != 0:
             raise ValueError(f"resolution={resolution} must be a positive multiple of 4 (16-byte output stores)")
         self.training, self.crop_size = training, int(resolution)
@@ -210,24 +253,29 @@ class ImageTransform(object):
         self.filter = BICUBIC if training else BILINEAR
         t = torch.tensor(normalize, dtype=torch.float32)          # the fp32 values the reference's Normalize holds
         self.mean, self.std = tuple(t[0].tolist()), tuple(t[1].tolist())
+        plan_draw = auto_augment_draw(auto_augment)               # parsed either way: a bad value raises for validation too
+        self.auto_augment = plan_draw if training else None       # validation never draws
 
     def draw(self, H, W):
-        """(geometry row, flip, erase box, noise) for one H x W image."""
+        """(geometry row, flip, erase box, noise, plan) for one H x W image; plan: (ops, args) or None."""
         S = self.crop_size
         if not self.training:
             OH, OW = short_side_size(H, W, self.resize_size)
             wy, wx = center_window(OH, OW, S)
-            return (0, 0, H, W, OH, OW, wy, wx), False, (0, 0, 0, 0), None
+            return (0, 0, H, W, OH, OW, wy, wx), False, (0, 0, 0, 0), None, None
         i, j, h, w = _draw_box(self.random_resize_scale, self.random_resize_aspect_ratio, H, W)
         flip = bool(np.random.uniform() < self.random_horizontal_flip) if self.random_horizontal_flip > 0 else False
+        plan = None if self.auto_augment is None else self.auto_augment.draw(S, S)
         ebox, noise = (0, 0, 0, 0), None
         if self.reprob > 0:
             ebox, noise = draw_erase(self.reprob, num_frames=1, img_h=S, img_w=S)
-        return (i, j, h, w, S, S, 0, 0), flip, ebox, noise
+        return (i, j, h, w, S, S, 0, 0), flip, ebox, noise, plan
 
     def __call__(self, image):
         img = torch.as_tensor(np.asarray(image))
         if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[-1] != 3:
             raise ValueError(f"ImageTransform: expected a uint8 [H,W,3] image, got {img.dtype} {tuple(img.shape)}")
-        geom, flip, ebox, noise = self.draw(img.shape[0], img.shape[1])
-        return RawImage(img.contiguous(), geom, flip, self.crop_size, self.filter, self.mean, self.std, ebox=ebox, noise=noise)
+        geom, flip, ebox, noise, plan = self.draw(img.shape[0], img.shape[1])
+        aug_ops, aug_args = (None, None) if plan is None else plan
+        return RawImage(img.contiguous(), geom, flip, self.crop_size, self.filter, self.mean, self.std, ebox=ebox, noise=noise,
+                        aug_ops=aug_ops, aug_args=aug_args)

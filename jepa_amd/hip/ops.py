@@ -262,13 +262,20 @@ def clip_randaug_ws_bytes(frames_bytes, B, T):
     return int(_query("vj_clip_randaug_ws_bytes", int(frames_bytes), int(B), int(T)))
 
 
-def clip_randaug(frames, desc, T, aug_ops, aug_args, stream=None, ws=None):
+def clip_randaug(frames, desc, T, aug_ops, aug_args, stream=None, ws=None, fill=None):
     """RandAugment in place on the uint8 frames of a flat clip buffer (the arguments `frames`, `desc` of clip_transform; T frames
     per clip): aug_ops int32 [B,L] and aug_args float64 [B,L,6], L <= 8, are the plans drawn by
     jepa_amd.app.vjepa.randaugment.RandAugmentDraw, one layer per column, applied in order; callers drop the columns in which no
     clip has an operation (every column costs two launches) and validate the tables on the host (RawClipBatch.validate).  Byte
     for byte what the reference's PIL path gives.  ws: a uint8 device buffer of at least clip_randaug_ws_bytes(...) bytes
-    (default: this stream's scratch buffer)."""
+    (default: this stream's scratch buffer).  fill: None (vj_clip_randaug: the affine family fills with the reference's video
+    colour (128, 128, 128)), or three bytes (r, g, b) (vj_clip_randaug_fill: timm's image policies fill with the dataset mean,
+    (124, 116, 104))."""
+    if fill is not None:
+        fill = tuple(fill)
+        if len(fill) != 3 or any(int(c) != c or not 0 <= c <= 255 for c in fill):
+            raise ValueError(f"clip_randaug: fill={fill} is not three bytes (r, g, b)")
+        fill = tuple(int(c) for c in fill)
     _req(frames, torch.uint8, "frames")
     _req(desc, I64, "desc")
     _req(aug_ops, torch.int32, "aug_ops")
@@ -286,8 +293,8 @@ def clip_randaug(frames, desc, T, aug_ops, aug_args, stream=None, ws=None):
         ws = Scratch.get(need, frames.device, tag="clip_randaug", stream=stream)
     elif ws.numel() < need:
         raise ValueError(f"clip_randaug: ws of {ws.numel()} bytes, {need} needed")
-    _launch("vj_clip_randaug", _ptr(frames), frames.numel(), _ptr(desc), B, int(T), _ptr(aug_ops), _ptr(aug_args), L, _ptr(ws),
-            ws.numel(), stream=stream)
+    _launch("vj_clip_randaug" if fill is None else "vj_clip_randaug_fill", _ptr(frames), frames.numel(), _ptr(desc), B, int(T),
+            _ptr(aug_ops), _ptr(aug_args), L, _ptr(ws), ws.numel(), *(fill or ()), stream=stream)
     return frames
 
 
@@ -338,6 +345,40 @@ class ImageResample:
         _launch("vj_image_resample", _ptr(frames), frames.numel(), _ptr(desc), _ptr(geom), _ptr(out), B, S, int(filter), int(taps_x),
                 int(taps_y), int(rows), _ptr(ws), ws.numel(), stream=stream)
         return out
+
+
+class _ImageHflip:
+    """`ops.image_hflip(images, desc, flips, stream=None)`: vj_image_hflip on the buffer ImageResample.run writes.  A callable object
+    beside that namespace, not a module-level function: the public functions of this module are the per-kernel wrappers of the
+    training step and the evals' compute path, which tests/test_ops_host.py tabulates row by row."""
+
+    @staticmethod
+    def __call__(images, desc, flips, stream=None):
+        """Mirror, in place, the flagged images of a uint8 [B,S,S,3] buffer (ImageResample.run's output, S % 4 == 0): what PIL's
+        transpose(FLIP_LEFT_RIGHT) gives, on the uint8 side, where timm flips before its AutoAugment policy.  desc: the device int64
+        [B,4] table whose column 3 holds the flags (RawImageBatch.resampled_tables); flips: the same flags on the HOST (B values) --
+        a batch without a flagged image, or without an image, launches nothing."""
+        _dev(images, torch.uint8, "images")
+        _req(desc, I64, "desc")
+        if images.dim() != 4 or images.shape[1] != images.shape[2] or images.shape[3] != 3 or tuple(desc.shape) != (images.shape[0], 4):
+            raise ValueError(f"image_hflip: images {tuple(images.shape)} / desc {tuple(desc.shape)}: expected [B,S,S,3], [B,4]")
+        B, S = images.shape[0], images.shape[1]
+        flips = [bool(f) for f in (flips.tolist() if torch.is_tensor(flips) else flips)]
+        if len(flips) != B:
+            raise ValueError(f"image_hflip: {len(flips)} host flags for {B} images")
+        if S % 4 != 0:
+            raise ValueError(f"image_hflip: S={S} must be a positive multiple of 4")
+        if B * S * S * 3 >= 1 << 31:
+            raise ValueError(f"image_hflip: a buffer of {B * S * S * 3} bytes, below 2^31 are taken")
+        _req(images, torch.uint8, "images")
+        flagged = sum(flips)
+        if B == 0 or flagged == 0:
+            return images
+        _launch("vj_image_hflip", _ptr(images), _ptr(desc), B, S, flagged, stream=stream)
+        return images
+
+
+image_hflip = _ImageHflip()
 
 
 def add_pos_bcast(y, pos, B, S, Gt, out=None, stream=None):
