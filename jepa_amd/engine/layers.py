@@ -98,6 +98,7 @@ class EncoderSaved(NamedTuple):
     rstd: Any
     drop: Any       # the forward's drop-path plan (_drop_plan)
     fan: Any        # the still front end's fan-out (B, cells, gt); None for every other input
+    recompute: Any = None   # the forward's activation-recomputation mode (_recompute_mode): None (every record kept), "mlp" or "block"
 
 
 class PredictorSaved(NamedTuple):
@@ -362,13 +363,63 @@ def _fc2_gb_route(views, li, plan):
     return views.blocks[li].fc2.gb
 
 
-def _trunk_forward(x, views, segs, save, ws_tag, gemm_flags=0, gates=None, drop=None):
+RECOMPUTE_MODES = ("none", "mlp", "block")
+_RECOMPUTE_ON_C_CHAIN = ("activation recomputation runs on the per-kernel block chain only: the C launch chains (ws_tag) serve the "
+                         "Trainer, which keeps every record")
+
+
+def recompute_mode(mode, what="recompute"):
+    """The activation-recomputation mode as the chain carries it: None for off (None or "none"), else "mlp" or "block".  Anything
+    else, a bool or a number included, raises and names the three."""
+    if mode is None or (isinstance(mode, str) and mode == "none"):
+        return None
+    if isinstance(mode, str) and mode in RECOMPUTE_MODES:
+        return mode
+    raise ValueError(f"{what}={mode!r}: activation recomputation is one of 'none', 'mlp', 'block'")
+
+
+def _recompute_mode(mode, save, ws_tag):
+    """recompute_mode for one encoder call: a mode goes with a forward that keeps a record (save=True) and with no workspace."""
+    mode = recompute_mode(mode, "encoder_forward: recompute")
+    if mode is None:
+        return None
+    if ws_tag is not None:
+        raise ValueError(_RECOMPUTE_ON_C_CHAIN)
+    if not save:
+        raise ValueError(f"encoder_forward: recompute={mode!r} with save=False: a forward that keeps nothing has nothing to recompute")
+    return mode
+
+
+def _slim(sv: BlockSaved, mode):
+    """What of a block's record survives the forward under a recomputation mode.  "block": the input x alone.  "mlp": everything but
+    u and g, the two [M, 4D] tensors -- half of the record."""
+    if mode == "block":
+        return BlockSaved(*(sv.x if f == "x" else None for f in BlockSaved._fields))
+    return sv._replace(u=None, g=None)
+
+
+def _refill(sv: BlockSaved, bw: BlockW, segs, heads, mode, drop):
+    """The full record of a block from its slimmed one, by the forward's own launches on the forward's own inputs: the same bits.
+    "block": block_forward again on the saved x with the block's plan entry (its output, the next block's x, is not kept).
+    "mlp": the fc1 GEMM on the saved y2, which writes g and, through aux_out, u."""
+    if mode == "block":
+        return block_forward(sv.x, bw, segs, heads, True, drop=drop)[1]
+    u = torch.empty((sv.y2.shape[0], bw.fc1.w.shape[0]), dtype=torch.bfloat16, device=sv.y2.device)
+    g = ops.gemm_nt(sv.y2, bw.fc1.w, bias=bw.fc1.b, aux_out=u, epilogue=ops.EPI_GELU)
+    return sv._replace(u=u, g=g)
+
+
+def _trunk_forward(x, views, segs, save, ws_tag, gemm_flags=0, gates=None, drop=None, recompute=None):
     """x through every block of `views` (EncoderW / PredictorW) -> (x, saved blocks): one C call per gated range, else the
     per-kernel Python chain.  drop: None, or a drop-path plan as _drop_plan returns it -- a plan only: a caller's raw list is
     neither validated nor normalised here.  A plan goes with the per-kernel chain only; the guard below keeps one from being
-    dropped silently in front of the C chain."""
+    dropped silently in front of the C chain.  recompute: None, "mlp" or "block" (_recompute_mode), under the same guard: every
+    block runs its plain save=True forward -- the unfolded LayerNorms, the same epilogues, the same bits -- and its record is slimmed at
+    once (_slim), so at most one full record is alive."""
     if drop is not None and ws_tag is not None:
         raise ValueError(_DROP_ON_C_CHAIN)
+    if recompute is not None and (ws_tag is not None or not save):
+        raise ValueError(_RECOMPUTE_ON_C_CHAIN if ws_tag is not None else "activation recomputation goes with save=True")
     if _chained(ws_tag):
         return chain.blocks_forward(x, views, segs, save, ws_tag, LN_EPS, gemm_flags=gemm_flags, gates=gates)
     folds = None if save else getattr(views, "folds", None)
@@ -376,13 +427,21 @@ def _trunk_forward(x, views, segs, save, ws_tag, gemm_flags=0, gates=None, drop=
     for bi, bw in enumerate(views.blocks):
         x, sv = block_forward(x, bw, segs, views.heads, save, fold=None if folds is None else folds[bi],
                               drop=_UNSCALED if drop is None else drop[bi])
-        saved_blocks.append(sv)
+        saved_blocks.append(sv if recompute is None else _slim(sv, recompute))
+        del sv
     return x, saved_blocks
 
 
-def _trunk_backward(dx, saved_blocks, views, segs, tag, alpha, beta, on_layer_done, ws_tag, drop=None):
+def _trunk_backward(dx, saved_blocks, views, segs, tag, alpha, beta, on_layer_done, ws_tag, drop=None, recompute=None):
     """The blocks of `views` in reverse, whichever chain the forward took; on_layer_done(tag, layer) after every block.  The caller's
-    LayerNorm backward, which produced dx, filled _fc2_gb_route(views, last block, drop).  drop: the forward's drop-path plan."""
+    LayerNorm backward, which produced dx, filled _fc2_gb_route(views, last block, drop).  drop: the forward's drop-path plan.
+    recompute: the forward's mode; directly before a block's backward its slimmed record is refilled (_refill), and the refilled
+    tensors go as a saved record goes, right after the block's backward: block_backward hands what the weight gradients read to
+    the side stream through side.fork like any saved tensor, so the allocator keeps that memory until the side stream is past it.
+    That alone is safe but saves nothing: the host issues the whole backward long before the GPU runs it, and every refilled record
+    would still be held back for the side stream when the next one is allocated (measured: the allocator's peak did not move).  So
+    under a mode the host waits, before refilling block i, for the side stream to be past block i + 2: at most three records exist,
+    the one being refilled and two awaiting their weight gradients, and the GPU always has two blocks of work queued."""
     done = None if on_layer_done is None else (lambda li: on_layer_done(tag, li))
     nb = len(views.blocks)
     fc2_gb = _fc2_gb_route(views, nb - 1, drop)
@@ -390,11 +449,21 @@ def _trunk_backward(dx, saved_blocks, views, segs, tag, alpha, beta, on_layer_do
         side = side_stream(dx.device)
         return chain.blocks_backward(dx, saved_blocks, views, alpha, side.stream.cuda_stream if side.enabled else None, done,
                                      beta_acc=beta, tag=ws_tag, last_fc2_bias_done=fc2_gb is not None)
+    side = side_stream(dx.device) if recompute is not None else None
+    behind = [] if side is not None and side.enabled else None      # events on the side stream, one per block whose backward is issued
     for li in range(nb - 1, -1, -1):
         prev_fc2_gb = _fc2_gb_route(views, li - 1, drop)
-        dx = block_backward(dx, saved_blocks[li], views.blocks[li], segs, views.heads, alpha, beta,
-                            fc2_bias_done=fc2_gb is not None, prev_fc2_gb=prev_fc2_gb, drop=_UNSCALED if drop is None else drop[li])
-        saved_blocks[li] = None     # the block's record goes as soon as its backward has run
+        entry = _UNSCALED if drop is None else drop[li]
+        rec = saved_blocks[li]
+        if recompute is not None:
+            if behind is not None and len(behind) == 2:
+                behind.pop(0).synchronize()
+            rec = _refill(rec, views.blocks[li], segs, views.heads, recompute, entry)
+        dx = block_backward(dx, rec, views.blocks[li], segs, views.heads, alpha, beta,
+                            fc2_bias_done=fc2_gb is not None, prev_fc2_gb=prev_fc2_gb, drop=entry)
+        saved_blocks[li] = rec = None     # the block's record goes as soon as its backward has run
+        if behind is not None:
+            behind.append(side.stream.record_event())     # (after the release: behind what the allocator recorded for it)
         fc2_gb = prev_fc2_gb
         if done is not None:
             done(li)      # bucket launch waits on the side stream's event, not on this stream
@@ -465,7 +534,7 @@ def _add_positions(x, pos, segs, masks, fan):
 
 
 def encoder_forward(ew: EncoderW, clips, masks: Optional[List[torch.Tensor]], save: bool, final_norm=True, ws_tag=None,
-                    gemm_flags=0, gates=None, pos=None, drop=None):
+                    gemm_flags=0, gates=None, pos=None, drop=None, recompute=None):
     """clips fp32 [B,3,T,H,W], or still images [B,3,H,W] standing for the clip that repeats each image along time; for the image
     model (ew.image) images [B,3,H,W], or frames [B,3,T,H,W] (or a list of such clips) each encoded on its own (_pack_tokens); masks:
     None (all N tokens) or a list of int64 [B,K_i] index tensors.  pos (fp32 [N, D], default ew.pos): the position table of
@@ -473,7 +542,10 @@ def encoder_forward(ew: EncoderW, clips, masks: Optional[List[torch.Tensor]], sa
     Returns (out [sum_i B*K_i, D] bf16, segs, saved).  With final_norm=False the last residual stream is returned
     (the target path fuses the final norm into vj_target_rows).  gates: see _wait_gates.  drop: stochastic depth, None or one
     (s_attn, s_mlp) entry per block, each entry or scale possibly None (_drop_plan).  save: keep what encoder_backward needs, an
-    EncoderSaved whose `fan` is the still front end's fan-out (B, cells, gt), None for every other input.
+    EncoderSaved whose `fan` is the still front end's fan-out (B, cells, gt), None for every other input.  recompute: None or
+    "none" (keep every block's record, the default), "mlp" (keep all but u and g; one fc1 GEMM refills them before the block's backward)
+    or "block" (keep the block's input alone; block_forward runs again before the block's backward).  The per-kernel chain only, with
+    save=True; outputs and gradients are the same bits in every mode.
 
     Still images: only the gh*gw distinct tubelets are packed and embedded (_pack_tokens, then a GEMM on B*gh*gw rows) and the gt
     temporal slices differ only in their position rows (_add_positions); with masks, the kept rows are packed one by one and go
@@ -482,17 +554,19 @@ def encoder_forward(ew: EncoderW, clips, masks: Optional[List[torch.Tensor]], sa
     section 5), and the position add is the same single fp32 rounding."""
     pos = ew.pos if pos is None else pos
     plan = _drop_plan(ew, clips, drop, ws_tag)
+    recompute = _recompute_mode(recompute, save, ws_tag)
     if ew.image and save:
         raise ValueError("encoder_forward: the image model is a frozen (save=False) path")
     tok, segs, fan = _pack_tokens(ew, clips, masks, pos.shape[0])     # (the packing launches go out before the gates are waited for)
     _wait_gates(gates, _chained(ws_tag))
     x = ops.gemm_nt(tok, ew.patch.w, bias=ew.patch.b, flags=(gemm_flags & 0xffff if not gemm_flags >> 16 else 0) or None)
     x = _add_positions(x, pos, segs, masks, fan)
-    x, saved_blocks = _trunk_forward(x, ew, segs, save, ws_tag, gemm_flags, gates, drop=plan)
+    x, saved_blocks = _trunk_forward(x, ew, segs, save, ws_tag, gemm_flags, gates, drop=plan, recompute=recompute)
     if not final_norm:
         return x, segs, None
     out, mean, rstd = ops.layernorm_fwd(x, ew.norm.g, ew.norm.b, LN_EPS, save_stats=save)
-    saved = EncoderSaved(tok=tok, blocks=saved_blocks, x=x, mean=mean, rstd=rstd, drop=plan, fan=fan) if save else None
+    saved = EncoderSaved(tok=tok, blocks=saved_blocks, x=x, mean=mean, rstd=rstd, drop=plan, fan=fan,
+                         recompute=recompute) if save else None
     return out, segs, saved
 
 
@@ -511,7 +585,8 @@ def encoder_backward(dout, saved, ew: EncoderW, segs, alpha: float, on_layer_don
     # (not for a last block whose MLP branch is scaled by stochastic depth: its fc2's dY is the scaled copy of dx)
     dx = ops.layernorm_bwd(dout, saved.x, ew.norm.g, saved.mean, saved.rstd, ew.norm.gg, ew.norm.gb, alpha=alpha,
                            accumulate=beta != 0.0, dxsum=_fc2_gb_route(ew, len(ew.blocks) - 1, saved.drop))
-    dx = _trunk_backward(dx, saved.blocks, ew, segs, "enc", alpha, beta, on_layer_done, ws_tag, drop=saved.drop)
+    dx = _trunk_backward(dx, saved.blocks, ew, segs, "enc", alpha, beta, on_layer_done, ws_tag, drop=saved.drop,
+                         recompute=saved.recompute)
     if saved.fan is not None:
         dx = ops.slice_sum(dx, *saved.fan)
     _linear_backward(dx, saved.tok, ew.patch, alpha, need_dx=False, beta=beta)

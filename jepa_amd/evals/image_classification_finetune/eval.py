@@ -6,7 +6,7 @@
 The reference releases no such loop; this one is the frozen image eval (..image_classification_frozen.eval) with the encoder left
 trainable, the way ..video_classification_finetune.eval sits on the frozen video eval.  It takes the frozen image eval's dictionary
 and the video fine-tuning eval's `optimization.finetune` section, key for key (encoder_lr, layer_decay, encoder_weight_decay,
-clip_grad, drop_path, mix and its sub-keys: that module's docstring has the semantics; parse_finetune, parse_mix and the mechanics
+clip_grad, drop_path, recompute, mix and its sub-keys: that module's docstring has the semantics; parse_finetune, parse_mix and the mechanics
 of the encoder's step and checkpoint are its definitions, not copies).
 
 A training iteration: the [B,C,H,W] batch goes through the video encoder with gradients enabled, in one call

@@ -14,6 +14,7 @@ left trainable.  It takes that eval's dictionary -- the same keys, `data.dataset
         encoder_weight_decay: 0.05    # constant; biases and 1-D tensors get 0
         clip_grad: null               # max global norm of the encoder's gradient
         drop_path: 0.0                # stochastic depth: block i of L drops each branch per clip at rate drop_path * i / (L - 1)
+        recompute: none               # none | mlp | block: recompute block activations in the backward instead of keeping them
         mix:                          # absent (the default): off.  Present: the sub-keys left out take these values
           mixup_alpha: 0.8            # lam ~ Beta(alpha, alpha): x_i <- lam x_i + (1 - lam) x_(B-1-i); 0: no mixup
           cutmix_alpha: 1.0           # a box of area (1 - lam) S^2 of x_(B-1-i) replaces that of x_i; 0: no cutmix
@@ -39,14 +40,21 @@ key an iteration issues the launches it issued before.  The data, the probe, its
 the frozen eval's load_pretrained(checkpoint_key='encoder') reads) and `encoder_opt` (Adam moments and step count in
 torch.optim.AdamW's format).
 
+`recompute` (VisionTransformer.set_activation_recompute) trades time for memory and nothing else: `block` keeps each block's input
+alone and runs the block's forward again directly before its backward (about one more forward per iteration), `mlp` keeps all but the
+two [M, 4D] tensors of the MLP and refills them with one fc1 GEMM per block.  Losses, gradients and weights are the same bits in every
+mode, validation (no_grad) is untouched, and the checkpoint does not hold the mode: a run resumed with another one continues
+bit-identically.  profiles/finetune_recompute.md has the measured time and memory.
+
 Limits, all raising: one rank; video encoders at their native clip size (image encoders are frozen-path features, and so are still
 images and off-native sizes unless the module opted in -- VisionTransformer.train_on_any_input, which this eval leaves off and
 ..image_classification_finetune.eval switches on); the lone probe (`optimization.multihead_kwargs` is the frozen evals'); every clip of a batch in one encoder call;
-0 <= drop_path < 1; `mix`: alphas >= 0, probabilities in [0, 1], 0 <= label_smoothing < 1, unknown sub-keys raise.
+0 <= drop_path < 1; `recompute` one of none, mlp, block (the words: true, 1 and anything else raise); `mix`: alphas >= 0, probabilities in [0, 1], 0 <= label_smoothing < 1, unknown sub-keys raise.
 """
 from types import SimpleNamespace
 
 from ...engine.finetune import EncoderFineTuner
+from ...engine.layers import recompute_mode
 from ...src.utils.logging import get_logger
 from ..mix import MixDraw
 from ..video_classification_frozen import eval as frozen_eval
@@ -92,7 +100,7 @@ def parse_mix(section):
 def parse_finetune(args_opt):
     """The `optimization.finetune` section with its defaults."""
     ft = args_opt.get('finetune', None) or {}
-    unknown = sorted(set(ft) - {'encoder_lr', 'layer_decay', 'encoder_weight_decay', 'clip_grad', 'drop_path', 'mix'})
+    unknown = sorted(set(ft) - {'encoder_lr', 'layer_decay', 'encoder_weight_decay', 'clip_grad', 'drop_path', 'mix', 'recompute'})
     if unknown:
         raise ValueError(f"optimization.finetune: unknown keys {unknown}")
     encoder_lr = ft.get('encoder_lr', None)
@@ -101,7 +109,8 @@ def parse_finetune(args_opt):
                            encoder_weight_decay=ft.get('encoder_weight_decay', 0.05),
                            clip_grad=ft.get('clip_grad', None),
                            drop_path=ft.get('drop_path', 0.0),
-                           mix=parse_mix(ft.get('mix', None)))
+                           mix=parse_mix(ft.get('mix', None)),
+                           recompute=recompute_mode(ft.get('recompute', 'none'), "optimization.finetune.recompute") or 'none')
 
 
 class _FineTune:
@@ -125,6 +134,7 @@ class _FineTune:
     def attach(self, cfg, run, aggregation):
         ft, encoder = self.ft, self.encoder_of(aggregation)
         encoder.set_drop_path_rate(ft.drop_path)
+        encoder.set_activation_recompute(ft.recompute)
         aggregation.train()     # training iterations drop in training mode only; validation runs under no_grad and drops nothing
         tuner = EncoderFineTuner(encoder, layer_decay=ft.layer_decay, world_size=run.world_size)
         lr_ratio = ft.encoder_lr / cfg.lr
@@ -145,7 +155,8 @@ class _FineTune:
 
         logger.info(f'fine-tuning the encoder: lr {ft.encoder_lr} x {ft.layer_decay} ** (layers below the last), weight decay '
                     f'{ft.encoder_weight_decay}, clip {ft.clip_grad}, {len(tuner.param_groups)} parameter ranges, stochastic depth '
-                    f'{ft.drop_path} (per block: {", ".join("%.3f" % r for r in encoder.drop_path_rates)})')
+                    f'{ft.drop_path} (per block: {", ".join("%.3f" % r for r in encoder.drop_path_rates)}), activation recomputation '
+                    f'{ft.recompute}')
         self.tuner = tuner
         epoch = dict(features_grad=True, after_update=after_update)
         if ft.mix is not None:

@@ -28,7 +28,7 @@ import torch.nn as nn
 
 from ...engine import hipmodule
 from ...engine.chain import Workspace
-from ...engine.layers import encoder_backward, encoder_forward
+from ...engine.layers import encoder_backward, encoder_forward, recompute_mode
 from ..utils.tensors import trunc_normal_
 from .utils.modules import Block
 from .utils.patch_embed import PatchEmbed, PatchEmbed3D
@@ -57,6 +57,7 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         self.last_drop_path_scales = None   # fp32 [L, 2, B]: the scales of the latest forward that dropped anything
         self.set_drop_path_rate(drop_path_rate, depth)
         self.any_input_trains = False       # train_on_any_input: still images and off-native sizes with gradients enabled
+        self.activation_recompute = None    # set_activation_recompute: None (off), "mlp" or "block"
         self.num_features = self.embed_dim = embed_dim
         self.num_heads = num_heads
         self.out_layers = out_layers
@@ -172,6 +173,16 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         position table is a constant.  Off, such inputs raise while gradients are enabled, as they always have.  The image model
         (num_frames=1) keeps raising either way."""
         self.any_input_trains = bool(flag)
+        return self
+
+    def set_activation_recompute(self, mode):
+        """Opt in (per module, default off, not part of the state dict) to recomputing block activations in the backward of every
+        forward that records one -- native clips, masks and, with train_on_any_input, still images and off-native clips -- instead of
+        keeping them: "block" keeps each block's input alone and runs the block's forward again directly before its backward, "mlp"
+        keeps all but the two [M, 4D] tensors of the MLP and refills them with one fc1 GEMM; None or "none" is off.  Outputs and
+        gradients are the same bits in every mode (the forward kernels are run-to-run deterministic); what changes is the memory held
+        between the forward and the backward, and the time of the backward.  The frozen / no-grad path keeps nothing and ignores it."""
+        self.activation_recompute = recompute_mode(mode, "set_activation_recompute: mode")
         return self
 
     def no_weight_decay(self):
@@ -348,7 +359,8 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         if masks is not None:
             masks = [m.contiguous() for m in masks]
         if self._needs_grad():
-            return hipmodule.run_with_autograd(self, _enc_fwd, _enc_bwd, (x, masks, self._drop_path_entries(x, inp), pos))
+            return hipmodule.run_with_autograd(self, _enc_fwd, _enc_bwd, (x, masks, self._drop_path_entries(x, inp), pos,
+                                                                             self.activation_recompute))
         # inference: one C call per trunk (no saved activations, a private workspace) and, because nothing else shares the
         # GPU with this stream, the two-workgroups-per-CU GEMM (gemm4w.hip; see DESIGN.md section 6 for why training does not)
         ew = self._hip_views(train=False)
@@ -366,8 +378,8 @@ INFER_GEMM_FLAGS = 0x100
 
 
 def _enc_fwd(module, ew, args, diff):
-    x, masks, drop, pos = args     # pos: None (the arena's table) or the interpolated table of x's grid, a constant
-    out, segs, saved = encoder_forward(ew, x, masks, save=True, drop=drop, pos=pos)
+    x, masks, drop, pos, recompute = args     # pos: None (the arena's table) or the interpolated table of x's grid, a constant
+    out, segs, saved = encoder_forward(ew, x, masks, save=True, drop=drop, pos=pos, recompute=recompute)
     return out, segs, (saved, segs)
 
 

@@ -39,14 +39,19 @@ times vj_drop_path_add / vj_drop_path_scale alone on the trunk's M x D rows, eve
 values (mixup 0.8, cutmix 1.0, prob 1, switch 0.5, label smoothing 0.1: vj_clip_mix on every segment, vj_soft_ce for the loss), and
 times vj_clip_mix alone on one segment batch [4,3,16,224,224] (a mixup plan, which moves every byte, and a cutmix plan with a box of
 half the side) beside vj_copy_rows on the same bytes, and vj_soft_ce at R = 4, C in {400, 1000}.
-python tools/eval_bench.py --finetune [--segments 1 8] [--rounds 4] [--reps 3] [--drop-path 0.1] [--mix]
+--recompute MODE (mlp or block) adds another arm in the same rotation: the fine-tuning iteration (rate 0) with
+VisionTransformer.set_activation_recompute(MODE); ms and peak memory as the other arms', the per-round difference to the plain
+fine-tuning arm, and for every arm the peak of what the allocator held (the whole process, after an empty_cache before the arm).
+--model NAME RES, --batch B and --no-frozen (no frozen arm) reach the configs the default does not, e.g. vit_huge 384.
+python tools/eval_bench.py --finetune [--segments 1 8] [--rounds 4] [--reps 3] [--drop-path 0.1] [--mix] [--recompute block]
+                           [--model vit_huge 384] [--batch 4] [--no-frozen]
 
 --image --finetune: one fine-tuning iteration of the image eval (jepa_amd/evals/image_classification_finetune: batch 16, 1000 classes,
 ViT-L/16-224 and ViT-H/16-384 at 16 frames) on still images, the same iteration on the materialised repeated clip (the ATen repeat
 inside it) and the frozen iteration, the three arms taking turns inside this process in rotating order: ms and peak memory of each,
 the rows the patch-embed GEMM and its weight gradient see on either route, and vj_slice_sum alone beside vj_copy_rows moving the same
-bytes (ms, GB/s).
-python tools/eval_bench.py --image --finetune [--image-configs vitl16_in1k vith16_384_in1k] [--rounds 4] [--reps 3]"""
+bytes (ms, GB/s).  --recompute MODE adds the still-image iteration with that activation-recomputation mode as a fourth arm.
+python tools/eval_bench.py --image --finetune [--image-configs vitl16_in1k vith16_384_in1k] [--rounds 4] [--reps 3] [--recompute mlp]"""
 import argparse
 import json
 import os
@@ -248,7 +253,7 @@ def bench_slice_sum(B, S, Gt, D, reps=20):
                 copy_rows=dict(ms=round(t_copy, 4), gb_per_s=round(2 * M * D * 2 / (t_copy * 1e-3) / 1e9, 1)))
 
 
-def bench_image_finetune(name, reps, rounds, B=16, frames=16):
+def bench_image_finetune(name, reps, rounds, B=16, frames=16, recompute=None):
     """One fine-tuning iteration of the image eval on still images against the same iteration on the materialised repeated clip (the
     ATen repeat inside the iteration: the only route there was) and against the frozen iteration, the three arms taking turns inside
     this process in rotating order; ms and peak memory of each, the rows the patch-embed GEMM and its weight gradient see, and
@@ -286,13 +291,19 @@ def bench_image_finetune(name, reps, rounds, B=16, frames=16):
     def repeated(imgs):     # a plain callable: run_one_epoch hands it the batch as it is
         return enc_t(imgs.unsqueeze(2).repeat(1, 1, frames, 1, 1))
 
-    def iteration(encoder, clf, opt, **kw):
+    def iteration(encoder, clf, opt, mode=None, **kw):
         optimizer, scaler, sched, wd_sched = opt
-        return lambda: IE.run_one_epoch(dev, True, encoder, clf, scaler, optimizer, sched, wd_sched, [(images, labels)], False, **kw)
+
+        def run():
+            enc_t.set_activation_recompute(mode)
+            IE.run_one_epoch(dev, True, encoder, clf, scaler, optimizer, sched, wd_sched, [(images, labels)], False, **kw)
+        return run
 
     tune = dict(features_grad=True, after_update=step)
     arms = {"still": iteration(enc_t, clf_t, opt_t, **tune), "repeat": iteration(repeated, clf_t, opt_t, **tune),
             "frozen": iteration(enc_f, clf_f, opt_f)}
+    if recompute:
+        arms[f"still_{recompute}"] = iteration(enc_t, clf_t, opt_t, mode=recompute, **tune)
     torch.cuda.synchronize()
     resident = torch.cuda.memory_allocated() - base
     for fn in arms.values():        # warm-up: code load, and what stays allocated afterwards (workspaces, scratch, the probes' .grad
@@ -308,7 +319,7 @@ def bench_image_finetune(name, reps, rounds, B=16, frames=16):
     ms = {arm: [] for arm in arms}
     names = list(arms)
     for r in range(rounds):
-        order = names[r % 3:] + names[:r % 3]
+        order = names[r % len(names):] + names[:r % len(names)]
         for arm in (order if r % 2 == 0 else order[::-1]):
             ms[arm].append(timed(arms[arm], reps))
     mean = {arm: statistics.mean(v) for arm, v in ms.items()}
@@ -326,6 +337,11 @@ def bench_image_finetune(name, reps, rounds, B=16, frames=16):
         out[f"peak_mem_gib_{arm}_iteration"] = peak[arm]
     out["still_minus_repeat_ms_rounds"] = [round(a - b, 2) for a, b in zip(ms["still"], ms["repeat"])]
     out["still_minus_repeat_ms"] = round(mean["still"] - mean["repeat"], 2)
+    if recompute:
+        enc_t.set_activation_recompute(None)
+        out["recompute"] = recompute
+        out[f"{recompute}_minus_still_ms_rounds"] = [round(a - b, 2) for a, b in zip(ms[f"still_{recompute}"], ms["still"])]
+        out[f"{recompute}_over_still"] = round(mean[f"still_{recompute}"] / mean["still"], 3)
     out["slice_sum_kernel"] = bench_slice_sum(B, cells, gt, enc_t.embed_dim)
     return out
 
@@ -585,7 +601,8 @@ def bench_mix_kernels(B=4, T=16, res=224, reps=20):
     return res_
 
 
-def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400, drop_path=None, mix=False):
+def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400, drop_path=None, mix=False, recompute=None,
+                   frozen_arm=True):
     from jepa_amd.evals.mix import MixDraw
     import statistics
     from jepa_amd.engine.finetune import EncoderFineTuner
@@ -615,9 +632,10 @@ def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400,
     def step(optimizer, grad_scale):
         tuner.step(optimizer.param_groups[0]['lr'], 0.05, grad_scale=grad_scale)
 
-    def finetune_at(rate, mix=None):
+    def finetune_at(rate, mix=None, recompute=None):
         def run():
             enc_t.model.set_drop_path_rate(rate)
+            enc_t.model.set_activation_recompute(recompute)
             run_one_epoch(dev, True, enc_t, clf_t, scaler_t, opt_t, sched_t, wd_t, [train], False, 1, S, True,
                           features_grad=True, after_update=step, mix=mix)
         return run
@@ -629,16 +647,22 @@ def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400,
     if mix:
         # (the clips are mixed in place iteration after iteration: convex combinations and swaps, they stay what they were in scale)
         arms["finetune_mix"] = finetune_at(0.0, MixDraw(num_classes=C, **MIX_RECIPE))
+    if recompute:
+        arms[f"finetune_{recompute}"] = finetune_at(0.0, recompute=recompute)
+    if not frozen_arm:      # (a model too large for two copies and the plain arm's activations: the fine-tuning arms alone)
+        del arms["frozen"]
     torch.cuda.synchronize()
     resident = torch.cuda.memory_allocated() - base
-    peak = {}
+    peak, reserved = {}, {}
     for arm, fn in arms.items():    # warm-up (workspace growth, code load) and the peak memory of each arm on its own
         torch.cuda.synchronize()
+        torch.cuda.empty_cache()    # so that what the allocator holds at this arm's peak is this arm's
         before = torch.cuda.memory_allocated()
         torch.cuda.reset_peak_memory_stats()
         fn()
         torch.cuda.synchronize()
         peak[arm] = round((torch.cuda.max_memory_allocated() - before) / 2 ** 30, 2)
+        reserved[arm] = round(torch.cuda.max_memory_reserved() / 2 ** 30, 2)
     ms = {arm: [] for arm in arms}
     names = list(arms)
     for r in range(rounds):
@@ -647,8 +671,21 @@ def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400,
         for arm in (order if r % 2 == 0 or len(names) == 2 else order[::-1]):
             ms[arm].append(timed(arms[arm], reps))
     enc_t.model.set_drop_path_rate(0.0)
+    enc_t.model.set_activation_recompute(None)
     mean = {arm: statistics.mean(v) for arm, v in ms.items()}
     drop = {}
+    if recompute:
+        arm = f"finetune_{recompute}"
+        d = ms[arm]
+        drop.update({"recompute": recompute, f"{arm}_ms_rounds": [round(v, 2) for v in d], f"{arm}_iteration_ms": round(mean[arm], 2),
+                     f"{arm}_ms_spread": round(max(d) - min(d), 2),
+                     f"{recompute}_minus_plain_ms_rounds": [round(a - b, 2) for a, b in zip(d, ms["finetune"])],
+                     f"{recompute}_minus_plain_ms": round(mean[arm] - mean["finetune"], 2),
+                     f"{recompute}_over_plain": round(mean[arm] / mean["finetune"], 3),
+                     f"peak_mem_gib_{arm}_iteration": peak[arm]})
+    drop["peak_reserved_gib_process"] = reserved     # (the whole process: both models and the clips included)
+    if not frozen_arm:
+        ms["frozen"], mean["frozen"], peak["frozen"] = [float("nan")], float("nan"), None
     if drop_path:
         d = ms["finetune_drop"]
         drop = dict(drop_path=drop_path, finetune_drop_ms_rounds=[round(v, 2) for v in d],
@@ -685,6 +722,12 @@ def main():
     ap.add_argument("--segments", nargs="*", type=int, default=[1, 8])
     ap.add_argument("--drop-path", type=float, default=None, help="with --finetune: a third arm, fine-tuning with stochastic depth at this rate")
     ap.add_argument("--mix", action="store_true", help="with --finetune: another arm, fine-tuning with mixup / cutmix / label smoothing")
+    ap.add_argument("--recompute", choices=["mlp", "block"], default=None,
+                    help="with --finetune: another arm, fine-tuning with this activation-recomputation mode")
+    ap.add_argument("--model", nargs=2, default=["vit_large", "224"], metavar=("NAME", "RES"),
+                    help="with --finetune: the encoder factory and the clip resolution (default vit_large 224)")
+    ap.add_argument("--batch", type=int, default=4, help="with --finetune: clips per segment")
+    ap.add_argument("--no-frozen", action="store_true", help="with --finetune: leave the frozen arm out (the fine-tuning arms alone)")
     ap.add_argument("--uint8", action="store_true", help="the video eval's input edge: fp32 views + .to(device) against uint8 frames + prefetch")
     ap.add_argument("--frames", action="store_true", help="FrameAggregation on the ViT-L/16 image model instead of the video eval")
     ap.add_argument("--image", action="store_true", help="the image-classification eval instead of the video one")
@@ -696,12 +739,14 @@ def main():
     a = ap.parse_args()
     if a.image and a.finetune:
         for name in a.image_configs:
-            print(json.dumps(bench_image_finetune(name, a.reps, a.rounds)), flush=True)
+            print(json.dumps(bench_image_finetune(name, a.reps, a.rounds, recompute=a.recompute)), flush=True)
             torch.cuda.empty_cache()
         return
     if a.finetune:
         for S in a.segments:
-            print(json.dumps(bench_finetune(a.reps, a.rounds, S, drop_path=a.drop_path, mix=a.mix)), flush=True)
+            print(json.dumps(bench_finetune(a.reps, a.rounds, S, drop_path=a.drop_path, mix=a.mix, recompute=a.recompute,
+                                            B=a.batch, model_name=a.model[0], res=int(a.model[1]), frozen_arm=not a.no_frozen)),
+                  flush=True)
             torch.cuda.empty_cache()
         return
     if a.uint8:
