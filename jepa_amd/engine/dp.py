@@ -9,6 +9,9 @@ launches the all-reduce of that layer's contiguous slice of the gradient arena o
 Small tensors (biases, LayerNorm affine, mask tokens) are reduced in one tail bucket.  The SUM is turned into the
 mean inside the fused AdamW kernel (gscale = 1/world), so no extra pass touches the gradients.
 
+The same reducer serves a stand-alone encoder that is fine-tuned (engine.finetune.EncoderFineTuner): its arena is laid out by
+layer, so it hands in an explicit bucket plan (finetune_bucket_plan) and the encoder's own backward drives the hooks.
+
 With world_size == 1 every method is a no-op.  On CPU tensors (gloo, used by the tests) the same bucket walk
 runs synchronously.
 
@@ -29,8 +32,80 @@ import torch.distributed as dist
 from .streams import independent_stream, side_stream
 
 
+def trainer_bucket_plan(sl, n_enc, n_pred, pred_layers_per_bucket=4):
+    """The buckets of the pretraining step's arena (slots `sl` named enc.* / pred.*): one per encoder block (its four matrices) at
+    hook ("enc", li), the patch embedding's weight at ("enc", -1), the predictor's blocks in groups of pred_layers_per_bucket at
+    the hook of each group's lowest block, predictor_proj.weight at ("pred", n_pred)."""
+    def span(prefix, names):
+        offs = [sl[prefix + n] for n in names]
+        return (min(s.off for s in offs), max(s.off + ((s.numel + 63) // 64) * 64 for s in offs))
+
+    buckets = {}
+    mats = ["attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight"]
+    for li in range(n_enc):
+        buckets[("enc", li)] = [span(f"enc.blocks.{li}.", mats)]
+    buckets[("enc", -1)] = [span("enc.", ["patch_embed.proj.weight"])]
+    group = []
+    for li in range(n_pred - 1, -1, -1):
+        group.append(span(f"pred.predictor_blocks.{li}.", mats))
+        if len(group) == pred_layers_per_bucket or li == 0:
+            buckets[("pred", li)] = [(min(g[0] for g in group), max(g[1] for g in group))]
+            group = []
+    buckets[("pred", n_pred)] = [span("pred.", ["predictor_proj.weight"])]
+    return buckets
+
+
+def finetune_bucket_plan(slots, group_ranges, total=None):
+    """The bucket plan of a fine-tuned encoder's arena (engine.finetune.EncoderFineTuner), from what weights.layout() returned for
+    optstate.layer_decay_groups(...): pure, no device, no process group.  -> {(kind, layer): [(lo, hi)]} for GradReducer(plan=...).
+
+    The decayed range of layer id l -- one contiguous range per (layer id, no-decay) group -- holds the matrices only:
+      ("enc", li)  the decayed range of layer li + 1: the four matrices of block li, final when the hook of block li fires (their
+                   weight gradients are on the side stream by then, which is what the bucket's launch waits for);
+      ("enc", -1)  the decayed range of layer 0, patch_embed.proj.weight, final at the hook after the patch embedding's backward.
+    No no-decay range is in the plan, so all of them fall to the tail, which finish() reduces after the whole backward.  They could
+    not ride with their block: the LayerNorm backward of a NEIGHBOURING block writes some of them -- block li's fc2.bias comes out of
+    norm1's backward of block li + 1 (the final norm's for the last block) or, under a stochastic-depth scale, out of block li's own
+    column sum (layers._fc2_gb_route), proj.bias out of norm2's backward or a column sum -- and every LayerNorm's affine gradients
+    are written on the main stream, which the hook's event (recorded on the side stream) does not cover.  Uncovered ranges that
+    touch go out as one collective: the last block's small tensors and the final norm's are neighbours, so the tail of a depth-L
+    encoder is L + 1 collectives (a range per block below the last, and the patch embedding's bias)."""
+    from .optstate import is_no_decay, layer_id
+    by_range = [[] for _ in group_ranges]
+    for s in slots.values():
+        hit = [i for i, (lo, hi) in enumerate(group_ranges) if lo <= s.off < hi]
+        if len(hit) != 1:
+            raise ValueError(f"finetune_bucket_plan: {s.name} at {s.off} lies in {len(hit)} of the ranges {group_ranges}")
+        by_range[hit[0]].append(s)
+    blocks = [int(s.name.split(".")[1]) for s in slots.values() if s.name.startswith("blocks.")]
+    depth = max(blocks) + 1 if blocks else 0
+    plan = {}
+    for (lo, hi), members in zip(group_ranges, by_range):
+        if not members:
+            raise ValueError(f"finetune_bucket_plan: the range {(lo, hi)} holds no tensor")
+        kinds = {is_no_decay(s.name, s.param) for s in members}
+        layers = {layer_id(s.name, depth) for s in members}
+        if len(kinds) != 1 or len(layers) != 1:
+            raise ValueError(f"finetune_bucket_plan: the range {(lo, hi)} mixes layers {sorted(layers)} or decayed and no-decay "
+                             "tensors: not the layout of optstate.layer_decay_groups")
+        lid = layers.pop()
+        if kinds.pop() or lid > depth:     # no-decay tensors, and anything decayed beside the blocks and the patch embedding: the tail
+            continue
+        key = ("enc", lid - 1)
+        if key in plan:
+            raise ValueError(f"finetune_bucket_plan: two decayed ranges for layer {lid}")
+        plan[key] = [(lo, hi)]
+    if total is not None and group_ranges and (group_ranges[0][0] != 0 or group_ranges[-1][1] != total):
+        raise ValueError(f"finetune_bucket_plan: the ranges {group_ranges[0]} ... {group_ranges[-1]} do not span [0, {total})")
+    return plan
+
+
 class GradReducer:
-    def __init__(self, arena, vit, pred, world_size, overlap=True, pred_layers_per_bucket=4):
+    def __init__(self, arena, vit, pred, world_size, overlap=True, pred_layers_per_bucket=4, plan=None):
+        """Two ways in.  The Trainer's: `vit` and `pred`, whose `enc.` / `pred.` names in the arena give the buckets
+        (trainer_bucket_plan).  Any other arena's: `plan`, a mapping (kind, layer) -> [(lo, hi), ...] over arena.G whose keys are the
+        hooks layer_done() is called with (vit and pred are then unused and may be None).  Either way the tail, reduced by finish(),
+        is whatever the buckets leave uncovered of [0, arena.total)."""
         self.arena = arena
         import os
         self.world = world_size
@@ -57,24 +132,11 @@ class GradReducer:
         self.exposed_samples = 0
         if not self.enabled:
             return
-        sl = arena.slots
-
-        def span(prefix, names):
-            offs = [sl[prefix + n] for n in names]
-            return (min(s.off for s in offs), max(s.off + ((s.numel + 63) // 64) * 64 for s in offs))
-
-        mats = ["attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight"]
-        for li in range(len(vit.blocks)):
-            self.buckets[("enc", li)] = [span(f"enc.blocks.{li}.", mats)]
-        self.buckets[("enc", -1)] = [span("enc.", ["patch_embed.proj.weight"])]
-        n_pred = len(pred.predictor_blocks)
-        group = []
-        for li in range(n_pred - 1, -1, -1):
-            group.append(span(f"pred.predictor_blocks.{li}.", mats))
-            if len(group) == pred_layers_per_bucket or li == 0:
-                self.buckets[("pred", li)] = [(min(g[0] for g in group), max(g[1] for g in group))]
-                group = []
-        self.buckets[("pred", n_pred)] = [span("pred.", ["predictor_proj.weight"])]
+        if plan is not None:
+            # an explicit plan (a tuner's arena, finetune_bucket_plan): the hooks and ranges are the caller's, in its order
+            self.buckets = {key: [(int(lo), int(hi)) for lo, hi in ranges] for key, ranges in plan.items()}
+        else:
+            self.buckets = trainer_bucket_plan(arena.slots, len(vit.blocks), len(pred.predictor_blocks), pred_layers_per_bucket)
         # everything not covered above (small tensors + predictor_embed + mask tokens) goes in the tail
         covered = sorted(r for rs in self.buckets.values() for r in rs)
         pos, total = 0, arena.total

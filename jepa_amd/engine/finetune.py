@@ -10,19 +10,31 @@ with layer-wise learning-rate decay.
 The encoder's parameters become views of the arena and their `.grad` views of the gradient arena, so `_ModuleFn.backward` hands
 autograd nothing for them: what the backward chain wrote IS the gradient (every backward overwrites it; nothing accumulates).
 No kernel of its own: vj_sqnorm_f32, vj_step_advance, vj_adamw_ema_guarded (tgt = NULL) and the single-launch transposed refresh.
-One rank only: reducing encoder gradients across ranks is engine.dp's job.
+
+Several ranks (world_size > 1 with torch.distributed initialised at that size; VJ_FORCE_DP=1 with a one-rank group takes the same path,
+as it does for the Trainer): the encoder is not wrapped in DistributedDataParallel -- autograd never sees its gradients, so DDP's
+hooks would never fire.  The tuner builds engine.dp.GradReducer over its arena from dp.finetune_bucket_plan, broadcasts the master
+weights from rank 0, and hands the reducer to the encoder, whose backward launches a block's bucket as soon as the block is done
+and the small tensors' tail at the end.  The arena then holds the SUM over the ranks; step() folds 1 / world into the factor the
+fused update already takes for the GradScaler, so the norm, the clip and the non-finite guard act on the averaged gradient, and a
+non-finite value on any rank -- which the sum carries to every rank -- skips the step everywhere without a collective of its own.
 """
+import os
+
 import torch
+import torch.distributed as dist
 
 from ..hip import ops
 from . import optstate
-from .streams import device_index
+from .dp import GradReducer, broadcast_parameters, finetune_bucket_plan
+from .streams import device_index, side_stream
 from .weights import ParamArena, bump_generation, wait_pending_update
 
 
 class EncoderFineTuner:
     def __init__(self, encoder, layer_decay=0.75, betas=(0.9, 0.999), eps=1e-8, world_size=1):
-        if world_size > 1:
+        group = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 0     # 0: no process group
+        if world_size > 1 and group != world_size:
             raise NotImplementedError(f"EncoderFineTuner: world_size={world_size}: fine-tuning runs on one rank (the encoder's "
                                       "gradients are not reduced across ranks; that is engine.dp's job)")
         if not getattr(encoder, "is_video", False):
@@ -54,6 +66,20 @@ class EncoderFineTuner:
         self._slot_of = {id(s.param): s for s in A.slots.values()}
         self._step_dev = torch.zeros(1, dtype=torch.float32, device=device)   # Adam step count t (advanced on the device)
         self._stat = torch.zeros(4, dtype=torch.float32, device=device)       # [sum g^2, non-finite count, 0, 0]
+        self.world = int(world_size)
+        self.reducer = None
+        if world_size > 1 or (group == 1 and os.environ.get("VJ_FORCE_DP", "0") == "1"):
+            self._attach_reducer()
+
+    def _attach_reducer(self):
+        """Every rank calls this at the same point: prepare() and the broadcast are collectives."""
+        A = self.arena
+        self.reducer = GradReducer(A, None, None, self.world, plan=finetune_bucket_plan(A.slots, A.group_ranges, A.total))
+        side = side_stream(self.device)
+        self.reducer.prepare(side.stream if side.enabled else None)
+        broadcast_parameters(A)      # nothing else makes the ranks start equal: no DDP wraps the encoder
+        self.sync_shadows()
+        self.encoder.grad_reducer = self.reducer
 
     # ------------------------------------------------------------------------------------------------ update
     @property
@@ -68,10 +94,10 @@ class EncoderFineTuner:
         """One AdamW step of every range at lr * lr_scale (weight decay wd, 0 for the no-decay ranges), the bf16 shadows in the
         same pass, then the transposed shadows.  clip: max global gradient norm (torch.nn.utils.clip_grad_norm_), None for none.
         grad_scale: the factor a GradScaler put on the loss of this backward; the gradients and their norm are divided by it inside
-        the update.  A non-finite gradient anywhere skips the whole step (weights, moments and the step count stay), decided on
-        the device."""
+        the update, and so is the number of ranks whose gradients the arena sums.  A non-finite gradient anywhere, on any rank,
+        skips the whole step (weights, moments and the step count stay), decided on the device."""
         A = self.arena
-        inv = 1.0 / float(grad_scale)
+        inv = 1.0 / (float(grad_scale) * self.world)      # (several ranks: the arena holds the sum of their gradients)
         ops.sqnorm(A.G, self._stat[0:2])     # the ranges tile the arena and its padding stays zero: one pass gives the global norm
         ops.step_advance(self._stat, self._step_dev)
         b1, b2 = self.betas
@@ -89,7 +115,9 @@ class EncoderFineTuner:
     def grad_stats(self):
         """(global gradient norm, number of non-finite gradient elements) of the last step -- one host sync."""
         sq, bad = self._stat[:2].tolist()
-        return sq ** 0.5, int(bad)     # (of the gradients as the backward left them: times grad_scale where one was given)
+        # (of the gradients as the backward left them, times grad_scale where one was given; on several ranks of their mean, so
+        #  that a log compares with a one-rank run's)
+        return sq ** 0.5 / self.world, int(bad)
 
     def zero_grad(self, set_to_none=False):
         """Clears the gradient arena.  The parameters' `.grad` stay views of it (set_to_none is ignored: a `.grad` that is not the

@@ -25,7 +25,11 @@ checkpoint adds `encoder` (a state dict in the reference's names, which the froz
 `data.auto_augment` (null, 'original' or a `rand-...` string such as 'rand-m9-mstd0.5-inc1', the usual image fine-tuning recipe) is
 the frozen image eval's key, read by its parser (`parse_auto_augment`, re-exported here); `mix` still mixes the finished fp32 buffer.
 
-Limits, all raising: one rank; `pretrain.frames_per_clip` == 1 (the 2-D image encoder runs on the frozen / no-grad path only); the
+Several ranks run as the video fine-tuning eval's do (its docstring: the sharded loader, the DistributedDataParallel probe, the
+encoder's gradients averaged by engine.dp.GradReducer under the backward, per-rank drop-path and mix seeds, rank 0 writing the
+checkpoint), tested with two ranks on one device; nothing about scaling is measured.
+
+Limits, all raising: `pretrain.frames_per_clip` == 1 (the 2-D image encoder runs on the frozen / no-grad path only); the
 lone probe (`optimization.multihead_kwargs` is the frozen evals'); every image of a batch in one encoder call (max_clips_per_call);
 with `mix`, an image width that is a multiple of 4 (vj_clip_mix moves four pixels at a time) and square images; and those of the
 `finetune` section itself.

@@ -46,12 +46,26 @@ two [M, 4D] tensors of the MLP and refills them with one fc1 GEMM per block.  Lo
 mode, validation (no_grad) is untouched, and the checkpoint does not hold the mode: a run resumed with another one continues
 bit-identically.  profiles/finetune_recompute.md has the measured time and memory.
 
-Limits, all raising: one rank; video encoders at their native clip size (image encoders are frozen-path features, and so are still
+Several ranks (launched as the frozen evals are: one process per GPU with one visible device each, RANK / WORLD_SIZE from the
+launcher): the loaders shard as the frozen eval's do, the probe is wrapped in DistributedDataParallel as there, and the encoder's
+gradients are averaged by the project's own bucketed reducer (engine.dp.GradReducer, driven by the encoder's backward: a block's
+matrices go out as soon as the block is done, the small tensors after the backward) with the 1 / world folded into the encoder's
+fused update, which therefore clips and guards the averaged gradient; a non-finite gradient on one rank skips the encoder's step
+on all.  The tuner broadcasts rank 0's encoder at construction.  Rank r seeds a drop-path generator of its own with the global
+seed + r and its MixDraw with `mix.seed` + r (rank_seeds), so the ranks drop different branches and each mixes its own local
+batch; rank 0's seeds are the one-rank run's.  Every rank builds the checkpoint's entries, rank 0 writes them, every rank restores
+them; the format is unchanged and a run may resume on another world size.  Only one-GPU hosts have been available: the path is
+tested with two ranks on one device and timed at one forced rank (profiles/finetune_dp.md); scaling, the overlap under real
+traffic and the cost of the small tensors' collectives are unmeasured.
+
+Limits, all raising: video encoders at their native clip size (image encoders are frozen-path features, and so are still
 images and off-native sizes unless the module opted in -- VisionTransformer.train_on_any_input, which this eval leaves off and
 ..image_classification_finetune.eval switches on); the lone probe (`optimization.multihead_kwargs` is the frozen evals'); every clip of a batch in one encoder call;
 0 <= drop_path < 1; `recompute` one of none, mlp, block (the words: true, 1 and anything else raise); `mix`: alphas >= 0, probabilities in [0, 1], 0 <= label_smoothing < 1, unknown sub-keys raise.
 """
 from types import SimpleNamespace
+
+import torch
 
 from ...engine.finetune import EncoderFineTuner
 from ...engine.layers import recompute_mode
@@ -113,6 +127,18 @@ def parse_finetune(args_opt):
                            recompute=recompute_mode(ft.get('recompute', 'none'), "optimization.finetune.recompute") or 'none')
 
 
+def rank_seeds(rank, world_size, mix_seed=0, global_seed=None):
+    """(seed of the encoder's drop-path generator, seed of the MixDraw) of one rank.  Every rank seeds torch's default generator
+    with the evals' global seed at import, so on several ranks the default generator would drop the same branches everywhere and a
+    shared `mix.seed` would mix every local batch alike: each rank takes the global seed + rank and mix.seed + rank instead.  Rank
+    0's are the one-rank seeds -- at world_size 1 the pair is returned for that comparison only: one rank installs no generator and
+    draws from the default one, as it always has."""
+    if not 0 <= rank < max(1, world_size):
+        raise ValueError(f"rank_seeds: rank {rank} of {world_size}")
+    base = frozen_eval._GLOBAL_SEED if global_seed is None else global_seed
+    return base + rank, (mix_seed + rank) % 2 ** 32
+
+
 class _FineTune:
     """What frozen_eval.main takes to leave the encoder trainable.  The image fine-tuning eval (..image_classification_finetune.eval)
     derives from it: `folder_name` and `encoder_of` are what differs."""
@@ -137,6 +163,15 @@ class _FineTune:
         encoder.set_activation_recompute(ft.recompute)
         aggregation.train()     # training iterations drop in training mode only; validation runs under no_grad and drops nothing
         tuner = EncoderFineTuner(encoder, layer_decay=ft.layer_decay, world_size=run.world_size)
+        mix_args = ft.mix
+        if run.world_size > 1:
+            drop_seed, mix_seed = rank_seeds(run.rank, run.world_size, 0 if ft.mix is None else ft.mix['seed'])
+            encoder.drop_path_generator = torch.Generator(device=run.device).manual_seed(drop_seed)
+            if ft.mix is not None:
+                mix_args = dict(ft.mix, seed=mix_seed)
+            logger.info(f'rank {run.rank} of {run.world_size}: the encoder\'s gradients are averaged over the ranks '
+                        f'({len(tuner.reducer.buckets)} buckets under the backward, {len(tuner.reducer.tail)} collectives after it); '
+                        f'drop-path seed {drop_seed}, mix seed {mix_seed}; each rank mixes its own local batch')
         lr_ratio = ft.encoder_lr / cfg.lr
 
         def after_update(optimizer, grad_scale):
@@ -160,8 +195,8 @@ class _FineTune:
         self.tuner = tuner
         epoch = dict(features_grad=True, after_update=after_update)
         if ft.mix is not None:
-            epoch['mix'] = self.mix = MixDraw(num_classes=cfg.num_classes, **ft.mix)
-            logger.info('mixing the training batches with their flipped selves: ' + ', '.join(f'{k} {v}' for k, v in ft.mix.items())
+            epoch['mix'] = self.mix = MixDraw(num_classes=cfg.num_classes, **mix_args)
+            logger.info('mixing the training batches with their flipped selves: ' + ', '.join(f'{k} {v}' for k, v in mix_args.items())
                         + ' (soft-target cross-entropy; the training top-1 is counted against the clips\' own labels)')
         return epoch, extra_state, restore_extra
 

@@ -29,6 +29,7 @@ import torch.nn as nn
 from ...engine import hipmodule
 from ...engine.chain import Workspace
 from ...engine.layers import encoder_backward, encoder_forward, recompute_mode
+from ...engine.streams import side_stream
 from ..utils.tensors import trunc_normal_
 from .utils.modules import Block
 from .utils.patch_embed import PatchEmbed, PatchEmbed3D
@@ -58,6 +59,8 @@ class VisionTransformer(nn.Module, hipmodule.HipModule):
         self.set_drop_path_rate(drop_path_rate, depth)
         self.any_input_trains = False       # train_on_any_input: still images and off-native sizes with gradients enabled
         self.activation_recompute = None    # set_activation_recompute: None (off), "mlp" or "block"
+        self.grad_reducer = None            # an engine.dp.GradReducer over the arena that owns the parameters (set by a data-parallel
+        #                                     EncoderFineTuner; not part of the state dict): the backward launches its buckets
         self.num_features = self.embed_dim = embed_dim
         self.num_heads = num_heads
         self.out_layers = out_layers
@@ -385,7 +388,17 @@ def _enc_fwd(module, ew, args, diff):
 
 def _enc_bwd(module, ew, ctx_saved, dout):
     saved, segs = ctx_saved
-    encoder_backward(dout, saved, ew, segs, alpha=1.0)
+    reducer = module.grad_reducer
+    if reducer is None:
+        encoder_backward(dout, saved, ew, segs, alpha=1.0)
+        return None
+    # data parallel (engine.finetune.EncoderFineTuner on several ranks): a block's bucket of the gradient arena goes out as soon as
+    # its backward is enqueued, waiting on the side stream the weight gradients run on; finish() reduces the small tensors and makes
+    # this stream wait for every collective -- the pretraining step's walk (engine/step.py)
+    side = side_stream(dout.device)
+    reducer.begin(side.stream if side.enabled else None)
+    encoder_backward(dout, saved, ew, segs, alpha=1.0, on_layer_done=reducer.layer_done)
+    reducer.finish()
     return None
 
 

@@ -43,7 +43,12 @@ half the side) beside vj_copy_rows on the same bytes, and vj_soft_ce at R = 4, C
 VisionTransformer.set_activation_recompute(MODE); ms and peak memory as the other arms', the per-round difference to the plain
 fine-tuning arm, and for every arm the peak of what the allocator held (the whole process, after an empty_cache before the arm).
 --model NAME RES, --batch B and --no-frozen (no frozen arm) reach the configs the default does not, e.g. vit_huge 384.
-python tools/eval_bench.py --finetune [--segments 1 8] [--rounds 4] [--reps 3] [--drop-path 0.1] [--mix] [--recompute block]
+--dp1 adds another arm in the same rotation, in a one-rank `nccl` (RCCL) process group this tool creates: the fine-tuning iteration
+with the data-parallel reducer forced (VJ_FORCE_DP=1: engine.dp.GradReducer on dp.finetune_bucket_plan, launched by the encoder's
+backward) on the SAME encoder and tuner as the plain arm, which runs with the encoder's reducer hook withdrawn.  Reports the arm's ms
+per round and their spread, the per-round difference to the plain arm, reducer.exposed_ms(), coll_check, the route and the number of
+collectives per iteration.  A one-rank all-reduce moves nothing: what is timed is the bucket walk, its events and stream joins.
+python tools/eval_bench.py --finetune [--segments 1 8] [--rounds 4] [--reps 3] [--drop-path 0.1] [--mix] [--recompute block] [--dp1]
                            [--model vit_huge 384] [--batch 4] [--no-frozen]
 
 --image --finetune: one fine-tuning iteration of the image eval (jepa_amd/evals/image_classification_finetune: batch 16, 1000 classes,
@@ -601,8 +606,23 @@ def bench_mix_kernels(B=4, T=16, res=224, reps=20):
     return res_
 
 
+def _one_rank_group():
+    """The one-rank RCCL group of --dp1, created once per process."""
+    import socket
+    import torch.distributed as dist
+    if dist.is_initialized():
+        return
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1")
+    torch.cuda.set_device(0)
+    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
+
+
 def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400, drop_path=None, mix=False, recompute=None,
-                   frozen_arm=True):
+                   frozen_arm=True, dp1=False):
     from jepa_amd.evals.mix import MixDraw
     import statistics
     from jepa_amd.engine.finetune import EncoderFineTuner
@@ -614,7 +634,15 @@ def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400,
         agg = ClipAggregation(model, tubelet_size=2, attend_across_segments=True).to(dev)
         tuner = None
         if trainable:
+            if dp1:
+                _one_rank_group()
+                forced = os.environ.get("VJ_FORCE_DP")
+                os.environ["VJ_FORCE_DP"] = "1"
             tuner = EncoderFineTuner(model, layer_decay=0.75)
+            if dp1 and forced is None:
+                del os.environ["VJ_FORCE_DP"]
+            elif dp1:
+                os.environ["VJ_FORCE_DP"] = forced
         else:
             agg.eval()
             for p in agg.parameters():
@@ -632,8 +660,9 @@ def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400,
     def step(optimizer, grad_scale):
         tuner.step(optimizer.param_groups[0]['lr'], 0.05, grad_scale=grad_scale)
 
-    def finetune_at(rate, mix=None, recompute=None):
+    def finetune_at(rate, mix=None, recompute=None, reducer=None):
         def run():
+            enc_t.model.grad_reducer = reducer      # (None: the backward issues the call it always has)
             enc_t.model.set_drop_path_rate(rate)
             enc_t.model.set_activation_recompute(recompute)
             run_one_epoch(dev, True, enc_t, clf_t, scaler_t, opt_t, sched_t, wd_t, [train], False, 1, S, True,
@@ -649,6 +678,8 @@ def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400,
         arms["finetune_mix"] = finetune_at(0.0, MixDraw(num_classes=C, **MIX_RECIPE))
     if recompute:
         arms[f"finetune_{recompute}"] = finetune_at(0.0, recompute=recompute)
+    if dp1:
+        arms["finetune_dp1"] = finetune_at(0.0, reducer=tuner.reducer)
     if not frozen_arm:      # (a model too large for two copies and the plain arm's activations: the fine-tuning arms alone)
         del arms["frozen"]
     torch.cuda.synchronize()
@@ -674,6 +705,21 @@ def bench_finetune(reps, rounds, S, B=4, model_name="vit_large", res=224, C=400,
     enc_t.model.set_activation_recompute(None)
     mean = {arm: statistics.mean(v) for arm, v in ms.items()}
     drop = {}
+    if dp1:
+        red, d = tuner.reducer, ms["finetune_dp1"]
+        arms["finetune_dp1"]()      # (the last arm timed may have been another: `launched` and the exposed samples are this arm's)
+        drop.update(finetune_dp1_ms_rounds=[round(v, 2) for v in d], finetune_dp1_iteration_ms=round(mean["finetune_dp1"], 2),
+                    finetune_dp1_ms_spread=round(max(d) - min(d), 2),
+                    dp1_minus_plain_ms_rounds=[round(a - b, 2) for a, b in zip(d, ms["finetune"])],
+                    dp1_minus_plain_ms=round(mean["finetune_dp1"] - mean["finetune"], 2),
+                    peak_mem_gib_finetune_dp1_iteration=peak["finetune_dp1"],
+                    dp=dict(world=1, route=red.route, coll_mode=red.coll_mode, coll_check=red.coll_check,
+                            buckets=len(red.buckets), tail_collectives=len(red.tail), collectives_per_iteration=len(red.launched),
+                            exposed_ms=None if red.exposed_ms() is None else round(red.exposed_ms(), 4),
+                            exposed_samples=red.exposed_samples,
+                            bucket_mib=[round((hi - lo) * 4 / 2 ** 20, 2) for lo, hi in sorted({r for rs in red.buckets.values() for r in rs})][:3],
+                            tail_kib=round(sum(hi - lo for lo, hi in red.tail) * 4 / 2 ** 10, 1)))
+        enc_t.model.grad_reducer = None
     if recompute:
         arm = f"finetune_{recompute}"
         d = ms[arm]
@@ -724,6 +770,8 @@ def main():
     ap.add_argument("--mix", action="store_true", help="with --finetune: another arm, fine-tuning with mixup / cutmix / label smoothing")
     ap.add_argument("--recompute", choices=["mlp", "block"], default=None,
                     help="with --finetune: another arm, fine-tuning with this activation-recomputation mode")
+    ap.add_argument("--dp1", action="store_true",
+                    help="with --finetune: another arm, the fine-tuning iteration with the data-parallel reducer forced in a one-rank RCCL group")
     ap.add_argument("--model", nargs=2, default=["vit_large", "224"], metavar=("NAME", "RES"),
                     help="with --finetune: the encoder factory and the clip resolution (default vit_large 224)")
     ap.add_argument("--batch", type=int, default=4, help="with --finetune: clips per segment")
@@ -745,7 +793,8 @@ def main():
     if a.finetune:
         for S in a.segments:
             print(json.dumps(bench_finetune(a.reps, a.rounds, S, drop_path=a.drop_path, mix=a.mix, recompute=a.recompute,
-                                            B=a.batch, model_name=a.model[0], res=int(a.model[1]), frozen_arm=not a.no_frozen)),
+                                            B=a.batch, model_name=a.model[0], res=int(a.model[1]), frozen_arm=not a.no_frozen,
+                                            dp1=a.dp1)),
                   flush=True)
             torch.cuda.empty_cache()
         return
