@@ -148,6 +148,31 @@ int vj_image_resample(const uint8_t* frames, int64_t frames_bytes, const int64_t
                       int64_t S, int filter, int64_t taps_x, int64_t taps_y, int64_t rows, void* ws, int64_t ws_bytes,
                       vj_stream_t stream);
 int64_t vj_image_resample_ws_bytes(int64_t B, int64_t S, int64_t taps_x, int64_t taps_y, int64_t rows);
+/* The short-side Resize of the video evals' validation transforms    evals/video_classification_frozen/utils.py:217-223, 297-321
+ * on frames that are PIL images (src/datasets/utils/video/functional.py:52-67): Image.resize((OW, OH), filter) of every frame of
+ * every clip, whole frames, byte for byte, with the arithmetic of vj_image_resample (the table entry and the two pass bodies are
+ * shared).  Bounds and coefficients are computed once per (clip, axis, output index) and read by all T frames.  The reference's
+ * numpy frames go through cv2.INTER_LINEAR, which is not antialiased; that arithmetic is not implemented.
+ *   frames, desc   exactly what vj_clip_transform_pre takes: clip b is [T,Hs,Ws,3] at desc[b] = (byte offset, Hs, Ws, flag); only read
+ *   rgeom     int32 [B,2] = (OH, OW); a clip with (OH, OW) == (Hs, Ws) comes out as a copy
+ *   out       flat uint8 buffer of out_bytes bytes, 16-byte aligned
+ *   desc_out  int64 [B,4] = (byte offset of the resized clip in out, a multiple of 16; OH; OW; the flag carried over), built and
+ *             validated by the caller on the host.  Clip b is written dense, [T,OH,OW,3]: out with desc_out is a frame buffer for
+ *             vj_clip_transform_pre, vj_clip_randaug and the box tables.  OW * 3 need not be a multiple of anything: the vertical
+ *             pass stores aligned words and single bytes at the row edges, and writes no byte outside
+ *             [offset, offset + T*OH*OW*3) of its clip -- padding between clips keeps its bytes
+ *   filter    0 bilinear, 1 bicubic
+ *   oh, ow, taps_x, taps_y, rows   capacities of the workspace, maxima over the batch: OH, OW, the taps per axis as for
+ *             vj_image_resample, and the source height Hs
+ *   ws        workspace of vj_clip_resample_ws_bytes(B, T, oh, ow, taps_x, taps_y, rows) bytes, 16-byte aligned
+ * Three launches.  Every kernel re-derives validity from the tables: a clip whose source leaves frames, whose destination leaves
+ * out, whose desc_out disagrees with rgeom or that needs more than the capacities is written as zeros over the part of out its
+ * desc_out row names; source indices are clamped; nothing outside frames, ws and the clip's own output range is touched.
+ * B == 0 launches nothing.  B, T < 65536, sides below 32768. */
+int vj_clip_resample(const uint8_t* frames, int64_t frames_bytes, const int64_t* desc, const int32_t* rgeom, uint8_t* out,
+                     int64_t out_bytes, const int64_t* desc_out, int64_t B, int64_t T, int filter, int64_t oh, int64_t ow,
+                     int64_t taps_x, int64_t taps_y, int64_t rows, void* ws, int64_t ws_bytes, vj_stream_t stream);
+int64_t vj_clip_resample_ws_bytes(int64_t B, int64_t T, int64_t oh, int64_t ow, int64_t taps_x, int64_t taps_y, int64_t rows);
 /* RandomHorizontalFlip of the S x S crop on the uint8 side, in place: PIL's Image.transpose(FLIP_LEFT_RIGHT), which timm's training
  * pipeline applies BEFORE its AutoAugment policy (RandomResizedCrop -> RandomHorizontalFlip -> AutoAugment -> ToTensor -> Normalize ->
  * RandomErasing; evals/image_classification_frozen/eval.py:392-403), so a batch that carries a policy plan is mirrored here and

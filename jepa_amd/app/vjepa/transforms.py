@@ -26,6 +26,13 @@ from torch.utils.data._utils.collate import default_collate_fn_map
 from .randaugment import MAX_LAYERS, MIN_SIDE, NUM_ARGS, NUM_OPS
 
 ALIGN = 16   # every clip of a RawClipBatch starts on a 16-byte boundary of the flat buffer
+MAX_SIDE = 1 << 15   # sides of a resize stay below it (csrc/image_resample.hip)
+
+
+def resample_taps(n, m, filter_support=1.0):
+    """Taps an output index of PIL's antialiased resample can have on an axis that takes n samples to m (the capacity
+    vj_clip_resample's tables are sized by): int(ceil(support * max(n / m, 1))) * 2 + 1, bilinear support 1."""
+    return int(math.ceil(filter_support * max(n / m, 1.0))) * 2 + 1
 
 
 def make_transforms(
@@ -102,11 +109,14 @@ class RawClip:
     mean and std).  `pre` selects the frozen eval's normalise-first arithmetic (mean / std in 0..1 units; otherwise 0..255).
     `ebox` = (top, left, h, w) and `noise` fp32 [T,3,h,w] are the RandomErasing draw of the clip (h == 0 / None: not erased).
     `aug_ops` int32 [8] and `aug_args` float64 [8,6] are its RandAugment plan (randaugment.RandAugmentDraw.draw; None: none), which
-    the device carries out on the uint8 frames before anything else."""
-    __slots__ = ("frames", "boxes", "flip", "crop_size", "mean", "std", "pre", "ebox", "noise", "aug_ops", "aug_args")
+    the device carries out on the uint8 frames before anything else.  `resize` = (OH, OW) (None: none) has the device bring every
+    frame to OH x OW first, as PIL's antialiased bilinear Image.resize does (vj_clip_resample); the boxes then refer to the resized
+    frames."""
+    __slots__ = ("frames", "boxes", "flip", "crop_size", "mean", "std", "pre", "ebox", "noise", "aug_ops", "aug_args", "resize")
 
     def __init__(self, frames, boxes, flip, crop_size, mean, std, pre=False, ebox=(0, 0, 0, 0), noise=None, aug_ops=None,
-                 aug_args=None):
+                 aug_args=None, resize=None):
+        self.resize = None if resize is None else (int(resize[0]), int(resize[1]))
         self.frames, self.boxes, self.flip = frames, boxes, bool(flip)
         self.crop_size, self.mean, self.std = int(crop_size), tuple(mean), tuple(std)
         self.pre, self.ebox, self.noise = bool(pre), tuple(int(v) for v in ebox), noise
@@ -235,12 +245,14 @@ class RawClipBatch:
         noise_off  int64 [R]        where the row's block starts in `noise`
         aug_ops    int32 [R,8]      RandAugment operation codes, layer by layer; 0: nothing (None: no row has a plan)
         aug_args   float64 [R,8,6]  their arguments (randaugment.py)
+        rgeom      int32 [R,2]      (OH, OW) the frames of the row are resized to before the boxes apply; a row that is not resized
+                                    has its source size (None: no row is resized, nothing about the batch changes)
     R = num_views * B rows, view-major: rows [v*B, (v+1)*B) are view v of the B clips, and the rows of one clip share its byte
     offset.  `pre`: the normalise-first form (mean / std in 0..1 units)."""
 
     def __init__(self, frames, desc, boxes, crop_size, mean, std, pre=False, num_views=1, ebox=None, noise=None, noise_off=None,
-                 aug_ops=None, aug_args=None):
-        self.frames, self.desc, self.boxes = frames, desc, boxes
+                 aug_ops=None, aug_args=None, rgeom=None):
+        self.frames, self.desc, self.boxes, self.rgeom = frames, desc, boxes, rgeom
         self.aug_ops, self.aug_args = aug_ops, aug_args
         self.crop_size, self.mean, self.std = int(crop_size), tuple(mean), tuple(std)
         self.pre, self.num_views = bool(pre), int(num_views)
@@ -265,6 +277,46 @@ class RawClipBatch:
     def augmented(self):
         """Whether any row of the batch carries a RandAugment operation (decided on the host: no upload and no launch otherwise)."""
         return self.aug_ops is not None and bool((self.aug_ops != 0).any())
+
+    @property
+    def resized(self):
+        """Whether any row of the batch is resized on the device (decided on the host: no buffer and no launch otherwise)."""
+        return self.rgeom is not None and bool((self.rgeom.to(torch.int64) != self.desc[:, 1:3]).any())
+
+    def _validate_rgeom(self):
+        """The extents the boxes refer to, int64 [R] each: the resized ones where the batch carries a resize table."""
+        d, rg = self.desc, self.rgeom
+        if rg is None:
+            return d[:, 1], d[:, 2]
+        if rg.dtype != torch.int32 or tuple(rg.shape) != (d.shape[0], 2):
+            raise ValueError(f"RawClipBatch: malformed resize table rgeom {tuple(rg.shape)} {rg.dtype}")
+        bad = ((rg <= 0) | (rg >= MAX_SIDE)).any(1)
+        if bool(bad.any()):
+            b = int(bad.nonzero()[0])
+            raise ValueError(f"RawClipBatch: resize {rg[b].tolist()} of clip {b} is not positive and below {MAX_SIDE}")
+        if self.aug_ops is not None and self.resized:
+            raise ValueError("RawClipBatch: a batch carries RandAugment plans or a resize, not both (no transform draws both)")
+        B = d.shape[0] // self.num_views
+        if bool((rg.reshape(self.num_views, B, 2) != rg[:B]).any()):
+            raise ValueError("RawClipBatch: the views of a clip share its frames and therefore its resize")
+        return rg[:, 0].to(torch.int64), rg[:, 1].to(torch.int64)
+
+    def resample_plan(self, filter_support=1.0):
+        """What vj_clip_resample needs for this (validated) batch: (rgeom int32 [B,2] of the B clips, desc_out int64 [R,4] that reads
+        the resized buffer -- every clip dense at a 16-byte boundary, once, its views sharing it --, the buffer's size in bytes,
+        caps = (oh, ow, taps_x, taps_y, rows))."""
+        R, T = len(self), self.num_frames
+        B = R // self.num_views
+        rg = self.rgeom[:B]
+        offs, total = buffer_offsets([T * OH * OW * 3 for OH, OW in rg.tolist()])
+        desc_out = torch.stack([torch.tensor(offs, dtype=torch.int64).reshape(B), rg[:, 0].to(torch.int64), rg[:, 1].to(torch.int64),
+                                self.desc[:B, 3]], dim=1).repeat(self.num_views, 1).contiguous()
+        desc_out[:, 3] = self.desc[:, 3]
+        oh = ow = tx = ty = rows = 1
+        for (_, Hs, Ws, _), (OH, OW) in zip(self.desc[:B].tolist(), rg.tolist()):
+            oh, ow, rows = max(oh, OH), max(ow, OW), max(rows, Hs)
+            tx, ty = max(tx, resample_taps(Ws, OW, filter_support)), max(ty, resample_taps(Hs, OH, filter_support))
+        return rg.contiguous(), desc_out, total, (oh, ow, tx, ty, rows)
 
     def _validate_aug(self):
         ao, aa, d = self.aug_ops, self.aug_args, self.desc
@@ -296,8 +348,8 @@ class RawClipBatch:
         if d.shape[0] == 0:
             return self
         T = bx.shape[1]
-        Hs, Ws = d[:, 1], d[:, 2]
         check_extents("RawClipBatch", f, d, T)
+        Hs, Ws = self._validate_rgeom()             # what the boxes must stay inside
         b64 = bx.to(torch.int64)
         i, j, h, w = b64[..., 0], b64[..., 1], b64[..., 2], b64[..., 3]
         bad = (i < 0) | (h <= 0) | (i + h > Hs[:, None]) | (j < 0) | (w <= 0) | (j + w > Ws[:, None])
@@ -320,6 +372,8 @@ class RawClipBatch:
         self.noise = self.noise.pin_memory() if self.noise.numel() else self.noise
         if self.aug_ops is not None:
             self.aug_ops, self.aug_args = self.aug_ops.pin_memory(), self.aug_args.pin_memory()
+        if self.rgeom is not None:
+            self.rgeom = self.rgeom.pin_memory()
         return self
 
     def to(self, device):
@@ -344,9 +398,13 @@ def collate_raw_clips(batch, *, collate_fn_map=None):
     boxes = torch.stack([c.boxes.reshape(V, T, 4)[v] for c, _, v in rows])
     ebox, noise, noise_off = collate_erase([c for c, _, _ in rows])
     aug_ops, aug_args = collate_aug([c for c, _, _ in rows])
+    rgeom = None
+    if any(c.resize is not None for c in batch):
+        rgeom = torch.tensor([c.resize if c.resize is not None else tuple(c.frames.shape[1:3]) for c, _, _ in rows],
+                             dtype=torch.int32).reshape(len(rows), 2)
     return RawClipBatch(flat, desc, boxes, first.crop_size, first.mean, first.std, pre=first.pre, num_views=V, ebox=ebox,
                         noise=noise, noise_off=noise_off, aug_ops=aug_ops,
-                        aug_args=aug_args).validate()
+                        aug_args=aug_args, rgeom=rgeom).validate()
 
 
 default_collate_fn_map[RawClip] = collate_raw_clips

@@ -25,6 +25,9 @@ eval's normalise-first form goes through `vj_clip_transform_pre`, and a batch th
 noise and has `vj_clip_erase` write it, on the copy stream after the transform (no copy and no launch when no clip is erased).
 A batch whose clips carry RandAugment plans ships the two plan tables too, and `vj_clip_randaug` rewrites the uploaded uint8 frames
 in place on the copy stream BEFORE the transform, with a workspace kept in the slot (again nothing when no clip has an operation).
+A batch in which some clip carries a resize (the validation transforms' `device_resize`: real frames of any size) has
+`vj_clip_resample` bring every clip to its short-side size once, into a second frame buffer kept in the slot, and the transform
+reads that buffer in place of the upload: the views of a clip are cut from the one resized copy (nothing when no clip is resized).
 
 `EvalPrefetcher` is the same machinery for the batch structure of the frozen video eval (a list over segments of `RawClipBatch`,
 labels, clip indices): it iterates like the loader it wraps and hands out what `run_one_epoch` takes.  `ImagePrefetcher` is its
@@ -102,6 +105,24 @@ class DevicePrefetcher:
             if ws is None or ws.numel() < need:
                 ws = self._dev[slot][("aug_ws", i)] = torch.empty(need + need // 4, dtype=torch.uint8, device=self.device)
             ops.clip_randaug(frames, desc, raw.num_frames, aug_ops, aug_args, stream=self.copy_stream.cuda_stream, ws=ws)
+        if raw.resized:
+            # The validation transforms' short-side Resize: every clip once, whole frames, into a second frame buffer that the
+            # transform reads in place of the upload (the views of a clip share the copy).  Buffer and workspace are the slot's
+            # and only ever grow.
+            B = len(raw) // raw.num_views
+            rgeom, desc_out, nbytes, caps = raw.resample_plan()
+            rgeom, desc_out = self._stage(slot, ("rgeom", i), rgeom), self._stage(slot, ("desc_out", i), desc_out)
+            dev = self._dev[slot]
+            resized = dev.get(("resized", i))
+            if resized is None or resized.numel() < nbytes:
+                resized = dev[("resized", i)] = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, device=self.device)
+            need = ops.clip_resample.ws_bytes(B, raw.num_frames, caps)
+            ws = dev.get(("resample_ws", i))
+            if ws is None or ws.numel() < need:
+                ws = dev[("resample_ws", i)] = torch.empty(need + need // 4, dtype=torch.uint8, device=self.device)
+            ops.clip_resample(frames, desc[:B], rgeom, raw.num_frames, ops.BILINEAR, caps, resized, desc_out[:B],
+                              stream=self.copy_stream.cuda_stream, ws=ws)
+            frames, desc = resized, desc_out
         shape =(len(raw), 3, raw.num_frames, raw.crop_size, raw.crop_size)
         out = self._dev[slot].get(("clip", i))
         if out is None or tuple(out.shape) != shape or out.dtype != torch.float32:

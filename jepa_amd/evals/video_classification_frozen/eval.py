@@ -13,13 +13,17 @@ arithmetic, CSV columns, checkpoint dictionary and folder / file names.  Differe
     src/datasets/data_manager.py: SyntheticVideoClassification) or `synthetic_frames` (seeded labelled uint8 frames of mixed source
     sizes, SyntheticFramesClassification, through the eval's own transforms: .utils make_transforms with the reference's
     reprob 0.25 for training and its centre-crop / multi-view forms for validation); extension keys `data.synthetic_length` (items
-    per split, default 8 batches) and `data.num_workers` (default 0).
+    per split, default 8 batches) and `data.num_workers` (default 0).  Real videos come as frames: `data.dataset_type: frame_folder`
+    reads `dataset_train` / `dataset_val` as the reference's index csv over folders of frame images or .npy frame arrays
+    (src/datasets/frame_folder.py: the reference's clip sampling, no video decoder) through the same transforms and input edge;
+    its validation frames may have any size (see below).  `VideoDataset` and the other reference names still raise.
   - uint8 frames are what crosses to the device: the transforms only draw, the views are made by vj_clip_transform_pre and
     vj_clip_erase on a copy stream, and batch k+1 uploads while batch k's frozen forward runs (engine.input.EvalPrefetcher).
     `auto_augment` stays false where the reference's probe training sets it true; its RandAugment is opt-in instead: with the
     extension key `data.rand_augment: true` (default false; `synthetic_frames` only) the training transform draws the reference's
     plan per clip and vj_clip_randaug applies it to the uint8 frames on the device, byte for byte what PIL gives.  The short-side
-    resize of the validation transforms is the loader's job (the synthetic frames have that short side).
+    resize of the validation transforms is done on the device for `frame_folder` (vj_clip_resample: PIL's antialiased bilinear
+    Image.resize, not the cv2.INTER_LINEAR the reference's decord frames get); the synthetic frames have that short side.
   - the classifier is wrapped in DistributedDataParallel only when a process group with more than one rank is active; its
     checkpoint keys carry the `module.` prefix either way, so checkpoints move between this package and the reference.
   - with `pretrain.frames_per_clip` == 1 the encoder is the 2-D image ViT under FrameAggregation, which (as in the reference) only
@@ -37,7 +41,7 @@ import torch.nn.functional as F
 
 from ...app.vjepa.randaugment import RandAugmentDraw
 from ...engine.input import EvalPrefetcher
-from ...src.datasets.data_manager import SyntheticFramesClassification, SyntheticVideoClassification
+from ...src.datasets.data_manager import SyntheticFramesClassification, SyntheticVideoClassification, init_data
 from ...src.models import vision_transformer as vit
 from ...src.models.attentive_pooler import AttentiveClassifier
 from ...src.utils.logging import get_logger
@@ -127,7 +131,7 @@ def main(args_eval, resume_preempt=False, finetune=None):
                                    num_views_per_segment=1, training=True, rand_augment=rand_augment, **common)
     val_loader = make_dataloader(root_path=val_data_path, num_segments=eval_num_segments,
                                  num_views_per_segment=eval_num_views_per_segment, training=False, **common)
-    if str(dataset_type).lower() == 'synthetic_frames':
+    if str(dataset_type).lower() in ('synthetic_frames', 'frame_folder'):
         # uint8 frames: the views are made on the device, and the upload of batch k+1 runs under batch k's frozen forward
         train_loader, val_loader = EvalPrefetcher(train_loader, device), EvalPrefetcher(val_loader, device)
     ipe = len(train_loader)
@@ -251,6 +255,10 @@ def make_dataloader(root_path, batch_size, world_size, rank, dataset_type='Video
     does.  rand_augment (extension, `data.rand_augment`): the training transform of `synthetic_frames` also draws the reference's
     RandAugment plan per clip ('rand-m7-n4-mstd0.5-inc1', utils.py:233-237), which the prefetcher carries out on the device."""
     kind = str(dataset_type).lower()
+    if kind == 'frame_folder':
+        return _frame_folder_dataloader(root_path, batch_size, world_size, rank, resolution, frames_per_clip, frame_step,
+                                        num_segments, eval_duration, num_views_per_segment, allow_segment_overlap, training,
+                                        num_workers, subset_file, rand_augment)
     if kind not in ('synthetic', 'synthetic_frames'):
         raise NotImplementedError(
             f"dataset_type={dataset_type!r}: the reference's decord/torchvision video pipeline is not part of this package; "
@@ -284,6 +292,28 @@ def make_dataloader(root_path, batch_size, world_size, rank, dataset_type='Video
             return SyntheticVideoClassification(length, num_classes, frames_per_clip, resolution, num_segments=num_segments,
                                                 num_views_per_segment=num_views_per_segment, frame_step=frame_step, seed=seed)
     return synthetic_dataloader(make_dataset, batch_size, world_size, rank, training, num_workers, synthetic_length, seed)
+
+
+def _frame_folder_dataloader(root_path, batch_size, world_size, rank, resolution, frames_per_clip, frame_step, num_segments,
+                             eval_duration, num_views_per_segment, allow_segment_overlap, training, num_workers, subset_file,
+                             rand_augment):
+    """`dataset_type: frame_folder`: real videos as folders of frames (src/datasets/frame_folder.py) through the eval's transforms
+    and init_data with the reference's arguments (eval.py:460-487).  The validation transforms resize frames of any size to the
+    reference's short side on the device (`device_resize`); the training transform takes any size as it is."""
+    if subset_file is not None:
+        raise NotImplementedError("dataset_type: frame_folder does not read a subset_file; write the subset as its own csv")
+    transform = make_transforms(training=training, num_views_per_clip=num_views_per_segment, random_horizontal_flip=False,
+                                random_resize_aspect_ratio=(0.75, 4/3), random_resize_scale=(0.08, 1.0), reprob=0.25,
+                                auto_augment=False, motion_shift=False, crop_size=resolution)
+    if training and rand_augment:
+        transform.rand_augment = RandAugmentDraw('rand-m7-n4-mstd0.5-inc1')
+    if not training:
+        transform.device_resize = True
+    data_loader, _ = init_data(data='frame_folder', root_path=root_path, transform=transform, batch_size=batch_size,
+                               world_size=world_size, rank=rank, clip_len=frames_per_clip, frame_sample_rate=frame_step,
+                               duration=eval_duration, num_clips=num_segments, allow_clip_overlap=allow_segment_overlap,
+                               num_workers=num_workers, copy_data=False, drop_last=False, subset_file=subset_file)
+    return data_loader
 
 
 def init_model(device, pretrained, model_name, patch_size=16, crop_size=224, frames_per_clip=16, tubelet_size=2, use_sdpa=False,

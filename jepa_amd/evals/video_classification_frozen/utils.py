@@ -11,9 +11,14 @@ do no pixel work: they take decoded uint8 [T,H,W,3] frames and return a `RawClip
 normalise-first form -- the frames as they came, the crop boxes of every view, the flip, the RandomErasing box and noise -- and
 `engine.input.EvalPrefetcher` makes the fp32 views on the device (vj_clip_transform_pre, vj_clip_erase).  RandAugment is opt-in
 behind the attribute `VideoTransform.rand_augment` (a `RandAugmentDraw` of app/vjepa/randaugment.py: the plan is drawn first, as
-the reference augments first, and vj_clip_randaug carries it out on the uint8 frames on the device).  Out of scope, raising:
-`auto_augment=True` in the constructors (PIL RandAugment on the CPU) and the short-side resize of the two validation forms (cv2.resize in the reference), which is
-the loader's job here.  The decord loader behind the transforms is not part of this package.
+the reference augments first, and vj_clip_randaug carries it out on the uint8 frames on the device).  The short-side resize of the
+two validation forms is opt-in too, behind the attribute `device_resize` of both (default False: frames must arrive with that short
+side, and anything else raises): the RawClip then names the size the reference's Resize would give, vj_clip_resample makes it on
+the device as PIL's antialiased Image.resize(BILINEAR) does -- what the reference applies to PIL frames
+(src/datasets/utils/video/functional.py:52-67) --, and the boxes refer to the resized frames.  The reference's decord frames are
+numpy arrays and go through cv2.INTER_LINEAR instead, which is not antialiased; that arithmetic is not implemented.  Out of scope,
+raising: `auto_augment=True` in the constructors (PIL RandAugment on the CPU).  The decord loader behind the transforms is not part
+of this package; src/datasets/frame_folder.py reads videos stored as frames.
 """
 import numpy as np
 import torch
@@ -251,6 +256,15 @@ def _normalize_constants(normalize):
     return tuple(t[0].tolist()), tuple(t[1].tolist())
 
 
+def _resize_sizes(H, W, size):
+    """(OH, OW) the reference's short-side Resize leaves (src/datasets/utils/video/functional.py:74-81): the short side becomes
+    `size`, the long one int(size * long / short); None when the short side already is `size` (functional.py:55-58 returns the
+    frames as they are)."""
+    if min(H, W) == size:
+        return None
+    return (int(size * H / W), size) if W < H else (size, int(size * W / H))
+
+
 def _require_short_side(H, W, want, who):
     if min(H, W) != want:
         raise ValueError(f"{who}: frames of {H}x{W} do not have the short side {want} that the reference's Resize would leave; the "
@@ -294,6 +308,9 @@ class VideoTransform(object):
         # (the reference's auto_augment=True is RandAugmentDraw('rand-m7-n4-mstd0.5-inc1'), utils.py:233-237); set after
         # construction, the constructor keeps the reference's signature
         self.rand_augment = None
+        # False: validation frames must come with the short side the reference's Resize leaves.  True (set after construction, as
+        # rand_augment is): frames of any size are resized to it on the device, as PIL's bilinear Image.resize does it
+        self.device_resize = False
         self.mean, self.std = _normalize_constants(normalize)
         # box(es) and flip are drawn exactly as in pretraining (the same functions of src/datasets/utils/video/transforms.py)
         self._spatial = _PretrainVideoTransform(
@@ -305,11 +322,15 @@ class VideoTransform(object):
         T, H, W, _ = frames.shape
         S = self.crop_size
         if not self.training:
-            _require_short_side(H, W, self.short_side_size, "VideoTransform(training=False)")
+            resize = _resize_sizes(H, W, self.short_side_size) if self.device_resize else None
+            if resize is None:
+                _require_short_side(H, W, self.short_side_size, "VideoTransform(training=False)")
+            else:
+                H, W = resize           # the centre crop is taken from the resized frames
             x1 = int(round((W - S) / 2.))
             y1 = int(round((H - S) / 2.))
             boxes = torch.tensor([y1, x1, S, S], dtype=torch.int32).repeat(1, T, 1)
-            return RawClip(frames, boxes, False, S, self.mean, self.std, pre=True)
+            return RawClip(frames, boxes, False, S, self.mean, self.std, pre=True, resize=resize)
         aug_ops = aug_args = None
         if self.rand_augment is not None:
             # the reference augments first (utils.py:258-259), so these draws come before the crop, flip and erase draws
@@ -339,6 +360,7 @@ class EvalVideoTransform(object):
             raise ValueError("EvalVideoTransform: the reference divides by num_views_per_clip - 1; one view is VideoTransform(training=False)")
         self.views_per_clip = num_views_per_clip
         self.short_side_size = short_side_size
+        self.device_resize = False      # as VideoTransform.device_resize
         self.mean, self.std = _normalize_constants(normalize)
 
     def view_starts(self, H, W):
@@ -349,7 +371,11 @@ class EvalVideoTransform(object):
         frames = _uint8_frames(buffer, "EvalVideoTransform")
         T, H, W, _ = frames.shape
         S = self.short_side_size
-        _require_short_side(H, W, S, "EvalVideoTransform")
+        resize = _resize_sizes(H, W, S) if self.device_resize else None
+        if resize is None:
+            _require_short_side(H, W, S, "EvalVideoTransform")
+        else:
+            H, W = resize               # the views are cut from the resized frames, which they share
         rows = [[start, 0, S, S] if H > W else [0, start, S, S] for start in self.view_starts(H, W)]
         boxes = torch.tensor(rows, dtype=torch.int32)[:, None, :].repeat(1, T, 1)
-        return RawClip(frames, boxes, False, S, self.mean, self.std, pre=True)
+        return RawClip(frames, boxes, False, S, self.mean, self.std, pre=True, resize=resize)

@@ -68,6 +68,8 @@ SIGNATURES = {
     "vj_clip_randaug_fill": (I32, [P, I64, P, I64, I64, P, P, I64, P, I64, I32, I32, I32, P]),
     "vj_image_resample": (I32, [P, I64, P, P, P, I64, I64, I32, I64, I64, I64, P, I64, P]),
     "vj_image_resample_ws_bytes": (I64, [I64, I64, I64, I64, I64]),
+    "vj_clip_resample": (I32, [P, I64, P, P, P, I64, P, I64, I64, I32, I64, I64, I64, I64, I64, P, I64, P]),
+    "vj_clip_resample_ws_bytes": (I64, [I64, I64, I64, I64, I64, I64, I64]),
     "vj_image_hflip": (I32, [P, P, I64, I64, I64, P]),
     "vj_image_pack": (I32, [P, P, P, I64, I64, I64, I64, I64, I64, I64, P]),
     "vj_add_pos_bcast": (I32, [P, P, P, I64, I64, I64, I64, P]),

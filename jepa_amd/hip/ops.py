@@ -347,6 +347,59 @@ class ImageResample:
         return out
 
 
+class _ClipResample:
+    """`ops.clip_resample(...)`: vj_clip_resample, the short-side Resize of the video evals' validation transforms on the device, with
+    `ops.clip_resample.ws_bytes(...)` sizing its workspace.  A callable object like image_hflip below, for the same reason."""
+
+    @staticmethod
+    def ws_bytes(B, T, caps):
+        """Bytes of workspace a call needs for B clips of T frames with the capacities caps = (oh, ow, taps_x, taps_y, rows)."""
+        need = int(_query("vj_clip_resample_ws_bytes", int(B), int(T), *(int(c) for c in caps)))
+        if need < 0:
+            raise ValueError(f"clip_resample.ws_bytes: bad dims B={B} T={T} (oh, ow, taps_x, taps_y, rows)={tuple(caps)}")
+        return need
+
+    @staticmethod
+    def __call__(frames, desc, rgeom, T, filter, caps, out, desc_out, stream=None, ws=None):
+        """vj_clip_resample: PIL's Image.resize((OW, OH), filter) of every frame of every clip, byte for byte, into a second frame buffer.
+        frames / desc as clip_transform takes them (clip b: [T,Hs,Ws,3]); rgeom int32 [B,2] = (OH, OW); out: a flat uint8 buffer;
+        desc_out int64 [B,4] = (byte offset in out, a multiple of 16; OH; OW; the flag): clip b is written as [T,OH,OW,3] there and no
+        other byte of out changes, so (out, desc_out) is what clip_transform / clip_randaug take next.  filter: BILINEAR or BICUBIC.
+        caps = (oh, ow, taps_x, taps_y, rows): the capacities of the batch, maxima of OH, OW, the taps per axis and the source height
+        (RawClipBatch.resample_plan gives them with rgeom and desc_out, validated on the host).  ws: a uint8 device buffer of at least
+        ws_bytes(...) bytes (default: this stream's scratch buffer).  B == 0 launches nothing."""
+        _req(frames, torch.uint8, "frames")
+        _req(desc, I64, "desc")
+        _req(rgeom, torch.int32, "rgeom")
+        _req(out, torch.uint8, "out")
+        _req(desc_out, I64, "desc_out")
+        _opt(ws, torch.uint8, "ws")
+        B = desc.shape[0]
+        if frames.dim() != 1 or out.dim() != 1 or desc.dim() != 2 or desc.shape[1] != 4 or tuple(rgeom.shape) != (B, 2) \
+                or tuple(desc_out.shape) != (B, 4):
+            raise ValueError(f"clip_resample: frames {tuple(frames.shape)} / desc {tuple(desc.shape)} / rgeom {tuple(rgeom.shape)} / out "
+                             f"{tuple(out.shape)} / desc_out {tuple(desc_out.shape)}: expected [nbytes], [B,4], [B,2], [nbytes], [B,4]")
+        if int(T) <= 0:
+            raise ValueError(f"clip_resample: T={T} frames per clip")
+        if int(filter) not in (BILINEAR, BICUBIC):
+            raise ValueError(f"clip_resample: filter={filter} (BILINEAR or BICUBIC)")
+        if len(caps) != 5:
+            raise ValueError(f"clip_resample: caps={caps} is not (oh, ow, taps_x, taps_y, rows)")
+        if B == 0:
+            return out
+        need = _ClipResample.ws_bytes(B, T, caps)
+        if ws is None:
+            ws = Scratch.get(need, frames.device, tag="clip_resample", stream=stream)
+        elif ws.numel() < need:
+            raise ValueError(f"clip_resample: ws of {ws.numel()} bytes, {need} needed")
+        _launch("vj_clip_resample", _ptr(frames), frames.numel(), _ptr(desc), _ptr(rgeom), _ptr(out), out.numel(), _ptr(desc_out), B, int(T),
+                int(filter), *(int(c) for c in caps), _ptr(ws), ws.numel(), stream=stream)
+        return out
+
+
+clip_resample = _ClipResample()
+
+
 class _ImageHflip:
     """`ops.image_hflip(images, desc, flips, stream=None)`: vj_image_hflip on the buffer ImageResample.run writes.  A callable object
     beside that namespace, not a module-level function: the public functions of this module are the per-kernel wrappers of the

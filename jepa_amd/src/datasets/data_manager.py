@@ -4,8 +4,9 @@ The reference's CPU video pipeline (decord decode, clip sampling, augmentation: 
 app/vjepa/transforms.py) sits OUTSIDE the accelerated hot path and needs packages that are not part of this
 image; `data='synthetic'` provides the seeded synthetic clip stream used by BASELINE.json's configs and the
 tests, and `data='synthetic_frames'` seeded uint8 [T,H,W,3] frame buffers of varying size that go through `transform`
-(app/vjepa/transforms.py) the way decoded video does.  Any real dataset type raises with an explanation instead of
-silently degrading.
+(app/vjepa/transforms.py) the way decoded video does.  `data='frame_folder'` reads real videos stored as folders of frame
+images or `.npy` frame arrays (frame_folder.py: the reference's index file, clip sampling and item layout, no decoder).  Any
+other dataset type raises with an explanation instead of silently degrading.
 """
 import numpy as np
 import torch
@@ -203,6 +204,20 @@ def init_data(batch_size, transform=None, shared_transform=None, data='ImageNet'
               filter_long_videos=int(1e9), decode_one_clip=True, datasets_weights=None, persistent_workers=False,
               repeat_wds=False, ipe=300, log_dir=None, crop_size=224, synthetic_length=None):
     kind = str(data).lower()
+    if kind == 'frame_folder':
+        # real videos as folders of frames / .npy frame arrays (frame_folder.py), with the arguments, the sampler and the loader of
+        # the reference's make_videodataset (src/datasets/video_dataset.py:27-88)
+        from .frame_folder import FrameFolderVideoDataset
+        dataset = FrameFolderVideoDataset(
+            data_paths=root_path, datasets_weights=datasets_weights, frames_per_clip=clip_len, frame_step=frame_sample_rate,
+            num_clips=num_clips, random_clip_sampling=random_clip_sampling, allow_clip_overlap=allow_clip_overlap,
+            filter_short_videos=filter_short_videos, filter_long_videos=filter_long_videos, duration=duration,
+            shared_transform=shared_transform, transform=transform)
+        sampler = torch.utils.data.distributed.DistributedSampler(dataset, num_replicas=world_size, rank=rank, shuffle=True)
+        loader = torch.utils.data.DataLoader(dataset, collate_fn=collator, sampler=sampler, batch_size=batch_size,
+                                             drop_last=drop_last, pin_memory=pin_mem, num_workers=num_workers,
+                                             persistent_workers=num_workers > 0)
+        return loader, sampler
     if kind not in ('synthetic', 'synthetic_frames'):
         raise NotImplementedError(
             f"dataset_type={data!r}: the reference's decord video decoding needs packages that are not available here. "

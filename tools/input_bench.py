@@ -20,6 +20,18 @@ Prints one JSON line per measurement; nothing here is a gate.
 5. the wait of the compute stream on the input edge (EvalPrefetcher, timing events) inside a loop of frozen ViT-L forwards over
    B = 4 training clips, with and without the plans, the two arms interleaved round by round.
 --randaug-pil times, for scale, the same plans carried out through PIL on one CPU core, per clip.
+
+    python tools/input_bench.py --resize [--launches 30] [--steps 4] [--rounds 2]
+    python tools/input_bench.py --resize-host          (CPU only, needs PIL)
+
+--resize measures the validation resize of real frames (vj_clip_resample) on a K400 16x8x3 validation batch (batch 4, 8 segments of
+16 frames of 256x340, resized to 224x297, 3 views):
+6. kernel time of vj_clip_resample over the batch's 32 clips, and beside it vj_image_resample computing the same three 224x224
+   windows of every frame -- the only way to express this without the clip kernel;
+7. the wait of the compute stream on the input edge inside a loop of frozen ViT-L forwards over such batches, with sources that
+   need the resize and with sources that arrive at 224x297, the two arms interleaved round by round.
+--resize-host times Pillow's resize of one clip on one CPU core, and the frames per second FrameFolderVideoDataset reads per worker
+from JPEG folders and from .npy arrays.
 """
 import argparse
 import json
@@ -281,6 +293,144 @@ def randaug_pil(clips=8):
                       "ms_per_applied_operation": round(1e3 * sum(secs) / max(1, int((po != 0).sum())), 1)}), flush=True)
 
 
+RS_B, RS_SEGMENTS, RS_VIEWS, RS_SRC, RS_OUT = 4, 8, 3, (256, 340), (224, 297)      # a K400 16x8x3 validation batch
+
+
+def _k400_segments(native, nb=RS_B, segments=RS_SEGMENTS):
+    """`segments` RawClipBatches of nb clips of 16 frames through EvalVideoTransform(3, 224): 256x340 sources that the device
+    resizes to 224x297, or (native) 224x297 sources that need nothing."""
+    from jepa_amd.evals.video_classification_frozen.utils import EvalVideoTransform
+    tf = EvalVideoTransform(num_views_per_clip=RS_VIEWS, short_side_size=S)
+    tf.device_resize = True
+    g = torch.Generator().manual_seed(3)
+    hw = RS_OUT if native else RS_SRC
+    return [torch.utils.data.default_collate([tf(torch.randint(0, 256, (RA_T,) + hw + (3,), generator=g, dtype=torch.uint8))
+                                              for _ in range(nb)]).pin_memory() for _ in range(segments)]
+
+
+def resize_kernel_times(dev, launches):
+    from jepa_amd.app.vjepa.transforms import RawClipBatch
+    from jepa_amd.evals.image_classification_frozen.transforms import axis_span, axis_taps
+    seg = _k400_segments(False, nb=RS_B * RS_SEGMENTS, segments=1)[0]          # all 32 clips of the batch in one launch
+    assert isinstance(seg, RawClipBatch) and seg.resized
+    nb = len(seg) // RS_VIEWS
+    frames, desc = seg.frames.to(dev), seg.desc[:nb].to(dev)
+    rgeom, desc_out, nbytes, caps = seg.resample_plan()
+    out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = torch.empty(ops.clip_resample.ws_bytes(nb, RA_T, caps), dtype=torch.uint8, device=dev)
+    rg, do = rgeom.to(dev), desc_out[:nb].to(dev)
+    us = _timed_us(lambda: ops.clip_resample(frames, desc, rg, RA_T, ops.BILINEAR, caps, out, do, ws=ws), launches)
+    med = statistics.median(us)
+    moved = frames.numel() + nbytes
+    print(json.dumps({"what": "vj_clip_resample, one launch for the batch", "clips": nb, "frames": RA_T, "source": list(RS_SRC),
+                      "resized": list(RS_OUT), "launches": launches, "median_us": round(med, 1), "min_us": round(min(us), 1),
+                      "max_us": round(max(us), 1), "source_plus_output_bytes": moved,
+                      "TB_per_s": round(moved / (med * 1e-6) / 1e12, 3), "workspace_bytes": ws.numel()}), flush=True)
+    # what the parent could express: every frame an image, every view an S x S window of its 224x297 resize (three launches)
+    H, W = RS_SRC
+    step = (max(RS_OUT) - S) // (RS_VIEWS - 1)
+    n = nb * RA_T
+    idesc = torch.tensor([[int(seg.desc[b, 0]) + t * H * W * 3, H, W, 0] for b in range(nb) for t in range(RA_T)], dtype=torch.int64)
+    assert bool((idesc[:, 0] % 16 == 0).all())
+    tx, ty = axis_taps(W, RS_OUT[1], ops.BILINEAR), axis_taps(H, RS_OUT[0], ops.BILINEAR)
+    rows = axis_span(H, RS_OUT[0], ops.BILINEAR, 0, S)[1]
+    idesc, u8 = idesc.to(dev), torch.empty((n, S, S, 3), dtype=torch.uint8, device=dev)
+    geoms = [torch.tensor([[0, 0, H, W, RS_OUT[0], RS_OUT[1], 0, v * step]] * n, dtype=torch.int32, device=dev) for v in range(RS_VIEWS)]
+    iws = torch.empty(ops.ImageResample.ws_bytes(n, S, tx, ty, rows), dtype=torch.uint8, device=dev)
+
+    def windows():
+        for geom in geoms:
+            ops.ImageResample.run(frames, idesc, geom, S, ops.BILINEAR, tx, ty, rows, out=u8, ws=iws)
+    us = _timed_us(windows, launches)
+    print(json.dumps({"what": "vj_image_resample, the same three 224x224 windows of every frame (three launches of clips x frames images)",
+                      "images_per_launch": n, "launches": launches, "median_us": round(statistics.median(us), 1),
+                      "min_us": round(min(us), 1), "max_us": round(max(us), 1)}), flush=True)
+
+
+def resize_edge(dev, steps, rounds):
+    from jepa_amd.engine.input import EvalPrefetcher
+    from jepa_amd.evals.video_classification_frozen.utils import ClipAggregation
+    from jepa_amd.src.models import vision_transformer as vit
+    torch.manual_seed(0)
+    enc = ClipAggregation(vit.vit_large(img_size=S, patch_size=16, num_frames=RA_T, tubelet_size=2, uniform_power=True),
+                          tubelet_size=2, attend_across_segments=True).to(dev).eval()
+    for p in enc.parameters():
+        p.requires_grad = False
+    arms = {}
+    for arm, native in (("native 224x297 (no resize)", True), ("256x340, resized on the device", False)):
+        segs = _k400_segments(native)
+        arms[arm] = (segs, torch.zeros(RS_B, dtype=torch.int64), [torch.arange(RA_T) for _ in segs])
+    rows = []
+    for r in range(rounds):
+        row = {}
+        for arm in (list(arms) if r % 2 == 0 else list(arms)[::-1]):
+            pf = EvalPrefetcher([arms[arm]] * (steps + 1), dev, timing=True)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.no_grad():
+                for k, (clips, _, idx) in enumerate(pf):
+                    if k == 1:
+                        e0.record()
+                    enc(clips, idx)
+            e1.record()
+            torch.cuda.synchronize()
+            waits = [max(0.0, a.elapsed_time(b)) for a, b in pf.edge_events]
+            row[arm] = dict(edge_wait_ms_first=round(waits[0], 3), edge_wait_ms_rest_mean=round(statistics.mean(waits[1:]), 4),
+                            edge_wait_ms_rest_max=round(max(waits[1:]), 4), iteration_ms=round(e0.elapsed_time(e1) / steps, 3),
+                            h2d_bytes_per_batch=int(pf.bytes_copied / (steps + 1)))
+        rows.append(row)
+    print(json.dumps({"what": "input-edge wait inside a loop of frozen ViT-L forwards over K400 16x8x3 validation batches, EvalPrefetcher, "
+                              "interleaved arms", "batch": RS_B, "segments": RS_SEGMENTS, "views": RS_VIEWS, "frames": RA_T,
+                      "steps": steps, "rounds": rows}), flush=True)
+
+
+def resize_host(videos=2, length=160):
+    """CPU only: Pillow's resize of a clip on one core, and the frames per second one worker reads from JPEG folders and .npy."""
+    import tempfile
+    import time
+
+    from PIL import Image
+
+    from jepa_amd.src.datasets.frame_folder import FrameFolderVideoDataset
+    torch.set_num_threads(1)
+    g = np.random.RandomState(0)
+    H, W = RS_SRC
+    clip = g.randint(0, 256, (RA_T, H, W, 3)).astype(np.uint8)
+    secs = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        np.stack([np.asarray(Image.fromarray(f).resize((RS_OUT[1], RS_OUT[0]), Image.BILINEAR)) for f in clip])
+        secs.append(time.perf_counter() - t0)
+    print(json.dumps({"what": "Pillow Image.resize(BILINEAR) of one clip on one CPU core", "frames": RA_T, "source": list(RS_SRC),
+                      "resized": list(RS_OUT), "ms_per_clip_median": round(1e3 * statistics.median(secs), 2),
+                      "ms_per_k400_item_of_8_segments": round(8e3 * statistics.median(secs), 1)}), flush=True)
+    with tempfile.TemporaryDirectory() as tmp:
+        y, x = np.mgrid[0:H, 0:W]
+        for v in range(videos):
+            os.makedirs(os.path.join(tmp, f"jpg{v}"))
+            video = np.stack([np.stack([(y + 3 * t + 40 * v) % 256, (x + 5 * t) % 256, (x + y + t) % 256], -1)
+                              for t in range(length)]).astype(np.uint8)
+            for t, f in enumerate(video):
+                Image.fromarray(f).save(os.path.join(tmp, f"jpg{v}", f"{t:06d}.jpg"), quality=90)
+            np.save(os.path.join(tmp, f"npy{v}.npy"), video)
+        for kind in ("jpg", "npy"):
+            index = os.path.join(tmp, f"{kind}.csv")
+            with open(index, "w") as f:
+                f.writelines(f"{kind}{v}{'.npy' if kind == 'npy' else ''} 0\n" for v in range(videos))
+            ds = FrameFolderVideoDataset([index], frames_per_clip=RA_T, frame_step=4, num_clips=RS_SEGMENTS, allow_clip_overlap=True)
+            np.random.seed(0)
+            ds[0]
+            t0, frames = time.perf_counter(), 0
+            for k in range(6):
+                clips, _, _ = ds[k % videos]
+                frames += sum(len(c) for c in clips)
+            dt = time.perf_counter() - t0
+            print(json.dumps({"what": "FrameFolderVideoDataset items on one worker (8 clips of 16 frames, no transform)",
+                              "storage": "JPEG folder (quality 90)" if kind == "jpg" else ".npy (memory-mapped)",
+                              "source": list(RS_SRC), "frames_per_s": round(frames / dt, 1),
+                              "ms_per_item": round(1e3 * dt / 6, 1)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=30)
@@ -289,9 +439,20 @@ def main():
     ap.add_argument("--randaug", action="store_true", help="the device-side RandAugment: kernel times and the input-edge wait")
     ap.add_argument("--randaug-pil", action="store_true", help="CPU only: the same plans through PIL, for scale")
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--resize", action="store_true", help="the device-side validation resize: kernel times and the input-edge wait")
+    ap.add_argument("--resize-host", action="store_true", help="CPU only: Pillow's resize and the frame-folder dataset's read rate")
     args = ap.parse_args()
     if args.randaug_pil:
         return randaug_pil()
+    if args.resize_host:
+        return resize_host()
+    if args.resize:
+        assert torch.cuda.is_available(), "needs an MI355X"
+        dev = torch.device("cuda", 0)
+        resize_kernel_times(dev, max(20, args.launches))
+        if not args.no_step_loop:
+            resize_edge(dev, args.steps, args.rounds)
+        return
     if args.randaug:
         assert torch.cuda.is_available(), "needs an MI355X"
         dev = torch.device("cuda", 0)
