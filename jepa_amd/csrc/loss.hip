@@ -9,6 +9,8 @@
 // latent_loss: sum |z-h|^p / p over all elements (z bf16, h fp32), deterministic two-stage reduction,
 // optionally writing dz = sign(z-h)*|z-h|^(p-1) * gscale (bf16) in the same pass.
 // part[blk] holds the block sums; finish kernel folds them:  out[slot] = scale * sum.
+// Non-finite d follows autograd of the reference expression: an infinite d gives +-gscale (p == 1) or +-inf; a NaN d gives 0
+// for p == 1 (sgn(NaN) = 0) and NaN otherwise, so that the gradient-norm guard of the optimizer sees it.
 // ---------------------------------------------------------------------------------------------
 #define LOSS_BLOCKS 512
 __global__ __launch_bounds__(256) void latent_loss_kernel(const bf16_t* __restrict__ z, const float* __restrict__ h,
@@ -33,7 +35,8 @@ __global__ __launch_bounds__(256) void latent_loss_kernel(const bf16_t* __restri
       } else {
         acc += __powf(a, p) / p;
         const float m = (a > 0.f) ? __powf(a, p - 1.0f) : 0.f;
-        g[j] = (d > 0.f) ? m * gscale : -m * gscale;
+        // a NaN d takes neither comparison and is passed on, as autograd does for p != 1 (p == 1: sgn(NaN) is 0 there too)
+        g[j] = (d > 0.f) ? m * gscale : ((d <= 0.f) ? -m * gscale : d);
       }
     }
     if (dz) store8(dz + q * 8, g);
