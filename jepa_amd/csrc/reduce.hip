@@ -131,7 +131,7 @@ extern "C" int vj_transpose_multi(const void* desc, const void* blocks, int64_t 
 // each group of `group` rows -- used both for plain bias grads (group = M) and for the mask-token grad,
 // which sums only the target rows j >= Ke of every [Ke+Kp]-row sample).  Deterministic two-stage sum.
 // ---------------------------------------------------------------------------------------------
-#define VJ_COLSUM_PARTS 256   // maximum number of row chunks (workspace sizing); the launcher picks 64 .. 256
+#define VJ_COLSUM_PARTS 256   // maximum number of row chunks (workspace sizing); the launcher picks 33 .. 256 (vj_colsum_bf16)
 __global__ __launch_bounds__(256) void colsum_bf16_kernel(const bf16_t* __restrict__ in, float* __restrict__ part,
                                                           int64_t M, int64_t N, int64_t ld, int64_t group,
                                                           int64_t row_lo, int64_t row_hi, int parts) {
@@ -300,8 +300,11 @@ extern "C" int vj_colsum_bf16(const void* in, int64_t M, int64_t N, int64_t ld, 
                (long)vj_colsum_ws_bytes(N));
   if (N == 0) return 0;
   if (group <= 0) group = (M > 0 ? M : 1);
-  // row chunks: enough workgroups (>= ~2048, 8 per CU) to keep HBM busy when N is narrow (N = 1024: 4 column groups), at
-  // least 8 rows per row lane and chunk; the chunk count only changes the (fixed, deterministic) summation order
+  // row chunks: enough workgroups (>= ~2048, 8 per CU) to keep HBM busy when N is narrow (N = 1024: 4 column groups), halved
+  // while a chunk would hold fewer than 64 rows (8 per row lane).  The count starts in 64 .. 256; the halving stops once it is at
+  // or below 64, so it ends in 64 .. 256 for N <= 2048 (the start there is 256) and can end below 64 for wider N, where
+  // the start is no power of two: N = 3072 and M < 5440 gives 171 -> 85 -> 42, N = 2056 and M < 7296 gives 228 -> 114 -> 57.  Never
+  // below 33.  The chunk count only changes the (fixed, deterministic) summation order
   const int64_t gx = cdiv64(N, 256);
   int64_t parts = cdiv64(2048, gx);
   if (parts < 64) parts = 64;
